@@ -190,6 +190,39 @@ def replicas_identical(stores, device):
     return lo == hi
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def timed_outputs(tr):
+    """What a caller of the timed path holds after its last step: the three losses and, per network, its trainable values, its
+    non-trainable state (pop_mean, batch-norm moving statistics) and its EMA shadow — each the network's variables in name order,
+    without the buffers' alignment padding, so that builds with another store layout still compare element for element."""
+    import torch
+    out = {'losses': tr.loss_dev}
+    for net, st in sorted(tr.cx.stores.items()):
+        trainable, state = sorted(st.names(True)), sorted(st.names(False))
+        out[net + '_params'] = torch.cat([st.value(nm) for nm in trainable])
+        if state:
+            out[net + '_state'] = torch.cat([st.value(nm) for nm in state])
+        if st.ema is not None:
+            out[net + '_ema'] = torch.cat([st._slice(st.ema, nm) for nm in trainable])
+    return out
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES):
+    """arrays -> out_dir/<name>.npy in float32, at most `budget` bytes in all: beyond it every array keeps the same share of its
+    elements, at indices drawn from a fixed seed (identical from run to run for the same shapes)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    total = 4 * sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if total > budget:
+            idx = np.random.default_rng(0).choice(t.numel(), t.numel() * budget // total, replace=False)
+            t = t[torch.from_numpy(np.sort(idx)).to(t.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), t.to(torch.float32).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -205,9 +238,14 @@ def main():
     ap.add_argument('--prof-iters', type=int, default=2)
     ap.add_argument('--soak-seconds', type=float, default=8.0,
                     help='untimed graph replays after the measurement so that a coarse GPU-utilisation sampler sees the run (0: none)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed (losses; per network its weights, running state and EMA) as DIR/<name>.npy '
+                         '(rank 0, float32, at most 64 MB)')
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # no launcher above us: start the N ranks here.  This process has made no GPU call (it only counts devices) and stays the
         # parent; rank 0's JSON line goes straight to our stdout.
@@ -264,6 +302,8 @@ def main():
     tgdist.barrier()
     dt = tgdist.max_over_ranks(dt_local, cx.device)
     dt_lo, dt_hi = tgdist.minmax_over_ranks([dt_local], cx.device)       # stragglers show as a gap between the fastest and the slowest rank
+    if args.dump_outputs and rank == 0:            # before any untimed step below moves the state on
+        dump_outputs(timed_outputs(tr), args.dump_outputs)
     losses = tr.losses()
     identical = replicas_identical(cx.stores, cx.device) if world > 1 else None
     # the launch path's own cost: host time to issue ONE iteration into an EMPTY queue (the figure above includes the time the host spends

@@ -101,12 +101,12 @@ def test_version_and_error_string_without_gpu(has_gpu):
         assert n >= 1
 
 
-def test_desc_struct_matches_header_layout():
+def test_desc_struct_matches_header_layout(tmp_path):
     """sizeof / offsets of the ctypes mirror against the C compiler's view of tg_igemm_desc."""
     from tg import lib
     src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){printf("%%zu %%zu %%zu %%zu %%zu\\n", sizeof(tg_igemm_desc), ' \
           'offsetof(tg_igemm_desc, dy), offsetof(tg_igemm_desc, tapw), offsetof(tg_igemm_desc, w_sn), offsetof(tg_igemm_desc, alpha));return 0;}' % HEADER
-    exe = "/tmp/tg_desc_layout"
+    exe = str(tmp_path / "tg_desc_layout")
     subprocess.run(["gcc", "-x", "c", "-", "-o", exe], input=src.encode(), check=True)
     got = [int(v) for v in subprocess.check_output([exe]).split()]
     D = lib.IgemmDesc

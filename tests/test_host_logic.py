@@ -222,6 +222,40 @@ def test_tape_split_at_gradient_bucket_boundary():
     cx.grad_bucket_boundary()                               # no tape: no-op
 
 
+def test_bench_dump_outputs_unpadded_in_name_order_and_within_budget(tmp_path):
+    """bench.py --dump-outputs: per network the variables' values without the store's padding, in name order, its running state and
+    EMA; float32 files; past the byte budget a seeded sample of the same share of every array, identical from call to call."""
+    import types
+    import torch
+    import bench
+    from tg.runtime import ParamStore
+    st = ParamStore('net', [('net/b', (33,), True), ('net/pop', (7,), False), ('net/a', (3, 5), True)], torch.device('cpu'))
+    st.set('net/a', np.arange(15))
+    st.set('net/b', 100 + np.arange(33))
+    st.set('net/pop', -np.ones(7))
+    st.enable_ema()
+    st.p.mul_(2)
+    tr = types.SimpleNamespace(loss_dev=torch.tensor([1.5, 2.5, 3.5]), cx=types.SimpleNamespace(stores={'net': st}))
+    out = bench.timed_outputs(tr)
+    bench.dump_outputs(out, str(tmp_path / 'full'))
+    got = {p.stem: np.load(p) for p in (tmp_path / 'full').iterdir()}
+    assert set(got) == {'losses', 'net_params', 'net_state', 'net_ema'} and all(v.dtype == np.float32 for v in got.values())
+    np.testing.assert_array_equal(got['net_ema'], np.concatenate([np.arange(15), 100 + np.arange(33)]))
+    np.testing.assert_array_equal(got['net_params'], 2 * got['net_ema'])
+    np.testing.assert_array_equal(got['net_state'], -np.ones(7))
+    np.testing.assert_array_equal(got['losses'], [1.5, 2.5, 3.5])
+    budget = 4 * 50
+    for d in ('s1', 's2'):
+        bench.dump_outputs(out, str(tmp_path / d), budget=budget)
+    s1 = {p.stem: np.load(p) for p in (tmp_path / 's1').iterdir()}
+    s2 = {p.stem: np.load(p) for p in (tmp_path / 's2').iterdir()}
+    total = sum(v.nbytes for v in got.values())
+    assert total > budget >= sum(v.nbytes for v in s1.values())
+    for k, v in s1.items():
+        np.testing.assert_array_equal(v, s2[k])
+        assert len(v) == len(got[k]) * budget // total and np.isin(v, got[k]).all()
+
+
 def test_bench_reads_the_committed_traffic_record_without_a_gpu(tmp_path, monkeypatch):
     """bench.measured_traffic(): the committed PMC record gives (bytes, detail) when it was collected for the kernel sources in the tree,
     (None, reason) when it is stale or incomplete — never an exception (a crash here would cost the round's bench line)."""
