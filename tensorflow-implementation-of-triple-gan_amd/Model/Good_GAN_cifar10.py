@@ -290,7 +290,7 @@ class cifar10_ZCA():
         cx = ctx()
         assert image.ld == image.c and image.h * image.w * image.c == self.dim
         out = cx.new_act(image.n, image.h, image.w, image.c, image.c)
-        splits = 4 if self.dim % 128 == 0 and image.n <= 1024 and os.environ.get('TG_ZCA_SPLITK', '1') != '0' else 1
+        splits = 4 if self.dim % 128 == 0 and image.n <= 1024 else 1
         if splits > 1:
             # few rows, long reduction (3072): four K-ranges as sub-problems of one launch, then one add-up pass
             import ctypes as C

@@ -116,7 +116,7 @@ class Train(Train_base):
             g_replay = []
             # (eager launches with the side stream, Context.wgrad_side: the generator's forward pass — small launches — runs beside the
             # classifier's, which it does not depend on; the two meet where the discriminator's batch is assembled)
-            with cx.wgrad_on_side('fwd'):
+            with cx.wgrad_on_side():
                 with cx.sub_tape(('good_generator',), replay=g_replay) as g_tape:
                     G = m.good_generator(self.z_g_ph, self.y_g_ph)
             self._g_saved = (G, g_tape, g_replay)
@@ -326,11 +326,9 @@ class Train(Train_base):
         cx.plan_tag = key
         # second-stream overlap (Context.wgrad_on_side): only beside eager launches — a captured graph with cross-stream edges replays slower
         # than the single chain on ROCm 7.2 (measured rounds 1 and 3), so graph replay stays one chain
-        side_was = (cx.wgrad_side, cx.wgrad_side_all)
-        on = cx.wgrad_side
-        if not cx.wgrad_side_env:
-            on = ((not use_graph) and mode in ('overlap', 'auto', 'plan')) or cx.side_fwd_only
-            cx.wgrad_side, cx.wgrad_side_all = on, on
+        side_was = cx.wgrad_side
+        on = (not use_graph) and mode in ('overlap', 'auto', 'plan')
+        cx.wgrad_side = on
         try:
             for i, (fn, grads, wait) in enumerate(segs):
                 if wait:                                    # this segment opens with an optimiser step: its network's buckets must be in
@@ -353,7 +351,7 @@ class Train(Train_base):
         finally:
             cx.prep_cache = None
             cx.join_wgrad_side()
-            cx.wgrad_side, cx.wgrad_side_all = side_was
+            cx.wgrad_side = side_was
         self._warm = True
         self._warm_keys.add(key)       # graphs of a mode are captured from its SECOND iteration on: the first one allocates its buffers eagerly
         if on and not use_graph:

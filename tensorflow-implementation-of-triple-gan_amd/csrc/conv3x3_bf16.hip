@@ -26,7 +26,6 @@
 // supplies k = 8g + 4h + s in step s), no conversion.
 // Numerics: every MFMA operand is rounded to bf16 (RNE) exactly as the generic tg_*_bf16 kernels do, products accumulate in fp32 —
 // the results differ from those kernels only by the order of the fp32 accumulation (channel chunks outermost here).
-#include <cstdlib>
 #include <type_traits>
 #include "tg_common.h"
 #include "tg_device.h"
@@ -62,13 +61,6 @@ __device__ unsigned long long tg_conv_stamps[8 * 64];
 #else
 #define CSTAMP(i) do {} while (0)
 #define LSTAMP(var) do {} while (0)
-#endif
-
-#ifndef TG_C3_PIPE
-#define TG_C3_PIPE 1                           // consumers: fragment reads software-pipelined behind the MFMAs — 1: bf16 operands only (shipped), 2: fp32 too (measured 1.5 - 2 % SLOWER: profiles/r04_c3pipe_ab.txt), 0: the compiler's order
-#endif
-#ifndef TG_ABL
-#define TG_ABL 0                               // timing ablations of conv3x3_pipe_kernel (tools only, results then wrong): 1 no stores, 8 half the halo loads, 16 half the filter loads, 32 no MFMAs
 #endif
 
 namespace {
@@ -241,7 +233,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pipe_kernel(ConvParams p) {
       const uint32_t so = (uint32_t)__builtin_amdgcn_readfirstlane(c0 * 4);
 #pragma unroll
       for (int i = 0; i < A_IT; ++i)
-        if (!(TG_ABL & 8) || i < A_IT / 2) ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, a_voff[i], so, 0);
+        ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, a_voff[i], so, 0);
     };
     auto pack_a = [&]() {
       if constexpr (BF16) {
@@ -277,7 +269,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pipe_kernel(ConvParams p) {
           const uint32_t so = (uint32_t)__builtin_amdgcn_readfirstlane(((p.tap[TPS * g + k] >> 16) * (int)p.w_st + c0) * 4);
 #pragma unroll
           for (int j = 0; j < B_IT; ++j)
-            if (!(TG_ABL & 16) || j < B_IT / 2) rb[k * B_IT + j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, b_voff, so + j * b_pass, 0);
+            rb[k * B_IT + j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, b_voff, so + j * b_pass, 0);
         }
       }
     };
@@ -422,13 +414,13 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pipe_kernel(ConvParams p) {
           const bool last_g = g == NG - 1;
           const bool more = !(last_g && last_c) || has_next;
           const unsigned char* B = Bs + bbuf * B_BYTES;
-          if constexpr (TG_C3_PIPE == 2 || (TG_C3_PIPE == 1 && BF16)) {
+          if constexpr (BF16) {
             // A wave issues in order: six fragment reads in front of the MFMAs of a (tap, k-slice) sub-step left the pipe idle for an LDS
             // latency, ~90 cycles per sub-step (stamps, conv1_2: fp32 26 084 cycles per step against 24 576 of MFMAs, bf16 4 829 against
             // 3 072 with 774 at the barriers).  Here the twelve sub-steps of a step are one software pipeline over two fragment register
             // sets: the six reads of sub-step i + 1 are issued one each behind the first six MFMAs of sub-step i (in the order their
             // MFMAs need them), so only the first reads of a step — behind its barrier — are waited for.  bf16: +1 ... 5 % (the launch is paced
-            // by its loaders); fp32 (TG_C3_PIPE=2): 1.5 - 2 % slower than the compiler's order, not shipped.
+            // by its loaders).
             using frag_t = typename std::conditional<BF16, bf16x8, f32x4>::type;
             constexpr int NM = BF16 ? 8 : 32;                     // MFMAs per sub-step: 2 x 4 tiles (x 4 k-pairs of the fp32 fragment)
             int a_row[TPS][2], a_swz[TPS][2];
@@ -573,7 +565,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pipe_kernel(ConvParams p) {
               for (int ni = 0; ni < 4; ++ni) {
                 const float x = acc[mi][ni][r] + bias_v[ni];
                 const float v = x > 0.f ? x : slope * x;
-                if (!(TG_ABL & 1)) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), rs_o, lane_off(ni, r), off, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), rs_o, lane_off(ni, r), off, 0);
               }
             }
         } else if (STAT2) {
@@ -712,10 +704,6 @@ void launch_pipe(ConvParams& p, hipStream_t s) {
   }
 }
 
-// A/B switches, read once at library load: the generic implicit GEMM takes the launches instead
-const bool g_disabled = getenv("TG_NO_CONV3X3_BF16") != nullptr;
-const bool g_disabled_f32 = getenv("TG_NO_CONV3X3_F32") != nullptr;
-
 // bytes of the packed bf16 filter of a launch (filter_pack_kernel): (c_out / 128) x (ld_in / 64) x 9 images of 16 KB
 int64_t pack_bytes(const tg_igemm_desc* d) { return (int64_t)(d->c_out / BN) * (d->ld_in / KC) * 9 * (BN * 128); }
 
@@ -735,7 +723,7 @@ void halo_count_launch() { ++g_launches; }
 
 // the layer has the kernel's shape (independent of how many images the launch holds)
 static bool conv3x3_fits(const tg_igemm_desc* d, int n_desc, const int32_t* seg_rows, int nseg, bool bf16) {
-  if ((bf16 ? g_disabled : g_disabled_f32) || g_policy == 2) return false;
+  if (g_policy == 2) return false;
   if (n_desc != 1 || d->n_taps != 9 || d->n_group != 0) return false;
   if (d->s_y != 1 || d->s_x != 1 || d->os_y != 1 || d->os_x != 1 || d->oo_y != 0 || d->oo_x != 0) return false;
   if (d->h_v != d->h_in || d->w_v != d->w_in || d->h_out != d->h_in || d->w_out != d->w_in) return false;
@@ -792,7 +780,7 @@ int conv3x3_bf16_split_images(const tg_igemm_desc* d, int n_desc, const int32_t*
 
 int64_t conv3x3_bf16_pack_bytes(const tg_igemm_desc* d, int n_desc) {
   const int32_t whole = d->n_img * d->h_in * d->w_in;         // shape only: one segment of whole images
-  if (g_disabled || !conv3x3_fits(d, n_desc, &whole, 0, true)) return 0;
+  if (!conv3x3_fits(d, n_desc, &whole, 0, true)) return 0;
   return pack_bytes(d);
 }
 

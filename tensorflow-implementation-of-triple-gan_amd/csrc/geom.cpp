@@ -5,8 +5,6 @@
 // Padding arithmetic is TensorFlow's: SAME: out = ceil(in / s), total = max((out-1)*s + k - in, 0),
 // before = total / 2 (the extra pixel goes after); VALID: out = (in - k) / s + 1, no padding.  conv2d_transpose 'same' with stride s:
 // out[s*i + k - before] += in[i] * W[k].
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 #include "tg_common.h"
@@ -55,18 +53,9 @@ int fill(tg_igemm_desc* d, int n_img, int h_in, int w_in, int ld_in, int h_v, in
 namespace tg {
 
 // ---- tile pick of igemm_impl (csrc/igemm.hip) — the quantisation cost model, see the comments there ------------------------------------
-static double g_eff64 = 1.02;
-static int g_force_bm = 0, g_force_bn = 0;
-static bool g_eff64_env = false;
-
-void igemm_tuning_from_env() {           // read ONCE, at library load (runtime.cpp), never per launch
-  if (const char* e = getenv("TG_IGEMM_EFF64")) { g_eff64 = atof(e); g_eff64_env = true; }
-  if (const char* f = getenv("TG_IGEMM_TILE")) sscanf(f, "%d,%d", &g_force_bm, &g_force_bn);
-}
-
 bool igemm_pick_tile(const tg_igemm_desc* descs, int n_desc, bool colsum, const int32_t* seg_rows, int nseg, bool bf16, int* bm_out, int* bn_out) {
   struct Cand { int bm, bn; double eff; };
-  const Cand cands[] = {{128, 128, 1.00}, {64, 128, 0.97}, {64, 64, g_eff64}, {128, 64, 0.95}, {32, 128, 0.85}, {128, 32, 0.70}};
+  const Cand cands[] = {{128, 128, 1.00}, {64, 128, 0.97}, {64, 64, 1.02}, {128, 64, 0.95}, {32, 128, 0.85}, {128, 32, 0.70}};
   const tg_igemm_desc* d = &descs[0];
   const int64_t M = (int64_t)d->n_img * d->h_v * d->w_v;
   double taps = 0;
@@ -74,13 +63,10 @@ bool igemm_pick_tile(const tg_igemm_desc* descs, int n_desc, bool colsum, const 
   for (int i = 0; i < n_desc; ++i) { taps += descs[i].n_taps; max_taps = descs[i].n_taps > max_taps ? descs[i].n_taps : max_taps; }
   int bm = 0, bn = 0;
   double best = 1e300;
-  // TG_IGEMM_TILE (tile audits, tools/tile_audit_step.sh): the named tile wherever it is a candidate, the model's pick elsewhere
-  for (int forced = g_force_bm ? 1 : 0; forced >= 0 && best >= 1e299; --forced)
   for (const Cand& c : cands) {
     // a tile may overhang the last columns (c_out = 544 = 8.5 x 64: nine 64-column tiles instead of seventeen 32-column ones); the
     // quantisation below charges the idle columns
     if (d->c_out % c.bn && c.bn > d->c_out) continue;
-    if (forced && (c.bm != g_force_bm || c.bn != g_force_bn)) continue;
     bool seg_ok = true;                                      // COLSUM: a tile may straddle at most one application boundary
     for (int i = 0; colsum && i < nseg; ++i) seg_ok = seg_ok && seg_rows[i] >= c.bm;
     if (!seg_ok) continue;
@@ -97,7 +83,7 @@ bool igemm_pick_tile(const tg_igemm_desc* descs, int n_desc, bool colsum, const 
       iters = total > max_taps ? total : max_taps;
     }
     // bf16 operands: the conversion work per tile favours the large tile (measured: CIFAR-10 bf16 step 8.06 ms with 0.96, 8.55 ms with 1.02)
-    const double eff = (bf16 && c.bm == 64 && c.bn == 64 && !g_eff64_env) ? 0.96 : c.eff;
+    const double eff = (bf16 && c.bm == 64 && c.bn == 64) ? 0.96 : c.eff;
     const double t = iters * c.bm * c.bn / eff;
     if (t < best) { best = t; bm = c.bm; bn = c.bn; }
   }
@@ -122,7 +108,6 @@ void igemm_sub_order(const tg_igemm_desc* descs, int n_desc, int* order) {
 // left alone.  MEASURED AND REJECTED (round 3, profiles/r03_split_ab.txt): cutting only the tiles of the last partial round of a launch
 // with more tiles than slots (1 128 tiles of conv3: 0.231 -> 0.272 ms) — workgroups do not run in lockstep rounds, a compute unit whose
 // partner slot is empty runs the remaining workgroup faster, and the fix-up launch waits for the whole main launch.
-static const bool g_no_split = getenv("TG_IGEMM_NOSPLIT") != nullptr;      // A/B switch, read once at library load
 
 void igemm_schedule(int n_sub, const int* nk, int64_t T, int bm, int bn, int slots, bool allow_split, IgemmSched* o) {
   std::memset(o, 0, sizeof *o);
@@ -132,7 +117,7 @@ void igemm_schedule(int n_sub, const int* nk, int64_t T, int bm, int bn, int slo
   const double ktile_us = 2.0 * bm * bn * 32 / (157.3e12 / slots) * 1e6;
   int mink = (int)(8.0 / ktile_us + 0.999);                // a unit is at least ~8 us of matrix work
   if (mink < 2) mink = 2;
-  const bool split_ok = allow_split && !g_no_split && T > 0;
+  const bool split_ok = allow_split && T > 0;
   if (n_sub == 1) {
     const int K = nk[0];
     o->nfull = (int)T;
@@ -187,8 +172,6 @@ void igemm_schedule(int n_sub, const int* nk, int64_t T, int bm, int bn, int slo
   o->n_fix = (int)(T * nsp);
   o->ws_bytes = T * nslot * (int64_t)bm * bn * 4;
 }
-
-static const int g_tuning_loaded = (igemm_tuning_from_env(), 0);      // at library load: never a getenv on the launch path
 
 // widest tile that divides the dimension; odd multiples of 32 from 160 on (288 = 256 + 32 label channels, 544, 160) take 64-wide tiles with
 // an overhanging last one instead of 32-wide ones

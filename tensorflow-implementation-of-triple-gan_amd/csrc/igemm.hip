@@ -22,7 +22,6 @@
 //    offset operand.  The fp32 MFMA executes on the vector ALUs, so the K loop carries next to no VALU address arithmetic.
 //  * workgroup order is XCD-aware in both kernels (tiles that share operand rows meet in one XCD's L2).
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include "tg_common.h"
 #include "tg_device.h"
@@ -54,29 +53,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u32x2 pack4_bf16(u32x4 v) {          // 4 fp32 -> 4 bf16 (RNE), channel order kept
   return __builtin_bit_cast(u32x2, __builtin_convertvector(__builtin_bit_cast(f32x4, v), bf16x4_t));
 }
-
-// register stages of igemm_f32_kernel's K pipeline per tile class (128x128 / 128x64 and 64x128 / smaller); -D overrides are for A/B builds
-#ifndef TG_PF_BIG
-#define TG_PF_BIG 1
-#endif
-#ifndef TG_PF_MID
-#define TG_PF_MID 2
-#endif
-#ifndef TG_PF_BF16_BIG
-#define TG_PF_BF16_BIG 1
-#endif
-#ifndef TG_PF_BF16_MID
-#define TG_PF_BF16_MID 2
-#endif
-#ifndef TG_PF_BF16_SMALL
-#define TG_PF_BF16_SMALL 2
-#endif
-#ifndef TG_INTERLEAVE
-#define TG_INTERLEAVE 1               // A/B: one memory instruction behind every MFMA in the K loop of the one-accumulator tiles (see the K loop)
-#endif
-#ifndef TG_PF_SMALL
-#define TG_PF_SMALL 2
-#endif
 
 constexpr int BK = 32;    // reduction depth per LDS tile
 constexpr int LDT = 36;   // padded LDS row stride (floats)
@@ -172,10 +148,9 @@ __global__ void __launch_bounds__(256, 2) igemm_f32_kernel(IgemmParams p) {
   static_assert(WAVES_M * WAVES_N == 4, "4 waves");
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, MI = WM / 32, NI = WN / 32;
   constexpr int AR = BM / 32, BR = BN / 32;   // 16-B loads per thread per tile
-  // register stages of the K pipeline (see the K loop); bf16 operands have their own depths: a K-tile's MFMAs take a sixteenth of the fp32 time
+  // register stages of the K pipeline (see the K loop): one for 128x128 tiles, two for the smaller ones, with fp32 and bf16 operands alike
   constexpr int NBUF = 2;                     // LDS buffers per operand
-  constexpr int PF = FIXUP ? 1 : (BF16 ? (BM * BN >= 128 * 128 ? TG_PF_BF16_BIG : (BM * BN >= 128 * 64 ? TG_PF_BF16_MID : TG_PF_BF16_SMALL))
-                                       : (BM * BN >= 128 * 128 ? TG_PF_BIG : (BM * BN >= 128 * 64 ? TG_PF_MID : TG_PF_SMALL)));
+  constexpr int PF = FIXUP ? 1 : (BM * BN >= 128 * 128 ? 1 : 2);
   __shared__ __attribute__((aligned(16))) float smem[NBUF * BM * LDT + NBUF * BN * LDT + 4 * BM];
   float* As = smem;
   float* Bs = smem + NBUF * BM * LDT;
@@ -416,7 +391,7 @@ __global__ void __launch_bounds__(256, 2) igemm_f32_kernel(IgemmParams p) {
   // steady state, PF iterations at a time, each issuing one tile UNCONDITIONALLY: straight-line code, so the wait in front of the LDS
   // write of stage rs + 1 is a counted one (the PF - 1 younger tiles stay in flight) — with a branch around the issue the compiler has to
   // assume the youngest loads are the ones it needs and drains the queue every iteration
-  if constexpr (TG_INTERLEAVE && MI == 1 && NI == 1 && !BF16 && PF >= 2 && 2 * (AR + BR) <= 10) {
+  if constexpr (MI == 1 && NI == 1 && !BF16 && PF >= 2 && 2 * (AR + BR) <= 10) {
     // Tiles with ONE accumulator per wave (64x64, 128x32, 32x128): the 16 MFMAs of a K-tile form one dependent chain, and a wave issues in
     // order — while MFMA k runs (64 cycles) the wave sits at MFMA k+1, so anything placed before or behind the chain is time the matrix pipe
     // idles when no second wave shares the SIMD (launches with at most one workgroup per CU: profiles/r04_stamp_small.txt).  Here every
@@ -1190,9 +1165,7 @@ static int igemm_impl(const tg_igemm_desc* descs, int n_desc, const float* in, c
     p.n_tiles = (p.c_out + bn - 1) / bn;
     int nk[MAX_SUB] = {0, 0, 0, 0};
     for (int i = 0; i < n_desc; ++i) nk[i] = descs[order[i]].n_taps * (d->ld_in / BK);
-    static const int dbg_mask = getenv("TG_IGEMM_SPLIT_MASK") ? atoi(getenv("TG_IGEMM_SPLIT_MASK")) : 7;      // debugging aid, read once: 1 plain, 2 column-sum variants, 4 several sub-problems
-    const int kind = n_desc > 1 ? 4 : (colsum ? 2 : 1);
-    tg::igemm_schedule(n_desc, nk, (int64_t)p.m_tiles * p.n_tiles, bm, bn, 2 * tg::halo_compute_units(), scratch != nullptr && (dbg_mask & kind), &sc);
+    tg::igemm_schedule(n_desc, nk, (int64_t)p.m_tiles * p.n_tiles, bm, bn, 2 * tg::halo_compute_units(), scratch != nullptr, &sc);
     if (sc.ws_bytes > scratch_bytes || (reinterpret_cast<uintptr_t>(scratch) & 15))      // less scratch than the cut needs: the one-launch schedule
       tg::igemm_schedule(n_desc, nk, (int64_t)p.m_tiles * p.n_tiles, bm, bn, 2 * tg::halo_compute_units(), false, &sc);
   }

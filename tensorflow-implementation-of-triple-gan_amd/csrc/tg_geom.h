@@ -21,7 +21,5 @@ void igemm_schedule(int n_sub, const int* nk, int64_t tiles, int bm, int bn, int
 void igemm_sub_order(const tg_igemm_desc* descs, int n_desc, int* order);
 // channel tile of the filter-gradient kernel for a dimension of n (rows: ld_in, columns: c_out)
 int wgrad_tile(int n);
-// TG_IGEMM_EFF64 / TG_IGEMM_TILE tuning aids: read once when the library is loaded
-void igemm_tuning_from_env();
 
 }  // namespace tg

@@ -19,7 +19,6 @@
 //     gradient image: 256-byte rows, 16-byte chunk XOR-swizzled by ((row & 3) << 2) | ((row >> 2) & 3) as in wgrad_f32_kernel's bf16 form.
 // Numerics: as the generic kernels — fp32 accumulation, operands exact (fp32) or RNE-rounded (bf16); only the order of the pixel sum
 // differs (and the pixel partition behind the `n_split` slabs, which tg_slab_reduce_f32 adds up anyway).
-#include <cstdlib>
 #include "tg_common.h"
 #include "tg_device.h"
 #include "tg_conv3x3_bf16.h"
@@ -231,9 +230,6 @@ void launch(const WParams& p, bool bf16, hipStream_t s) {
   else hipLaunchKernelGGL((wgrad3x3_kernel<W, false>), grid, dim3(512), 0, s, p);
 }
 
-const bool g_off = getenv("TG_NO_WGRAD3X3") != nullptr;          // A/B switches, read once at library load
-const bool g_no_f32 = getenv("TG_NO_WGRAD3X3_F32") != nullptr;   // fp32 launches stay on the generic kernel
-
 }  // namespace
 
 namespace tg {
@@ -242,7 +238,7 @@ namespace tg {
 // with the default policy (tg_conv3x3_policy 0) only when the launch puts a workgroup on 60 % ... 200 % of the compute units (a caller
 // that passes the split of tg_wgrad_splits[_bf16] does)
 bool wgrad3x3_applicable(const tg_igemm_desc* d, int n_split, bool bf16, int policy, int compute_units) {
-  if (g_off || policy == 2) return false;
+  if (policy == 2) return false;
   if (d->n_taps != 9 || d->n_group != 0) return false;
   if (d->s_y != 1 || d->s_x != 1 || d->os_y != 1 || d->os_x != 1 || d->oo_y != 0 || d->oo_x != 0) return false;
   if (d->h_v != d->h_in || d->w_v != d->w_in || d->h_out != d->h_in || d->w_out != d->w_in) return false;
@@ -259,8 +255,7 @@ bool wgrad3x3_applicable(const tg_igemm_desc* d, int n_split, bool bf16, int pol
   }
   if (policy == 0) {
     // exact fp32: 130 / 128 / 139 TFLOP/s on conv1_2 / conv2_1 / conv2_2 with one workgroup on every CU (the split rule below) against
-    // the generic kernel's 125 / 118 / 129; TG_NO_WGRAD3X3_F32 switches it off for A/B runs
-    if (!bf16 && g_no_f32) return false;
+    // the generic kernel's 125 / 118 / 129
     const long wgs = (long)(d->ld_in / CC) * (d->c_out / NT) * n_split;
     if (wgs * 10 < (long)compute_units * 6 || wgs > 2L * compute_units) return false;
   }

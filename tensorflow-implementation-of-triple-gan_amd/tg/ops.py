@@ -8,18 +8,8 @@ from . import geom, lib
 from .lib import ACT
 from .runtime import Act, ctx, pad32, seg_array
 
-import os as _os
-_BNSTAT = _os.environ.get('TG_BN_STAT_FUSE', '1') != '0'   # A/B switch: batch-norm statistics taken in the producing convolution's epilogue
-_BNBWDSTAT = _os.environ.get('TG_BN_BWD_STAT_FUSE', '1') != '0'   # A/B switch: batch-norm BACKWARD statistics taken in the epilogue of the launch that produces dy
-_BNACT = _os.environ.get('TG_BN_ACT_FUSE', '1') != '0'      # A/B switch: activation derivative + bias gradient folded into the batch-norm backward pass
-_NARROW = _os.environ.get('TG_NARROW_DECONV', '1') != '0'     # A/B switch of csrc/narrow.hip (the generator's image layer, backward)
-_ACTSUM = _os.environ.get('TG_ACTSUM', '1') != '0'      # A/B switch of the input-gradient + activation-derivative + column-sum fusion
 _MFMA_F32 = ('tg_igemm_f32', 'tg_igemm_multi_f32', 'tg_igemm_colsum_f32', 'tg_igemm_actsum_f32', 'tg_igemm_bnstat_f32', 'tg_igemm_bnbwdstat_f32', 'tg_wgrad_f32',
              'tg_igemm_labels_f32')
-_PACKED = _os.environ.get('TG_PACKED_CONV', '1') != '0'       # A/B switch of csrc/packed_conv.hip (3x3 convolutions of <= 16 input channels: the discriminators' first layer)
-_WIDE_SIDE = _os.environ.get('TG_WIDE_SIDE', '1') != '0'         # A/B switch: the many-split filter gradients of small filters (and their reduction) on the second stream
-_POOL_FUSE = _os.environ.get('TG_POOL_FUSE', '1') != '0'         # A/B switch: mean-only-BN apply + max-pool 2x2 + dropout in one launch (tg_mobn_apply_pool_f32)
-_CONCAT_FUSE = _os.environ.get('TG_CONCAT_FUSE', '1') != '0'     # A/B switch: conv -> cond_concat pairs written by the convolution's own epilogue (tg_igemm_labels_*)
 
 
 def _call(name, *args):
@@ -54,7 +44,7 @@ def _single_consumer(y, gy):
     buffer: a second consumer's raw contribution in the same buffer cannot be told apart afterwards — refuse instead of training on it."""
     if (y.grad_is_dpre or y.grad_fused is not None) and gy.contribs > 1:
         raise lib.TgError("fused backward: the gradient of a %dx%dx%dx%d activation was written by %d consumers, but one of them already folded "
-                          "the activation derivative into it (TG_BN_ACT_FUSE=0 / TG_ACTSUM=0 run such a topology unfused)" % (y.n, y.h, y.w, y.c, gy.contribs))
+                          "the activation derivative into it" % (y.n, y.h, y.w, y.c, gy.contribs))
 
 
 def _segs(x, segments):
@@ -108,10 +98,10 @@ def filter_grad(desc, in_act_t, dout_t, t, c_dim, n_dim, dst, wn=None, defer=Tru
     deferred = defer and (cx.tape is not None or cx._phase_depth > 0)
     small = desc.n_img * desc.h_v * desc.w_v * desc.ld_in * desc.c_out * desc.n_taps < (1 << 34)      # < 34 GFLOP: the generic kernel's launches
     wide = ns >= 32 and t * c_dim * n_dim <= 65536
-    if deferred and (small or cx.wgrad_side_all) and not wide:
+    if deferred and (small or cx.wgrad_side) and not wide:
         with cx.wgrad_on_side():                                 # beside the input-gradient chain (Context.wgrad_on_side; joined in flush_tails)
             _call('tg_wgrad_f32', desc, _p(in_act_t), _p(dout_t), _p(slab), ns, cx.stream)
-    elif deferred and small and wide and _WIDE_SIDE:
+    elif deferred and small and wide:
         # many splits of a small filter (the discriminator's first layers, the classifier's first): the launch AND its own reduction go to
         # the second stream, so the input-gradient chain does not wait for them (round 4: they were 0.18 ms of the D-update's launch stream)
         with cx.wgrad_on_side():
@@ -130,11 +120,10 @@ def filter_grad(desc, in_act_t, dout_t, t, c_dim, n_dim, dst, wn=None, defer=Tru
                       ns, t, desc.ld_in, desc.c_out, c_dim, n_dim)
         cx.tail_jobs.append(j)
         return
-    with cx.on_side(after_main=True):              # nothing on the main stream consumes dst before the phase's join
-        _call('tg_slab_reduce_f32', _p(slab), ns, t, desc.ld_in, desc.c_out, c_dim, n_dim, _p(dst), cx.stream)
-        if wn is not None:
-            coef = cx.scratch('coef', 2 * n_dim)
-            _call('tg_wn_bwd_f32', _p(dst), _p(wn[0]), _p(wn[1]), t * c_dim, n_dim, _p(wn[2]), _p(wn[3]), _p(coef), cx.stream)
+    _call('tg_slab_reduce_f32', _p(slab), ns, t, desc.ld_in, desc.c_out, c_dim, n_dim, _p(dst), cx.stream)
+    if wn is not None:
+        coef = cx.scratch('coef', 2 * n_dim)
+        _call('tg_wn_bwd_f32', _p(dst), _p(wn[0]), _p(wn[1]), t * c_dim, n_dim, _p(wn[2]), _p(wn[3]), _p(coef), cx.stream)
 
 
 # ------------------------------------------------------------------ conv / dense (plain and weight-normalised)
@@ -177,21 +166,18 @@ def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=N
     else:
         scale = None
         c_before = cx.counter
-        with cx.on_side(forward=True):                 # weights are final since the phase's fork: runs ahead, beside the previous layer's launch
-            # (buffers written on the side stream are also ALLOCATED under it: a first-use zero fill is a launch on the current stream)
-            w_oti = cx.scratch('woti', co_p * t * ci_p)
-            w_hwio = cx.scratch('whwio', t * ci_p * co_p) if (needs_x or cx.prep_cache is not None) else None
-            if wn is not None:
-                scale = cx.scratch('wns', c_out)
-                _call('tg_wn_scale_f32', _p(kernel), _p(wn[0]), t * c_in, c_out, _p(scale), cx.stream)
-            _call('tg_filter_prep_f32', _p(kernel), _p(scale), None, t, c_in, c_out, ci_p, co_p, _p(w_hwio), _p(w_oti), t * ci_p, ci_p, cx.stream)
-        cx.main_waits_side()
+        w_oti = cx.scratch('woti', co_p * t * ci_p)
+        w_hwio = cx.scratch('whwio', t * ci_p * co_p) if (needs_x or cx.prep_cache is not None) else None
+        if wn is not None:
+            scale = cx.scratch('wns', c_out)
+            _call('tg_wn_scale_f32', _p(kernel), _p(wn[0]), t * c_in, c_out, _p(scale), cx.stream)
+        _call('tg_filter_prep_f32', _p(kernel), _p(scale), None, t, c_in, c_out, ci_p, co_p, _p(w_hwio), _p(w_oti), t * ci_p, ci_p, cx.stream)
         if cx.prep_cache is not None:
             cx.prep_cache[key] = (scale, w_oti, w_hwio)
-            if cx._prep_rec is not None and w_hwio is not None and not cx.use_side_stream:
+            if cx._prep_rec is not None and w_hwio is not None:
                 cx._prep_rec.append(dict(key=key, kernel=kernel, g=wn[0] if wn is not None else None, scale=scale, w_oti=w_oti, w_hwio=w_hwio,
                                          t=t, a=c_in, b=c_out, a_pad=ci_p, b_pad=co_p, bump=cx.counter - c_before))
-    fuse_cat = (_CONCAT_FUSE and concat is not None and mobn is None and not bn_stats and n_store_ld is None and c_out == co_p)
+    fuse_cat = (concat is not None and mobn is None and not bn_stats and n_store_ld is None and c_out == co_p)
     if fuse_cat:
         n_store, ld_out = c_out, pad32(c_out + concat[1])
     elif n_store_ld is None:
@@ -205,7 +191,7 @@ def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=N
     pooled = None
     seg_rows = _segs(y, segments)
     fused = (mobn is not None and train and c_out == co_p and c_out <= 512 and stride == 1 and geom.colsum_supported(d, seg_rows))
-    packed = (_PACKED and cx.mfma_dtype != 'bf16' and k == 3 and stride == 1 and padding == 'SAME' and wn is None and mobn is None and not bn_stats
+    packed = (cx.mfma_dtype != 'bf16' and k == 3 and stride == 1 and padding == 'SAME' and wn is None and mobn is None and not bn_stats
               and n_store_ld is None and c_out == co_p and act in (None, 'relu', 'lrelu') and c_in <= 16
               and bool(_call('tg_conv3x3_packed_supported', x.n, x.h, x.w, c_in, c_out)))
     if fused:
@@ -213,14 +199,14 @@ def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=N
         b, b_grad, pop = mobn
         sums, zd = cx.zscratch('cs64', 2 * len(seg_rows) * c_out)     # fp64 accumulators
         _call('tg_igemm_colsum_f32', d, x.ptr, _p(w_oti), y.ptr, seg_array(seg_rows), len(seg_rows), _p(sums), zd, cx.stream)
-        if _POOL_FUSE and pool is not None and y.h % 2 == 0 and y.w % 2 == 0 and all(r % (y.h * y.w) == 0 for r in seg_rows):
+        if pool is not None and y.h % 2 == 0 and y.w % 2 == 0 and all(r % (y.h * y.w) == 0 for r in seg_rows):
             pooled = cx.new_act(y.n, y.h // 2, y.w // 2, c_out, co_p, requires_grad=needs_w or needs_x)
             _call('tg_mobn_apply_pool_f32', y.ptr, y.ld, y.n, y.h, y.w, c_out, seg_array(seg_rows), len(seg_rows), _p(sums), _p(b), _p(pop), 0.9, ACT[act],
                   alpha, pooled.ptr, pooled.ld, _p(pool[0]), c_out, pool[1], cx.stream)
         else:
             _call('tg_mobn_apply_f32', y.ptr, y.ld, y.rows, c_out, seg_array(seg_rows), len(seg_rows), _p(sums), _p(b), _p(pop), 0.9, ACT[act],
                   alpha, cx.stream)
-    elif (_BNSTAT and bn_stats and mobn is None and act in (None, 'relu', 'lrelu') and c_out == co_p == ld_out and len(seg_rows) <= 8
+    elif (bn_stats and mobn is None and act in (None, 'relu', 'lrelu') and c_out == co_p == ld_out and len(seg_rows) <= 8
           and geom.colsum_supported(d, seg_rows)):
         bsum, zd = cx.zscratch('bn64', 32 * len(seg_rows) * c_out)     # the batch norm's buffer: 8 replicas x nseg x 2 x c doubles
         _call('tg_igemm_bnstat_f32', d, x.ptr, _p(w_oti), _p(bias), y.ptr, seg_array(seg_rows), len(seg_rows), _p(bsum), zd, cx.stream)
@@ -310,7 +296,7 @@ def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=N
             gx = cx.grad_of(x)
             dlist = geom.conv_dgrad(x.n, x.h, x.w, ci_p, co_p, k, stride, padding, ld_out=gx.ld, n_store=ci_p)
             sink = x.grad_sink
-            if (_ACTSUM and sink is not None and fresh and len(dlist) == 1 and x.c == ci_p == gx.ld == x.ld and sum(sink[2]) == x.rows
+            if (sink is not None and fresh and len(dlist) == 1 and x.c == ci_p == gx.ld == x.ld and sum(sink[2]) == x.rows
                     and geom.colsum_supported(dlist[0], sink[2])):
                 # x is the output of a mean-only-BN layer: this launch also applies that layer's activation derivative and sums the
                 # columns per application, so its backward pass needs no statistics pass of its own (tg_mobn_center_f32)
@@ -319,7 +305,7 @@ def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=N
                 _call('tg_igemm_actsum_f32', dlist[0], _p(dpre), _p(w_hwio), x.ptr, ACT[sink[0]], sink[1], gx.ptr, seg_array(sink[2]), nsg,
                       _p(gsum), zd, cx.stream)
                 x.grad_fused = (gsum, 1)
-            elif (_BNBWDSTAT and x.bn_bwd_sink is not None and fresh and len(dlist) == 1 and x.c == ci_p == gx.ld == x.ld
+            elif (x.bn_bwd_sink is not None and fresh and len(dlist) == 1 and x.c == ci_p == gx.ld == x.ld
                   and x.bn_bwd_sink[0].ld == gx.ld and len(x.bn_bwd_sink[1]) <= 8 and sum(x.bn_bwd_sink[1]) == x.rows
                   and geom.colsum_supported(dlist[0], x.bn_bwd_sink[1])):
                 # x is a training-mode batch norm's output and this launch is the first to write its gradient: the batch norm's backward
@@ -365,23 +351,21 @@ def deconv2d(x, kernel, bias, c_out, act=None, kernel_grad=None, bias_grad=None,
     # (geom.deconv_fwd_merged): the four parities share one 32-column tile instead of padding 3 -> 32 four times (0.118 -> 0.050 ms).
     # Measured on the 128-channel layer the merged form is slower (0.19 -> 0.22 ms: 36/25 of the arithmetic outweighs the balance).
     merged = pad32(4 * c_out) < 4 * co_p and pad32(4 * c_out) <= 128
-    with cx.on_side(forward=True):
-        if wn is not None:
-            scale_a = cx.scratch('wnsa', c_out)
-            _call('tg_wn_scale_tab_f32', _p(kernel), _p(wn[0]), 25, c_out, c_in, _p(scale_a), cx.stream)
-        # the 3-channel image layer's backward runs as K-packed products straight from the [5,5,Cout,Cin] variable (csrc/narrow.hip): no transposed copy
-        narrow = _NARROW and x.ld == ci_p and bool(lib.call('tg_deconv5x5s2_narrow_supported', x.n, x.h, x.w, c_out, ci_p))
-        w_tr = cx.scratch('wtr', 25 * ci_p * co_p) if (needs_x and not narrow) else None
-        if merged:
-            d, ng, tapmap = geom.deconv_fwd_merged(x.n, x.h, x.w, ci_p, c_out, ld_out, n_store=c_out, act=act)
-            w_m = cx.scratch('wmrg', d.c_out * 9 * ci_p)
-            _call('tg_deconv_merge_prep_f32', _p(kernel), _p(scale_a), c_out, c_in, ng, d.c_out, ci_p, (C.c_int32 * 36)(*tapmap), _p(w_m), cx.stream)
-            if w_tr is not None:
-                _call('tg_filter_prep_f32', _p(kernel), None, _p(scale_a), 25, c_out, c_in, co_p, ci_p, None, _p(w_tr), co_p, ci_p * co_p, cx.stream)
-        else:
-            w_pad = cx.scratch('wpad', 25 * co_p * ci_p)
-            _call('tg_filter_prep_f32', _p(kernel), None, _p(scale_a), 25, c_out, c_in, co_p, ci_p, _p(w_pad), _p(w_tr), co_p, ci_p * co_p, cx.stream)
-    cx.main_waits_side()
+    if wn is not None:
+        scale_a = cx.scratch('wnsa', c_out)
+        _call('tg_wn_scale_tab_f32', _p(kernel), _p(wn[0]), 25, c_out, c_in, _p(scale_a), cx.stream)
+    # the 3-channel image layer's backward runs as K-packed products straight from the [5,5,Cout,Cin] variable (csrc/narrow.hip): no transposed copy
+    narrow = x.ld == ci_p and bool(lib.call('tg_deconv5x5s2_narrow_supported', x.n, x.h, x.w, c_out, ci_p))
+    w_tr = cx.scratch('wtr', 25 * ci_p * co_p) if (needs_x and not narrow) else None
+    if merged:
+        d, ng, tapmap = geom.deconv_fwd_merged(x.n, x.h, x.w, ci_p, c_out, ld_out, n_store=c_out, act=act)
+        w_m = cx.scratch('wmrg', d.c_out * 9 * ci_p)
+        _call('tg_deconv_merge_prep_f32', _p(kernel), _p(scale_a), c_out, c_in, ng, d.c_out, ci_p, (C.c_int32 * 36)(*tapmap), _p(w_m), cx.stream)
+        if w_tr is not None:
+            _call('tg_filter_prep_f32', _p(kernel), None, _p(scale_a), 25, c_out, c_in, co_p, ci_p, None, _p(w_tr), co_p, ci_p * co_p, cx.stream)
+    else:
+        w_pad = cx.scratch('wpad', 25 * co_p * ci_p)
+        _call('tg_filter_prep_f32', _p(kernel), None, _p(scale_a), 25, c_out, c_in, co_p, ci_p, _p(w_pad), _p(w_tr), co_p, ci_p * co_p, cx.stream)
     y = cx.new_act(x.n, 2 * x.h, 2 * x.w, c_out, ld_out, requires_grad=needs_w or needs_x)
     y.strided_grad_ok = True
     if act in ('relu', 'lrelu') and needs_w and bias_grad is not None and c_out == co_p == ld_out:
@@ -428,8 +412,7 @@ def deconv2d(x, kernel, bias, c_out, act=None, kernel_grad=None, bias_grad=None,
             else:
                 filter_grad(geom.deconv_wgrad(x.n, x.h, x.w, co_p, ci_p), dpre, x.t, 25, c_out, c_in, dw, defer=False)   # consumed right below
             if wn is not None:
-                with cx.on_side():
-                    _call('tg_wn_bwd_tab_f32', _p(dw), _p(kernel), _p(wn[0]), 25, c_out, c_in, _p(kernel_grad), _p(wn[1]), cx.stream)
+                _call('tg_wn_bwd_tab_f32', _p(dw), _p(kernel), _p(wn[0]), 25, c_out, c_in, _p(kernel_grad), _p(wn[1]), cx.stream)
         if needs_x:
             gx = cx.grad_of(x)
             if narrow and gx.ld >= ci_p:
@@ -538,7 +521,7 @@ def batch_norm_train(x, gamma, beta, mm, mv, eps, decay, gamma_grad=None, beta_g
             bsums, zdb = y.bn_bwd_sums[0], 2                # the launch that produced gy took the statistics in its epilogue (tg_igemm_bnbwdstat_*)
         else:
             bsums, zdb = cx.zscratch('bnb64', 32 * nseg * c)
-        sink = x.bias_sink if _BNACT else None
+        sink = x.bias_sink
         if sink is not None and x.ld == gx.ld and c % 4 == 0 and (c <= 256 and 256 % (c // 4) == 0 or c % 256 == 0):
             # x = act(conv + bias) of the layer in front (Act.bias_sink): this pass also multiplies by act'(x) and sums the columns — gx IS
             # that layer's pre-activation gradient and its bias gradient is done (no tg_actgrad_bias_f32 pass over the activation)
@@ -648,7 +631,7 @@ def _record_maxpool_bwd(cx, y, out, mask_t, mscale):
             fresh = y.grad is None
             gy = cx.grad_of(y)
             sink = y.grad_sink
-            if (_ACTSUM and sink is not None and fresh and y.c % 4 == 0 and y.c <= 512 and sum(sink[2]) == y.rows
+            if (sink is not None and fresh and y.c % 4 == 0 and y.c <= 512 and sum(sink[2]) == y.rows
                     and all(r % (y.h * y.w) == 0 for r in sink[2])):
                 # y is the output of a mean-only-BN layer: route, multiply by its activation derivative and sum the columns in one pass
                 nsg = len(sink[2])

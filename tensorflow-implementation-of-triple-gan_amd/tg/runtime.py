@@ -10,7 +10,6 @@ variable scopes and a Session there is ONE `Context` holding
 torch is used only as the device-buffer substrate (allocation, H2D copies, streams).
 """
 import contextlib
-import os
 import ctypes as C
 
 import numpy as np
@@ -226,7 +225,7 @@ class PhiloxRNG(object):
     # ---- per solver run -------------------------------------------------------------------------
     def begin_phase(self, ctx):
         key = (ctx.plan_tag, ctx.phase)
-        on = ctx.prep_cache is not None and os.environ.get('TG_RNG_MULTI', '1') != '0'   # only inside Train.train_iteration
+        on = ctx.prep_cache is not None                  # only inside Train.train_iteration
         self._plan = self.plans.get(key) if on else None
         self._rec = [] if (on and self._plan is None) else None
         self._cursor = 0
@@ -280,7 +279,6 @@ class PhiloxRNG(object):
 
 
 class Context(object):
-    side_fwd_only = os.environ.get('TG_SIDE_FWD_ONLY') == '1'
     capturing = False                                 # a hipGraph capture is open on the launch stream (Train._capture)
     _wgrad_side_pending = False                       # launches on the second stream not yet joined (wgrad_on_side)
 
@@ -291,30 +289,18 @@ class Context(object):
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         # a dedicated non-default stream: hipStream capture is illegal on the legacy null stream
-        # TG_STREAM_PRIO=1 (A/B): the launch stream above the second stream in the hardware queues' priority
-        prio = os.environ.get('TG_STREAM_PRIO') == '1'
-        self.torch_stream = torch.cuda.Stream(device=self.device, priority=-1) if prio else torch.cuda.Stream(device=self.device)
+        self.torch_stream = torch.cuda.Stream(device=self.device)
         torch.cuda.set_stream(self.torch_stream)
-        # Optional side stream for the small dependent chains that are off the critical path (weight-norm scale + filter re-layouts
-        # ahead of a convolution; slab reduce + weight-norm gradient behind a filter-gradient launch), forked from / joined to the
-        # main stream by events inside every phase_scope so that a hipGraph capture records them as parallel branches.
-        # MEASURED NEGATIVE (round 1, MI355X, ROCm 7.2): 5 571 images/s without it, 5 386 with the backward chains only, 5 403 with
-        # both — a captured graph with cross-stream edges replays slower than the single chain even though ~1 ms of small launches
-        # become concurrent.  OFF by default; TG_SIDE_STREAM=1 (forward + backward) or 2 (backward only) re-enables it.
-        self.side_stream = torch.cuda.Stream(device=self.device)
-        mode = os.environ.get('TG_SIDE_STREAM', '0')
-        self.use_side_stream = mode != '0'
-        self.side_forward = mode == '1'
-        # Round 3: second-stream overlap of EAGER launches (config.EXEC_MODE = 'overlap', switched on by Train.train_iteration): every
+        # Second-stream overlap of EAGER launches (config.EXEC_MODE = 'overlap', switched on by Train.train_iteration): every
         # filter-gradient launch of a backward pass runs on the side stream beside the input-gradient chain it does not feed (joined once
         # where the slabs are reduced, flush_tails; ops.filter_grad), and the D-update's generator forward beside the classifier's.  The
         # bandwidth-bound passes of one chain (mean-only-BN centring, pooling, activation gradients) then overlap the matrix kernels of the
         # other.  MEASURED (one MI355X, bench.py 100 steps, same box): eager one stream 14.96 ms, eager + overlap 14.59 ms; replayed
-        # hipGraphs 14.98 ms, hipGraphs captured WITH the cross-stream edges 15.37 ms — graphs stay a single chain.  TG_WGRAD_SIDE=0/1/2
-        # (off / small launches only / all) overrides for A/B runs.
-        self.wgrad_side_env = 'TG_WGRAD_SIDE' in os.environ                    # set: the environment decides (A/B runs), Train.train_iteration does not
-        self.wgrad_side = os.environ.get('TG_WGRAD_SIDE', '0') in ('1', '2')
-        self.wgrad_side_all = os.environ.get('TG_WGRAD_SIDE', '0') == '2'      # also the large (wgrad3x3) launches
+        # hipGraphs 14.98 ms, hipGraphs captured WITH the cross-stream edges 15.37 ms — graphs stay a single chain.
+        # (Round 1 measured a fork / join of the small off-critical-path chains inside every solver run instead: 5 571 images/s without
+        # it, 5 386 - 5 403 with it — a captured graph with cross-stream edges replays slower than the single chain.)
+        self.side_stream = torch.cuda.Stream(device=self.device)
+        self.wgrad_side = False
         self._wgrad_side_pending = False
         # fp64 statistics accumulators (fused mean-only BN / batch norm) of one solver run live in ONE arena per phase, zeroed by one
         # launch at the start of the phase instead of one memset per layer and direction (36 -> 3 launches per iteration)
@@ -330,7 +316,7 @@ class Context(object):
         self._zarena = {}              # phase -> dict(sizes=[...], buf=tensor or None, cursor=int, recording=bool)
         self._events = {}
         self._side_depth = 0
-        self._phase_depth = 0          # the side stream is only used between a phase's fork and join
+        self._phase_depth = 0          # the side stream is only used inside a solver run
         self.buffers = {}
         self.stores = {}
         self.tape = None
@@ -374,43 +360,6 @@ class Context(object):
         stream.wait_event(ev)
         if lib._recorder is not None:
             lib._recorder.add_wait(stream.cuda_stream, ev)
-
-    def _fork_side(self):
-        if self.use_side_stream:
-            ev = self._event('fork')
-            self._ev_record(ev, self.torch_stream)
-            self._ev_wait(self.side_stream, ev)
-
-    def _join_side(self):
-        if self.use_side_stream:
-            ev = self._event('join')
-            self._ev_record(ev, self.side_stream)
-            self._ev_wait(self.torch_stream, ev)
-
-    @contextlib.contextmanager
-    def on_side(self, after_main=False, forward=False):
-        """run the enclosed launches on the side stream (after_main: only after what the main stream has enqueued so far)."""
-        if not self.use_side_stream or self._side_depth or not self._phase_depth or (forward and not self.side_forward):
-            yield
-            return
-        if after_main:
-            ev = self._event('m2s')
-            self._ev_record(ev, self.torch_stream)
-            self._ev_wait(self.side_stream, ev)
-        self._side_depth += 1
-        torch.cuda.set_stream(self.side_stream)
-        try:
-            yield
-        finally:
-            torch.cuda.set_stream(self.torch_stream)
-            self._side_depth -= 1
-
-    def main_waits_side(self):
-        """the main stream continues only after what the side stream has enqueued so far."""
-        if self.use_side_stream and self.side_forward and not self._side_depth and self._phase_depth:
-            ev = self._event('s2m')
-            self._ev_record(ev, self.side_stream)
-            self._ev_wait(self.torch_stream, ev)
 
     # ---- workspace -------------------------------------------------------------------------------
     def ws(self, key, numel, zero=False):
@@ -513,7 +462,6 @@ class Context(object):
         self.phase, self.counter = name, counter
         self.tape = [] if record else None
         self.train_nets = set(train_nets)
-        self._fork_side()
         self._phase_depth += 1
         self._zarena_begin(resume=counter != 0)
         if counter == 0 and hasattr(self.rng, 'begin_phase'):
@@ -533,7 +481,6 @@ class Context(object):
                 self.rng.end_phase(self)
             self._zarena_end()
             self._phase_depth -= 1
-            self._join_side()
             self.phase, self.counter, self.tape, self.train_nets = prev
 
     @contextlib.contextmanager
@@ -663,12 +610,11 @@ class Context(object):
         return self._run_reverse(tape, stop_at_boundary)
 
     @contextlib.contextmanager
-    def wgrad_on_side(self, kind='wgrad'):
-        """run the enclosed filter-gradient launch on the side stream, after what the main stream has enqueued so far (its operands are
-        final); the main stream goes on with the input-gradient chain and waits for the side stream in join_wgrad_side().
-        kind = 'fwd': a forward chain (the D-update's generator forward).  Context.side_fwd_only (TG_SIDE_FWD_ONLY=1, A/B runs inside
-        captured graphs): only those go to the side stream — two cross-stream edges per iteration instead of one pair per filter gradient."""
-        if not self.wgrad_side or self._side_depth or not self._phase_depth or (self.side_fwd_only and kind != 'fwd'):
+    def wgrad_on_side(self):
+        """run the enclosed filter-gradient launch (or the D-update's generator forward) on the side stream, after what the main stream has
+        enqueued so far (its operands are final); the main stream goes on with the input-gradient chain and waits for the side stream in
+        join_wgrad_side()."""
+        if not self.wgrad_side or self._side_depth or not self._phase_depth:
             yield
             return
         ev = self._event('m2w')

@@ -16,7 +16,7 @@ ACT_TOL, GRAD_TOL = 1e-4, 1e-3
 def check_classifier_grad(name, got, ref):
     """The classifier's gradients on FIVE images: tight (GRAD_TOL of the largest element) unless a kink flipped.  The network is full of
     kinks (leaky-ReLU signs, max-pool arg-max); forward values agree with float64 to ~1e-6, and of the ~2 M activations a handful sit closer
-    to zero than that.  Measured (round 3, tests/debug/debug_split_nets.py): evaluating the SAME launches with the reduction of some tiles
+    to zero than that.  Measured (round 3, with and without the work-unit schedule's cut tiles): evaluating the SAME launches with the reduction of some tiles
     cut in K segments — values equal to 1e-6 — flipped lrelu'(y) for ONE element of conv2_2's output: that layer's b / g gradient moved in one
     channel (5.4e-2 of the largest element: a bias gradient is a sum over only 1 280 pixels here), its V gradient in that channel's 2 304
     entries, and every layer below by 5e-3 ... 9e-3.  So: GRAD_TOL, or — the flip budget — 6e-2 of the largest element and 2e-2 in L2 (the one moved element

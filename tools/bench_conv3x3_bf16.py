@@ -2,8 +2,7 @@
 """The classifier's 3x3 layers on the halo kernels (csrc/conv3x3_bf16.hip, csrc/wgrad3x3.hip), N = 250 images (TG_BENCH_N), standard-normal
 operands: TFLOP/s of tg_igemm_bf16 / tg_igemm_colsum_bf16 / tg_igemm_f32 (forward) and tg_wgrad_bf16 / tg_wgrad_f32 (filter gradient, pixel
 split from tg_wgrad_splits[_bf16]).  TG_BENCH_ONLY=<bf16|bf16_colsum|f32|wgrad_bf16|wgrad_f32> runs one of them; the generic kernels for
-comparison: TG_NO_CONV3X3_BF16=1 / TG_NO_CONV3X3_F32=1 / TG_NO_WGRAD3X3=1.  One JSON
-line per layer; bf16 fractions against 2 500 TFLOP/s dense bf16 (MI355X_MICROARCH.md)."""
+comparison: the same calls after lib.call('tg_conv3x3_policy', 2) (never the halo kernels).  One JSON line per layer; bf16 fractions against 2 500 TFLOP/s dense bf16 (MI355X_MICROARCH.md)."""
 import ctypes as C
 import json
 import os

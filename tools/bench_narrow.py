@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The generator's image layer backward on the vector ALUs (csrc/narrow.hip) at the CIFAR-10 step's shape: 100 images, 16x16x138 -> 32x32x3.
-Prints us per launch of tg_deconv5x5s2_narrow_dgrad_f32 and tg_deconv5x5s2_narrow_wgrad_f32 (TG_LIB selects an A/B build)."""
+Prints us per launch of tg_deconv5x5s2_narrow_dgrad_f32 and tg_deconv5x5s2_narrow_wgrad_f32."""
 import os
 import sys
 

@@ -2,10 +2,10 @@
 """Every launch shape of the CIFAR-10 step that the GENERIC MFMA kernels serve (igemm_f32_kernel / wgrad_f32_kernel: discriminator,
 generator, conv3 / NiN, ZCA, dense — profiles/rNN_launches.csv), timed one by one through the C ABI with the launch's own scratch.
 
-    python tools/bench_step_shapes.py [f32|bf16] [csv path]          TG_LIB=libtg_<tag>.so selects an A/B build of the library
+    python tools/bench_step_shapes.py [f32|bf16] [csv path]
 
-Prints per shape: ms, executed GFLOP, TFLOP/s, launches per step, and the per-step total — the A/B harness of kernel changes (the
-in-step times differ by cache state and by what runs beside them; the ORDER between builds carries over)."""
+Prints per shape: ms, executed GFLOP, TFLOP/s, launches per step, and the per-step total — run on two checkouts, it compares kernel
+changes (the in-step times differ by cache state and by what runs beside them; the ORDER between builds carries over)."""
 import os
 import sys
 import torch
