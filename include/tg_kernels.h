@@ -86,8 +86,8 @@ typedef struct tg_igemm_desc {
 /* Scratch of the MFMA launches (every tg_igemm_* entry point takes `scratch, scratch_bytes` in front of `stream`): device memory the
  * launch may overwrite, OWNED BY THE CALLER — the library never allocates device memory — 16-byte aligned, free for reuse once the launch
  * has completed on `stream` (launches on concurrent streams need their own).  tg_igemm_workspace_bytes answers, on the host, how much a
- * launch of these descriptors can use (seg_rows / nseg as passed to tg_igemm_colsum_* / _actsum_*, nseg = 0 otherwise; bf16: the
- * *_bf16 entry point; < 0 on a bad descriptor).  Two users:
+ * launch of these descriptors can use (seg_rows / nseg as passed to tg_igemm_colsum_* / _actsum_*, nseg = 0 otherwise; bf16: 1 for the
+ * *_bf16 entry point, 2 for the *_bf16in_bf16 one, 0 otherwise; < 0 on a bad descriptor).  Two users:
  *   - the generic kernel cuts the tiles of the last partial round of resident workgroups (1 128 tiles on 512 slots), of an under-filled
  *     launch (225 tiles) or of the long sub-problems of a stride-2 launch (9 / 6 / 6 / 4 taps) along K; the partial sums pass through the
  *     scratch and a second launch adds them up in a fixed order (deterministic) and runs the epilogue.  OPTIONAL: with scratch == NULL or
@@ -175,6 +175,17 @@ int tg_igemm_multi_bf16(const tg_igemm_desc* descs, int n_desc, const float* in,
 int tg_igemm_colsum_bf16(const tg_igemm_desc* d, const float* in, const float* w, float* out, const int32_t* seg_rows, int nseg,
                          double* colsum, int colsum_zeroed, void* scratch, int64_t scratch_bytes, void* stream);
 int tg_wgrad_bf16(const tg_igemm_desc* d, const float* in, const float* dout, float* slab, int n_split, void* stream);
+/* The same bf16 MFMA launches with the gathered activation `in` STORED as bf16 ([n_img,h_in,w_in,ld_in] of 2-byte elements, written by
+ * tg_bn_train[_apply]_bf16): the operands reach LDS without conversion, so every MFMA operand — and the result — is bit-identical to the
+ * fp32-input *_bf16 launch on an fp32 tensor whose values round to these bf16s.  Scratch (igemm forms): tg_igemm_workspace_bytes(...,
+ * bf16 = 2).  Served for every layer of the halo kernels' shape (3x3 / stride 1 / SAME, width 16 / 32 / 64, 64 | ld_in, 128 | c_out):
+ * the halo forward (its leading images when a launch is cut; the rest, and layers it does not take, widen their input into the scratch
+ * and run the generic kernel) and wgrad3x3 for the filter gradient at any n_split; another shape is TG_ERR_INVALID. */
+int tg_igemm_bf16in_bf16(const tg_igemm_desc* d, const void* in, const float* w, const float* bias, float* out, void* scratch, int64_t scratch_bytes,
+                         void* stream);
+int tg_igemm_bnstat_bf16in_bf16(const tg_igemm_desc* d, const void* in, const float* w, const float* bias, float* out, const int32_t* seg_rows, int nseg,
+                                double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream);
+int tg_wgrad_bf16in_bf16(const tg_igemm_desc* d, const void* in, const float* dout, float* slab, int n_split, void* stream);
 
 /* 3x3 / stride 1 / SAME convolution of FEW input channels (c_in <= 16; the discriminators' first layer: 3 image + 10 label channels -> 32,
  * Model/Good_GAN_cifar10.py:63-66, Model/Good_GAN.py:129-132; tf.layers.conv2d, Model/modle_base.py:157-168) as K-PACKED fp32 MFMA products:
@@ -379,6 +390,17 @@ int tg_bn_train_f32(const float* x, int ld_x, float* y, int ld_y, int rows, int 
 int tg_bn_train_apply_f32(const float* x, int ld_x, float* y, int ld_y, int rows, int c, const int32_t* seg_rows, int nseg, const float* gamma,
                           const float* beta, float eps, float decay, float* moving_mean, float* moving_var, const double* sums, float* mean_inv,
                           void* stream);
+/* tg_bn_train_f32 / tg_bn_train_apply_f32 storing y as bf16 (config.ACT_DTYPE = 'bf16'): y is computed by the same expression as the
+ * fp32 form and rounded to nearest even on the store, 8 bytes per four columns; ld_y counts bf16 elements, y must be 8-byte aligned.
+ * Statistics, mean_inv and the moving statistics are those of the fp32 form, bit for bit.  For a batch norm whose output only feeds
+ * the bf16-input convolutions below (tg_igemm_bf16in_bf16 / tg_igemm_bnstat_bf16in_bf16 / tg_wgrad_bf16in_bf16), which would round
+ * each fp32 value to exactly these bits on their way into LDS. */
+int tg_bn_train_bf16(const float* x, int ld_x, void* y, int ld_y, int rows, int c, const int32_t* seg_rows, int nseg, const float* gamma,
+                     const float* beta, float eps, float decay, float* moving_mean, float* moving_var, double* sums, int sums_zeroed, float* mean_inv,
+                     void* stream);
+int tg_bn_train_apply_bf16(const float* x, int ld_x, void* y, int ld_y, int rows, int c, const int32_t* seg_rows, int nseg, const float* gamma,
+                           const float* beta, float eps, float decay, float* moving_mean, float* moving_var, const double* sums, float* mean_inv,
+                           void* stream);
 /* One more moving-statistics update from the batch sums a tg_bn_train_f32 launch left in `sums` (same seg_rows / nseg / c / decay; the
  * buffer must not have been cleared since): what TensorFlow does when a later sess.run re-executes the same training-mode batch norm on
  * the same feed and weights (tf.contrib.layers.batch_norm, updates_collections=None, Model/modle_base.py:229-237) while this build

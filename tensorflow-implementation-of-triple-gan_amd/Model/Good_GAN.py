@@ -206,11 +206,12 @@ class Good_GAN(model_base.NN_Base):
         cx = ctx()
         lre = self._leaky_relu
 
-        def cbr(x, cname, bname, cout, k=3):
-            # conv -> leaky relu -> batch norm: in training the batch-norm statistics are taken in the convolution's epilogue
+        def cbr(x, cname, bname, cout, k=3, bf16_out=False):
+            # conv -> leaky relu -> batch norm: in training the batch-norm statistics are taken in the convolution's epilogue.
+            # bf16_out: the next layer is a 3x3 / stride-1 convolution and nothing else reads the batch norm's output (config.ACT_DTYPE)
             x = self._conv2d(x, cout, k_h=k, k_w=k, d_h=1, d_w=1, name=cname, activation=lre,
                              bn_segments=(segments or [x.n]) if train_ph else None)
-            return self._batch_norm_contrib(x, name=bname, train=train_ph, segments=segments)
+            return self._batch_norm_contrib(x, name=bname, train=train_ph, segments=segments, bf16_out=bf16_out)
 
         def pool_drop(x, key):
             mask = cx.rng.keep_mask(cx, key, x.rows // 4 * x.c, 0.5) if train_ph else None
@@ -231,12 +232,12 @@ class Good_GAN(model_base.NN_Base):
             else:                                                                                  # :249-299
                 image = self._drop_out(image, 0.2, train_ph, name='drop0')
                 x = ops.im2col3x3_add(image, None)
-                x = cbr(x, 'c_h0_conv0', 'c_h0_bn0', 128, k=1)
-                x = cbr(x, 'c_h0_conv1', 'c_h0_bn1', 128)
+                x = cbr(x, 'c_h0_conv0', 'c_h0_bn0', 128, k=1, bf16_out=True)
+                x = cbr(x, 'c_h0_conv1', 'c_h0_bn1', 128, bf16_out=True)
                 x = cbr(x, 'c_h0_conv2', 'c_h0_bn2', 128)
                 x = pool_drop(x, 'drop1')
-                x = cbr(x, 'c_h1_conv0', 'c_h1_bn0', 256)
-                x = cbr(x, 'c_h1_conv1', 'c_h1_bn1', 256)
+                x = cbr(x, 'c_h1_conv0', 'c_h1_bn0', 256, bf16_out=True)
+                x = cbr(x, 'c_h1_conv1', 'c_h1_bn1', 256, bf16_out=True)
                 x = cbr(x, 'c_h1_conv2', 'c_h1_bn2', 256)
                 x = pool_drop(x, 'drop2')
                 x = cbr(x, 'c_h2_conv0', 'c_h2_bn0', 512)

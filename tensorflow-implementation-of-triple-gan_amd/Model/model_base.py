@@ -104,10 +104,12 @@ class NN_Base(object):
                                 kernel_grad=cx.var_grad('kernel') if tr else None, bias_grad=cx.var_grad('bias') if tr else None,
                                 narrow_out=narrow)
 
-    def _batch_norm_contrib(self, x, name, train=False, segments=None):
+    def _batch_norm_contrib(self, x, name, train=False, segments=None, bf16_out=False):
         """tf.contrib.layers.batch_norm(decay, eps, scale=True, updates_collections=None) (modle_base.py:229-237).
         train=True: batch statistics, moving statistics updated in place; train=False: moving statistics.
-        segments (extension): image counts of the applications batched into x — statistics per application."""
+        segments (extension): image counts of the applications batched into x — statistics per application.
+        bf16_out (extension): the output's only reader is a bf16-operand 3x3 convolution — in training it is stored as bf16 when
+        config.ACT_DTYPE = 'bf16' (ops.batch_norm_train(out_bf16=True)); evaluation stays fp32."""
         cx = ctx()
         with cx.variable_scope(name):
             if not train:
@@ -117,7 +119,7 @@ class NN_Base(object):
             return ops.batch_norm_train(x, cx.var('gamma'), cx.var('beta'), cx.var('moving_mean'), cx.var('moving_variance'),
                                         self._batch_norm_epsilon, self._batch_norm_decay,
                                         gamma_grad=cx.var_grad('gamma') if tr else None, beta_grad=cx.var_grad('beta') if tr else None,
-                                        segments=segments)
+                                        segments=segments, out_bf16=bf16_out)
 
     def _WN_dense(self, input_, output_size, scope, init_scale=1.0, init=False, activation=None, narrow=False):
         """g * (x @ l2_normalize(V,[0])) + b (modle_base.py:50-73; the data-dependent init branch is never taken)."""

@@ -29,6 +29,18 @@ from tg.batching import concat_acts
 from tg.runtime import Act, Context, PhiloxRNG, ctx, set_context
 
 
+def check_act_dtype(config):
+    """config.ACT_DTYPE ('f32' default | 'bf16') checked against config.MFMA_DTYPE: bf16-stored activations are only the same numbers when
+    every reader rounds its operands to bf16 anyway — with fp32 MFMA operands they would silently stop being the reference's arithmetic."""
+    act = getattr(config, 'ACT_DTYPE', 'f32')
+    if act not in ('f32', 'bf16'):
+        raise ValueError("ACT_DTYPE must be 'f32' or 'bf16', got %r" % (act,))
+    if act == 'bf16' and getattr(config, 'MFMA_DTYPE', 'f32') != 'bf16':
+        raise ValueError("ACT_DTYPE = 'bf16' needs MFMA_DTYPE = 'bf16' (got %r): fp32 products of bf16-stored values would not be the "
+                         "fp32 arithmetic of the reference" % (getattr(config, 'MFMA_DTYPE', 'f32'),))
+    return act
+
+
 class Train(Train_base):
     def __init__(self, config, log_dir, save_dir, **kwargs):
         super(Train, self).__init__()
@@ -47,6 +59,9 @@ class Train(Train_base):
         cx.mfma_dtype = getattr(config, 'MFMA_DTYPE', 'f32')
         if cx.mfma_dtype not in ('f32', 'bf16'):
             raise ValueError("MFMA_DTYPE must be 'f32' or 'bf16', got %r" % (cx.mfma_dtype,))
+        # 'bf16': the batch norms the model marks store their output as bf16 — same numbers, half the bytes (Context.act_dtype)
+        cx.act_dtype = check_act_dtype(config)
+        cx.bf16_act_layers = set()
         # device-resident hyper-parameters (the reference's lr_ph / cla_lr_ph / lambda placeholders, :30-31,416-420)
         self.hyper = torch.zeros(4, dtype=torch.float32, device=cx.device)       # lr, cla_lr, lambda_1, lambda_2
         self.loss_dev = torch.zeros(3, dtype=torch.float32, device=cx.device)    # d_loss, g_loss, c_loss
@@ -63,6 +78,12 @@ class Train(Train_base):
             from Training.Summary import Summary
             self.summary_train = Summary(log_dir, config, log_type='train', log_comments=kwargs.get('comments', ''))
             self.summary_val = Summary(log_dir, config, log_type='val', log_comments=kwargs.get('comments', ''))
+
+    @property
+    def bf16_act_edges(self):
+        """how many batch-norm outputs this trainer's step stores as bf16 (config.ACT_DTYPE = 'bf16'; 0 with 'f32' or on a model with no
+        eligible edge, e.g. Good_GAN_cifar10) — counted per layer, after the first iteration."""
+        return len(self.cx.bf16_act_layers)
 
     # ------------------------------------------------------------------ graph build
     def _build_train_graph(self, Model):

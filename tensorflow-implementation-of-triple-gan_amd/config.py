@@ -58,6 +58,10 @@ class Config(object):
                              # 'graph': hipGraph replay (single chain); 'eager': eager launches on one stream
     ZCA = None               # (mean, mat) arrays when DATA_DIR holds no cifar10_zca_*.npy
     MFMA_DTYPE = 'f32'       # 'bf16': conv/deconv/dense operands rounded to bf16 inside the MFMA kernels (fp32 accumulate)
+    ACT_DTYPE = 'f32'        # 'bf16' (needs MFMA_DTYPE = 'bf16', else ValueError): the training-mode batch norms whose only reader is a
+                             # bf16-operand 3x3 convolution store their output as bf16 (the SVHN classifier's c_h0_bn0/bn1, c_h1_bn0/bn1) —
+                             # the bits that convolution would round it to, so the step is bit-identical with half the bytes on those
+                             # edges; Train.bf16_act_edges counts them (0 on a model without such an edge: the switch changes nothing)
 
     def __init__(self):
         """Set values of computed attributes (config.py:70-73)."""

@@ -86,6 +86,7 @@ struct ConvParams {
   uint32_t in_bytes, w_bytes, out_bytes;
   const void* wpk;                             // bf16 filter packed as consecutive LDS images (filter_pack_kernel) — conv3x3_pipe_kernel<.., BF16 = true>
   int f32;                                     // 1: exact-fp32 operands (conv3x3_pipe_kernel<..., BF16 = false>)
+  int in16;                                    // 1: `in` is stored as bf16 (tg_*_bf16in_bf16): the halo goes global -> LDS without conversion
   int stat2;                                   // COLSUM launches: 2 = the output is a gradient dy, colsum[seg][0][c] += dy, colsum[seg][1][c] += dy * ymul (tg_igemm_bnbwdstat_*); 1 = statistics of the ACTIVATED output act(acc + bias): colsum[seg][0][c] += v, colsum[seg][1][c] += v*v (batch norm behind the layer)
 };
 
@@ -160,9 +161,10 @@ __device__ __forceinline__ void barrier_keep() { asm volatile("s_waitcnt vmcnt(%
 // Tile order: XCD x (= blockIdx & 7) owns a contiguous eighth of the tiles (neighbouring tiles share halo rows and all share the filter
 // in that XCD's L2); its 32 workgroups stride through it.
 // ---------------------------------------------------------------------------------------------------------------------------------
-template <int W, bool COLSUM, bool BF16, bool STAT2 = false>
+template <int W, bool COLSUM, bool BF16, bool STAT2 = false, bool IN16 = false>
 __global__ void __launch_bounds__(512, 2) conv3x3_pipe_kernel(ConvParams p) {
   static_assert(!STAT2 || COLSUM, "STAT2 is a COLSUM mode");
+  static_assert(!IN16 || BF16, "a bf16-stored input feeds bf16 operands only");
   constexpr int BM = 256, TPS = 3, NG = 3;
   constexpr int KCH = BF16 ? 64 : 32;
   constexpr int UPR = BF16 ? 16 : 8;
@@ -216,7 +218,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pipe_kernel(ConvParams p) {
         const int hy = hp / HW_, hx = hp - hy * HW_;
         const int iy = row0 + hy - 1, ix = hx - 1;
         const bool ok = hp < HP && (unsigned)iy < (unsigned)p.h && (unsigned)ix < (unsigned)W;
-        a_voff[i] = ok ? (uint32_t)(((img * p.h + iy) * W + ix) * p.ld_in + 4 * qu) * 4u : OOB;
+        a_voff[i] = ok ? (uint32_t)(((img * p.h + iy) * W + ix) * p.ld_in + 4 * qu) * (IN16 ? 2u : 4u) : OOB;
       }
     };
     int nt_b = 0, bbuf_w = 0;                                   // filter column tile the fetches read; filter buffer the next fetch fills
@@ -226,17 +228,26 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pipe_kernel(ConvParams p) {
     };
     // The next halo waits in registers from step g = 1 (loads issued, after that step's filter group has been written, so that the two
     // register images are never live together) to the end of step g = 2; with bf16 operands it is packed at the top of step 2
-    // (88 -> 44 registers) before that step's filter loads take their 96.
-    u32x4 ra[A_IT], rb[BF16 ? 1 : TPS * B_IT];
+    // (88 -> 44 registers) before that step's filter loads take their 96.  A bf16-stored input (IN16) is loaded as it goes to LDS — four
+    // channels per 8-byte load, the same A_IT loads per halo as the fp32 form (so the loads-in-flight counts of barrier_keep hold) — straight
+    // into the 44 registers of the packed image: nothing to convert, the fp32 staging registers are not needed.
+    u32x4 ra[IN16 ? 1 : A_IT], rb[BF16 ? 1 : TPS * B_IT];
     u32x2 rap[BF16 ? A_IT : 1];
     auto gload_a = [&](int c0) {
-      const uint32_t so = (uint32_t)__builtin_amdgcn_readfirstlane(c0 * 4);
+      if constexpr (IN16) {
+        const uint32_t so = (uint32_t)__builtin_amdgcn_readfirstlane(c0 * 2);
 #pragma unroll
-      for (int i = 0; i < A_IT; ++i)
-        ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, a_voff[i], so, 0);
+        for (int i = 0; i < A_IT; ++i)
+          rap[i] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_in, a_voff[i], so, 0));
+      } else {
+        const uint32_t so = (uint32_t)__builtin_amdgcn_readfirstlane(c0 * 4);
+#pragma unroll
+        for (int i = 0; i < A_IT; ++i)
+          ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, a_voff[i], so, 0);
+      }
     };
     auto pack_a = [&]() {
-      if constexpr (BF16) {
+      if constexpr (BF16 && !IN16) {
 #pragma unroll
         for (int i = 0; i < A_IT; ++i) rap[i] = pack4(ra[i]);
       }
@@ -693,7 +704,10 @@ template <int W>
 void launch_pipe(ConvParams& p, hipStream_t s) {
   const int tiles = p.n_tiles_m * p.n_tiles_n, cus = compute_units();
   const dim3 grid(tiles < cus ? tiles : cus);                  // one resident workgroup per CU (LDS), each walking its share of the tiles
-  if (p.f32) {
+  if (p.in16) {                                                 // (the igemm entry points of a bf16-stored input: plain and batch-norm statistics)
+    if (p.colsum && p.stat2) hipLaunchKernelGGL((conv3x3_pipe_kernel<W, true, true, true, true>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((conv3x3_pipe_kernel<W, false, true, false, true>), grid, dim3(512), 0, s, p);
+  } else if (p.f32) {
     if (p.colsum && p.stat2) hipLaunchKernelGGL((conv3x3_pipe_kernel<W, true, false, true>), grid, dim3(512), 0, s, p);
     else if (p.colsum) hipLaunchKernelGGL((conv3x3_pipe_kernel<W, true, false>), grid, dim3(512), 0, s, p);
     else hipLaunchKernelGGL((conv3x3_pipe_kernel<W, false, false>), grid, dim3(512), 0, s, p);
@@ -786,9 +800,12 @@ int64_t conv3x3_bf16_pack_bytes(const tg_igemm_desc* d, int n_desc) {
 
 int conv3x3_bf16_launch(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, double* colsum,
                         const int32_t* seg_rows, int nseg, const float* ymul, int ymul_act, float ymul_alpha, uint32_t in_bytes, uint32_t w_bytes,
-                        uint32_t out_bytes, hipStream_t s, bool bf16, void* scratch, int64_t scratch_bytes, int stat2) {
+                        uint32_t out_bytes, hipStream_t s, bool bf16, void* scratch, int64_t scratch_bytes, int stat2, bool in16) {
+  TG_REQUIRE(!in16 || (bf16 && (colsum == nullptr || stat2 == 1) && ymul == nullptr),
+             "conv3x3: a bf16-stored input is served for the bf16 forward and its batch-norm statistics form only");
   ConvParams p;
   p.stat2 = stat2;
+  p.in16 = in16 ? 1 : 0;
   p.in = in; p.w = w; p.bias = bias; p.out = out; p.colsum = colsum; p.ymul = ymul; p.ymul_act = ymul_act; p.ymul_alpha = ymul_alpha;
   p.nseg = nseg;
   for (int i = 0; i < 8; ++i) p.seg_rows[i] = (seg_rows && i < nseg) ? seg_rows[i] : 0;

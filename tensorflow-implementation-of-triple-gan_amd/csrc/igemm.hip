@@ -1032,6 +1032,17 @@ int check_desc(const tg_igemm_desc* d) {
 
 }  // namespace
 
+// A bf16-stored input (tg_igemm_*bf16in_bf16) on the images the halo kernel does not take: widened to fp32 in the caller's scratch (exact), then
+// the generic bf16 kernel rounds each value back to the same bf16 on its way into LDS — the operands are the stored bits.
+__global__ void __launch_bounds__(256) widen_bf16_kernel(const uint2* __restrict__ in, float4* __restrict__ out, int64_t n4) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const uint2 v = in[i];
+    out[i] = make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
+  }
+}
+
+static int64_t widen_bytes(const tg_igemm_desc* d) { return ((int64_t)d->n_img * d->h_in * d->w_in * d->ld_in * 4 + 255) / 256 * 256; }
+
 template <int BM, int BN, int WM_, int WN_>
 static void launch_igemm(IgemmParams& p, hipStream_t s, bool bf16) {
   const dim3 grid(p.n_units);               // one workgroup per work unit (tg::igemm_schedule); the last column tile may overhang: filter rows >= c_out read zeros / unused data, stores are masked by n_store
@@ -1077,7 +1088,7 @@ static int head_tail(const tg_igemm_desc* descs, int n_desc, const int32_t* seg_
 static int igemm_impl(const tg_igemm_desc* descs, int n_desc, const float* in, const float* w, const float* bias, float* out, void* stream,
                       double* colsum, const int32_t* seg_rows, int nseg, bool bf16 = false, const float* ymul = nullptr, int ymul_act = 0,
                       float ymul_alpha = 0.f, void* scratch = nullptr, int64_t scratch_bytes = 0, int stat2 = 0, const float* lab = nullptr,
-                      int lab_n = 0) {
+                      int lab_n = 0, bool in16 = false) {
   TG_REQUIRE(descs && n_desc >= 1 && n_desc <= MAX_SUB, "igemm: n_desc=%d out of range", n_desc);
   TG_REQUIRE(in && w && out, "igemm: null buffer");
   if (lab) {
@@ -1090,15 +1101,35 @@ static int igemm_impl(const tg_igemm_desc* descs, int n_desc, const float* in, c
   // A 3x3 layer of the halo kernel's shape whose launch does not fill whole rounds of one workgroup per CU (conv3x3_bf16.hip): the leading
   // images that do go to that kernel, the few left over to the generic one — two launches over disjoint image ranges of the same buffers
   // (the column sums of both accumulate into the same per-segment accumulators).
+  TG_REQUIRE(!in16 || (bf16 && !lab && !ymul && n_desc == 1), "igemm: a bf16-stored input is served for one bf16 sub-problem without labels / multiplier");
   HeadTail ht;
   if (const int head = lab ? 0 : head_tail(descs, n_desc, seg_rows, nseg, colsum != nullptr, bf16, &ht)) {
     const int64_t per_img = (int64_t)descs[0].h_in * descs[0].w_in;
-    int rc = igemm_impl(&ht.dh, 1, in, w, bias, out, stream, colsum, colsum ? ht.seg_h : nullptr, ht.nh, bf16, ymul, ymul_act, ymul_alpha, scratch, scratch_bytes, stat2);
+    int rc = igemm_impl(&ht.dh, 1, in, w, bias, out, stream, colsum, colsum ? ht.seg_h : nullptr, ht.nh, bf16, ymul, ymul_act, ymul_alpha, scratch, scratch_bytes, stat2,
+                        nullptr, 0, in16);
     if (rc != TG_OK) return rc;
     const int64_t o_in = (int64_t)head * per_img * descs[0].ld_in, o_out = (int64_t)head * per_img * descs[0].ld_out;
+    const float* in_t = reinterpret_cast<const float*>(reinterpret_cast<const char*>(in) + o_in * (in16 ? 2 : 4));
     // (the tail is stream-ordered behind the head: both may use the same scratch)
-    return igemm_impl(&ht.dt, 1, in + o_in, w, bias, out + o_out, stream, colsum ? colsum + (int64_t)ht.k0 * descs[0].c_out * (stat2 ? 2 : 1) : nullptr,
-                      colsum ? ht.seg_t : nullptr, ht.nt, bf16, ymul ? ymul + o_out : nullptr, ymul_act, ymul_alpha, scratch, scratch_bytes, stat2);
+    return igemm_impl(&ht.dt, 1, in_t, w, bias, out + o_out, stream, colsum ? colsum + (int64_t)ht.k0 * descs[0].c_out * (stat2 ? 2 : 1) : nullptr,
+                      colsum ? ht.seg_t : nullptr, ht.nt, bf16, ymul ? ymul + o_out : nullptr, ymul_act, ymul_alpha, scratch, scratch_bytes, stat2, nullptr, 0,
+                      in16);
+  }
+  if (in16 && !tg::conv3x3_bf16_applicable(descs, n_desc, seg_rows, colsum ? nseg : 0, bf16)) {
+    // images the halo kernel does not take: widen them into the front of the scratch, the generic kernel's cut tiles use the rest
+    TG_REQUIRE(check_desc(&descs[0]) == TG_OK, "igemm: bad descriptor");
+    const int64_t wb = widen_bytes(&descs[0]);
+    TG_REQUIRE(scratch != nullptr && scratch_bytes >= wb && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0,
+               "igemm (bf16-stored input): this launch needs %lld bytes of 16-byte aligned scratch to widen its input, got %lld (query "
+               "tg_igemm_workspace_bytes(..., bf16 = 2))", (long long)wb, (long long)(scratch ? scratch_bytes : 0));
+    const int64_t n4 = (int64_t)descs[0].n_img * descs[0].h_in * descs[0].w_in * descs[0].ld_in / 4;
+    const int64_t nb = (n4 + 255) / 256;
+    hipLaunchKernelGGL(widen_bf16_kernel, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, tg::as_stream(stream), reinterpret_cast<const uint2*>(in),
+                       static_cast<float4*>(scratch), n4);
+    TG_CHECK_LAUNCH("widen_bf16_kernel");
+    char* rest = static_cast<char*>(scratch) + wb;
+    return igemm_impl(descs, n_desc, static_cast<const float*>(scratch), w, bias, out, stream, colsum, seg_rows, nseg, bf16, ymul, ymul_act, ymul_alpha,
+                      scratch_bytes > wb ? rest : nullptr, scratch_bytes - wb, stat2);
   }
   IgemmParams p;
   p.in = in; p.w = w; p.bias = bias; p.out = out; p.n_sub = n_desc;
@@ -1149,7 +1180,7 @@ static int igemm_impl(const tg_igemm_desc* descs, int n_desc, const float* in, c
   double taps = 0;
   for (int i = 0; i < n_desc; ++i) taps += descs[i].n_taps;
   const double flops = 2.0 * p.M * d->c_out * taps * d->ld_in;
-  const double bytes = 4.0 * ((double)p.M * d->ld_in + (double)p.M * d->n_store * n_desc + (double)d->c_out * taps * d->ld_in);
+  const double bytes = (in16 ? 2.0 : 4.0) * p.M * d->ld_in + 4.0 * ((double)p.M * d->n_store * n_desc + (double)d->c_out * taps * d->ld_in);
   hipStream_t s = tg::as_stream(stream);
   const bool halo = !lab && tg::conv3x3_bf16_applicable(descs, n_desc, seg_rows, colsum ? nseg : 0, bf16);      // the classifier's 3x3 layers: halo-tiled kernel (both operand types)
   // tile choice by the quantisation cost model of geom.cpp (tg::igemm_pick_tile; also behind tg_igemm_tile / tg_igemm_colsum_supported)
@@ -1174,8 +1205,8 @@ static int igemm_impl(const tg_igemm_desc* descs, int n_desc, const float* in, c
            d->w_in, d->s_y, d->os_y, bf16 ? " bf16" : "", bm, bn, sc.n_units, sc.n_fix, sc.ks[0], sc.ks[1], sc.ks[2], sc.ks[3]);
   tg::ProfScope prof(tg::PC_IGEMM, flops, bytes, s, desc);
   if (halo)
-    return tg::conv3x3_bf16_launch(d, in, w, bias, out, colsum, seg_rows, nseg, ymul, ymul_act, ymul_alpha, p.in_bytes, p.w_bytes, p.out_bytes, s, bf16,
-                                   scratch, scratch_bytes, stat2);
+    return tg::conv3x3_bf16_launch(d, in, w, bias, out, colsum, seg_rows, nseg, ymul, ymul_act, ymul_alpha, in16 ? p.in_bytes / 2 : p.in_bytes, p.w_bytes,
+                                   p.out_bytes, s, bf16, scratch, scratch_bytes, stat2, in16);
   p.n_units = sc.n_units; p.n_fix = sc.n_fix; p.nfull = sc.nfull; p.pat_len = sc.pat_len; p.n_pat_split = sc.n_pat_split; p.n_split_sub = sc.n_split_sub;
   for (int i = 0; i < MAX_SUB; ++i) { p.ks[i] = sc.ks[i]; p.split_sub[i] = sc.split_sub[i]; p.first_slot[i] = sc.first_slot[i]; }
   for (int i = 0; i < 16; ++i) { p.pat_sub[i] = sc.pat_sub[i]; p.pat_k[i] = sc.pat_k[i]; p.pat_slot[i] = sc.pat_slot[i]; }
@@ -1227,15 +1258,16 @@ extern "C" int tg_igemm_labels_bf16(const tg_igemm_desc* d, const float* in, con
 // scratch a launch of these descriptors can use: the larger of the halo kernel's packed bf16 filter (REQUIRED by such a launch) and the
 // partial sums of the tiles the generic kernel's schedule cuts along K (optional: with less the launch runs as one unit per tile);
 // a launch that is cut into a halo head and a generic tail uses the scratch for one after the other.  Mirrors the routing of igemm_impl.
-static int64_t igemm_ws_bytes(const tg_igemm_desc* descs, int n_desc, const int32_t* seg_rows, int nseg, bool bf16) {
+static int64_t igemm_ws_bytes(const tg_igemm_desc* descs, int n_desc, const int32_t* seg_rows, int nseg, bool bf16, bool in16 = false) {
   const bool colsum = nseg > 0;
   HeadTail ht;
   if (head_tail(descs, n_desc, seg_rows, nseg, colsum, bf16, &ht)) {
-    const int64_t a = igemm_ws_bytes(&ht.dh, 1, colsum ? ht.seg_h : nullptr, ht.nh, bf16);
-    const int64_t b = igemm_ws_bytes(&ht.dt, 1, colsum ? ht.seg_t : nullptr, ht.nt, bf16);
+    const int64_t a = igemm_ws_bytes(&ht.dh, 1, colsum ? ht.seg_h : nullptr, ht.nh, bf16, in16);
+    const int64_t b = igemm_ws_bytes(&ht.dt, 1, colsum ? ht.seg_t : nullptr, ht.nt, bf16, in16);
     return a > b ? a : b;
   }
   if (tg::conv3x3_bf16_applicable(descs, n_desc, seg_rows, colsum ? nseg : 0, bf16)) return bf16 ? tg::conv3x3_bf16_pack_bytes(descs, n_desc) : 0;
+  if (in16) return widen_bytes(&descs[0]) + igemm_ws_bytes(descs, n_desc, seg_rows, nseg, bf16, false);      // widened input in front (igemm_impl)
   int bm = 0, bn = 0;
   if (!tg::igemm_pick_tile(descs, n_desc, colsum, seg_rows, nseg, bf16, &bm, &bn)) return 0;
   int order[MAX_SUB] = {0, 1, 2, 3}, nk[MAX_SUB] = {0, 0, 0, 0};
@@ -1251,7 +1283,7 @@ extern "C" int64_t tg_igemm_workspace_bytes(const tg_igemm_desc* descs, int n_de
   if (!descs || n_desc < 1 || n_desc > MAX_SUB || nseg < 0 || nseg > 8 || (nseg > 0 && !seg_rows)) { tg::set_error("igemm_workspace_bytes: bad arguments"); return TG_ERR_INVALID; }
   for (int i = 0; i < n_desc; ++i)
     if (descs[i].ld_in <= 0 || descs[i].c_out <= 0 || descs[i].n_taps <= 0 || descs[i].n_taps > TG_MAX_TAPS || descs[i].n_img <= 0) { tg::set_error("igemm_workspace_bytes: bad descriptor"); return TG_ERR_INVALID; }
-  return igemm_ws_bytes(descs, n_desc, seg_rows, nseg, bf16 != 0);
+  return igemm_ws_bytes(descs, n_desc, seg_rows, nseg, bf16 != 0, bf16 == 2);
 }
 
 static int igemm_colsum_impl(const tg_igemm_desc* d, const float* in, const float* w, float* out, const int32_t* seg_rows, int nseg,
@@ -1282,7 +1314,7 @@ extern "C" int tg_igemm_colsum_bf16(const tg_igemm_desc* d, const float* in, con
 
 // conv + bias + activation whose output feeds a batch norm: the statistics of the ACTIVATED output are taken in the epilogue
 static int igemm_bnstat_impl(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, const int32_t* seg_rows, int nseg,
-                             double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream, bool bf16) {
+                             double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream, bool bf16, bool in16 = false) {
   TG_REQUIRE(d && sums && seg_rows && nseg >= 1 && nseg <= 8, "igemm_bnstat: bad args");
   TG_REQUIRE(d->n_group == 0, "igemm_bnstat: grouped columns are not supported");
   TG_REQUIRE(d->act == TG_ACT_NONE || d->act == TG_ACT_RELU || d->act == TG_ACT_LRELU, "igemm_bnstat: activation %d is not none / relu / leaky relu", d->act);
@@ -1293,7 +1325,32 @@ static int igemm_bnstat_impl(const tg_igemm_desc* d, const float* in, const floa
     hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * 8 * 2 * nseg * d->c_out, tg::as_stream(stream));      // all eight replicas of the batch norm's buffer
     if (e != hipSuccess) return tg::hip_fail(e, "hipMemsetAsync(bn statistics)");
   }
-  return igemm_impl(d, 1, in, w, bias, out, stream, sums, seg_rows, nseg, bf16, nullptr, 0, 0.f, scratch, scratch_bytes, 1);
+  return igemm_impl(d, 1, in, w, bias, out, stream, sums, seg_rows, nseg, bf16, nullptr, 0, 0.f, scratch, scratch_bytes, 1, nullptr, 0, in16);
+}
+
+// the gathered activation is stored as bf16 (include/tg_kernels.h): only layers of the halo kernels' shape
+static int require_halo_shape(const tg_igemm_desc* d, const char* what) {
+  TG_REQUIRE(d != nullptr, "%s: null descriptor", what);
+  TG_REQUIRE(d->n_taps == 9 && d->n_group == 0 && d->s_y == 1 && d->s_x == 1 && d->os_y == 1 && d->os_x == 1 && d->oo_y == 0 && d->oo_x == 0 &&
+             d->h_v == d->h_in && d->w_v == d->w_in && d->h_out == d->h_in && d->w_out == d->w_in && (d->w_in == 16 || d->w_in == 32 || d->w_in == 64) &&
+             (d->h_in * d->w_in) % 256 == 0 && d->ld_in % 64 == 0 && d->c_out % 128 == 0,
+             "%s: a bf16-stored input is served for 3x3 / stride-1 / SAME layers of width 16 / 32 / 64 with 64 | ld_in and 128 | c_out only", what);
+  return TG_OK;
+}
+
+extern "C" int tg_igemm_bnstat_bf16in_bf16(const tg_igemm_desc* d, const void* in, const float* w, const float* bias, float* out, const int32_t* seg_rows,
+                                           int nseg, double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
+  int rc = require_halo_shape(d, "igemm_bnstat_bf16in");
+  if (rc != TG_OK) return rc;
+  return igemm_bnstat_impl(d, static_cast<const float*>(in), w, bias, out, seg_rows, nseg, sums, sums_zeroed, scratch, scratch_bytes, stream, true, true);
+}
+
+extern "C" int tg_igemm_bf16in_bf16(const tg_igemm_desc* d, const void* in, const float* w, const float* bias, float* out, void* scratch,
+                                    int64_t scratch_bytes, void* stream) {
+  int rc = require_halo_shape(d, "igemm_bf16in");
+  if (rc != TG_OK) return rc;
+  return igemm_impl(d, 1, static_cast<const float*>(in), w, bias, out, stream, nullptr, nullptr, 0, true, nullptr, 0, 0.f, scratch, scratch_bytes, 0,
+                    nullptr, 0, true);
 }
 
 extern "C" int tg_igemm_bnstat_f32(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, const int32_t* seg_rows, int nseg,
@@ -1409,4 +1466,25 @@ extern "C" int tg_wgrad_f32(const tg_igemm_desc* d, const float* in, const float
 
 extern "C" int tg_wgrad_bf16(const tg_igemm_desc* d, const float* in, const float* dout, float* slab, int n_split, void* stream) {
   return wgrad_impl(d, in, dout, slab, n_split, stream, true);
+}
+
+// bf16-stored activation: always wgrad3x3 (its shape rule without the occupancy rule of the default policy — any n_split is served)
+extern "C" int tg_wgrad_bf16in_bf16(const tg_igemm_desc* d, const void* in, const float* dout, float* slab, int n_split, void* stream) {
+  int rc = check_desc(d);
+  if (rc != TG_OK) return rc;
+  TG_REQUIRE(in && dout && slab, "wgrad_bf16in: null buffer");
+  TG_REQUIRE(n_split >= 1, "wgrad_bf16in: n_split=%d", n_split);
+  TG_REQUIRE(tg::wgrad3x3_applicable(d, n_split, true, 1, tg::halo_compute_units()),
+             "wgrad_bf16in: a bf16-stored input is served for 3x3 / stride-1 / SAME layers of width 16 / 32 / 64 (128 pixels per tile), 32 | ld_in, "
+             "128 | c_out only");
+  const int64_t ib = (int64_t)d->n_img * d->h_in * d->w_in * d->ld_in * 2, ob = (int64_t)d->n_img * d->h_out * d->w_out * d->ld_out * 4;
+  TG_REQUIRE(ib < 0x7FFFFFF0LL && ob < 0x7FFFFFF0LL, "wgrad_bf16in: operand exceeds the 2 GiB buffer-descriptor range");
+  const int64_t M = (int64_t)d->n_img * d->h_v * d->w_v;
+  char desc[96];
+  snprintf(desc, sizeof(desc), "M=%lld N=%d K=%dx%d in=%dx%d split=%d bf16in", (long long)M, d->c_out, d->n_taps, d->ld_in, d->h_in, d->w_in, n_split);
+  hipStream_t s = tg::as_stream(stream);
+  tg::ProfScope prof(tg::PC_WGRAD, 2.0 * M * d->c_out * d->n_taps * d->ld_in,
+                     2.0 * M * d->ld_in + 4.0 * M * d->c_out + 4.0 * n_split * d->c_out * d->n_taps * d->ld_in, s, desc);
+  tg::halo_count_launch();
+  return tg::wgrad3x3_launch(d, static_cast<const float*>(in), dout, slab, n_split, (uint32_t)ib, (uint32_t)ob, s, true, true);
 }

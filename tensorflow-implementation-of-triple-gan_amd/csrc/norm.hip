@@ -11,6 +11,9 @@
 #include "tg_common.h"
 #include "tg_device.h"
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
 namespace {
 
 constexpr int RCH = 256;         // rows per stage-1 chunk
@@ -679,7 +682,20 @@ __device__ __forceinline__ void bn_repl(const double* __restrict__ sums, int nse
   *s0 = a; *s1 = b;
 }
 
-__global__ void __launch_bounds__(256) bn_train_apply(const float* __restrict__ x, int ld_x, float* __restrict__ y, int ld_y, int c, SegTable st, int chunk,
+// y = x * scale + shift of four columns: the one expression both output types of bn_train_apply store (same FMA contraction)
+__device__ __forceinline__ float4 bn_apply4(float4 xv, const float* sc, const float* sh) {
+  float4 o;
+  o.x = xv.x * sc[0] + sh[0];
+  o.y = xv.y * sc[1] + sh[1];
+  o.z = xv.z * sc[2] + sh[2];
+  o.w = xv.w * sc[3] + sh[3];
+  return o;
+}
+
+// Y16: y is stored as bf16 (round to nearest even, one 8-byte store per four columns) — the batch norms whose only reader is a bf16-operand
+// convolution (tg_bn_train_bf16 / tg_bn_train_apply_bf16); ld_y then counts bf16 elements
+template <bool Y16>
+__global__ void __launch_bounds__(256) bn_train_apply(const float* __restrict__ x, int ld_x, void* __restrict__ y, int ld_y, int c, SegTable st, int chunk,
                                                       const double* __restrict__ sums, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       float eps, float decay, float* __restrict__ mm, float* __restrict__ mv,
                                                       float* __restrict__ mean_inv) {
@@ -731,12 +747,14 @@ __global__ void __launch_bounds__(256) bn_train_apply(const float* __restrict__ 
   for (int i = threadIdx.x; i < total; i += 256) {
     const int rr = i / cgn, cg = i - rr * cgn;
     const float4 xv = *reinterpret_cast<const float4*>(x + (int64_t)(r0 + rr) * ld_x + c0 + cg * 4);
-    float4 o;
-    o.x = xv.x * sc[cg * 4] + sh[cg * 4];
-    o.y = xv.y * sc[cg * 4 + 1] + sh[cg * 4 + 1];
-    o.z = xv.z * sc[cg * 4 + 2] + sh[cg * 4 + 2];
-    o.w = xv.w * sc[cg * 4 + 3] + sh[cg * 4 + 3];
-    *reinterpret_cast<float4*>(y + (int64_t)(r0 + rr) * ld_y + c0 + cg * 4) = o;
+    const float4 o = bn_apply4(xv, sc + cg * 4, sh + cg * 4);
+    const int64_t yo = (int64_t)(r0 + rr) * ld_y + c0 + cg * 4;
+    if constexpr (Y16) {
+      const f32x4 v = {o.x, o.y, o.z, o.w};
+      *reinterpret_cast<bf16x4*>(static_cast<__bf16*>(y) + yo) = __builtin_convertvector(v, bf16x4);
+    } else {
+      *reinterpret_cast<float4*>(static_cast<float*>(y) + yo) = o;
+    }
   }
 }
 
@@ -1107,46 +1125,61 @@ static int bn_grid(const SegTable& st, int rows, int c, int* chunk, dim3* grid) 
   return TG_OK;
 }
 
-int tg_bn_train_f32(const float* x, int ld_x, float* y, int ld_y, int rows, int c, const int32_t* seg_rows, int nseg, const float* gamma,
-                    const float* beta, float eps, float decay, float* moving_mean, float* moving_var, double* sums, int sums_zeroed, float* mean_inv,
-                    void* stream) {
+static int bn_train_impl(const float* x, int ld_x, void* y, int ld_y, int rows, int c, const int32_t* seg_rows, int nseg, const float* gamma,
+                         const float* beta, float eps, float decay, float* moving_mean, float* moving_var, double* sums, int sums_zeroed, float* mean_inv,
+                         void* stream, bool stats, bool y16) {
+  const char* what = stats ? (y16 ? "bn_train_bf16" : "bn_train") : (y16 ? "bn_train_apply_bf16" : "bn_train_apply");
   SegTable st;
   int rc = make_segs(st, seg_rows, nseg, rows);
   if (rc != TG_OK) return rc;
-  TG_REQUIRE(x && y && gamma && beta && sums && mean_inv, "bn_train: null buffer");
-  TG_REQUIRE(c > 0 && ld_x % 4 == 0 && ld_y % 4 == 0 && (c + 3) / 4 * 4 <= ld_x && (c + 3) / 4 * 4 <= ld_y, "bn_train: c=%d vs ld=%d/%d", c, ld_x, ld_y);
-  TG_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), "bn_train: moving_mean / moving_var must both be given or both be NULL");
+  TG_REQUIRE(x && y && gamma && beta && sums && mean_inv, "%s: null buffer", what);
+  TG_REQUIRE(c > 0 && ld_x % 4 == 0 && ld_y % 4 == 0 && (c + 3) / 4 * 4 <= ld_x && (c + 3) / 4 * 4 <= ld_y, "%s: c=%d vs ld=%d/%d", what, c, ld_x, ld_y);
+  TG_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), "%s: moving_mean / moving_var must both be given or both be NULL", what);
+  TG_REQUIRE(!y16 || (reinterpret_cast<uintptr_t>(y) & 7) == 0, "%s: y must be 8-byte aligned", what);
   hipStream_t s = tg::as_stream(stream);
-  if (!sums_zeroed) {
+  if (stats && !sums_zeroed) {
     hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * REPL * 2 * nseg * c, s);
     if (e != hipSuccess) return tg::hip_fail(e, "hipMemsetAsync(bn sums)");
   }
-  tg::ProfScope prof(tg::PC_NORM, 0, 12.0 * rows * c, s);
+  tg::ProfScope prof(tg::PC_NORM, 0, ((stats ? 8.0 : 4.0) + (y16 ? 2.0 : 4.0)) * rows * c, s);
   int chunk; dim3 grid;
   bn_grid(st, rows, c, &chunk, &grid);
-  hipLaunchKernelGGL(bn_sums<false>, grid, dim3(256), 0, s, x, ld_x, (const float*)nullptr, 0, c, st, chunk, sums);
-  TG_CHECK_LAUNCH("bn_sums");
-  hipLaunchKernelGGL(bn_train_apply, grid, dim3(256), 0, s, x, ld_x, y, ld_y, c, st, chunk, sums, gamma, beta, eps, decay, moving_mean, moving_var, mean_inv);
+  if (stats) {
+    hipLaunchKernelGGL(bn_sums<false>, grid, dim3(256), 0, s, x, ld_x, (const float*)nullptr, 0, c, st, chunk, sums);
+    TG_CHECK_LAUNCH("bn_sums");
+  }
+  if (y16) hipLaunchKernelGGL(bn_train_apply<true>, grid, dim3(256), 0, s, x, ld_x, y, ld_y, c, st, chunk, sums, gamma, beta, eps, decay, moving_mean, moving_var, mean_inv);
+  else hipLaunchKernelGGL(bn_train_apply<false>, grid, dim3(256), 0, s, x, ld_x, y, ld_y, c, st, chunk, sums, gamma, beta, eps, decay, moving_mean, moving_var, mean_inv);
   TG_CHECK_LAUNCH("bn_train_apply");
   return TG_OK;
+}
+
+int tg_bn_train_f32(const float* x, int ld_x, float* y, int ld_y, int rows, int c, const int32_t* seg_rows, int nseg, const float* gamma,
+                    const float* beta, float eps, float decay, float* moving_mean, float* moving_var, double* sums, int sums_zeroed, float* mean_inv,
+                    void* stream) {
+  return bn_train_impl(x, ld_x, y, ld_y, rows, c, seg_rows, nseg, gamma, beta, eps, decay, moving_mean, moving_var, sums, sums_zeroed, mean_inv, stream,
+                       true, false);
+}
+
+int tg_bn_train_bf16(const float* x, int ld_x, void* y, int ld_y, int rows, int c, const int32_t* seg_rows, int nseg, const float* gamma,
+                     const float* beta, float eps, float decay, float* moving_mean, float* moving_var, double* sums, int sums_zeroed, float* mean_inv,
+                     void* stream) {
+  return bn_train_impl(x, ld_x, y, ld_y, rows, c, seg_rows, nseg, gamma, beta, eps, decay, moving_mean, moving_var, sums, sums_zeroed, mean_inv, stream,
+                       true, true);
 }
 
 int tg_bn_train_apply_f32(const float* x, int ld_x, float* y, int ld_y, int rows, int c, const int32_t* seg_rows, int nseg, const float* gamma,
                           const float* beta, float eps, float decay, float* moving_mean, float* moving_var, const double* sums, float* mean_inv,
                           void* stream) {
-  SegTable st;
-  int rc = make_segs(st, seg_rows, nseg, rows);
-  if (rc != TG_OK) return rc;
-  TG_REQUIRE(x && y && gamma && beta && sums && mean_inv, "bn_train_apply: null buffer");
-  TG_REQUIRE(c > 0 && ld_x % 4 == 0 && ld_y % 4 == 0 && (c + 3) / 4 * 4 <= ld_x && (c + 3) / 4 * 4 <= ld_y, "bn_train_apply: c=%d vs ld=%d/%d", c, ld_x, ld_y);
-  TG_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), "bn_train_apply: moving_mean / moving_var must both be given or both be NULL");
-  hipStream_t s = tg::as_stream(stream);
-  tg::ProfScope prof(tg::PC_NORM, 0, 8.0 * rows * c, s);
-  int chunk; dim3 grid;
-  bn_grid(st, rows, c, &chunk, &grid);
-  hipLaunchKernelGGL(bn_train_apply, grid, dim3(256), 0, s, x, ld_x, y, ld_y, c, st, chunk, sums, gamma, beta, eps, decay, moving_mean, moving_var, mean_inv);
-  TG_CHECK_LAUNCH("bn_train_apply");
-  return TG_OK;
+  return bn_train_impl(x, ld_x, y, ld_y, rows, c, seg_rows, nseg, gamma, beta, eps, decay, moving_mean, moving_var, const_cast<double*>(sums), 1,
+                       mean_inv, stream, false, false);
+}
+
+int tg_bn_train_apply_bf16(const float* x, int ld_x, void* y, int ld_y, int rows, int c, const int32_t* seg_rows, int nseg, const float* gamma,
+                           const float* beta, float eps, float decay, float* moving_mean, float* moving_var, const double* sums, float* mean_inv,
+                           void* stream) {
+  return bn_train_impl(x, ld_x, y, ld_y, rows, c, seg_rows, nseg, gamma, beta, eps, decay, moving_mean, moving_var, const_cast<double*>(sums), 1,
+                       mean_inv, stream, false, true);
 }
 
 int tg_bn_moving_update_f32(const double* sums, int rows, int c, const int32_t* seg_rows, int nseg, float decay, float* moving_mean,

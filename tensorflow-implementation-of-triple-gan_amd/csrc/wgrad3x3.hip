@@ -19,6 +19,7 @@
 //     gradient image: 256-byte rows, 16-byte chunk XOR-swizzled by ((row & 3) << 2) | ((row >> 2) & 3) as in wgrad_f32_kernel's bf16 form.
 // Numerics: as the generic kernels — fp32 accumulation, operands exact (fp32) or RNE-rounded (bf16); only the order of the pixel sum
 // differs (and the pixel partition behind the `n_split` slabs, which tg_slab_reduce_f32 adds up anyway).
+#include <type_traits>
 #include "tg_common.h"
 #include "tg_device.h"
 #include "tg_conv3x3_bf16.h"
@@ -60,8 +61,11 @@ __device__ __forceinline__ int dy_off(int row, int ch) { return 256 * row + 16 *
 template <int N>
 __device__ __forceinline__ void barrier_keep() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory"); }
 
-template <int W, bool BF16>
+// IN16: the activation x is STORED as bf16 (tg_wgrad_bf16in_bf16) — 8-byte loads of four channels, the same X_IT loads per tile as the
+// fp32 form, written to the halo image as they arrive (no conversion); dy stays fp32
+template <int W, bool BF16, bool IN16 = false>
 __global__ void __launch_bounds__(512, 2) wgrad3x3_kernel(WParams p) {
+  static_assert(!IN16 || BF16, "a bf16-stored input feeds bf16 operands only");
   constexpr int BMW = BF16 ? 128 : 64;                           // pixels per tile
   constexpr int R = BMW / W, HW_ = W + 2, HP = (R + 2) * HW_;
   constexpr int XROW = BF16 ? 64 : 128, DROW = BF16 ? 256 : 512; // bytes per halo pixel (32 channels) / per gradient pixel (128 columns)
@@ -105,13 +109,17 @@ __global__ void __launch_bounds__(512, 2) wgrad3x3_kernel(WParams p) {
       const int hy = hp / HW_, hx = hp - hy * HW_;
       const int iy = row0 + hy - 1, ix = hx - 1;
       const bool ok = hp < HP && (unsigned)iy < (unsigned)p.h && (unsigned)ix < (unsigned)W;
-      return ok ? (uint32_t)(((img * p.h + iy) * W + ix) * p.ld_in + c0 + 4 * xq) * 4u : OOB;
+      return ok ? (uint32_t)(((img * p.h + iy) * W + ix) * p.ld_in + c0 + 4 * xq) * (IN16 ? 2u : 4u) : OOB;
     };
-    struct Set { u32x4 x[X_IT], d[D_IT]; };
+    typedef typename std::conditional<IN16, u32x2, u32x4>::type XReg;
+    struct Set { XReg x[X_IT]; u32x4 d[D_IT]; };
     auto gload = [&](Set& r, int t) {
       const uint32_t so = (uint32_t)__builtin_amdgcn_readfirstlane(t * BMW * p.ld_out * 4);
 #pragma unroll
-      for (int i = 0; i < X_IT; ++i) r.x[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, x_voff(t, i), 0, 0);
+      for (int i = 0; i < X_IT; ++i) {
+        if constexpr (IN16) r.x[i] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_x, x_voff(t, i), 0, 0));
+        else r.x[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, x_voff(t, i), 0, 0);
+      }
 #pragma unroll
       for (int i = 0; i < D_IT; ++i) r.d[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_d, d_voff, so + (uint32_t)i * d_step, 0);
     };
@@ -122,7 +130,8 @@ __global__ void __launch_bounds__(512, 2) wgrad3x3_kernel(WParams p) {
       for (int i = 0; i < X_IT; ++i)
         if (i + 1 < X_IT || xhp + 32 * i < HP) {
           unsigned char* dst = xs + (xhp + 32 * i) * XROW + xq * (BF16 ? 8 : 16);
-          if constexpr (BF16) *reinterpret_cast<u32x2*>(dst) = pack4(r.x[i]);
+          if constexpr (IN16) *reinterpret_cast<u32x2*>(dst) = r.x[i];
+          else if constexpr (BF16) *reinterpret_cast<u32x2*>(dst) = pack4(r.x[i]);
           else *reinterpret_cast<u32x4*>(dst) = r.x[i];
         }
 #pragma unroll
@@ -224,9 +233,10 @@ __global__ void __launch_bounds__(512, 2) wgrad3x3_kernel(WParams p) {
 }
 
 template <int W>
-void launch(const WParams& p, bool bf16, hipStream_t s) {
+void launch(const WParams& p, bool bf16, bool in16, hipStream_t s) {
   const dim3 grid(p.n_cc * p.n_nt * p.n_split);
-  if (bf16) hipLaunchKernelGGL((wgrad3x3_kernel<W, true>), grid, dim3(512), 0, s, p);
+  if (in16) hipLaunchKernelGGL((wgrad3x3_kernel<W, true, true>), grid, dim3(512), 0, s, p);
+  else if (bf16) hipLaunchKernelGGL((wgrad3x3_kernel<W, true>), grid, dim3(512), 0, s, p);
   else hipLaunchKernelGGL((wgrad3x3_kernel<W, false>), grid, dim3(512), 0, s, p);
 }
 
@@ -274,7 +284,8 @@ int wgrad3x3_splits(const tg_igemm_desc* d, bool bf16, int policy, int compute_u
 }
 
 int wgrad3x3_launch(const tg_igemm_desc* d, const float* in, const float* dout, float* slab, int n_split, uint32_t in_bytes, uint32_t dout_bytes,
-                    hipStream_t s, bool bf16) {
+                    hipStream_t s, bool bf16, bool in16) {
+  TG_REQUIRE(!in16 || bf16, "wgrad3x3: a bf16-stored input feeds bf16 operands only");
   WParams p;
   p.x = in; p.dy = dout; p.slab = slab;
   p.n_img = d->n_img; p.h = d->h_in; p.ld_in = d->ld_in; p.ld_out = d->ld_out; p.c_out = d->c_out;
@@ -284,9 +295,9 @@ int wgrad3x3_launch(const tg_igemm_desc* d, const float* in, const float* dout, 
   p.tiles_per_split = (p.tiles_total + n_split - 1) / n_split;
   for (int t = 0; t < 9; ++t) p.tap_of[(d->dy[t] + 1) * 3 + d->dx[t] + 1] = t;
   p.x_bytes = in_bytes; p.dy_bytes = dout_bytes;
-  if (d->w_in == 16) launch<16>(p, bf16, s);
-  else if (d->w_in == 32) launch<32>(p, bf16, s);
-  else launch<64>(p, bf16, s);
+  if (d->w_in == 16) launch<16>(p, bf16, in16, s);
+  else if (d->w_in == 32) launch<32>(p, bf16, in16, s);
+  else launch<64>(p, bf16, in16, s);
   TG_CHECK_LAUNCH("wgrad3x3_kernel");
   return TG_OK;
 }

@@ -160,7 +160,7 @@ def igemm_workspace_bytes(name, args):
         seg, nseg = args[5], args[6]
     elif '_actsum_' in name:
         seg, nseg = args[7], args[8]
-    return call('tg_igemm_workspace_bytes', d0, n_desc, seg, nseg, 1 if name.endswith('bf16') else 0)
+    return call('tg_igemm_workspace_bytes', d0, n_desc, seg, nseg, 2 if '_bf16in_' in name else 1 if name.endswith('bf16') else 0)
 
 
 def call_igemm(name, *args, scratch=True):

@@ -4,6 +4,8 @@ context's stream and, when a tape is active, records a closure producing the inp
 gradients.  Gradient of an activation `a` lives in `a.grad` (an Act of identical layout)."""
 import ctypes as C
 
+import torch
+
 from . import geom, lib
 from .lib import ACT
 from .runtime import Act, ctx, pad32, seg_array
@@ -35,7 +37,17 @@ def igemm_scratch(cx, name, args, bf16):
 
 
 def _p(t):
+    if t is not None and t.dtype == torch.bfloat16:
+        raise lib.TgError("a bf16-stored tensor was handed to a launch that reads fp32")
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def require_f32(x, op):
+    """refuse a bf16-stored activation (Act.dtype, config.ACT_DTYPE) in an op that has no bf16 reader — never reinterpret its bytes."""
+    for a in (x if isinstance(x, (list, tuple)) else (x,)):
+        if getattr(a, 'dtype', 'f32') != 'f32':
+            raise lib.TgError("ops.%s: the %dx%dx%dx%d input is stored as %s; this op reads fp32 activations only (a bf16-stored activation "
+                              "may feed conv2d only)" % (op, a.n, a.h, a.w, a.c, a.dtype))
 
 
 def _single_consumer(y, gy):
@@ -87,12 +99,20 @@ def _run_prep_plan(cx, plan):
         cx.prep_cache[j['key']] = (j['scale'], j['w_oti'], j['w_hwio'], j['bump'], cx.phase)
 
 
-def filter_grad(desc, in_act_t, dout_t, t, c_dim, n_dim, dst, wn=None, defer=True):
+def filter_grad(desc, in_act_t, dout_t, t, c_dim, n_dim, dst, wn=None, defer=True, in16=False):
     """dst[t][c_dim][n_dim] = filter gradient via tg_wgrad_f32 slabs + deterministic reduce.
     wn=(v, g, dv, dg): weight-normalised layer — dst is the gradient of the effective filter (scratch), dv / dg the variables'.
     The tail (slab reduction [+ weight-norm gradient]) is DEFERRED to Context.flush_tails (end of the backward pass / bucket
-    boundary), where the tails of all layers go out as three launches; the 512-split first convolution keeps its own reduce."""
+    boundary), where the tails of all layers go out as three launches; the 512-split first convolution keeps its own reduce.
+    in16: in_act_t is a bf16-stored activation (tg_wgrad_bf16in_bf16)."""
     cx = ctx()
+
+    def wgrad(slab, ns):
+        if in16:
+            lib.call('tg_wgrad_bf16in_bf16', desc, C.c_void_p(in_act_t.data_ptr()), _p(dout_t), _p(slab), ns, cx.stream)
+        else:
+            _call('tg_wgrad_f32', desc, _p(in_act_t), _p(dout_t), _p(slab), ns, cx.stream)
+
     ns = geom.wgrad_splits(desc, cx.mfma_dtype == 'bf16')      # pixel split and slab size: the library's rule (tg_wgrad_splits[_bf16])
     slab = cx.scratch('slab', geom.wgrad_slab_floats(desc, ns))
     deferred = defer and (cx.tape is not None or cx._phase_depth > 0)
@@ -100,19 +120,19 @@ def filter_grad(desc, in_act_t, dout_t, t, c_dim, n_dim, dst, wn=None, defer=Tru
     wide = ns >= 32 and t * c_dim * n_dim <= 65536
     if deferred and (small or cx.wgrad_side) and not wide:
         with cx.wgrad_on_side():                                 # beside the input-gradient chain (Context.wgrad_on_side; joined in flush_tails)
-            _call('tg_wgrad_f32', desc, _p(in_act_t), _p(dout_t), _p(slab), ns, cx.stream)
+            wgrad(slab, ns)
     elif deferred and small and wide:
         # many splits of a small filter (the discriminator's first layers, the classifier's first): the launch AND its own reduction go to
         # the second stream, so the input-gradient chain does not wait for them (round 4: they were 0.18 ms of the D-update's launch stream)
         with cx.wgrad_on_side():
-            _call('tg_wgrad_f32', desc, _p(in_act_t), _p(dout_t), _p(slab), ns, cx.stream)
+            wgrad(slab, ns)
             _call('tg_slab_reduce_f32', _p(slab), ns, t, desc.ld_in, desc.c_out, c_dim, n_dim, _p(dst), cx.stream)
             if wn is not None:
                 coef = cx.scratch('coef', 2 * n_dim)
                 _call('tg_wn_bwd_f32', _p(dst), _p(wn[0]), _p(wn[1]), t * c_dim, n_dim, _p(wn[2]), _p(wn[3]), _p(coef), cx.stream)
         return
     else:
-        _call('tg_wgrad_f32', desc, _p(in_act_t), _p(dout_t), _p(slab), ns, cx.stream)
+        wgrad(slab, ns)
     if deferred and not wide:
         coef = cx.scratch('coef', 2 * n_dim) if wn is not None else None
         j = lib.WnJob(slab.data_ptr(), dst.data_ptr(), wn[0].data_ptr() if wn else None, wn[1].data_ptr() if wn else None,
@@ -143,6 +163,11 @@ def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=N
     activation; on the fused mean-only-BN path the apply pass and the pooling are one launch (tg_mobn_apply_pool_f32)."""
     cx = ctx()
     assert x.ld % 32 == 0, "conv input must be channel-padded to 32"
+    x16 = x.dtype == 'bf16'                # a bf16-stored input (config.ACT_DTYPE): the *_bf16in_bf16 launches read it as it is
+    if x16 and not (cx.mfma_dtype == 'bf16' and k == 3 and stride == 1 and padding == 'SAME' and wn is None and mobn is None and concat is None
+                    and n_store_ld is None and pool is None):
+        raise lib.TgError("conv2d: a bf16-stored input is read by the bf16-operand 3x3 / stride-1 / SAME convolution without weight norm, "
+                          "mean-only BN, concat or pooling only (MFMA_DTYPE %r)" % (cx.mfma_dtype,))
     c_in, ci_p, co_p = x.c, x.ld, pad32(c_out)
     t = k * k
     needs_w = cx.trains() and kernel_grad is not None
@@ -209,8 +234,15 @@ def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=N
     elif (bn_stats and mobn is None and act in (None, 'relu', 'lrelu') and c_out == co_p == ld_out and len(seg_rows) <= 8
           and geom.colsum_supported(d, seg_rows)):
         bsum, zd = cx.zscratch('bn64', 32 * len(seg_rows) * c_out)     # the batch norm's buffer: 8 replicas x nseg x 2 x c doubles
-        _call('tg_igemm_bnstat_f32', d, x.ptr, _p(w_oti), _p(bias), y.ptr, seg_array(seg_rows), len(seg_rows), _p(bsum), zd, cx.stream)
+        if x16:
+            args = (d, x.ptr, _p(w_oti), _p(bias), y.ptr, seg_array(seg_rows), len(seg_rows), _p(bsum), zd, cx.stream)
+            lib.call('tg_igemm_bnstat_bf16in_bf16', *igemm_scratch(cx, 'tg_igemm_bnstat_bf16in_bf16', args, True))
+        else:
+            _call('tg_igemm_bnstat_f32', d, x.ptr, _p(w_oti), _p(bias), y.ptr, seg_array(seg_rows), len(seg_rows), _p(bsum), zd, cx.stream)
         y.bn_sums = (bsum, tuple(seg_rows))
+    elif x16:
+        args = (d, x.ptr, _p(w_oti), _p(bias), y.ptr, cx.stream)
+        lib.call('tg_igemm_bf16in_bf16', *igemm_scratch(cx, 'tg_igemm_bf16in_bf16', args, True))
     elif packed:
         # K-packed products straight from the [3,3,Cin,Cout] variable (csrc/packed_conv.hip); with concat the label channels ride along
         _call('tg_conv3x3_packed_fwd_f32', x.ptr, x.ld, c_in, _p(kernel), _p(bias), ACT[act], alpha, _p(concat[0]) if fuse_cat else None,
@@ -287,7 +319,7 @@ def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=N
         elif needs_w:
             dw_desc = geom.conv_wgrad(x.n, x.h, x.w, ci_p, co_p, k, stride, padding)
             if wn is None:
-                filter_grad(dw_desc, x.t, dpre, t, c_in, c_out, kernel_grad)
+                filter_grad(dw_desc, x.t, dpre, t, c_in, c_out, kernel_grad, in16=x16)
             else:
                 dw = cx.scratch('dw', t * c_in * c_out)
                 filter_grad(dw_desc, x.t, dpre, t, c_in, c_out, dw, wn=(kernel, wn[0], kernel_grad, wn[1]))
@@ -340,6 +372,7 @@ def deconv2d(x, kernel, bias, c_out, act=None, kernel_grad=None, bias_grad=None,
     """tf.layers.conv2d_transpose 5x5 s2 'same' + bias + act (Model/modle_base.py:246-259);
     kernel [5,5,c_out,c_in].  narrow_out: store only the logical channels (generator output).
     wn=(g, g_grad): W = g * l2_normalize(V,[0,1,3]) (NN_Base._WN_deconv2d, Model/modle_base.py:130-155)."""
+    require_f32(x, 'deconv2d')
     cx = ctx()
     assert x.ld % 32 == 0
     c_in, ci_p, co_p = x.c, x.ld, pad32(c_out)
@@ -429,6 +462,7 @@ def deconv2d(x, kernel, bias, c_out, act=None, kernel_grad=None, bias_grad=None,
 def mean_only_batch_norm(x, pop_mean, b, b_grad=None, train=True, decay=0.9, segments=None):
     """x - mean + b (training, pop_mean updated) or x - pop_mean + b (Model/nn.py:147-187) as a stand-alone op on an activation
     (the layers of the models use the version fused into the convolution, conv2d(mobn=...))."""
+    require_f32(x, 'mean_only_batch_norm')
     cx = ctx()
     c = x.c
     seg_rows = _segs(x, segments)
@@ -469,6 +503,7 @@ def mean_only_batch_norm(x, pop_mean, b, b_grad=None, train=True, decay=0.9, seg
 
 def batch_norm_eval(x, gamma, beta, mm, mv, eps):
     """contrib batch_norm with is_training=False: y = gamma*(x-moving_mean)/sqrt(moving_var+eps)+beta (no tape: evaluation only)."""
+    require_f32(x, 'batch_norm_eval')
     cx = ctx()
     c = x.c
     scale, shift = cx.scratch('bnsc', c), cx.scratch('bnsh', c)
@@ -479,12 +514,15 @@ def batch_norm_eval(x, gamma, beta, mm, mv, eps):
     return y
 
 
-def batch_norm_train(x, gamma, beta, mm, mv, eps, decay, gamma_grad=None, beta_grad=None, relu_input=False, segments=None):
+def batch_norm_train(x, gamma, beta, mm, mv, eps, decay, gamma_grad=None, beta_grad=None, relu_input=False, segments=None, out_bf16=False):
     """y = gamma*(x-mu)/sqrt(var+eps)+beta over all rows (Model/modle_base.py:229-237); with `segments` (image counts of the
     applications batched into x) the statistics are per application and the moving statistics are updated application by
     application.  Fused: one statistics launch (fp64 atomics) + one apply launch per direction.
     relu_input: x is the output of a fused ReLU; the backward then also masks by x > 0 and the
-    gradient it produces is wrt the PRE-ReLU value (consumed by the producing conv's backward)."""
+    gradient it produces is wrt the PRE-ReLU value (consumed by the producing conv's backward).
+    out_bf16: the caller's promise that y is read ONLY by bf16-operand 3x3 convolutions (conv2d) — with Context.act_dtype 'bf16' y is then
+    stored as bf16 (tg_bn_train[_apply]_bf16), the bits those convolutions would have rounded it to; the backward pass reads x and dy only."""
+    require_f32(x, 'batch_norm_train')
     cx = ctx()
     c = x.c
     trains = cx.trains()
@@ -492,14 +530,20 @@ def batch_norm_train(x, gamma, beta, mm, mv, eps, decay, gamma_grad=None, beta_g
     seg_rows = _segs(x, segments)
     nseg = len(seg_rows)
     mean_inv = cx.scratch('bnmi', 2 * nseg * c)
-    y = cx.new_act(x.n, x.h, x.w, c, x.ld, requires_grad=needs)
+    y16 = out_bf16 and cx.act_dtype == 'bf16'
+    if y16 and cx.mfma_dtype != 'bf16':
+        raise lib.TgError("batch_norm_train: a bf16-stored output needs the bf16 MFMA path (MFMA_DTYPE 'bf16') behind it")
+    y = cx.new_act(x.n, x.h, x.w, c, x.ld, requires_grad=needs, dtype='bf16' if y16 else 'f32')
+    sfx = 'bf16' if y16 else 'f32'
+    if y16:
+        cx.bf16_act_layers.add(cx.scope_name())
     if x.bn_sums is not None and x.bn_sums[1] == tuple(seg_rows):
         sums = x.bn_sums[0]                                   # the producing convolution took the statistics in its epilogue (conv2d(bn_stats=True))
-        _call('tg_bn_train_apply_f32', x.ptr, x.ld, y.ptr, y.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(beta), eps, decay, _p(mm), _p(mv),
+        _call('tg_bn_train_apply_' + sfx, x.ptr, x.ld, y.ptr, y.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(beta), eps, decay, _p(mm), _p(mv),
               _p(sums), _p(mean_inv), cx.stream)
     else:
         sums, zd = cx.zscratch('bn64', 32 * nseg * c)         # 8 replicas x 2 x nseg x c doubles
-        _call('tg_bn_train_f32', x.ptr, x.ld, y.ptr, y.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(beta), eps, decay, _p(mm), _p(mv),
+        _call('tg_bn_train_' + sfx, x.ptr, x.ld, y.ptr, y.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(beta), eps, decay, _p(mm), _p(mv),
               _p(sums), zd, _p(mean_inv), cx.stream)
     if cx.state_replay is not None and mm is not None:
         # this forward pass is being KEPT for a later solver run that TensorFlow would re-execute (Context.sub_tape(replay=...)): the
@@ -545,6 +589,7 @@ def scale_mask(x, mask_t, mscale, defer=False):
     """y = x*mask*mscale (inverted dropout, Model/modle_base.py:190-191).  defer: return a handle WITHOUT storage whose dropout the next
     op applies inside its own launch — only cond_concat does (the discriminator's dropout -> concat pairs, Good_GAN_cifar10.py:63-65,
     73-75); anything else touching the handle fails loudly on its missing buffer."""
+    require_f32(x, 'scale_mask')
     cx = ctx()
     if defer:
         y = Act(None, x.n, x.h, x.w, x.c, x.ld, requires_grad=x.requires_grad)
@@ -562,6 +607,7 @@ def scale_mask(x, mask_t, mscale, defer=False):
 
 def cond_concat(x, y_onehot_t, ncls):
     """concat([x, y*ones], 3), output channel-padded to 32 (Model/modle_base.py:239-244)."""
+    require_f32(x, 'cond_concat')
     cx = ctx()
     ld = pad32(x.c + ncls)
     if x.labels is not None and x.labels == (y_onehot_t.data_ptr(), ncls) and x.ld == ld and x.pending is None:
@@ -599,6 +645,7 @@ def cond_concat(x, y_onehot_t, ncls):
 
 def pad_add(x, add_t, ld_out):
     """x + noise, channel-padded (classifier input; no gradient is ever needed upstream)."""
+    require_f32(x, 'pad_add')
     cx = ctx()
     out = cx.new_act(x.n, x.h, x.w, x.c, ld_out)
     _call('tg_pad_add_f32', x.ptr, x.ld, x.c, _p(add_t), x.c, out.ptr, ld_out, x.rows, cx.stream)
@@ -608,6 +655,7 @@ def pad_add(x, add_t, ld_out):
 def im2col3x3_add(x, add_t):
     """3x3 SAME patches of (x + noise) as a [n,h,w,9*c] activation (channel stride padded to 32): the classifier's
     first conv then runs as a 1x1 product over K = 27 instead of K = 9*32 (no gradient is needed upstream)."""
+    require_f32(x, 'im2col3x3_add')
     cx = ctx()
     assert x.ld == x.c
     out = cx.new_act(x.n, x.h, x.w, 9 * x.c, pad32(9 * x.c))
@@ -617,6 +665,7 @@ def im2col3x3_add(x, add_t):
 
 def maxpool2_dropout(y, mask_t, mscale):
     """tf.nn.max_pool 2x2 + tf.layers.dropout (Model/Good_GAN_cifar10.py:123-124)."""
+    require_f32(y, 'maxpool2_dropout')
     cx = ctx()
     out = cx.new_act(y.n, y.h // 2, y.w // 2, y.c, y.ld, requires_grad=y.requires_grad)
     _call('tg_maxpool2_fwd_f32', y.ptr, y.ld, out.ptr, out.ld, _p(mask_t), y.c, mscale, y.n, y.h, y.w, y.c, cx.stream)
@@ -646,6 +695,7 @@ def _record_maxpool_bwd(cx, y, out, mask_t, mscale):
 
 
 def global_maxpool(x):
+    require_f32(x, 'global_maxpool')
     cx = ctx()
     out = cx.new_act(x.n, 1, 1, x.c, pad32(x.c), requires_grad=x.requires_grad)
     _call('tg_gmaxpool_fwd_f32', x.ptr, x.ld, out.ptr, out.ld, x.n, x.h * x.w, x.c, cx.stream)
@@ -659,6 +709,7 @@ def global_maxpool(x):
 
 def global_avgpool_concat(x, y_onehot_t, ncls):
     """average_pooling2d over the whole map + squeeze + concat([h, y], 1) (Good_GAN_cifar10.py:94-96)."""
+    require_f32(x, 'global_avgpool_concat')
     cx = ctx()
     out = cx.new_act(x.n, 1, 1, x.c + ncls, pad32(x.c + ncls), requires_grad=x.requires_grad)
     _call('tg_gavgpool_concat_f32', x.ptr, x.ld, x.c, _p(y_onehot_t), ncls, out.ptr, out.ld, x.n, x.h * x.w, cx.stream)
@@ -674,6 +725,7 @@ def minibatch_discrimination(x, w, b, num_kernels, dim, w_grad=None, b_grad=None
     """NN_Base._minibatch_discrimination (Model/modle_base.py:110-128) on a dense [n, c] activation: A = x @ W (a 1-tap MFMA product),
     f[i,k] = sum_j exp(-|A[i,k,:] - A[j,k,:]|_1) + b[k].  Returns f, or concat([x, f], 1) when concat_input (what the SVHN
     discriminator does with it, Model/Good_GAN.py:160-161)."""
+    require_f32(x, 'minibatch_discrimination')
     cx = ctx()
     holder = {}
     skip = concat_input and cx.tape is not None and x.requires_grad
@@ -698,6 +750,7 @@ def minibatch_discrimination(x, w, b, num_kernels, dim, w_grad=None, b_grad=None
 
 
 def argmax_onehot(logits, k):
+    require_f32(logits, 'argmax_onehot')
     cx = ctx()
     out = cx.scratch('oh', logits.n * k)
     _call('tg_argmax_onehot_f32', logits.ptr, logits.ld, logits.n, k, _p(out), cx.stream)
@@ -729,6 +782,7 @@ def copy_many(jobs):
 
 def reshape(x, n, h, w, c):
     """view change of a dense (ld == c) buffer, e.g. [N,8192] -> [N,4,4,512]; gradients share storage."""
+    require_f32(x, 'reshape')
     cx = ctx()
     assert x.ld == x.c and n * h * w * c == x.rows * x.c
     y = Act(x.t, n, h, w, c, c, x.requires_grad)
@@ -742,6 +796,7 @@ def reshape(x, n, h, w, c):
 
 def add_noise(x, noise_t):
     """x + noise on a dense activation (NN_Base._add_noise, Model/modle_base.py:193-202); the gradient passes through."""
+    require_f32(x, 'add_noise')
     cx = ctx()
     y = cx.new_act(x.n, x.h, x.w, x.c, x.ld, requires_grad=x.requires_grad)
     _call('tg_pad_add_f32', x.ptr, x.ld, x.c, _p(noise_t), x.c, y.ptr, y.ld, x.rows, cx.stream)
@@ -754,6 +809,7 @@ def add_noise(x, noise_t):
 
 def global_avgpool(x):
     """tf.reduce_mean(x, axis=[1,2]) (Model/Good_GAN.py:198,346) -> [N,C]."""
+    require_f32(x, 'global_avgpool')
     cx = ctx()
     out = cx.new_act(x.n, 1, 1, x.c, pad32(x.c), requires_grad=x.requires_grad)
     _call('tg_gavgpool_concat_f32', x.ptr, x.ld, x.c, None, 0, out.ptr, out.ld, x.n, x.h * x.w, cx.stream)
@@ -772,6 +828,7 @@ def view(x, h, w, c):
 
 def concat_batch(acts):
     """tf.concat(acts, 0) of network OUTPUTS: the parts receive views of the concatenated gradient."""
+    require_f32(acts, 'concat_batch')
     from .batching import concat_acts
     cx = ctx()
     out = concat_acts(acts)
@@ -793,6 +850,7 @@ def concat_batch(acts):
 def activation(x, act, alpha=0.2):
     """y = act(x) as its own launch (an activation CALLED on a tensor, e.g. Good_GAN_cifar10.leakyReLu(x), NN_Base._relu(x)); the models
     pass their activations as `nonlinearity=` / `activation=` instead and get them fused into the producing kernel's epilogue."""
+    require_f32(x, 'activation')
     cx = ctx()
     y = cx.new_act(x.n, x.h, x.w, x.c, x.ld, requires_grad=x.requires_grad)
     y.strided_grad_ok = True
@@ -809,6 +867,7 @@ def batch_norm_moments(x, scale, beta, pop_mean, pop_var, eps, decay, train, sca
     """nn.batch_norm_impl (Model/nn.py:192-217): tf.nn.moments + tf.nn.batch_normalization with the running statistics updated
     as pop <- pop*decay + batch*(1-decay) from the BIASED batch variance (tf.nn.moments; contrib's fused batch_norm — ops.batch_norm_train —
     feeds the unbiased one), or, train=False, normalisation by the running statistics.  Two-pass centred variance as tf.nn.moments."""
+    require_f32(x, 'batch_norm_moments')
     cx = ctx()
     c = x.c
     if not train:
@@ -845,6 +904,7 @@ def moments_normalize(x, eps, init_scale=1.0):
     """scale_init * (x - m_init) with m, v = tf.nn.moments(x, all axes but the last), scale_init = init_scale / sqrt(v + eps): the value
     the data-dependent-initialisation branch (init=True) of the Salimans layers returns (Model/nn.py:230-243,263-277,302-316).
     Forward only (the reference never differentiates that branch: its models call it once to create variables)."""
+    require_f32(x, 'moments_normalize')
     cx = ctx()
     c = x.c
     s1, _ = colstats(0, x.t, x.ld, None, 0, x.rows, c, [x.rows])

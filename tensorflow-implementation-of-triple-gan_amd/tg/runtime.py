@@ -24,12 +24,19 @@ def pad32(c):
 
 class Act(object):
     """Handle of an NHWC activation buffer: logical shape [n,h,w,c], channel stride ld >= c
-    (channels c..ld are zero when the buffer feeds an MFMA kernel)."""
-    __slots__ = ('t', 'n', 'h', 'w', 'c', 'ld', 'grad', 'requires_grad', 'strided_grad_ok', 'grad_sink', 'grad_fused', 'pending', 'bias_sink',
+    (channels c..ld are zero when the buffer feeds an MFMA kernel).
+    dtype: storage type of the elements — 'f32', or 'bf16' (config.ACT_DTYPE: a batch norm's output whose only reader is a bf16-operand
+    convolution; t is then a torch.bfloat16 view of the workspace, ld and the offsets count bf16 elements).  Only the ops that name a
+    bf16 reader accept such a handle (ops.require_f32)."""
+    __slots__ = ('t', 'n', 'h', 'w', 'c', 'ld', 'dtype', 'grad', 'requires_grad', 'strided_grad_ok', 'grad_sink', 'grad_fused', 'pending', 'bias_sink',
                  'grad_is_dpre', 'bn_sums', 'bn_bwd_sink', 'bn_bwd_sums', 'contribs', 'labels')
 
-    def __init__(self, t, n, h, w, c, ld, requires_grad=False):
-        self.t, self.n, self.h, self.w, self.c, self.ld = t, n, h, w, c, ld
+    def __init__(self, t, n, h, w, c, ld, requires_grad=False, dtype='f32'):
+        if dtype not in ('f32', 'bf16'):
+            raise lib.TgError("Act dtype must be 'f32' or 'bf16', got %r" % (dtype,))
+        if t is not None and (t.dtype == torch.bfloat16) != (dtype == 'bf16'):
+            raise lib.TgError("Act dtype %r does not match its storage (%s)" % (dtype, t.dtype))
+        self.t, self.n, self.h, self.w, self.c, self.ld, self.dtype = t, n, h, w, c, ld, dtype
         self.grad = None
         self.requires_grad = requires_grad
         self.strided_grad_ok = False      # set by producers whose backward reads .grad through (pointer, channel stride) only
@@ -55,14 +62,14 @@ class Act(object):
         return C.c_void_p(self.t.data_ptr())
 
     def numpy(self):
-        """logical [n,h,w,c] (or [n,c] when h=w=1) host copy — tests / evaluation only."""
-        a = self.t.detach().cpu().numpy().reshape(self.n, self.h, self.w, self.ld)[..., :self.c]
+        """logical [n,h,w,c] (or [n,c] when h=w=1) host copy, fp32 whatever the storage type — tests / evaluation only."""
+        a = self.t.detach().float().cpu().numpy().reshape(self.n, self.h, self.w, self.ld)[..., :self.c]
         return a.reshape(self.n, self.c) if self.h == 1 and self.w == 1 else a
 
     def view_rows(self, r0, r1):
         """sub-batch [r0:r1) of images sharing the same storage."""
         per = self.h * self.w * self.ld
-        return Act(self.t[r0 * per:r1 * per], r1 - r0, self.h, self.w, self.c, self.ld, self.requires_grad)
+        return Act(self.t[r0 * per:r1 * per], r1 - r0, self.h, self.w, self.c, self.ld, self.requires_grad, self.dtype)
 
 
 class ParamStore(object):
@@ -328,7 +335,11 @@ class Context(object):
         self.rng = PhiloxRNG(seed, self.device)
         self.train_nets = set()
         self._stream = None
-        self.mfma_dtype = 'f32'          # 'bf16': MFMA operands rounded to bf16 inside the kernels (tensors stay fp32)
+        self.mfma_dtype = 'f32'          # 'bf16': MFMA operands rounded to bf16 inside the kernels (tensors in HBM fp32, except below)
+        self.act_dtype = 'f32'           # 'bf16' (needs mfma_dtype 'bf16'): the batch norms a model marks (Model/Good_GAN.py, the SVHN classifier)
+                                         # store their output as bf16 — its only reader is a bf16-operand 3x3 convolution, which rounds each
+                                         # value to exactly those bits itself, so the step computes the same numbers with half the bytes
+        self.bf16_act_layers = set()     # scopes of the batch norms that have stored a bf16 output (Train.bf16_act_edges)
 
     # ---- streams ---------------------------------------------------------------------------------
     @property
@@ -376,11 +387,16 @@ class Context(object):
             lib.call('tg_fill_f32', lib.ptr(t), 0.0, int(numel), self.stream)
         return t[:numel]
 
-    def new_act(self, n, h, w, c, ld=None, requires_grad=False, tag='a'):
+    def new_act(self, n, h, w, c, ld=None, requires_grad=False, tag='a', dtype='f32'):
+        """dtype 'bf16': the same call-site buffer of the fp32 workspace, half as many words, seen as torch.bfloat16 (zero-filled on
+        allocation like every workspace buffer: the padding channels c..ld read as bf16 zeros)."""
         ld = c if ld is None else ld
         self.counter += 1
         key = '%s/%s%d' % (self.phase, tag, self.counter)
-        return Act(self.ws(key, n * h * w * ld), n, h, w, c, ld, requires_grad)
+        numel = n * h * w * ld
+        if dtype == 'bf16':
+            return Act(self.ws(key, (numel + 1) // 2).view(torch.bfloat16)[:numel], n, h, w, c, ld, requires_grad, 'bf16')
+        return Act(self.ws(key, numel), n, h, w, c, ld, requires_grad)
 
     def scratch(self, tag, numel):
         self.counter += 1

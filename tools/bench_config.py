@@ -3,6 +3,8 @@
 
     python tools/bench_config.py --config stress64   synthetic 64x64x3, bs 256, deeper G/D/C (configs[4]; HBM-side roofline capture)
     python tools/bench_config.py --config svhn-bf16  SVHN 32x32x3, Good_GAN svhn, bf16 MFMA conv path (configs[3])
+    python tools/bench_config.py --config svhn-bf16-act   the same with ACT_DTYPE = 'bf16' (the classifier's four batch-norm -> 3x3 conv edges
+                                                     stored as bf16; the launches' algorithmic bytes count 2 bytes per such element)
     python tools/bench_config.py --config svhn       the same in fp32
     python tools/bench_config.py --config mnist      MNIST 28x28x1, Good_GAN mnist (configs[0] shape)
     python tools/bench_config.py --config cifar10[-bf16]   the bench.py workload (Good_GAN_cifar10, synthetic ZCA), fp32 / bf16 operands
@@ -34,6 +36,7 @@ SHAPES = {   # name: (data, H, C, B_G, L_C, U_C, L_D, U_D, mfma dtype, lambda_1,
     'stress64': ('stress64', 64, 3, 256, 128, 128, 51, 205, 'f32', 0.3, 3e-4, 3e-3),
     'svhn': ('svhn', 32, 3, 100, 50, 50, 20, 80, 'f32', 0.1, 3e-4, 3e-4),
     'svhn-bf16': ('svhn', 32, 3, 100, 50, 50, 20, 80, 'bf16', 0.1, 3e-4, 3e-4),
+    'svhn-bf16-act': ('svhn', 32, 3, 100, 50, 50, 20, 80, 'bf16', 0.1, 3e-4, 3e-4),      # + ACT_DTYPE = 'bf16' (bf16-stored batch-norm outputs)
     'mnist': ('mnist', 28, 1, 100, 100, 100, 20, 80, 'f32', 0.1, 1e-3, 3e-4),
     'cifar10': ('cifar10', 32, 3, 100, 50, 50, 20, 80, 'f32', 0.3, 3e-4, 3e-3),
     'cifar10-bf16': ('cifar10', 32, 3, 100, 50, 50, 20, 80, 'bf16', 0.3, 3e-4, 3e-3),
@@ -69,6 +72,7 @@ def make_config(name='stress64'):
         EXEC_MODE = os.environ.get('TG_EXEC_MODE', 'auto')
         SEED = 0
         MFMA_DTYPE = prec
+        ACT_DTYPE = 'bf16' if name.endswith('-act') else 'f32'
 
     return TempConfig()
 
@@ -168,6 +172,7 @@ def main():
     print(json.dumps({"workload": "%s: synthetic %dx%dx%d, B_G/L_C/U_C/L_D/U_D=%d/%d/%d/%d/%d, %s D+G+C step, MFMA operands %s" % (
                           args.config, cfg.IMAGE_HEIGHT, cfg.IMAGE_WIDTH, cfg.CHANNEL, cfg.BATCH_SIZE_G, cfg.BATCH_SIZE_L_C, cfg.BATCH_SIZE_U_C,
                           cfg.BATCH_SIZE_L_D, cfg.BATCH_SIZE_U_D, Model.__name__, cfg.MFMA_DTYPE),
+                      "act_dtype": cfg.ACT_DTYPE, "bf16_act_edges": tr.bf16_act_edges,
                       "ms_per_step": round(dt * 1e3, 3), "images_per_sec": round(cfg.BATCH_SIZE_G / dt, 1), "steps": args.steps, "hbm_gib_allocated": round(mem, 2),
                       "host_issue_ms_per_step": round(t_issue_free * 1e3, 3), "host_issue_ms_per_step_queue_full": round(t_issue * 1e3, 3),
                       "largest_mfma_launches": largest, "exec_mode": cfg.EXEC_MODE, "exec_mode_chosen": tr.exec_mode_chosen()[0] if cfg.EXEC_MODE == 'auto' else cfg.EXEC_MODE,
