@@ -258,6 +258,9 @@ int64_t tg_filter_workspace_bytes(int n_taps, int c_in_pad, int c_out_pad);
  * tile straddles at most one segment boundary), and whether tg_igemm_colsum_f32 / tg_igemm_actsum_f32 accept (d, seg_rows): 1 / 0. */
 int tg_igemm_tile(const tg_igemm_desc* descs, int n_desc, const int32_t* seg_rows, int nseg, int bf16, int32_t* bm_out, int32_t* bn_out);
 int tg_igemm_colsum_supported(const tg_igemm_desc* d, const int32_t* seg_rows, int nseg);
+/* the filter-gradient tile (CT x NT: reduction channels x output channels) tg_wgrad_f32 / _bf16 launch on the generic kernel:
+ * tg::wgrad_tile of ld_in and of c_out (csrc/geom.cpp).  Host query, no device work. */
+int tg_wgrad_tile(const tg_igemm_desc* d, int32_t* ct_out, int32_t* nt_out);
 
 /* The halo-tiled 3x3 / stride-1 / SAME kernel (csrc/conv3x3_bf16.hip) behind tg_igemm_{f32,bf16} and tg_igemm_colsum_{f32,bf16}:
  * one 256-pixel tile of whole image rows per workgroup, the halo loaded once for the nine taps.  policy 0 (default): taken where the

@@ -55,7 +55,11 @@ namespace tg {
 // ---- tile pick of igemm_impl (csrc/igemm.hip) — the quantisation cost model, see the comments there ------------------------------------
 bool igemm_pick_tile(const tg_igemm_desc* descs, int n_desc, bool colsum, const int32_t* seg_rows, int nseg, bool bf16, int* bm_out, int* bn_out) {
   struct Cand { int bm, bn; double eff; };
-  const Cand cands[] = {{128, 128, 1.00}, {64, 128, 0.97}, {64, 64, 1.02}, {128, 64, 0.95}, {32, 128, 0.85}, {128, 32, 0.70}};
+  // No 128 x 64 candidate: it could never win.  Wherever it is allowed, 64 x 64 is too (same BN; a smaller BM passes the segment rule),
+  // and ceil(M / 64) <= 2 ceil(M / 128) means 64 x 64 never takes more than twice its rounds at half the tile area; 64 x 64's worst
+  // efficiency (0.96, bf16) against 128 x 64's 0.95 makes its charged cost strictly lower: 2 * 4096 / 0.96 = 8533 < 8192 / 0.95 = 8623 per
+  // 128 x 64 round.  The same bound holds for the mixed-sub-problem formula below (twice the tiles give at most twice its load).
+  const Cand cands[] = {{128, 128, 1.00}, {64, 128, 0.97}, {64, 64, 1.02}, {32, 128, 0.85}, {128, 32, 0.70}};
   const tg_igemm_desc* d = &descs[0];
   const int64_t M = (int64_t)d->n_img * d->h_v * d->w_v;
   double taps = 0;
@@ -358,6 +362,13 @@ int tg_igemm_tile(const tg_igemm_desc* descs, int n_desc, const int32_t* seg_row
   TG_REQUIRE(tg::igemm_pick_tile(descs, n_desc, nseg > 0, seg_rows, nseg, bf16 != 0, &bm, &bn), "igemm_tile: no tile fits c_out=%d with the given segments",
              descs[0].c_out);
   *bm_out = bm; *bn_out = bn;
+  return TG_OK;
+}
+
+int tg_wgrad_tile(const tg_igemm_desc* d, int32_t* ct_out, int32_t* nt_out) {
+  TG_REQUIRE(d && ct_out && nt_out && d->ld_in > 0 && d->c_out > 0, "wgrad_tile: bad arguments");
+  *ct_out = tg::wgrad_tile(d->ld_in);
+  *nt_out = tg::wgrad_tile(d->c_out);
   return TG_OK;
 }
 

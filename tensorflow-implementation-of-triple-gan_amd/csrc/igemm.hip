@@ -1212,7 +1212,6 @@ static int igemm_impl(const tg_igemm_desc* descs, int n_desc, const float* in, c
   for (int i = 0; i < 16; ++i) { p.pat_sub[i] = sc.pat_sub[i]; p.pat_k[i] = sc.pat_k[i]; p.pat_slot[i] = sc.pat_slot[i]; }
   p.ws = static_cast<float*>(scratch);
   if (bm == 128 && bn == 128) launch_igemm<128, 128, 2, 2>(p, s, bf16);
-  else if (bm == 128 && bn == 64) launch_igemm<128, 64, 2, 2>(p, s, bf16);
   else if (bm == 64 && bn == 128) launch_igemm<64, 128, 2, 2>(p, s, bf16);
   else if (bm == 64 && bn == 64) launch_igemm<64, 64, 2, 2>(p, s, bf16);
   else if (bm == 32 && bn == 128) launch_igemm<32, 128, 1, 4>(p, s, bf16);

@@ -1,4 +1,5 @@
-"""Shared checks of the per-kernel float64 tests (tests/test_gpu_elementwise.py, _prep.py, _norm_finalize.py, _loss_heads.py).
+"""Shared checks of the per-kernel float64 tests (tests/test_gpu_elementwise.py, _prep.py, _norm_finalize.py, _loss_heads.py, _gemm_tiles.py),
+and the float64 oracle of an implicit-GEMM descriptor (igemm_ref64, on the device).
 
 Every output a test reads is allocated by `guarded`: the buffer is followed by GUARD floats holding a fixed bit pattern, and the output
 itself starts as NaN.  After the launch every element the kernel owns must hold a number (no NaN left = it was written), the guard must
@@ -190,3 +191,42 @@ def y_for(rng, shape, a):
     x[..., ::7] = 0
     y = act64(x, a)
     return y.astype(np.float32)
+
+
+# ---- float64 oracle of a tg_igemm_desc (csrc/igemm.hip's operation restated on the device in torch float64) ----
+def igemm_gather(x, d, tap):
+    """rows of the gathered operand of tap `tap` of descriptor d: x [n, h_in, w_in, ld_in] -> [M, ld_in], zeros outside the image."""
+    dy, dx = int(d.dy[tap]), int(d.dx[tap])
+    iy = torch.arange(d.h_v, device=x.device) * d.s_y + dy
+    ix = torch.arange(d.w_v, device=x.device) * d.s_x + dx
+    my, mx = (iy >= 0) & (iy < d.h_in), (ix >= 0) & (ix < d.w_in)
+    g = x[:, iy.clamp(0, d.h_in - 1)][:, :, ix.clamp(0, d.w_in - 1)]
+    g = g * (my[:, None] & mx[None, :]).to(x.dtype)[None, :, :, None]
+    return g.reshape(-1, d.ld_in)
+
+
+def igemm_filter(wf, d, tap):
+    """[c_out, ld_in] filter rows of tap `tap`: w[n * w_sn + tapw * w_st + c]."""
+    return wf.as_strided((d.c_out, d.ld_in), (d.w_sn, 1), int(d.tapw[tap]) * d.w_st)
+
+
+def igemm_ref64(descs, x, wf):
+    """float64 accumulators of every descriptor: [(acc, sum|a||b|, the last K-tile's share of acc)], each [M, c_out].  The last K-tile is
+    channels [ld_in - 32, ld_in) of the descriptor's last tap."""
+    out = []
+    for d in descs:
+        acc = sab = last = None
+        for t in range(d.n_taps):
+            a, w = igemm_gather(x, d, t), igemm_filter(wf, d, t)
+            p, s = a @ w.T, a.abs() @ w.abs().T
+            acc = p if acc is None else acc + p
+            sab = s if sab is None else sab + s
+        last = a[:, -32:] @ w[:, -32:].T
+        out.append((acc, sab, last))
+    return out
+
+
+def igemm_scatter(d, vals, out):
+    """store [M, n_store] rows of descriptor d into out [n, h_out, w_out, ld_out] as the kernel does."""
+    v = vals.reshape(d.n_img, d.h_v, d.w_v, -1)
+    out[:, d.oo_y::d.os_y, d.oo_x::d.os_x][:, :d.h_v, :d.w_v, :d.n_store] = v[..., :d.n_store]

@@ -72,7 +72,7 @@ def test_tile_and_colsum_rules_live_in_the_library():
     big = geom.conv_fwd(250, 32, 32, 128, 128, 3, 1, 'SAME')
     assert tile(big) == (64, 64)                                     # 64x64 tiles interleave their epilogues
     assert tile(big, bf16=True) == (128, 128)                        # bf16 operands: conversion work favours the large tile
-    assert tile(geom.dense_fwd(100, 128, 8192)) in ((32, 128), (64, 128), (64, 64), (128, 128), (128, 64))
+    assert tile(geom.dense_fwd(100, 128, 8192)) in ((32, 128), (64, 128), (64, 64), (128, 128))
     # colsum: every segment at least as long as some tile that divides c_out, at most 8 segments, rows must add up
     assert geom.colsum_supported(big, [50 * 1024, 50 * 1024, 50 * 1024, 100 * 1024])
     assert not geom.colsum_supported(big, [250 * 1024 - 16, 16])     # a 16-row segment is shorter than every tile
@@ -98,3 +98,14 @@ def test_wgrad_split_rule_for_bf16_operands():
     for n, hw, ci, co, k, s in ((250, 8, 256, 512, 3, 1), (100, 32, 32, 64, 3, 2), (250, 6, 512, 256, 1, 1)):      # width 8 / stride 2 / 1x1: generic rule
         d = geom.conv_wgrad(n, hw, hw, ci, co, k, s, 'SAME')
         assert geom.wgrad_splits(d, True) == geom.wgrad_splits(d)
+
+
+def test_wgrad_tile_query_equals_the_rule():
+    """tg_wgrad_tile (host query) = tg::wgrad_tile of ld_in and c_out: the widest of 128 / 64 / 32 that divides the channel count, 64 from 160
+    on (an overhanging last tile instead of 32-wide ones)."""
+    rule = lambda n: 128 if n % 128 == 0 else (64 if n % 64 == 0 or n >= 160 else 32)
+    assert [rule(n) for n in (32, 64, 96, 128, 160, 288, 544)] == [32, 64, 32, 128, 64, 64, 64]
+    for ci, co in itertools.product((32, 64, 96, 128, 160, 288, 544), repeat=2):
+        ct, nt = C.c_int32(), C.c_int32()
+        lib.call('tg_wgrad_tile', C.byref(geom.conv_wgrad(2, 6, 6, ci, co, 3, 1, 'SAME')), C.byref(ct), C.byref(nt))
+        assert (ct.value, nt.value) == (rule(ci), rule(co)), (ci, co)

@@ -269,6 +269,41 @@ def _run_both(lib, name, args, out, colsum=None):
     return res[0], res[2]
 
 
+
+_ACT_NAME = {0: None, 1: 'lrelu', 2: 'relu', 3: 'tanh'}
+
+
+def _f64_check(prec, descs, x, w, bias, outs, yact=None, what=''):
+    """every output of `outs` (device tensors in the output layout, all from the same launch geometry) within the float64 bound of the
+    descriptors' operation on the same operands (kernel_check.igemm_ref64; bf16: rounded as the kernel rounds them).  yact: the
+    tg_igemm_actsum_* multiplier act'(yact) (leaky relu)."""
+    import kernel_check as kc
+    q = lambda t: torch.from_numpy(_q(prec, t.float().cpu().numpy())).double().cuda()
+    d0 = descs[0]
+    xq, wq = q(x).reshape(d0.n_img, d0.h_in, d0.w_in, d0.ld_in), q(w).reshape(-1)
+    shape = (d0.n_img, d0.h_out, d0.w_out, d0.ld_out)
+    ref = torch.zeros(shape, dtype=torch.float64, device='cuda')
+    sab = torch.zeros_like(ref)
+    b64 = bias.double() if bias is not None else torch.zeros(d0.c_out, dtype=torch.float64, device='cuda')
+    for d, (acc, s_, _) in zip(descs, kc.igemm_ref64(descs, xq, wq)):
+        if yact is not None:
+            y = yact.double()[:, d.oo_y::d.os_y, d.oo_x::d.os_x][:, :d.h_v, :d.w_v].reshape(-1, d.ld_out)[:, :d.c_out]
+            g = torch.where(y > 0, torch.ones_like(y), torch.full_like(y, float(np.float32(0.2))))
+            kc.igemm_scatter(d, acc * g, ref)
+            kc.igemm_scatter(d, s_ * g, sab)
+            continue
+        t = acc + b64
+        a = _ACT_NAME[d.act]
+        t = torch.where(t > 0, t, float(np.float32(d.alpha)) * t) if a == 'lrelu' else torch.relu(t) if a == 'relu' else t
+        assert a in (None, 'lrelu', 'relu')
+        kc.igemm_scatter(d, t, ref)
+        kc.igemm_scatter(d, s_ + b64.abs(), sab)
+    for got in outs:
+        g = got.reshape(shape)[..., :d0.n_store].double()
+        r = float(((g - ref[..., :d0.n_store]).abs() / (TOL * sab[..., :d0.n_store] + 1e-300)).max())
+        assert r <= 1.0, "%s: error is %.2f x the float64 bound (TOL %.0e of the per-output sum |a||b|)" % (what, r, TOL)
+
+
 @pytest.mark.parametrize("prec", PRECS)
 def test_cut_tiles_of_under_filled_launches(prec):
     import ctypes as C
@@ -299,6 +334,7 @@ def test_cut_tiles_of_under_filled_launches(prec):
             scale = float(x.abs().max() * w.abs().max()) * d.n_taps * d.ld_in
             assert float((a - b).abs().max()) <= 3e-5 * scale, (tag, float((a - b).abs().max()), scale)
             assert float(a.abs().max()) > 0 and not bool((a == 7.0).any()), tag
+            _f64_check(prec, [d], x, w, bias, (a, b), what=tag)      # cut and uncut launch against float64
     finally:
         lib.call('tg_conv3x3_policy', was)
 
@@ -362,6 +398,7 @@ def test_cut_tiles_with_column_sums_and_activation_gradient(prec, n, hw, ci, co,
             assert np.abs(cs_a - cs_b).max() <= 3e-5 * scale * max(segs), name
             ref = np.stack([a.cpu().numpy().reshape(-1, co)[:segs[0]].astype(np.float64).sum(0), a.cpu().numpy().reshape(-1, co)[segs[0]:].astype(np.float64).sum(0)])
             assert np.abs(cs_a.reshape(2, co) - ref).max() <= 1e-4 * max(1.0, np.abs(ref).max()), name      # the sums are of the stored values
+            _f64_check(prec, [d], x, w, None, (a, b), yact=yact if 'actsum' in name else None, what=name)      # cut and uncut against float64
     finally:
         lib.call('tg_conv3x3_policy', was)
 

@@ -521,6 +521,19 @@ def test_filter_gradient_with_the_activation_tile_read_once_equals_the_generic_k
     assert got[0][0] * (cin // 32) * (cout // 128) in (256, 2 * 256 // 2) and got[0][0] != got[2][0]
     scale = float(x.abs().max()) * float(dy.abs().max()) * np.sqrt(n * hw * hw)          # random-sign sums grow like sqrt(pixels)
     assert np.abs(got[0][1] - got[2][1]).max() <= (2e-2 if prec == 'bf16' else 2e-5) * scale * 4
+    # both against float64 on the same operands (bf16: rounded as the kernels round them), at the 1e-6 bound of tests/test_gpu_igemm.py
+    # (the oracle runs on the device in float64: kernel_check.igemm_gather gives the gathered rows of each tap)
+    import kernel_check as kc
+    q = (lambda a: T.bf16_round(a)) if prec == 'bf16' else (lambda a: a)
+    xq, dq = (torch.from_numpy(q(t.cpu().numpy()).astype(np.float64)).cuda() for t in (x, dy))
+    dm = dq.reshape(-1, cout)
+    dw_ref, dw_abs = np.zeros((9, cin, cout)), np.zeros((9, cin, cout))
+    for t in range(9):
+        a = kc.igemm_gather(xq, d, t)
+        dw_ref[t], dw_abs[t] = (a.T @ dm).cpu().numpy(), (a.abs().T @ dm.abs()).cpu().numpy()
+    for policy in (0, 2):
+        r = float((np.abs(got[policy][1] - dw_ref) / (1e-6 * dw_abs + 1e-300)).max())
+        assert r <= 1.0, "policy %d: error is %.2f x the float64 bound" % (policy, r)
 
 
 @pytest.mark.parametrize("prec", ['f32', 'bf16'])
