@@ -531,6 +531,23 @@ int tg_true_fake_loss_f32(const float* unl_logits, int ld_u, int n_unl, const fl
 /* T = mean_n sum_k (a - b)^2 (train_base.py:299); loss[2] = {w T, T}; da / db (either may be NULL) written or added. */
 int tg_sqdiff_rows_loss_f32(const float* a, int ld_a, const float* b, int ld_b, int n, int k, float w, float* da, int ld_da, int accumulate_a,
                             float* db, int ld_db, int accumulate_b, float* loss, void* stream);
+/* ---- WGAN-GP (_loss_WGAN_GP / _gradient_penalty, train_base.py:576-620; csrc/wgan_gp.hip) ----------------------------------------
+ * tg_wgan_interp_f32   out[i,p,k] = real + alpha[i] (fake - real) for k < c, 0 for c <= k < ld_out (interpolate, :601-606); hw pixels per
+ *                      image, alpha: device [n].
+ * tg_grad_penalty_f32  gx [n,h,w,ld_g] (c logical channels): s[i,x,k] = sqrt(sum_y gx[i,y,x,k]^2) — reduce_sum over axis 1 of NHWC, i.e. H
+ *                      (:610); gp[0] = weight * mean over n*w*c of (s - 1)^2, r = weight * 2 (s - 1) / s * gx / (n w c) with ld_r, padding
+ *                      columns c..ld_r written 0 (s = 0 gives non-finite r, as TF's sqrt gradient does).  partials: scratch of
+ *                      ceil(n*w*ld_r / 256) doubles.  Two launches (columns, then one workgroup sums the partials in index order).
+ * tg_wgan_loss_f32     rows [real | fake | unl] (column 0, row stride ld): loss[5] = {d_loss without the penalty, g_loss, wd1, wd2, wd3},
+ *                      wd1 = (mean real - mean fake)/2, wd2 = (mean real - mean unl)/2, wd3 = (mean unl - mean fake)/2,
+ *                      d_loss = -(wd1 + lambda_1 wd2 + lambda_2 wd3), g_loss = -mean fake (:577-589); dlogits = d d_loss / d logits
+ *                      (stride ld_d), dfake = d g_loss / d fake logits (stride ld_df; may be NULL); padding columns written 0. */
+int tg_wgan_interp_f32(const float* real, int ld_r, const float* fake, int ld_f, const float* alpha, float* out, int ld_out, int n, int hw, int c,
+                       void* stream);
+int tg_grad_penalty_f32(const float* gx, int ld_g, int n, int h, int w, int c, float weight, float* r, int ld_r, double* partials, float* gp,
+                        void* stream);
+int tg_wgan_loss_f32(const float* logits, int ld, int n_real, int n_fake, int n_unl, float lambda_1, float lambda_2, float* dlogits, int ld_d,
+                     float* dfake, int ld_df, float* loss, void* stream);
 /* minibatch discrimination (Model/modle_base.py:110-128): act = x @ W viewed [n][kernels][dim] (dim <= 8);
  * out[i] = [x[i,:c], f[i,:], 0...] with f[i,k] = sum_j exp(-sum_d |act[i,k,d] - act[j,k,d]|) + b[k].
  * bwd: df = the gradient's columns c.. ([n][kernels], stride ld_df) -> dact (pads zeroed), db[k] = sum_i df[i,k] (db may be NULL). */

@@ -315,3 +315,82 @@ class Train_base(object):
     def _loss_GoodRegGAN_BS_cifar10(self, D, C, Y, Lambda):
         """train_base.py:444-515 (config.FAST_MODE drops the generated-sample cross-entropy)."""
         return self._good_reg(D, C, Y, Lambda, 'BS_cifar10')
+
+    # ---- WGAN-GP (train_base.py:576-620) --------------------------------------------------------------------------------------------
+    # The penalty differentiates the discriminator's input gradient; with its dropout masks fixed the network is piecewise linear in the
+    # image, so the model computes d gp / d theta_D with four first-order sweeps (Model/Good_GAN_cifar10.discriminator_gradient_penalty,
+    # DESIGN §9.1).  It goes to a flat buffer laid out like the discriminator's ParamStore.g, `self.last_gp_grad`, never into store.g
+    # (the caller's D backward owns that, and its filter-gradient launches overwrite); `_add_gp_grad()` adds it once that backward ran.
+
+    @staticmethod
+    def _gp_sweeps(f):
+        """the model method behind the discriminator callable `f` (a bound Model.discriminator, or the model itself)."""
+        model = getattr(f, '__self__', f)
+        fn = getattr(model, 'discriminator_gradient_penalty', None)
+        if fn is None:
+            raise lib.TgError("_gradient_penalty: %s has no discriminator_gradient_penalty; WGAN-GP is implemented for the CIFAR-10 "
+                              "discriminator family (Good_GAN_cifar10, Good_GAN_stress64) only — the weight-norm / minibatch-discrimination "
+                              "discriminators of Good_GAN (MNIST / SVHN) are not piecewise linear in the image" % type(model).__name__)
+        return fn
+
+    def _gradient_penalty(self, real, fake, label, f, weight=1.0):
+        """train_base.py:598-620: gp = mean((sqrt(reduce_sum(gx^2, axis=1)) - 1)^2) with gx = d sum(logits) / dx at x = real + alpha
+        (fake - real), alpha ~ U[0,1) per image ('GP/alpha').  real, fake: Act [N,H,W,3]; label: Act [N,NUM_CLASSES]; f: the
+        discriminator (its logits, element [1] of the pair it returns, are differentiated).  Returns weight * gp (1-element device tensor)
+        and leaves weight * d gp / d theta_D in self.last_gp_grad.  No gradient reaches the generator or `real` (TF's d_solver)."""
+        if not (real.n == fake.n == label.n):
+            raise lib.TgError("_gradient_penalty: batch sizes differ (real %d, fake %d, labels %d)" % (real.n, fake.n, label.n))
+        gp, self.last_gp_grad = self._gp_sweeps(f)(real, fake, label, weight)
+        return gp
+
+    def _loss_WGAN_GP(self, G, D, C, X, Y, Lambda, discriminator):
+        """train_base.py:576-596 -> (d_loss, g_loss, c_loss) as Python floats.  G: the generated images (the penalty's `fake`);
+        D: the reference's 9-tuple (D_real, D_real_logits, fm_real, D_fake, D_fake_logits, fm_fake, D_unl, D_unl_logits, fm_unl; the fm
+        entries may be None) or this port's 6-tuple; C = (C_real_logits, C_fake_logits, C_unlabel_logits); X: real images; Y: their
+        labels (one tensor for both cross-entropies, as the reference); Lambda = (lambda_1, lambda_2).
+        Gradients: self.last_d_cat.grad <- d_loss w.r.t. the [real | fake | unl] logits (without the penalty), D_fake_logits.grad <-
+        g_loss, the three classifier logit tensors' .grad <- c_loss, and self.last_gp_grad <- 10 d gp / d theta_D (add it to the
+        discriminator's store.g after its backward pass: _add_gp_grad)."""
+        import ctypes as C_
+        from tg.batching import concat_acts
+        if len(D) == 9:
+            _, d_real, _, _, d_fake, _, _, d_unl, _ = D
+        elif len(D) == 6:
+            _, d_real, _, d_fake, _, d_unl = D
+        else:
+            raise lib.TgError("_loss_WGAN_GP: D must be the reference's 9-tuple or the 6-tuple of forward_pass, got %d entries" % len(D))
+        c_real, c_fake, c_unl = C
+        lam1, lam2 = (float(v) for v in Lambda[:2])
+        if not (X.n == G.n == Y.n == c_real.n == c_fake.n):
+            raise lib.TgError("_loss_WGAN_GP: batch sizes differ (X %d, G %d, Y %d, C_real %d, C_fake %d)" % (X.n, G.n, Y.n, c_real.n, c_fake.n))
+        cx = ctx()
+        lv = torch.zeros(16, dtype=torch.float32, device=cx.device)
+        P = lambda i: lib.ptr(lv[i:])
+        dcat = concat_acts([d_real, d_fake, d_unl])
+        g = cx.new_act(dcat.n, 1, 1, 1, 32, tag='dl')
+        gf = cx.new_act(d_fake.n, 1, 1, 1, 32, tag='dl')
+        lib.call('tg_wgan_loss_f32', dcat.ptr, dcat.ld, d_real.n, d_fake.n, d_unl.n, lam1, lam2, g.ptr, g.ld, gf.ptr, gf.ld, P(0), cx.stream)
+        dcat.grad, d_fake.grad = g, gf
+        self.last_d_cat = dcat
+        ccat = concat_acts([c_real, c_unl, c_fake])                  # tg_c_loss_terms_f32 rows [real | unl | fake]; the unl terms weigh 0
+        gc = cx.new_act(ccat.n, 1, 1, ccat.c, ccat.ld, tag='dl')
+        lib.call('tg_c_loss_terms_f32', ccat.ptr, ccat.ld, c_real.n, c_unl.n, 0, c_fake.n, Y.ptr, Y.ptr, None, 0,
+                 (C_.c_float * 6)(1.0, 0.0, 0.0, 0.0, lam2, 0.0), gc.ptr, gc.ld, P(5), P(6), cx.stream)
+        ccat.grad = gc
+        off = 0
+        for m in (c_real, c_unl, c_fake):
+            m.grad = gc.view_rows(off, off + m.n)
+            off += m.n
+        gp10 = self._gradient_penalty(X, G, Y, discriminator, weight=10.0)
+        lv[12:13].copy_(gp10)
+        v = [float(x) for x in lv.cpu().numpy()]
+        self.last_wgan_terms = dict(wd1=v[2], wd2=v[3], wd3=v[4], gp=v[12] / 10.0)
+        return v[0] + v[12], v[1], v[5]
+
+    def _add_gp_grad(self, store=None):
+        """store.g += self.last_gp_grad (the discriminator's store by default): call after the D backward pass that wrote store.g."""
+        store = store if store is not None else ctx().stores['discriminator']
+        gp = getattr(self, 'last_gp_grad', None)
+        if gp is None or gp.numel() != store.n_p:
+            raise lib.TgError("_add_gp_grad: no gradient-penalty gradient laid out like store %r (run _gradient_penalty first)" % store.name)
+        lib.call('tg_add_f32', lib.ptr(store.g), lib.ptr(store.g), lib.ptr(gp), store.n_p, ctx().stream)

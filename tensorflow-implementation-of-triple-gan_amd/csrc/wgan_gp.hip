@@ -1,0 +1,165 @@
+// WGAN-GP loss of Train_base (Training/train_base.py:576-620): the interpolation of _gradient_penalty, the penalty on the input
+// gradient of the discriminator, and the WGAN loss head.  The sweeps through the discriminator (forward, input gradient, tangent
+// forward, filter gradients) run on the implicit-GEMM launches; these are the arithmetic around them.  Reductions are deterministic:
+// fixed per-thread orders, fixed block trees, and the block partials of the penalty summed by one workgroup in index order.
+#include "tg_common.h"
+#include "tg_device.h"
+
+namespace {
+
+constexpr int BLK = 256;
+
+// out[i,p,k] = real[i,p,k] + alpha[i]*(fake[i,p,k] - real[i,p,k]) for k < c, 0 for c <= k < ld_out
+__global__ void __launch_bounds__(BLK) wgan_interp(const float* __restrict__ real, int ld_r, const float* __restrict__ fake, int ld_f,
+                                                   const float* __restrict__ alpha, float* __restrict__ out, int ld_out, int n, int hw, int c) {
+  const int64_t total = (int64_t)n * hw * ld_out;
+  for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < total; i += (int64_t)gridDim.x * BLK) {
+    const int64_t row = i / ld_out;
+    const int k = (int)(i - row * ld_out);
+    float v = 0.f;
+    if (k < c) {
+      const float a = real[row * ld_r + k], b = fake[row * ld_f + k];
+      v = a + alpha[row / hw] * (b - a);
+    }
+    out[i] = v;
+  }
+}
+
+__device__ double block_sum_d(double v, double* red) {   // BLK threads = 4 waves, fixed order
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// One thread per column (i, x, k) of the padded [n, w, ld_r] index: s = sqrt(sum_y g[i,y,x,k]^2) (the reference's reduce_sum over
+// axis 1 of an NHWC tensor, i.e. over H), r[i,y,x,k] = weight * 2 (s - 1) / s * g / (n w c); padding columns k >= c get r = 0.
+// partials[block] = sum over the block's columns of (s - 1)^2 in double.
+__global__ void __launch_bounds__(BLK) gp_columns(const float* __restrict__ g, int ld_g, int n, int h, int w, int c, float weight, float* __restrict__ r,
+                                                  int ld_r, double* __restrict__ partials) {
+  __shared__ double red[4];
+  const int64_t cols = (int64_t)n * w * ld_r;
+  const int64_t q = (int64_t)blockIdx.x * BLK + threadIdx.x;
+  double part = 0.0;
+  if (q < cols) {
+    const int64_t ix = q / ld_r;                       // i * w + x
+    const int k = (int)(q - ix * ld_r);
+    const int64_t i = ix / w, x = ix - i * w;
+    const int64_t g0 = (i * h * w + x) * ld_g + k, r0 = (i * h * w + x) * ld_r + k;
+    const int64_t gs = (int64_t)w * ld_g, rs = (int64_t)w * ld_r;
+    if (k < c) {
+      float ss = 0.f;
+      for (int y = 0; y < h; ++y) {
+        const float v = g[g0 + y * gs];
+        ss += v * v;
+      }
+      const float s = sqrtf(ss);
+      const float coef = 2.f * (s - 1.f) / s * (weight / (float)((int64_t)n * w * c));   // s = 0: non-finite, as TF's sqrt gradient
+      for (int y = 0; y < h; ++y) r[r0 + y * rs] = coef * g[g0 + y * gs];
+      const double d = (double)s - 1.0;
+      part = d * d;
+    } else {
+      for (int y = 0; y < h; ++y) r[r0 + y * rs] = 0.f;
+    }
+  }
+  part = block_sum_d(part, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = part;
+}
+
+__global__ void __launch_bounds__(BLK) gp_finish(const double* __restrict__ partials, int nb, double scale, float* __restrict__ gp) {
+  __shared__ double red[4];
+  double v = 0.0;
+  for (int b = threadIdx.x; b < nb; b += BLK) v += partials[b];
+  v = block_sum_d(v, red);
+  if (threadIdx.x == 0) gp[0] = (float)(v * scale);
+}
+
+__device__ float block_sum_f(float v, float* red) {
+  v = tgd::wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+// rows [real | fake | unl] of the discriminator logits (column 0, row stride ld):
+//   wd1 = 1/2 (mean real - mean fake), wd2 = 1/2 (mean real - mean unl), wd3 = 1/2 (mean unl - mean fake)
+//   d_loss = -(wd1 + l1 wd2 + l2 wd3), g_loss = -mean fake;  loss[5] = {d_loss, g_loss, wd1, wd2, wd3}
+__global__ void __launch_bounds__(BLK) wgan_loss(const float* __restrict__ z, int ld, int n_real, int n_fake, int n_unl, float l1, float l2,
+                                                 float* __restrict__ dz, int ld_d, float* __restrict__ dfake, int ld_df, float* __restrict__ loss) {
+  __shared__ float red[4];
+  const int n = n_real + n_fake + n_unl;
+  float s[3] = {0.f, 0.f, 0.f};
+  const float w_real = (-0.5f - 0.5f * l1) / n_real, w_fake = (0.5f + 0.5f * l2) / n_fake, w_unl = (0.5f * l1 - 0.5f * l2) / n_unl;
+  for (int r = threadIdx.x; r < n; r += BLK) {
+    const float v = z[(int64_t)r * ld];
+    const int which = r < n_real ? 0 : (r < n_real + n_fake ? 1 : 2);
+    s[which] += v;
+    float* o = dz + (int64_t)r * ld_d;
+    o[0] = which == 0 ? w_real : (which == 1 ? w_fake : w_unl);
+    for (int k = 1; k < ld_d; ++k) o[k] = 0.f;
+    if (dfake && which == 1) {
+      float* f = dfake + (int64_t)(r - n_real) * ld_df;
+      f[0] = -1.f / n_fake;
+      for (int k = 1; k < ld_df; ++k) f[k] = 0.f;
+    }
+  }
+  const float m_real = block_sum_f(s[0], red) / n_real;
+  const float m_fake = block_sum_f(s[1], red) / n_fake;
+  const float m_unl = block_sum_f(s[2], red) / n_unl;
+  if (threadIdx.x == 0) {
+    const float wd1 = 0.5f * (m_real - m_fake), wd2 = 0.5f * (m_real - m_unl), wd3 = 0.5f * (m_unl - m_fake);
+    loss[0] = -(wd1 + l1 * wd2 + l2 * wd3);
+    loss[1] = -m_fake;
+    loss[2] = wd1;
+    loss[3] = wd2;
+    loss[4] = wd3;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int tg_wgan_interp_f32(const float* real, int ld_r, const float* fake, int ld_f, const float* alpha, float* out, int ld_out, int n, int hw, int c,
+                       void* stream) {
+  TG_REQUIRE(real && fake && alpha && out && n > 0 && hw > 0 && c > 0 && c <= ld_r && c <= ld_f && c <= ld_out,
+             "wgan_interp: bad args (n=%d hw=%d c=%d ld_r=%d ld_f=%d ld_out=%d)", n, hw, c, ld_r, ld_f, ld_out);
+  hipStream_t s = tg::as_stream(stream);
+  const int64_t total = (int64_t)n * hw * ld_out;
+  tg::ProfScope prof(tg::PC_ELEMWISE, 0, 4.0 * (double)n * hw * (2 * c + ld_out), s);
+  const int64_t b = (total + BLK - 1) / BLK;
+  hipLaunchKernelGGL(wgan_interp, dim3((unsigned)(b > 4096 ? 4096 : b)), dim3(BLK), 0, s, real, ld_r, fake, ld_f, alpha, out, ld_out, n, hw, c);
+  TG_CHECK_LAUNCH("wgan_interp");
+  return TG_OK;
+}
+
+int tg_grad_penalty_f32(const float* gx, int ld_g, int n, int h, int w, int c, float weight, float* r, int ld_r, double* partials, float* gp,
+                        void* stream) {
+  TG_REQUIRE(gx && r && partials && gp && n > 0 && h > 0 && w > 0 && c > 0 && c <= ld_g && c <= ld_r,
+             "grad_penalty: bad args (n=%d h=%d w=%d c=%d ld_g=%d ld_r=%d)", n, h, w, c, ld_g, ld_r);
+  const int64_t cols = (int64_t)n * w * ld_r, nb = (cols + BLK - 1) / BLK;
+  TG_REQUIRE(nb < (1LL << 31), "grad_penalty: %lld columns", (long long)cols);
+  hipStream_t s = tg::as_stream(stream);
+  tg::ProfScope prof(tg::PC_LOSS, 0, 4.0 * (double)n * h * w * (2 * c + ld_r), s);
+  hipLaunchKernelGGL(gp_columns, dim3((unsigned)nb), dim3(BLK), 0, s, gx, ld_g, n, h, w, c, weight, r, ld_r, partials);
+  TG_CHECK_LAUNCH("gp_columns");
+  hipLaunchKernelGGL(gp_finish, dim3(1), dim3(BLK), 0, s, partials, (int)nb, (double)weight / (double)((int64_t)n * w * c), gp);
+  TG_CHECK_LAUNCH("gp_finish");
+  return TG_OK;
+}
+
+int tg_wgan_loss_f32(const float* logits, int ld, int n_real, int n_fake, int n_unl, float lambda_1, float lambda_2, float* dlogits, int ld_d,
+                     float* dfake, int ld_df, float* loss, void* stream) {
+  TG_REQUIRE(logits && dlogits && loss && n_real > 0 && n_fake > 0 && n_unl > 0 && ld >= 1 && ld_d >= 1 && (!dfake || ld_df >= 1),
+             "wgan_loss: bad args");
+  hipStream_t s = tg::as_stream(stream);
+  tg::ProfScope prof(tg::PC_LOSS, 0, 0, s);
+  hipLaunchKernelGGL(wgan_loss, dim3(1), dim3(BLK), 0, s, logits, ld, n_real, n_fake, n_unl, lambda_1, lambda_2, dlogits, ld_d, dfake, ld_df, loss);
+  TG_CHECK_LAUNCH("wgan_loss");
+  return TG_OK;
+}
+
+}  // extern "C"

@@ -206,6 +206,14 @@ class InjectedRNG(object):
     def normal(self, ctx, name, n, std):
         return self._get(ctx, name, n)       # injected noise is already scaled by std
 
+    def uniform(self, ctx, name, n, lo, hi, out=None):
+        """injected draws are already in [lo, hi) (the WGAN-GP interpolation weights, 'GP/alpha')."""
+        a = self._get(ctx, name, n)
+        if out is None:
+            return a
+        out.copy_(a)
+        return out
+
     def advance(self, ctx):
         pass
 

@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""Time of Train_base._gradient_penalty (WGAN-GP, reference Training/train_base.py:598-620) on the CIFAR-10 discriminator, eager, fp32,
+at n images (default 100), after warm-up — and, for scale, one plain discriminator forward + backward (weight gradients) at the same n.
+Prints ONE JSON line.
+
+    python tools/bench_wgan_gp.py [--n 100] [--iters 50]
+
+The penalty is four sweeps through the discriminator (forward, input gradient, tangent forward, filter gradients: DESIGN §9.1), so
+about twice a forward + backward is the expectation."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "tensorflow-implementation-of-triple-gan_amd")
+for p in (ROOT, PKG):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+
+
+def timed(fn, iters, warmup=5):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--n', type=int, default=100)
+    ap.add_argument('--iters', type=int, default=50)
+    args = ap.parse_args()
+    from config import Config
+    from Model.Good_GAN_cifar10 import Good_GAN_cifar10
+    from Training.train_base import Train_base
+    from tg import runtime
+
+    class Cfg(Config):
+        Z_DIM, NUM_CLASSES, BATCH_SIZE, IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = 100, 10, 100, 32, 32, 3
+
+    cx = runtime.set_context(runtime.Context())
+    model = Good_GAN_cifar10(Cfg())
+    rng = np.random.default_rng(0)
+    n = args.n
+    real = cx.from_numpy(np.tanh(rng.standard_normal((n, 32, 32, 3))), key='bench:real')
+    fake = cx.from_numpy(np.tanh(rng.standard_normal((n, 32, 32, 3))), key='bench:fake')
+    y = cx.from_numpy(np.eye(10)[rng.integers(0, 10, n)], key='bench:y')
+    tb = Train_base()
+
+    def gp():
+        with cx.phase_scope('bench_gp', record=False):
+            tb._gradient_penalty(real, fake, y, model.discriminator)
+
+    ones = cx.from_numpy(np.ones((n, 1)), ld=32, key='bench:ones')
+
+    def d_fwd_bwd():
+        with cx.phase_scope('bench_d', train_nets=('discriminator',)):
+            with cx.rng_scoped('bench_d/D'):
+                _, lg = model.discriminator(real, y, want_prob=False)
+            lg.grad = ones
+            cx.backward()
+
+    ms_gp = timed(gp, args.iters)
+    ms_d = timed(d_fwd_bwd, args.iters)
+    print(json.dumps(dict(tool='bench_wgan_gp', n=n, iters=args.iters, gradient_penalty_ms=round(ms_gp, 4), d_fwd_bwd_ms=round(ms_d, 4),
+                          ratio=round(ms_gp / ms_d, 3))))
+
+
+if __name__ == '__main__':
+    main()
