@@ -538,6 +538,10 @@ int tg_sqdiff_rows_loss_f32(const float* a, int ld_a, const float* b, int ld_b, 
  *                      (:610); gp[0] = weight * mean over n*w*c of (s - 1)^2, r = weight * 2 (s - 1) / s * gx / (n w c) with ld_r, padding
  *                      columns c..ld_r written 0 (s = 0 gives non-finite r, as TF's sqrt gradient does).  partials: scratch of
  *                      ceil(n*w*ld_r / 256) doubles.  Two launches (columns, then one workgroup sums the partials in index order).
+ * tg_grad_penalty_rows_f32  the same for the port's rank-2 image layout [n, f] (h = w = 1), where axis 1 is the feature axis:
+ *                      s[i] = sqrt(sum_k gx[i,k]^2) per image; gp[0] = weight * mean_i (s - 1)^2, r = weight * 2 (s - 1) / s * gx / n with
+ *                      ld_r, padding columns f..ld_r written 0 (s = 0: non-finite r, not masked).  partials: scratch of n doubles.  Two
+ *                      launches (one workgroup per row, then one workgroup sums the partials in index order): bit-identical run to run.
  * tg_wgan_loss_f32     rows [real | fake | unl] (column 0, row stride ld): loss[5] = {d_loss without the penalty, g_loss, wd1, wd2, wd3},
  *                      wd1 = (mean real - mean fake)/2, wd2 = (mean real - mean unl)/2, wd3 = (mean unl - mean fake)/2,
  *                      d_loss = -(wd1 + lambda_1 wd2 + lambda_2 wd3), g_loss = -mean fake (:577-589); dlogits = d d_loss / d logits
@@ -546,6 +550,7 @@ int tg_wgan_interp_f32(const float* real, int ld_r, const float* fake, int ld_f,
                        void* stream);
 int tg_grad_penalty_f32(const float* gx, int ld_g, int n, int h, int w, int c, float weight, float* r, int ld_r, double* partials, float* gp,
                         void* stream);
+int tg_grad_penalty_rows_f32(const float* gx, int ld_g, int n, int f, float weight, float* r, int ld_r, double* partials, float* gp, void* stream);
 int tg_wgan_loss_f32(const float* logits, int ld, int n_real, int n_fake, int n_unl, float lambda_1, float lambda_2, float* dlogits, int ld_d,
                      float* dfake, int ld_df, float* loss, void* stream);
 /* minibatch discrimination (Model/modle_base.py:110-128): act = x @ W viewed [n][kernels][dim] (dim <= 8);

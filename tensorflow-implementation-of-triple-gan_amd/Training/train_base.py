@@ -317,9 +317,9 @@ class Train_base(object):
         return self._good_reg(D, C, Y, Lambda, 'BS_cifar10')
 
     # ---- WGAN-GP (train_base.py:576-620) --------------------------------------------------------------------------------------------
-    # The penalty differentiates the discriminator's input gradient; with its dropout masks fixed the network is piecewise linear in the
-    # image, so the model computes d gp / d theta_D with four first-order sweeps (Model/Good_GAN_cifar10.discriminator_gradient_penalty,
-    # DESIGN §9.1).  It goes to a flat buffer laid out like the discriminator's ParamStore.g, `self.last_gp_grad`, never into store.g
+    # The penalty differentiates the discriminator's input gradient; with its dropout masks and noise fixed the network is piecewise linear
+    # in the image, so the model computes d gp / d theta_D with four first-order sweeps (Model/Good_GAN_cifar10.py and Model/Good_GAN.py:
+    # discriminator_gradient_penalty).  It goes to a flat buffer laid out like the discriminator's ParamStore.g, `self.last_gp_grad`, never into store.g
     # (the caller's D backward owns that, and its filter-gradient launches overwrite); `_add_gp_grad()` adds it once that backward ran.
 
     @staticmethod
@@ -328,14 +328,16 @@ class Train_base(object):
         model = getattr(f, '__self__', f)
         fn = getattr(model, 'discriminator_gradient_penalty', None)
         if fn is None:
-            raise lib.TgError("_gradient_penalty: %s has no discriminator_gradient_penalty; WGAN-GP is implemented for the CIFAR-10 "
-                              "discriminator family (Good_GAN_cifar10, Good_GAN_stress64) only — the weight-norm / minibatch-discrimination "
-                              "discriminators of Good_GAN (MNIST / SVHN) are not piecewise linear in the image" % type(model).__name__)
+            raise lib.TgError("_gradient_penalty: %s has no discriminator_gradient_penalty; WGAN-GP is implemented for Good_GAN (MNIST / "
+                              "SVHN), Good_GAN_cifar10 and Good_GAN_stress64 — of their discriminators only the one with minibatch "
+                              "discrimination (MINIBATCH_DIS = True) is not piecewise linear in the image, and the model refuses it"
+                              % type(model).__name__)
         return fn
 
     def _gradient_penalty(self, real, fake, label, f, weight=1.0):
         """train_base.py:598-620: gp = mean((sqrt(reduce_sum(gx^2, axis=1)) - 1)^2) with gx = d sum(logits) / dx at x = real + alpha
-        (fake - real), alpha ~ U[0,1) per image ('GP/alpha').  real, fake: Act [N,H,W,3]; label: Act [N,NUM_CLASSES]; f: the
+        (fake - real), alpha ~ U[0,1) per image ('GP/alpha').  real, fake: Act [N,H,W,C], or [N,F] (MNIST: axis 1 is then the feature
+        axis, one slope per image), of one shape; label: Act [N,NUM_CLASSES]; f: the
         discriminator (its logits, element [1] of the pair it returns, are differentiated).  Returns weight * gp (1-element device tensor)
         and leaves weight * d gp / d theta_D in self.last_gp_grad.  No gradient reaches the generator or `real` (TF's d_solver)."""
         if not (real.n == fake.n == label.n):

@@ -76,6 +76,51 @@ __global__ void __launch_bounds__(BLK) gp_finish(const double* __restrict__ part
   if (threadIdx.x == 0) gp[0] = (float)(v * scale);
 }
 
+// One workgroup per image row of a rank-2 input gradient gx [n, f] (the port's [N, F] image layout, h = w = 1): the reference's axis 1
+// is then the feature axis, s_i = sqrt(sum_k gx[i,k]^2), r[i,k] = weight * 2 (s_i - 1) / s_i * gx[i,k] / n, padding columns f..ld_r
+// written 0, partials[i] = (s_i - 1)^2 in double.  Loads are coalesced across the row (float4 where the layout allows, V = 4); the
+// row's first RB*BLK vectors (RB per thread) stay in registers between the sum and the r write, longer rows re-read the rest.  The sum is
+// taken in double in a fixed order (per-thread strides, then block_sum_d): bit-identical run to run.
+constexpr int RB = 4;
+
+__device__ __forceinline__ double sq_sum(float v) { return (double)v * v; }
+__device__ __forceinline__ double sq_sum(float4 v) { return (((double)v.x * v.x + (double)v.y * v.y) + (double)v.z * v.z) + (double)v.w * v.w; }
+__device__ __forceinline__ float scaled(float v, float a) { return v * a; }
+__device__ __forceinline__ float4 scaled(float4 v, float a) { return make_float4(v.x * a, v.y * a, v.z * a, v.w * a); }
+template <typename T> __device__ __forceinline__ T zero_of();
+template <> __device__ __forceinline__ float zero_of<float>() { return 0.f; }
+template <> __device__ __forceinline__ float4 zero_of<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+
+template <typename T>
+__global__ void __launch_bounds__(BLK) gp_rows(const float* __restrict__ g, int ld_g, int f, float weight, int n, float* __restrict__ r, int ld_r,
+                                               double* __restrict__ partials) {
+  __shared__ double red[4];
+  constexpr int V = sizeof(T) / sizeof(float);
+  const int64_t i = blockIdx.x;
+  const T* __restrict__ gi = reinterpret_cast<const T*>(g + i * ld_g);
+  T* __restrict__ ri = reinterpret_cast<T*>(r + i * ld_r);
+  const int fv = f / V, lv = ld_r / V;
+  T keep[RB];
+  double ss = 0.0;
+#pragma unroll
+  for (int j = 0; j < RB; ++j) {
+    const int q = threadIdx.x + j * BLK;
+    keep[j] = q < fv ? gi[q] : zero_of<T>();
+    ss += sq_sum(keep[j]);
+  }
+  for (int q = threadIdx.x + RB * BLK; q < fv; q += BLK) ss += sq_sum(gi[q]);
+  ss = block_sum_d(ss, red);
+  const double s = sqrt(ss);
+  const float coef = (float)(2.0 * (s - 1.0) / s * ((double)weight / (double)n));      // s = 0: non-finite, as TF's sqrt gradient
+#pragma unroll
+  for (int j = 0; j < RB; ++j) {
+    const int q = threadIdx.x + j * BLK;
+    if (q < lv) ri[q] = q < fv ? scaled(keep[j], coef) : zero_of<T>();
+  }
+  for (int q = threadIdx.x + RB * BLK; q < lv; q += BLK) ri[q] = q < fv ? scaled(gi[q], coef) : zero_of<T>();
+  if (threadIdx.x == 0) partials[i] = (s - 1.0) * (s - 1.0);
+}
+
 __device__ float block_sum_f(float v, float* red) {
   v = tgd::wave_sum(v);
   __syncthreads();
@@ -147,6 +192,22 @@ int tg_grad_penalty_f32(const float* gx, int ld_g, int n, int h, int w, int c, f
   hipLaunchKernelGGL(gp_columns, dim3((unsigned)nb), dim3(BLK), 0, s, gx, ld_g, n, h, w, c, weight, r, ld_r, partials);
   TG_CHECK_LAUNCH("gp_columns");
   hipLaunchKernelGGL(gp_finish, dim3(1), dim3(BLK), 0, s, partials, (int)nb, (double)weight / (double)((int64_t)n * w * c), gp);
+  TG_CHECK_LAUNCH("gp_finish");
+  return TG_OK;
+}
+
+int tg_grad_penalty_rows_f32(const float* gx, int ld_g, int n, int f, float weight, float* r, int ld_r, double* partials, float* gp, void* stream) {
+  TG_REQUIRE(gx && r && partials && gp && n > 0 && f > 0 && f <= ld_g && f <= ld_r, "grad_penalty_rows: bad args (n=%d f=%d ld_g=%d ld_r=%d)", n, f,
+             ld_g, ld_r);
+  hipStream_t s = tg::as_stream(stream);
+  tg::ProfScope prof(tg::PC_LOSS, 0, 4.0 * (double)n * (f + ld_r), s);
+  const bool vec = f % 4 == 0 && ld_g % 4 == 0 && ld_r % 4 == 0 && reinterpret_cast<uintptr_t>(gx) % 16 == 0 && reinterpret_cast<uintptr_t>(r) % 16 == 0;
+  if (vec)
+    hipLaunchKernelGGL(gp_rows<float4>, dim3((unsigned)n), dim3(BLK), 0, s, gx, ld_g, f, weight, n, r, ld_r, partials);
+  else
+    hipLaunchKernelGGL(gp_rows<float>, dim3((unsigned)n), dim3(BLK), 0, s, gx, ld_g, f, weight, n, r, ld_r, partials);
+  TG_CHECK_LAUNCH("gp_rows");
+  hipLaunchKernelGGL(gp_finish, dim3(1), dim3(BLK), 0, s, partials, n, (double)weight / (double)n, gp);
   TG_CHECK_LAUNCH("gp_finish");
   return TG_OK;
 }

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Time of Train_base._gradient_penalty (WGAN-GP, reference Training/train_base.py:598-620) on the CIFAR-10 discriminator, eager, fp32,
-at n images (default 100), after warm-up — and, for scale, one plain discriminator forward + backward (weight gradients) at the same n.
-Prints ONE JSON line.
+"""Time of Train_base._gradient_penalty (WGAN-GP, reference Training/train_base.py:598-620) on the CIFAR-10 discriminator (default),
+or on the MNIST / SVHN one of Good_GAN (--data), eager, fp32, at n images (default 100), after warm-up — and, for scale, one plain
+discriminator forward + backward (weight gradients) at the same n.  Prints ONE JSON line (with --data mnist / svhn it names the data).
 
-    python tools/bench_wgan_gp.py [--n 100] [--iters 50]
+    python tools/bench_wgan_gp.py [--data cifar10|mnist|svhn] [--n 100] [--iters 50]
 
 The penalty is four sweeps through the discriminator (forward, input gradient, tangent forward, filter gradients: DESIGN §9.1), so
 about twice a forward + backward is the expectation."""
@@ -39,21 +39,27 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=100)
     ap.add_argument('--iters', type=int, default=50)
+    ap.add_argument('--data', choices=('cifar10', 'mnist', 'svhn'), default='cifar10')
     args = ap.parse_args()
     from config import Config
+    from Model.Good_GAN import Good_GAN
     from Model.Good_GAN_cifar10 import Good_GAN_cifar10
     from Training.train_base import Train_base
     from tg import runtime
 
+    shape = (784,) if args.data == 'mnist' else (32, 32, 3)        # MNIST: the generator's rank-2 layout (one slope per image)
+
     class Cfg(Config):
-        Z_DIM, NUM_CLASSES, BATCH_SIZE, IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = 100, 10, 100, 32, 32, 3
+        Z_DIM, NUM_CLASSES, BATCH_SIZE = 100, 10, 100
+        IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = (28, 28, 1) if args.data == 'mnist' else (32, 32, 3)
+        DATA_NAME = args.data
 
     cx = runtime.set_context(runtime.Context())
-    model = Good_GAN_cifar10(Cfg())
+    model = Good_GAN_cifar10(Cfg()) if args.data == 'cifar10' else Good_GAN(Cfg())
     rng = np.random.default_rng(0)
     n = args.n
-    real = cx.from_numpy(np.tanh(rng.standard_normal((n, 32, 32, 3))), key='bench:real')
-    fake = cx.from_numpy(np.tanh(rng.standard_normal((n, 32, 32, 3))), key='bench:fake')
+    real = cx.from_numpy(np.tanh(rng.standard_normal((n,) + shape)), key='bench:real')
+    fake = cx.from_numpy(np.tanh(rng.standard_normal((n,) + shape)), key='bench:fake')
     y = cx.from_numpy(np.eye(10)[rng.integers(0, 10, n)], key='bench:y')
     tb = Train_base()
 
@@ -72,8 +78,11 @@ def main():
 
     ms_gp = timed(gp, args.iters)
     ms_d = timed(d_fwd_bwd, args.iters)
-    print(json.dumps(dict(tool='bench_wgan_gp', n=n, iters=args.iters, gradient_penalty_ms=round(ms_gp, 4), d_fwd_bwd_ms=round(ms_d, 4),
-                          ratio=round(ms_gp / ms_d, 3))))
+    out = dict(tool='bench_wgan_gp', n=n, iters=args.iters, gradient_penalty_ms=round(ms_gp, 4), d_fwd_bwd_ms=round(ms_d, 4),
+               ratio=round(ms_gp / ms_d, 3))
+    if args.data != 'cifar10':
+        out = dict(out, data=args.data)
+    print(json.dumps(out))
 
 
 if __name__ == '__main__':
