@@ -553,6 +553,21 @@ int tg_grad_penalty_f32(const float* gx, int ld_g, int n, int h, int w, int c, f
 int tg_grad_penalty_rows_f32(const float* gx, int ld_g, int n, int f, float weight, float* r, int ld_r, double* partials, float* gp, void* stream);
 int tg_wgan_loss_f32(const float* logits, int ld, int n_real, int n_fake, int n_unl, float lambda_1, float lambda_2, float* dlogits, int ld_d,
                      float* dfake, int ld_df, float* loss, void* stream);
+/* loss heads of the training step with config.LOSS = 'WGAN_GP' (Training/Train_goodGAN.py): replayable — lambdas is the trainer's device
+ * pair {lambda_1, lambda_2} (hyper[2:4]), nothing is a host value that a recorded plan or graph would freeze.  One workgroup each, fixed
+ * summation order (bit-identical run to run); padding columns of the gradients are written 0.
+ * tg_wgan_d_head_f32  rows [real | fake | unl] (column 0, row stride ld): loss[0] = -(wd1 + l1 wd2 + l2 wd3) + gp_w[0] (gp_w: the penalty
+ *                     times gp_weight, as the sweeps return it), dlogits = d loss / d logits (stride ld_d); terms (optional, device [4])
+ *                     = {wd1, wd2, wd3, gp_w[0] / gp_weight}.
+ * tg_wgan_g_head_f32  loss[0] = -mean logits over n rows, dlogits = -1/n.
+ * tg_wgan_c_head_f32  rows [real | zero (n_zero) | fake] of k logits: loss[0] = mean CE(y_real, real) + lambdas[1] mean CE(y_fake, fake);
+ *                     labels dense [n, k]; the zero rows get a zero gradient; n_fake may be 0 (then y_fake / lambdas may be NULL);
+ *                     terms (optional, device [2]) = the two means. */
+int tg_wgan_d_head_f32(const float* logits, int ld, int n_real, int n_fake, int n_unl, const float* lambdas, const float* gp_w, float gp_weight,
+                       float* dlogits, int ld_d, float* loss, float* terms, void* stream);
+int tg_wgan_g_head_f32(const float* logits, int ld, int n, float* dlogits, int ld_d, float* loss, void* stream);
+int tg_wgan_c_head_f32(const float* logits, int ld, int n_real, int n_zero, int n_fake, int k, const float* y_real, const float* y_fake,
+                       const float* lambdas, float* dlogits, int ld_d, float* loss, float* terms, void* stream);
 /* minibatch discrimination (Model/modle_base.py:110-128): act = x @ W viewed [n][kernels][dim] (dim <= 8);
  * out[i] = [x[i,:c], f[i,:], 0...] with f[i,k] = sum_j exp(-sum_d |act[i,k,d] - act[j,k,d]|) + b[k].
  * bwd: df = the gradient's columns c.. ([n][kernels], stride ld_df) -> dact (pads zeroed), db[k] = sum_i df[i,k] (db may be NULL). */

@@ -205,7 +205,7 @@ class Good_GAN(model_base.NN_Base):
             return self._d_out(self._WN_dense(h3, 1, 'd_h3_wndense', narrow=True), want_prob)
 
     # ------------------------------------------------------------------ WGAN-GP
-    def discriminator_gradient_penalty(self, real, fake, y, weight=1.0):
+    def discriminator_gradient_penalty(self, real, fake, y, weight=1.0, in_step=False):
         """gp and d gp / d theta_D of the reference's _gradient_penalty (Training/train_base.py:598-620) on this discriminator, with the
         contract of Good_GAN_cifar10.discriminator_gradient_penalty: x = real + alpha (fake - real), alpha ~ U[0,1) per image, gx =
         d sum(logits) / dx, s = sqrt(reduce_sum(gx^2, axis=1)), gp = mean((s - 1)^2).  Returns (weight * gp as a 1-element device tensor,
@@ -225,7 +225,8 @@ class Good_GAN(model_base.NN_Base):
              maps each to dV, dg at the store offsets of .../V and .../g; every .../b entry stays exactly 0.
         Masks, noise and alpha are drawn in the RNG scope 'GP' ('alpha', 'drop0..2' / 'noise0..5'); buffers live under the phase
         'wgan_gp'.  Minibatch discrimination (config.MINIBATCH_DIS) couples the images of a batch and is refused, as are the bf16 MFMA
-        operands."""
+        operands.  in_step=True: inside the caller's solver run, as
+        Good_GAN_cifar10.discriminator_gradient_penalty."""
         from tg import lib
         cx = ctx()
         if getattr(self.config, 'MINIBATCH_DIS', False):
@@ -241,8 +242,8 @@ class Good_GAN(model_base.NN_Base):
         if y.n != real.n or y.ld != y.c or getattr(real, 'dtype', 'f32') != 'f32' or getattr(fake, 'dtype', 'f32') != 'f32':
             raise lib.TgError("discriminator_gradient_penalty: dense fp32 labels [%d] and fp32 images of %d expected" % (y.n, real.n))
         st = cx.stores['discriminator']
-        grad = cx.ws('wgan_gp:grad', st.n_p)
-        with cx.phase_scope('wgan_gp', record=False), cx.rng_scoped('GP'):
+        grad = cx.scratch('gpgrad', st.n_p) if in_step else cx.ws('wgan_gp:grad', st.n_p)
+        with (cx.detached() if in_step else cx.phase_scope('wgan_gp', record=False)), cx.rng_scoped('GP'):
             lib.call('tg_fill_f32', lib.ptr(grad), 0.0, st.n_p, cx.stream)
             alpha = cx.rng.uniform(cx, 'alpha', real.n, 0.0, 1.0)
             sweeps = self._gp_mnist if self.mnist else self._gp_svhn

@@ -177,7 +177,7 @@ class Good_GAN_cifar10(model_base.NN_Base):
             h3 = self._linear_fc(h3, 1, 'lin', narrow=True)
         return (self._sigmoid_no_grad(h3) if want_prob else None), h3
 
-    def discriminator_gradient_penalty(self, real, fake, y, weight=1.0):
+    def discriminator_gradient_penalty(self, real, fake, y, weight=1.0, in_step=False):
         """gp and d gp / d theta_D of the reference's _gradient_penalty (Training/train_base.py:598-620) on this discriminator:
         x = real + alpha (fake - real) with alpha ~ U[0,1) per image, gx = d sum(logits) / dx, s = sqrt(reduce_sum(gx^2, axis=1)) (axis 1
         of NHWC is H), gp = mean((s - 1)^2).  real, fake: Act [N,H,W,3]; y: label Act [N,NUM_CLASSES].  Returns (weight * gp as a
@@ -192,7 +192,9 @@ class Good_GAN_cifar10(model_base.NN_Base):
              convolution without its bias, * lrelu'(y_k) * dropout mask (tg_actgrad_f32),
           4. d gp / dW_k = wgrad(tangent input of layer k, dpre_k); d gp / d w_lin = sum over images of the pooled tangent; biases 0.
         Dropout masks and alpha are drawn in their own RNG scope 'GP' ('alpha', 'drop0', 'drop1', ...); buffers live under the phase
-        'wgan_gp', apart from every buffer a recorded launch plan or graph of the trainer names."""
+        'wgan_gp', apart from every buffer a recorded launch plan or graph of the trainer names.  in_step=True (the trainer's D-update with
+        config.LOSS = 'WGAN_GP'): the same sweeps inside the caller's solver run (Context.detached) — no phase of their own, buffers and
+        draws at call sites of the caller's phase, so that its launch plan or graph records them."""
         from tg import geom, lib
         from tg.lib import ACT
         from tg.runtime import pad32
@@ -211,8 +213,8 @@ class Good_GAN_cifar10(model_base.NN_Base):
         var = lambda nm, leaf: st.value('discriminator/%s/%s/%s' % (nm, nm, leaf))
         igemm = lambda name, *args: lib.call(name, *ops.igemm_scratch(cx, name, args, False))
         P = lambda t: None if t is None else lib.ptr(t)
-        grad = cx.ws('wgan_gp:grad', st.n_p)
-        with cx.phase_scope('wgan_gp', record=False), cx.rng_scoped('GP'):
+        grad = cx.scratch('gpgrad', st.n_p) if in_step else cx.ws('wgan_gp:grad', st.n_p)
+        with (cx.detached() if in_step else cx.phase_scope('wgan_gp', record=False)), cx.rng_scoped('GP'):
             s = cx.stream
             lib.call('tg_fill_f32', lib.ptr(grad), 0.0, st.n_p, s)
             zlab = cx.scratch('zlab', n * ncls)

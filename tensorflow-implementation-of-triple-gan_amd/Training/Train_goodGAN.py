@@ -41,6 +41,32 @@ def check_act_dtype(config):
     return act
 
 
+LOSSES = ('GAN', 'WGAN_GP')
+
+
+def check_loss(config):
+    """config.LOSS ('GAN' default | 'WGAN_GP': the reference's _loss_WGAN_GP, train_base.py:576-620, in the three-player step).
+    Needs no device.  ValueError for an unknown value; lib.TgError for what the WGAN-GP step cannot run: bf16 MFMA operands (and with them
+    ACT_DTYPE = 'bf16'), minibatch discrimination, and a penalty batch whose real and fake halves differ in size."""
+    loss = getattr(config, 'LOSS', 'GAN')
+    if loss not in LOSSES:
+        raise ValueError("LOSS must be one of %s, got %r" % (', '.join(repr(v) for v in LOSSES), loss))
+    if loss != 'WGAN_GP':
+        return loss
+    if getattr(config, 'MFMA_DTYPE', 'f32') == 'bf16':
+        raise lib.TgError("LOSS = 'WGAN_GP' needs MFMA_DTYPE = 'f32' (got 'bf16', which ACT_DTYPE = %r also needs): the gradient penalty "
+                          "differentiates a gradient, and its sweeps are pinned to a reference on the fp32 path only"
+                          % (getattr(config, 'ACT_DTYPE', 'f32'),))
+    if getattr(config, 'MINIBATCH_DIS', False):
+        raise lib.TgError("LOSS = 'WGAN_GP' does not support MINIBATCH_DIS = True: minibatch discrimination couples the images of a batch, so "
+                          "the discriminator is not piecewise linear in one image")
+    l_d, u_d, b_g = (getattr(config, k, None) for k in ('BATCH_SIZE_L_D', 'BATCH_SIZE_U_D', 'BATCH_SIZE_G'))
+    if l_d is None or u_d is None or b_g is None or l_d + u_d != b_g:
+        raise lib.TgError("LOSS = 'WGAN_GP' needs BATCH_SIZE_L_D + BATCH_SIZE_U_D == BATCH_SIZE_G (got %r + %r, %r): the penalty "
+                          "interpolates the discriminator's real images X_P with the generated ones image for image" % (l_d, u_d, b_g))
+    return loss
+
+
 class Train(Train_base):
     def __init__(self, config, log_dir, save_dir, **kwargs):
         super(Train, self).__init__()
@@ -61,6 +87,8 @@ class Train(Train_base):
             raise ValueError("MFMA_DTYPE must be 'f32' or 'bf16', got %r" % (cx.mfma_dtype,))
         # 'bf16': the batch norms the model marks store their output as bf16 — same numbers, half the bytes (Context.act_dtype)
         cx.act_dtype = check_act_dtype(config)
+        self.loss_kind = check_loss(config)          # 'GAN' | 'WGAN_GP': the loss heads of the three solver runs
+        self._gp_w = self._gp_grad = None            # WGAN-GP: the D-update's weighted penalty and its parameter gradient (device)
         cx.bf16_act_layers = set()
         # device-resident hyper-parameters (the reference's lr_ph / cla_lr_ph / lambda placeholders, :30-31,416-420)
         self.hyper = torch.zeros(4, dtype=torch.float32, device=cx.device)       # lr, cla_lr, lambda_1, lambda_2
@@ -137,9 +165,15 @@ class Train(Train_base):
             g_replay = []
             # (eager launches with the side stream, Context.wgrad_side: the generator's forward pass — small launches — runs beside the
             # classifier's, which it does not depend on; the two meet where the discriminator's batch is assembled)
+            wgan = self.loss_kind == 'WGAN_GP'
             with cx.wgrad_on_side():
                 with cx.sub_tape(('good_generator',), replay=g_replay) as g_tape:
                     G = m.good_generator(self.z_g_ph, self.y_g_ph)
+                if wgan:
+                    # the penalty needs X_P, G, y_g and the discriminator's weights only: it goes beside the classifier's forward pass too,
+                    # and the join below completes it before anything reads it
+                    xp = concat_acts([m.as_image(self.x_l_d_ph), m.as_image(self.x_u_d_ph)])
+                    self._gp_w, self._gp_grad = m.discriminator_gradient_penalty(xp, m.as_image(G), self.y_g_ph, self.GP_WEIGHT, in_step=True)
             self._g_saved = (G, g_tape, g_replay)
             xz = concat_acts([m.as_image(self.x_u_c_ph), m.as_image(self.x_u_d_ph)])
             if m.zca() is not None:
@@ -159,7 +193,11 @@ class Train(Train_base):
             yall = concat_acts([self.y_l_d_ph, oh_unl_d, self.y_g_ph, oh_unl])
             with cx.rng_scoped('D/D'):
                 _, d_logits = m.discriminator(ximg, yall, want_prob=False)
-            self._d_loss(d_logits, c.BATCH_SIZE_L_D + c.BATCH_SIZE_U_D, c.BATCH_SIZE_G, c.BATCH_SIZE_U_C, self.loss_dev[0:1])
+            if wgan:
+                self._wgan_d_head(d_logits, c.BATCH_SIZE_L_D + c.BATCH_SIZE_U_D, c.BATCH_SIZE_G, c.BATCH_SIZE_U_C, self.hyper[2:4], self._gp_w,
+                                  self.loss_dev[0:1])
+            else:
+                self._d_loss(d_logits, c.BATCH_SIZE_L_D + c.BATCH_SIZE_U_D, c.BATCH_SIZE_G, c.BATCH_SIZE_U_C, self.loss_dev[0:1])
             self._rest['D'] = (cx.backward(stop_at_boundary='discriminator' if split else False), cx.counter)
 
     def _g_forward_backward(self, split=False):
@@ -175,7 +213,10 @@ class Train(Train_base):
                 G, g_tape = m.good_generator(self.z_g_ph, self.y_g_ph), None
             with cx.rng_scoped('G/D'):
                 _, d_fake = m.discriminator(G, self.y_g_ph, want_prob=False)
-            self._g_loss(d_fake, self.loss_dev[1:2])
+            if self.loss_kind == 'WGAN_GP':
+                self._wgan_g_head(d_fake, self.loss_dev[1:2])
+            else:
+                self._g_loss(d_fake, self.loss_dev[1:2])
             rest = cx.backward(stop_at_boundary='good_generator' if (split and g_tape is None) else False)
             if g_tape is not None:                      # the discriminator's input gradient is complete: now the kept generator tape
                 rest = cx.run_tape(g_tape, stop_at_boundary='good_generator' if split else False)
@@ -195,6 +236,12 @@ class Train(Train_base):
             with cx.rng_scoped('C/C'):
                 c_logits, _ = m.classifier(xc, True, segments=segs)
             c_unl = c_logits.view_rows(segs[0], segs[0] + segs[1])
+            if self.loss_kind == 'WGAN_GP':
+                # CE(y_l_c, C_real) + lambda_2 CE(y_g, C_fake): the unl / rep rows weigh 0 and nothing reads D(x_u_c), so it is not run
+                self._c_logits = c_unl
+                self._wgan_c_head(c_logits, segs[0], sum(segs[1:-1]), G.n, self.y_l_c_ph, self.y_g_ph, self.hyper[2:4], self.loss_dev[2:3])
+                self._rest['C'] = (cx.backward(stop_at_boundary='classifier' if split else False), cx.counter)
+                return
             k = c.NUM_CLASSES
             oh_c = ops.argmax_onehot(c_unl, k)
             self._c_logits = c_unl
@@ -214,6 +261,13 @@ class Train(Train_base):
             with self.cx.phase_scope(phase, train_nets=(net,), counter=counter):
                 rest = self.cx.run_tape(rest, stop_at_boundary=net if split else False)
                 self._rest[phase] = (rest, self.cx.counter)
+
+    def _add_gp_slice(self, sl):
+        """WGAN-GP: add the penalty's parameter gradient to the slice `sl` of the discriminator's store.g, once the D backward pass has
+        finished that slice and before it is exchanged (with replicas it is averaged like every other gradient)."""
+        st = self.cx.stores['discriminator']
+        off = (sl.data_ptr() - st.g.data_ptr()) // sl.element_size()
+        lib.call('tg_add_f32', lib.ptr(sl), lib.ptr(sl), lib.ptr(self._gp_grad[off:off + sl.numel()]), sl.numel(), self.cx.stream)
 
     def _c_apply(self):
         st = self.cx.stores['classifier']
@@ -242,6 +296,8 @@ class Train(Train_base):
         for k, sl in enumerate(slices[1:]):
             last = k == len(slices) - 2
             segs.append((lambda last=last: self._backward_rest(phase, net, not last), sl))
+        if net == 'discriminator' and self.loss_kind == 'WGAN_GP':
+            segs = [(lambda fn=fn, sl=sl: (fn(), self._add_gp_slice(sl)), sl) for fn, sl in segs]
         return segs
 
     def _segments(self, pre_train=False):
@@ -533,7 +589,14 @@ class Train(Train_base):
         return accuracy, update_op, accuracy.reset, ops.argmax_onehot(real_lab_logits, real_lab_logits.c), None
 
     def _goodGAN_loss(self, G, D, C, X, Y, Lambda, discriminator=None):
-        """:449-454."""
+        """:449-454, dispatched on config.LOSS.  'WGAN_GP': X = None (the reference's training call) stands for the discriminator's real
+        images X_P = [x_l_d | x_u_d], the penalty's `real`."""
+        if self.loss_kind == 'WGAN_GP':
+            m = self.model
+            if X is None:
+                from tg.batching import concat_acts
+                X = concat_acts([m.as_image(self.x_l_d_ph), m.as_image(self.x_u_d_ph)])
+            return self._loss_WGAN_GP_step(m.as_image(G), D, C, X, Y, Lambda, discriminator or m.discriminator)
         return self._loss_GAN(D, C, Y, Lambda)
 
     def evaluate(self, batches):

@@ -1,6 +1,7 @@
 """Train_base — loss / optimiser library, counterpart of the reference's Training/train_base.py.
 
-`_loss_GAN(D, C, Y, Lambda)` (train_base.py:113-154) is kept as the one loss the entry point calls; it is evaluated by three fused
+`_loss_GAN(D, C, Y, Lambda)` (train_base.py:113-154) is the loss the entry point calls by default (config.LOSS = 'WGAN_GP' selects the
+WGAN-GP heads further down instead); it is evaluated by three fused
 single-launch kernels (tg_d_loss_f32 / tg_g_loss_f32 / tg_c_loss_f32) that also write d(loss)/d(logits) into the
 logits' gradient buffers.  The helper methods it is written with in the reference — `_entropy`, `_balance_entropy` (:43-57),
 `_softmax_cross_entropy_loss_w_logits`, `_sigmoid_cross_entopy_w_logits` (:75-84), `_accuracy_metric` (:107) — keep their names and
@@ -388,6 +389,66 @@ class Train_base(object):
         v = [float(x) for x in lv.cpu().numpy()]
         self.last_wgan_terms = dict(wd1=v[2], wd2=v[3], wd3=v[4], gp=v[12] / 10.0)
         return v[0] + v[12], v[1], v[5]
+
+    # ---- the training step's WGAN-GP (config.LOSS = 'WGAN_GP', Training/Train_goodGAN.py): replayable heads ---------------
+    # lambda_1 / lambda_2 are read from a device pair (the trainer's hyper[2:4]) and the weighted penalty from the device scalar the sweeps
+    # wrote, so a recorded launch plan or graph follows set_hyper(); nothing is synchronised.
+    GP_WEIGHT = 10.0                                   # train_base.py:581: d_loss = -(...) + 10 gp
+
+    def _wgan_d_head(self, d_logits, n_real, n_fake, n_unl, lambdas_dev, gp_w, loss_out):
+        """d_loss = -(wd1 + l1 wd2 + l2 wd3) + gp_w (rows [real | fake | unl]); d(loss)/d(logits) in d_logits.grad.  The unweighted terms
+        {wd1, wd2, wd3, gp} stay on the device in self.wgan_terms_dev."""
+        cx = ctx()
+        g = cx.new_act(d_logits.n, 1, 1, 1, 32, tag='dl')
+        self.wgan_terms_dev = cx.scratch('wgterms', 4)
+        lib.call('tg_wgan_d_head_f32', d_logits.ptr, d_logits.ld, n_real, n_fake, n_unl, lib.ptr(lambdas_dev), lib.ptr(gp_w), self.GP_WEIGHT,
+                 g.ptr, g.ld, lib.ptr(loss_out), lib.ptr(self.wgan_terms_dev), cx.stream)
+        d_logits.grad = g
+
+    def _wgan_g_head(self, d_fake_logits, loss_out):
+        """g_loss = -mean(D_fake_logits) (train_base.py:588)."""
+        cx = ctx()
+        g = cx.new_act(d_fake_logits.n, 1, 1, 1, 32, tag='dl')
+        lib.call('tg_wgan_g_head_f32', d_fake_logits.ptr, d_fake_logits.ld, d_fake_logits.n, g.ptr, g.ld, lib.ptr(loss_out), cx.stream)
+        d_fake_logits.grad = g
+
+    def _wgan_c_head(self, c_logits, n_real, n_zero, n_fake, y_l_c, y_g, lambdas_dev, loss_out):
+        """c_loss = CE(y_l_c, C_real) + l2 CE(y_g, C_fake) (train_base.py:590-594); rows of c_logits [real | zero (n_zero) | fake], the
+        zero rows (unl / rep) get a zero gradient."""
+        cx = ctx()
+        g = cx.new_act(c_logits.n, 1, 1, c_logits.c, c_logits.ld, tag='dl')
+        lib.call('tg_wgan_c_head_f32', c_logits.ptr, c_logits.ld, n_real, n_zero, n_fake, c_logits.c, y_l_c.ptr, y_g.ptr, lib.ptr(lambdas_dev),
+                 g.ptr, g.ld, lib.ptr(loss_out), None, cx.stream)
+        c_logits.grad = g
+
+    def _loss_WGAN_GP_step(self, G, D, C, X, Y, Lambda, discriminator):
+        """the loss of the training step with config.LOSS = 'WGAN_GP' on the outputs of Model.forward_pass (the port decisions of DESIGN §9.1):
+        D = [D_real, D_real_logits, D_fake, D_fake_logits, D_unl, D_unl_logits]; C = [C_real_logits, C_unl_logits, C_unl_d_logits,
+        C_fake_logits(, C_unl_logits_rep)]; X: the real images of the penalty (X_P), G: its fake ones, both as model.as_image() gives them;
+        Y = [y_g, y_l_c] (the penalty's labels are y_g); Lambda: device pair or numbers.  Returns (d_loss, g_loss, c_loss), 1-element device
+        tensors — the penalty runs in the caller's phase (discriminator_gradient_penalty(in_step=True)); its parameter gradient is left in
+        self.last_gp_grad."""
+        from tg.batching import concat_acts
+        cx = ctx()
+        loss_out = cx.scratch('loss_wgan', 4)
+        if isinstance(Lambda, torch.Tensor):
+            lam = Lambda
+        else:
+            vals = [float(v) for v in Lambda] + [0.0, 0.0]
+            lam = cx.scratch('loss_lambda', 2)
+            lam.copy_(torch.tensor(vals[:2], dtype=torch.float32))
+        _, d_real, _, d_fake, _, d_unl = D
+        y_g, y_l_c = Y
+        gp_w, self.last_gp_grad = self._gp_sweeps(discriminator)(X, G, y_g, self.GP_WEIGHT, in_step=True)
+        dcat = concat_acts([d_real, d_fake, d_unl])
+        self._wgan_d_head(dcat, d_real.n, d_fake.n, d_unl.n, lam, gp_w, loss_out[0:1])
+        self._wgan_g_head(d_fake, loss_out[1:2])
+        c_real, c_unl, _c_unl_d, c_fake = C[:4]
+        c_rep = C[4] if len(C) > 4 else None
+        ccat = concat_acts([c_real, c_unl] + ([c_rep] if c_rep is not None else []) + [c_fake])
+        self._wgan_c_head(ccat, c_real.n, c_unl.n + (c_rep.n if c_rep is not None else 0), c_fake.n, y_l_c, y_g, lam, loss_out[2:3])
+        self.last_loss_inputs = (dcat, ccat)
+        return loss_out[0:1], loss_out[1:2], loss_out[2:3]
 
     def _add_gp_grad(self, store=None):
         """store.g += self.last_gp_grad (the discriminator's store by default): call after the D backward pass that wrote store.g."""

@@ -57,6 +57,9 @@ class Config(object):
                              # include/tg_plan.h) - no interpreter on the launch path;
                              # 'graph': hipGraph replay (single chain); 'eager': eager launches on one stream
     ZCA = None               # (mean, mat) arrays when DATA_DIR holds no cifar10_zca_*.npy
+    LOSS = 'GAN'             # the loss of the three solver runs: 'GAN' (_loss_GAN, the reference's training loss) or 'WGAN_GP' (its
+                             # _loss_WGAN_GP with the gradient penalty, wired into the step as DESIGN §9.1 decides; fp32 MFMA operands, no
+                             # minibatch discrimination, BATCH_SIZE_L_D + BATCH_SIZE_U_D == BATCH_SIZE_G — Training/Train_goodGAN.check_loss)
     MFMA_DTYPE = 'f32'       # 'bf16': conv/deconv/dense operands rounded to bf16 inside the MFMA kernels (fp32 accumulate)
     ACT_DTYPE = 'f32'        # 'bf16' (needs MFMA_DTYPE = 'bf16', else ValueError): the training-mode batch norms whose only reader is a
                              # bf16-operand 3x3 convolution store their output as bf16 (the SVHN classifier's c_h0_bn0/bn1, c_h1_bn0/bn1) —

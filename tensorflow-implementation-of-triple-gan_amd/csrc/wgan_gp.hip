@@ -164,6 +164,101 @@ __global__ void __launch_bounds__(BLK) wgan_loss(const float* __restrict__ z, in
   }
 }
 
+// ---- loss heads of the three-player step (Training/Train_goodGAN.py with config.LOSS = 'WGAN_GP').  Unlike wgan_loss they read lambda_1 /
+// lambda_2 from device memory (the trainer's hyper[2:4]) and the weighted penalty from the device scalar the sweeps wrote, so a recorded
+// launch plan or graph follows set_hyper().  One workgroup each; every thread sums a fixed strided set of rows, block_sum_f adds the waves
+// in a fixed order: bit-identical run to run.
+
+// rows [real | fake | unl]: dz = d d_loss / dz (column 0, padding 0), loss[0] = -(wd1 + l1 wd2 + l2 wd3) + gp_w[0],
+// terms[4] = {wd1, wd2, wd3, gp_w[0] / gp_weight}
+__global__ void __launch_bounds__(BLK) wgan_d_head(const float* __restrict__ z, int ld, int n_real, int n_fake, int n_unl, const float* __restrict__ lam,
+                                                   const float* __restrict__ gp_w, float gp_weight, float* __restrict__ dz, int ld_d,
+                                                   float* __restrict__ loss, float* __restrict__ terms) {
+  __shared__ float red[4];
+  const int n = n_real + n_fake + n_unl;
+  const float l1 = lam[0], l2 = lam[1];
+  const float w_real = (-0.5f - 0.5f * l1) / n_real, w_fake = (0.5f + 0.5f * l2) / n_fake, w_unl = (0.5f * l1 - 0.5f * l2) / n_unl;
+  float s[3] = {0.f, 0.f, 0.f};
+  for (int r = threadIdx.x; r < n; r += BLK) {
+    const float v = z[(int64_t)r * ld];
+    const int which = r < n_real ? 0 : (r < n_real + n_fake ? 1 : 2);
+    s[which] += v;
+    float* o = dz + (int64_t)r * ld_d;
+    o[0] = which == 0 ? w_real : (which == 1 ? w_fake : w_unl);
+    for (int k = 1; k < ld_d; ++k) o[k] = 0.f;
+  }
+  const float m_real = block_sum_f(s[0], red) / n_real;
+  const float m_fake = block_sum_f(s[1], red) / n_fake;
+  const float m_unl = block_sum_f(s[2], red) / n_unl;
+  if (threadIdx.x == 0) {
+    const float wd1 = 0.5f * (m_real - m_fake), wd2 = 0.5f * (m_real - m_unl), wd3 = 0.5f * (m_unl - m_fake);
+    const float gp = gp_w[0];
+    loss[0] = -(wd1 + l1 * wd2 + l2 * wd3) + gp;
+    if (terms) {
+      terms[0] = wd1;
+      terms[1] = wd2;
+      terms[2] = wd3;
+      terms[3] = gp / gp_weight;
+    }
+  }
+}
+
+// g_loss = -mean z over n rows (column 0): dz = -1/n, padding 0
+__global__ void __launch_bounds__(BLK) wgan_g_head(const float* __restrict__ z, int ld, int n, float* __restrict__ dz, int ld_d, float* __restrict__ loss) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int r = threadIdx.x; r < n; r += BLK) {
+    s += z[(int64_t)r * ld];
+    float* o = dz + (int64_t)r * ld_d;
+    o[0] = -1.f / n;
+    for (int k = 1; k < ld_d; ++k) o[k] = 0.f;
+  }
+  const float m = block_sum_f(s, red) / n;
+  if (threadIdx.x == 0) loss[0] = -m;
+}
+
+// rows [real | zero (n_zero) | fake] of k logits: c_loss = mean CE(y_real, real) + lam[1] mean CE(y_fake, fake), CE = lse sum_j y_j - y . l;
+// dl = w (softmax * sum_j y_j - y) / n on the labelled rows, 0 on the zero rows, padding columns k..ld_d 0; terms[2] = the two means
+__global__ void __launch_bounds__(BLK) wgan_c_head(const float* __restrict__ cl, int ld, int n_real, int n_zero, int n_fake, int k,
+                                                   const float* __restrict__ y_real, const float* __restrict__ y_fake, const float* __restrict__ lam,
+                                                   float* __restrict__ dl, int ld_d, float* __restrict__ loss, float* __restrict__ terms) {
+  __shared__ float red[4];
+  const float l2 = n_fake > 0 ? lam[1] : 0.f;
+  float ce[2] = {0.f, 0.f};
+  for (int pass = 0; pass < 2; ++pass) {
+    const int n = pass == 0 ? n_real : n_fake, off = pass == 0 ? 0 : n_real + n_zero;
+    const float* y = pass == 0 ? y_real : y_fake;
+    const float w = (pass == 0 ? 1.f : l2) / n;
+    for (int r = threadIdx.x; r < n; r += BLK) {
+      const float* l = cl + (int64_t)(off + r) * ld;
+      const float* yr = y + (int64_t)r * k;
+      float m = l[0];
+      for (int j = 1; j < k; ++j) m = fmaxf(m, l[j]);
+      float se = 0.f, ysum = 0.f, yl = 0.f;
+      for (int j = 0; j < k; ++j) {
+        se += expf(l[j] - m);
+        ysum += yr[j];
+        yl += yr[j] * l[j];
+      }
+      const float lse = m + logf(se), inv = 1.f / se;
+      ce[pass] += lse * ysum - yl;
+      float* o = dl + (int64_t)(off + r) * ld_d;
+      for (int j = 0; j < k; ++j) o[j] = w * (expf(l[j] - m) * inv * ysum - yr[j]);
+      for (int j = k; j < ld_d; ++j) o[j] = 0.f;
+    }
+  }
+  for (int64_t i = threadIdx.x; i < (int64_t)n_zero * ld_d; i += BLK) dl[(int64_t)n_real * ld_d + i] = 0.f;
+  const float t_real = block_sum_f(ce[0], red) / n_real;
+  const float t_fake = n_fake > 0 ? block_sum_f(ce[1], red) / n_fake : 0.f;
+  if (threadIdx.x == 0) {
+    loss[0] = t_real + l2 * t_fake;
+    if (terms) {
+      terms[0] = t_real;
+      terms[1] = t_fake;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -220,6 +315,39 @@ int tg_wgan_loss_f32(const float* logits, int ld, int n_real, int n_fake, int n_
   tg::ProfScope prof(tg::PC_LOSS, 0, 0, s);
   hipLaunchKernelGGL(wgan_loss, dim3(1), dim3(BLK), 0, s, logits, ld, n_real, n_fake, n_unl, lambda_1, lambda_2, dlogits, ld_d, dfake, ld_df, loss);
   TG_CHECK_LAUNCH("wgan_loss");
+  return TG_OK;
+}
+
+int tg_wgan_d_head_f32(const float* logits, int ld, int n_real, int n_fake, int n_unl, const float* lambdas, const float* gp_w, float gp_weight,
+                       float* dlogits, int ld_d, float* loss, float* terms, void* stream) {
+  TG_REQUIRE(logits && lambdas && gp_w && dlogits && loss && n_real > 0 && n_fake > 0 && n_unl > 0 && ld >= 1 && ld_d >= 1 && gp_weight != 0.f,
+             "wgan_d_head: bad args (n=%d/%d/%d ld=%d ld_d=%d)", n_real, n_fake, n_unl, ld, ld_d);
+  hipStream_t s = tg::as_stream(stream);
+  tg::ProfScope prof(tg::PC_LOSS, 0, 0, s);
+  hipLaunchKernelGGL(wgan_d_head, dim3(1), dim3(BLK), 0, s, logits, ld, n_real, n_fake, n_unl, lambdas, gp_w, gp_weight, dlogits, ld_d, loss, terms);
+  TG_CHECK_LAUNCH("wgan_d_head");
+  return TG_OK;
+}
+
+int tg_wgan_g_head_f32(const float* logits, int ld, int n, float* dlogits, int ld_d, float* loss, void* stream) {
+  TG_REQUIRE(logits && dlogits && loss && n > 0 && ld >= 1 && ld_d >= 1, "wgan_g_head: bad args (n=%d ld=%d ld_d=%d)", n, ld, ld_d);
+  hipStream_t s = tg::as_stream(stream);
+  tg::ProfScope prof(tg::PC_LOSS, 0, 0, s);
+  hipLaunchKernelGGL(wgan_g_head, dim3(1), dim3(BLK), 0, s, logits, ld, n, dlogits, ld_d, loss);
+  TG_CHECK_LAUNCH("wgan_g_head");
+  return TG_OK;
+}
+
+int tg_wgan_c_head_f32(const float* logits, int ld, int n_real, int n_zero, int n_fake, int k, const float* y_real, const float* y_fake,
+                       const float* lambdas, float* dlogits, int ld_d, float* loss, float* terms, void* stream) {
+  TG_REQUIRE(logits && y_real && dlogits && loss && n_real > 0 && n_zero >= 0 && n_fake >= 0 && k > 0 && k <= ld && k <= ld_d &&
+                 (n_fake == 0 || (y_fake && lambdas)),
+             "wgan_c_head: bad args (n=%d/%d/%d k=%d ld=%d ld_d=%d)", n_real, n_zero, n_fake, k, ld, ld_d);
+  hipStream_t s = tg::as_stream(stream);
+  tg::ProfScope prof(tg::PC_LOSS, 0, 0, s);
+  hipLaunchKernelGGL(wgan_c_head, dim3(1), dim3(BLK), 0, s, logits, ld, n_real, n_zero, n_fake, k, y_real, y_fake, lambdas, dlogits, ld_d, loss,
+                     terms);
+  TG_CHECK_LAUNCH("wgan_c_head");
   return TG_OK;
 }
 

@@ -255,6 +255,11 @@ class PhiloxRNG(object):
         lib.call('tg_rng_multi_f32', arr, len(jobs), lib.ptr(self.state), ctx.stream)
 
     def _draw(self, ctx, name, n, mode, a, b, out=None):
+        if ctx.detached_draws:                             # Context.detached: one launch into a buffer of the phase's call sites, off the plan
+            if out is None:
+                out = ctx.scratch('rng', n * (int(a) if mode == 3 else 1))
+            self._multi(ctx, [(out, int(n), mode, float(a), float(b), self._sid(ctx, name))])
+            return out
         if out is None:
             out = ctx.ws('rng:' + ctx.rng_scope + '/' + name, n * (int(a) if mode == 3 else 1))
         sid = self._sid(ctx, name)
@@ -296,6 +301,7 @@ class PhiloxRNG(object):
 class Context(object):
     capturing = False                                 # a hipGraph capture is open on the launch stream (Train._capture)
     _wgrad_side_pending = False                       # launches on the second stream not yet joined (wgrad_on_side)
+    detached_draws = False                            # inside Context.detached
 
     def __init__(self, device='cuda:0', seed=0):
         lib.load()                                   # fails loudly when the HIP extension is missing
@@ -520,6 +526,21 @@ class Context(object):
             yield tape
         finally:
             self.tape, self.train_nets, self.state_replay = prev
+
+    @contextlib.contextmanager
+    def detached(self):
+        """ops issued inside belong to the running solver run — their buffers are call sites of its phase, so a launch plan or graph of
+        the run records them and nothing outside the run can regrow them — but stay off its backward tape, and their random draws stay out
+        of the run's Philox draw plan: each is one launch into a buffer of its own call site, on whichever stream is current (the in-step
+        WGAN-GP penalty runs on the second stream while the plan's draws of the phase go out on the first)."""
+        if not self._phase_depth:
+            raise lib.TgError("Context.detached() needs a running phase (phase_scope)")
+        prev = (self.tape, self.detached_draws)
+        self.tape, self.detached_draws = None, True
+        try:
+            yield
+        finally:
+            self.tape, self.detached_draws = prev
 
     @contextlib.contextmanager
     def no_record(self):

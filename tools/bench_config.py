@@ -8,6 +8,8 @@
     python tools/bench_config.py --config svhn       the same in fp32
     python tools/bench_config.py --config mnist      MNIST 28x28x1, Good_GAN mnist (configs[0] shape)
     python tools/bench_config.py --config cifar10[-bf16]   the bench.py workload (Good_GAN_cifar10, synthetic ZCA), fp32 / bf16 operands
+    --loss wgan_gp                                   any fp32 configuration trained with config.LOSS = 'WGAN_GP' (the gradient penalty in the
+                                                     D-update); the default --loss gan is the step above, with exactly the output it always had
 
 Runs the D+G+C step on synthetic images already resident in HBM, then one instrumented eager iteration with
 per-kernel-class HIP-event timing.  Prints ONE JSON line: ms/step, images/sec and, per kernel class, launches,
@@ -43,7 +45,7 @@ SHAPES = {   # name: (data, H, C, B_G, L_C, U_C, L_D, U_D, mfma dtype, lambda_1,
 }
 
 
-def make_config(name='stress64'):
+def make_config(name='stress64', loss='gan'):
     from config import Config
     data, hw, ch, bg, lc, uc, ld, ud, prec, lam, lr, clr = SHAPES[name]
 
@@ -73,6 +75,7 @@ def make_config(name='stress64'):
         SEED = 0
         MFMA_DTYPE = prec
         ACT_DTYPE = 'bf16' if name.endswith('-act') else 'f32'
+        LOSS = {'gan': 'GAN', 'wgan_gp': 'WGAN_GP'}[loss]
 
     return TempConfig()
 
@@ -82,6 +85,7 @@ def main():
     ap.add_argument('--config', choices=sorted(SHAPES), default='stress64')
     ap.add_argument('--steps', type=int, default=60)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--loss', choices=('gan', 'wgan_gp'), default='gan')
     args = ap.parse_args()
     import torch
     from tg import lib
@@ -93,7 +97,7 @@ def main():
     else:
         from Model.Good_GAN import Good_GAN as Model
 
-    cfg = make_config(args.config)
+    cfg = make_config(args.config, args.loss)
     if args.config.startswith('cifar10'):
         q, _ = np.linalg.qr(np.random.default_rng(4321).standard_normal((3072, 3072)))      # SURVEY §8d synthetic whitening
         cfg.ZCA = (np.zeros(3072, np.float32), q.astype(np.float32))
@@ -171,7 +175,7 @@ def main():
     mem = torch.cuda.max_memory_allocated() / 2 ** 30
     print(json.dumps({"workload": "%s: synthetic %dx%dx%d, B_G/L_C/U_C/L_D/U_D=%d/%d/%d/%d/%d, %s D+G+C step, MFMA operands %s" % (
                           args.config, cfg.IMAGE_HEIGHT, cfg.IMAGE_WIDTH, cfg.CHANNEL, cfg.BATCH_SIZE_G, cfg.BATCH_SIZE_L_C, cfg.BATCH_SIZE_U_C,
-                          cfg.BATCH_SIZE_L_D, cfg.BATCH_SIZE_U_D, Model.__name__, cfg.MFMA_DTYPE),
+                          cfg.BATCH_SIZE_L_D, cfg.BATCH_SIZE_U_D, Model.__name__, cfg.MFMA_DTYPE) + (", WGAN-GP loss" if args.loss == 'wgan_gp' else ""),
                       "act_dtype": cfg.ACT_DTYPE, "bf16_act_edges": tr.bf16_act_edges,
                       "ms_per_step": round(dt * 1e3, 3), "images_per_sec": round(cfg.BATCH_SIZE_G / dt, 1), "steps": args.steps, "hbm_gib_allocated": round(mem, 2),
                       "host_issue_ms_per_step": round(t_issue_free * 1e3, 3), "host_issue_ms_per_step_queue_full": round(t_issue * 1e3, 3),
