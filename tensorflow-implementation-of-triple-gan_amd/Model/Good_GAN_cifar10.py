@@ -392,8 +392,9 @@ class cifar10_ZCA():
         cx = ctx()
         zc = getattr(config, 'ZCA', None)
         if zc is None:
-            m = np.load(os.path.join(config.DATA_DIR, "cifar10_zca_mean.npy"))
-            mat = np.load(os.path.join(config.DATA_DIR, "cifar10_zca_mat.npy"))
+            pre = "cifar100" if getattr(config, 'DATA_NAME', None) == "cifar100" else "cifar10"      # cifar100_zca_*.npy for CIFAR-100
+            m = np.load(os.path.join(config.DATA_DIR, pre + "_zca_mean.npy"))
+            mat = np.load(os.path.join(config.DATA_DIR, pre + "_zca_mat.npy"))
         else:
             m, mat = zc
         m = np.asarray(m, np.float32).reshape(-1)

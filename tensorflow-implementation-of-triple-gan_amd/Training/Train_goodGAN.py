@@ -67,6 +67,19 @@ def check_loss(config):
     return loss
 
 
+NUM_CLASSES_RANGE = (2, 1024)
+
+
+def check_num_classes(config):
+    """config.NUM_CLASSES: an int in 2..1024, the range of the classifier's loss heads (csrc/loss.hip; 10 runs the ten-class kernels, any
+    other count the general ones).  Needs no device; ValueError outside it."""
+    k = getattr(config, 'NUM_CLASSES', None)
+    lo, hi = NUM_CLASSES_RANGE
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not lo <= k <= hi:
+        raise ValueError("NUM_CLASSES must be an integer in %d..%d (the classifier's loss heads), got %r" % (lo, hi, k))
+    return int(k)
+
+
 class Train(Train_base):
     def __init__(self, config, log_dir, save_dir, **kwargs):
         super(Train, self).__init__()
@@ -87,6 +100,7 @@ class Train(Train_base):
             raise ValueError("MFMA_DTYPE must be 'f32' or 'bf16', got %r" % (cx.mfma_dtype,))
         # 'bf16': the batch norms the model marks store their output as bf16 — same numbers, half the bytes (Context.act_dtype)
         cx.act_dtype = check_act_dtype(config)
+        check_num_classes(config)
         self.loss_kind = check_loss(config)          # 'GAN' | 'WGAN_GP': the loss heads of the three solver runs
         self._gp_w = self._gp_grad = None            # WGAN-GP: the D-update's weighted penalty and its parameter gradient (device)
         cx.bf16_act_layers = set()
@@ -827,6 +841,48 @@ def _main_training_cifar10(FLAGS=None, Dataset=None, epochs=None):
         q, _ = np.linalg.qr(np.random.default_rng(4321).standard_normal((3072, 3072)))      # SURVEY §8d synthetic whitening
         TempConfig.ZCA = (np.zeros(3072, np.float32), q.astype(np.float32))
     return _run(TempConfig, Model, Dataset, FLAGS, "This training is for cifar10 dataset.", epochs)
+
+
+def _main_training_cifar100(FLAGS=None, Dataset=None, epochs=None):
+    """CIFAR-100 (not an entry point of the reference): the networks and algorithm of _main_training_cifar10 with NUM_CLASSES = 100, so the
+    classifier heads run the general-K kernels (csrc/loss.hip).  config.ZCA must carry (mean, mat) when DATA_DIR holds no
+    cifar100_zca_*.npy; without either, the synthetic whitening of the CIFAR-10 entry point."""
+    from config import Config
+    from Model.Good_GAN_cifar10 import Good_GAN_cifar10 as Model
+
+    class TempConfig(Config):
+        NAME = "Good_GAN"
+        DATA_NAME = "cifar100"
+        DATA_DIR = os.path.join(_root_dir(), "DataSet/cifar_100")
+        NUM_LABEL = 10000
+        BATCH_SIZE_G = 100
+        BATCH_SIZE_bG = 10
+        BATCH_SIZE_L_C = 50
+        BATCH_SIZE_U_C = 50
+        BATCH_SIZE_L_D = 20
+        BATCH_SIZE_U_D = 80
+        BATCH_SIZE = BATCH_SIZE_G
+        IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = 32, 32, 3
+        REPEAT = -1
+        FAKE_G_LAMBDA = 0.3
+        Z_DIM = 100
+        NUM_CLASSES = 100
+        MINIBATCH_DIS = False
+        RESTORE = False
+        LEARNING_RATE = 3e-4
+        CLA_LEARNINIG_RATE = 3e-3
+        EPOCHS = 1000
+        TRAIN_SIZE = 50000 - NUM_LABEL
+        SAVE_PER_EPOCH = 1
+        VAL_STEP = None
+        SAMPLE_DIR = "cifar100_good_GAN_10000"
+        WEIGHT_DIR = os.path.join(_root_dir(), "Training/Weight_cifar100")
+        LOG_DIR = os.path.join(_root_dir(), "Training/Log_cifar100")
+
+    if TempConfig.ZCA is None and not os.path.exists(os.path.join(TempConfig.DATA_DIR, "cifar100_zca_mat.npy")):
+        q, _ = np.linalg.qr(np.random.default_rng(4321).standard_normal((3072, 3072)))      # the synthetic whitening of _main_training_cifar10
+        TempConfig.ZCA = (np.zeros(3072, np.float32), q.astype(np.float32))
+    return _run(TempConfig, Model, Dataset, FLAGS, "This training is for cifar100 dataset.", epochs)
 
 
 def _main_training_mnist(FLAGS=None, Dataset=None, epochs=None):

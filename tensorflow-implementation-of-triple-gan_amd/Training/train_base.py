@@ -144,7 +144,9 @@ class Train_base(object):
         """c_loss (train_base.py:118,130-152); rows of c_logits [real|unl|unl_rep|fake]."""
         cx = ctx()
         g = cx.new_act(c_logits.n, 1, 1, c_logits.c, c_logits.ld, tag='dl')
-        lib.call('tg_c_loss_f32', c_logits.ptr, c_logits.ld, n_real, n_unl, n_rep, n_fake, y_l_c.ptr, y_g.ptr,
+        k = c_logits.c
+        head, kk = ('tg_c_loss_f32', ()) if k == 10 else ('tg_c_loss_k_f32', (k,))       # K = 10 keeps the ten-class launch
+        lib.call(head, c_logits.ptr, c_logits.ld, n_real, n_unl, n_rep, n_fake, *kk, y_l_c.ptr, y_g.ptr,
                  d_unl_logits.ptr, d_unl_logits.ld, lib.ptr(lambdas_dev), g.ptr, g.ld, lib.ptr(loss_out), cx.stream)
         c_logits.grad = g
 
@@ -210,7 +212,9 @@ class Train_base(object):
         g = cx.new_act(ccat.n, 1, 1, ccat.c, ccat.ld, tag='dl')
         n_rep = c_rep.n if c_rep is not None else 0
         n_gf = c_gfake.n if c_gfake is not None else 0
-        lib.call('tg_c_loss_terms_f32', ccat.ptr, ccat.ld, c_real.n, c_unl.n, n_rep, n_gf, y_l_c.ptr, y_g.ptr if c_gfake is not None else None,
+        k = ccat.c
+        head, kk = ('tg_c_loss_terms_f32', ()) if k == 10 else ('tg_c_loss_terms_k_f32', (k,))
+        lib.call(head, ccat.ptr, ccat.ld, c_real.n, c_unl.n, n_rep, n_gf, *kk, y_l_c.ptr, y_g.ptr if c_gfake is not None else None,
                  d_unl.ptr if d_unl is not None else None, d_unl.ld if d_unl is not None else 0, (C.c_float * 6)(*w6), g.ptr, g.ld, P(5), P(6),
                  cx.stream)
         ccat.grad = g
@@ -221,7 +225,9 @@ class Train_base(object):
         g_unl = c_unl.grad
         gb = cx.new_act(c_bfake.n, 1, 1, c_bfake.c, c_bfake.ld, tag='dl')
         unl_rows = ccat.view_rows(c_real.n, c_real.n + c_unl.n)
-        lib.call('tg_true_fake_loss_f32', unl_rows.ptr, ccat.ld, c_unl.n, c_bfake.ptr, c_bfake.ld, c_bfake.n, w_bad, w_bad, g_unl.ptr, g_unl.ld, 1,
+        assert c_bfake.c == k, (c_bfake.c, k)
+        head = 'tg_true_fake_loss_f32' if k == 10 else 'tg_true_fake_loss_k_f32'
+        lib.call(head, unl_rows.ptr, ccat.ld, c_unl.n, c_bfake.ptr, c_bfake.ld, c_bfake.n, *kk, w_bad, w_bad, g_unl.ptr, g_unl.ld, 1,
                  gb.ptr, gb.ld, 0, P(12), cx.stream)
         c_bfake.grad = gb
         if c_pert is not None:
@@ -377,7 +383,9 @@ class Train_base(object):
         self.last_d_cat = dcat
         ccat = concat_acts([c_real, c_unl, c_fake])                  # tg_c_loss_terms_f32 rows [real | unl | fake]; the unl terms weigh 0
         gc = cx.new_act(ccat.n, 1, 1, ccat.c, ccat.ld, tag='dl')
-        lib.call('tg_c_loss_terms_f32', ccat.ptr, ccat.ld, c_real.n, c_unl.n, 0, c_fake.n, Y.ptr, Y.ptr, None, 0,
+        k = ccat.c
+        head, kk = ('tg_c_loss_terms_f32', ()) if k == 10 else ('tg_c_loss_terms_k_f32', (k,))
+        lib.call(head, ccat.ptr, ccat.ld, c_real.n, c_unl.n, 0, c_fake.n, *kk, Y.ptr, Y.ptr, None, 0,
                  (C_.c_float * 6)(1.0, 0.0, 0.0, 0.0, lam2, 0.0), gc.ptr, gc.ld, P(5), P(6), cx.stream)
         ccat.grad = gc
         off = 0

@@ -1,6 +1,7 @@
 // Loss heads of Train_base._loss_GAN (Training/train_base.py:113-154) fused per network into ONE
 // single-workgroup launch each: value + gradient wrt the logits.  These are latency-bound (<= 250 rows of
-// <= 10 logits); reductions are wavefront shuffles + one LDS hop.  Also the feature-matching and pull-away
+// 10 logits, one thread per row; the *_k_kernel heads take any 2 <= K <= 1024 classes, one wave per row);
+// reductions are wavefront shuffles + one LDS hop.  Also the feature-matching and pull-away
 // terms of train_base.py:172-182,202-207 (unit parity; not on the Train_goodGAN.py path) and the
 // streaming accuracy counter of Train_goodGAN.py:428-447.
 #include "tg_common.h"
@@ -398,6 +399,288 @@ __global__ void __launch_bounds__(256) entropy_terms_kernel(const float* __restr
   }
 }
 
+// ---- general-K heads (2 <= K <= KMAX; K = 10 keeps the kernels above) ------------------------------------------------------
+// One workgroup of KW waves; each wave owns a row at a time (rows strided over the waves), the row's K classes spread over the 64 lanes
+// (lane owns classes lane, lane + 64, ...; KCH chunks, the first nch = ceil(K/64) of them live).  Row reductions are xor butterflies, so
+// every lane holds the same bits; the class marginals of the balance term are per-wave partials in LDS summed in wave order; the scalar
+// terms are summed over the workgroup in thread order.  No atomics: two launches on the same inputs are bit-identical.
+constexpr int KMAX = 1024;
+constexpr int KCH = KMAX / 64;
+constexpr int KW = 16;                 // waves per workgroup (1024 threads): <= 16 rows per wave at the step's 250 rows
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+__device__ float block_sum_k(float v, float* red) {   // KW waves, summed in wave order
+  v = tgd::wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = 0.f;
+  for (int i = 0; i < KW; ++i) s += red[i];
+  return s;
+}
+
+// softmax of one row of k logits over the wave: l, p per lane (0 for classes >= k, never read), lse wave-uniform
+__device__ __forceinline__ void softmax_row(const float* __restrict__ row, int k, int nch, int lane, float (&l)[KCH], float (&p)[KCH], float* lse) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < KCH; ++c) {
+    const int j = c * 64 + lane;
+    l[c] = (c < nch && j < k) ? row[j] : 0.f;
+    if (c < nch && j < k) m = fmaxf(m, l[c]);
+  }
+  m = wave_max(m);
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < KCH; ++c) {
+    p[c] = (c < nch && c * 64 + lane < k) ? expf(l[c] - m) : 0.f;
+    s += p[c];
+  }
+  s = tgd::wave_sum(s);
+  const float inv = 1.f / s;
+#pragma unroll
+  for (int c = 0; c < KCH; ++c) p[c] *= inv;
+  *lse = m + logf(s);
+}
+
+// q[j] = mean over the n rows of softmax(z)_j, j < k (qp: KW x KMAX scratch of per-wave partials); ends with a barrier
+__device__ void class_marginals(const float* __restrict__ z, int ld, int n, int k, int nch, float (*qp)[KMAX], float* q) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  float l[KCH], p[KCH], lse, qa[KCH];
+#pragma unroll
+  for (int c = 0; c < KCH; ++c) qa[c] = 0.f;
+  for (int r = wv; r < n; r += KW) {
+    softmax_row(z + (int64_t)r * ld, k, nch, lane, l, p, &lse);
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) qa[c] += p[c];
+  }
+#pragma unroll
+  for (int c = 0; c < KCH; ++c)
+    if (c < nch && c * 64 + lane < k) qp[wv][c * 64 + lane] = qa[c];
+  __syncthreads();
+  for (int j = threadIdx.x; j < k; j += 64 * KW) {
+    float s = 0.f;
+    for (int i = 0; i < KW; ++i) s += qp[i][j];
+    q[j] = s / n;
+  }
+  __syncthreads();
+}
+
+// -sum_j (1/k) log(q_j + 1e-12), workgroup-uniform
+__device__ float balance_entropy(const float* q, int k, float* red) {
+  float b = 0.f;
+  for (int j = threadIdx.x; j < k; j += 64 * KW) b -= logf(q[j] + 1e-12f) / k;
+  return block_sum_k(b, red);
+}
+
+// (sum_j y_j, sum_j y_j l_j) of one label row, wave-uniform
+__device__ __forceinline__ void label_dots(const float* __restrict__ y, int k, int nch, int lane, const float (&l)[KCH], float* ysum, float* yl) {
+  float a = 0.f, b = 0.f;
+#pragma unroll
+  for (int c = 0; c < KCH; ++c) {
+    const int j = c * 64 + lane;
+    if (c < nch && j < k) { a += y[j]; b += y[j] * l[c]; }
+  }
+  *ysum = tgd::wave_sum(a);
+  *yl = tgd::wave_sum(b);
+}
+
+// c_loss_kernel for k classes; rows, weights, outputs and term order as there
+__global__ void __launch_bounds__(64 * KW) c_loss_k_kernel(const float* __restrict__ cl, int ld, int n_real, int n_unl, int n_rep, int n_fake, int k,
+                                                          const float* __restrict__ y_real, const float* __restrict__ y_fake,
+                                                          const float* __restrict__ d_unl, int ld_dunl, const float* __restrict__ lam, CW w,
+                                                          float* __restrict__ dl, int ld_d, float* __restrict__ loss, float* __restrict__ terms) {
+  __shared__ float red[KW];
+  __shared__ float qp[KW][KMAX];
+  __shared__ float q[KMAX];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nch = (k + 63) >> 6;
+  const float lam1 = lam ? lam[0] : w.fake, lam2 = n_rep > 0 ? (lam ? lam[1] : w.mse) : 0.f;
+  const int o_unl = n_real, o_rep = n_real + n_unl, o_fake = o_rep + n_rep;
+  // row terms are wave-uniform and counted on lane 0; the MSE is per-lane partials counted on every lane
+  float acc = 0.f, t_real = 0.f, t_fake = 0.f, t_unl = 0.f, t_h = 0.f, t_mse = 0.f;
+  class_marginals(cl + (int64_t)o_unl * ld, ld, n_unl, k, nch, qp, q);
+  const float bal = balance_entropy(q, k, red);
+  float l[KCH], p[KCH], lse;
+  for (int pass = 0; pass < 2; ++pass) {                 // labelled rows (real, then fake)
+    const int n = pass == 0 ? n_real : n_fake, off = pass == 0 ? 0 : o_fake;
+    const float* y = pass == 0 ? y_real : y_fake;
+    const float wt = pass == 0 ? w.real : lam1;
+    for (int r = wv; r < n; r += KW) {
+      softmax_row(cl + (int64_t)(off + r) * ld, k, nch, lane, l, p, &lse);
+      const float* yr = y + (int64_t)r * k;
+      float ysum, yl;
+      label_dots(yr, k, nch, lane, l, &ysum, &yl);
+      if (lane == 0) {
+        acc += wt * (lse * ysum - yl) / n;
+        if (pass == 0) t_real += (lse * ysum - yl) / n; else t_fake += (lse * ysum - yl) / n;
+      }
+      float* o = dl + (int64_t)(off + r) * ld_d;
+#pragma unroll
+      for (int c = 0; c < KCH; ++c) {
+        const int j = c * 64 + lane;
+        if (c < nch && j < k) o[j] = wt * (p[c] * ysum - yr[j]) / n;
+      }
+      for (int j = k + lane; j < ld_d; j += 64) o[j] = 0.f;
+    }
+  }
+  for (int r = wv; r < n_unl; r += KW) {                // unlabelled rows
+    softmax_row(cl + (int64_t)(o_unl + r) * ld, k, nch, lane, l, p, &lse);
+    float pm = -1.f, pl = 0.f, pdq = 0.f;
+    int am = KMAX;
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) {
+      const int j = c * 64 + lane;
+      if (c < nch && j < k) {
+        if (p[c] > pm) { pm = p[c]; am = j; }
+        pl += p[c] * l[c];
+        pdq += p[c] * (-1.f / (k * (q[j] + 1e-12f)) / n_unl);   // d Bal / d q_j, recomputed below (registers)
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {                   // arg-max, the lowest class among equal maxima (as the K = 10 loop)
+      const float pv = __shfl_xor(pm, o, 64);
+      const int av = __shfl_xor(am, o, 64);
+      if (pv > pm || (pv == pm && av < am)) { pm = pv; am = av; }
+    }
+    pl = tgd::wave_sum(pl);
+    pdq = tgd::wave_sum(pdq);
+    const float rr = d_unl ? bce(d_unl[(int64_t)r * ld_dunl], 1.f) : 0.f;
+    if (lane == 0) {
+      acc += w.unl * pm * rr / n_unl + w.h * (lse - pl) / n_unl;
+      t_unl += pm * rr / n_unl;
+      t_h += (lse - pl) / n_unl;
+    }
+    float* o = dl + (int64_t)(o_unl + r) * ld_d;
+    float* orep = dl + (int64_t)(o_rep + r) * ld_d;
+    const float* lrep = cl + (int64_t)(o_rep + r) * ld;
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) {
+      const int j = c * 64 + lane;
+      if (!(c < nch && j < k)) continue;
+      float g = w.unl * rr * pm * ((j == am ? 1.f : 0.f) - p[c]) / n_unl;     // C fools D
+      g += w.h * (p[c] - p[c] * (1.f + l[c] - pl)) / n_unl;                   // entropy
+      g += w.bal * p[c] * (-1.f / (k * (q[j] + 1e-12f)) / n_unl - pdq);        // balance entropy
+      if (n_rep > 0) {
+        const float d = lrep[j] - l[c];
+        const float gm = lam2 * 2.f * d / (n_unl * k);
+        acc += lam2 * d * d / (n_unl * k);
+        t_mse += d * d / (n_unl * k);
+        g -= gm;
+        orep[j] = gm;
+      }
+      o[j] = g;
+    }
+    for (int j = k + lane; j < ld_d; j += 64) { o[j] = 0.f; if (n_rep > 0) orep[j] = 0.f; }
+  }
+  acc = block_sum_k(acc, red);
+  if (threadIdx.x == 0) loss[0] = acc + w.bal * bal;
+  if (terms) {                                           // block-uniform
+    const float v[6] = {t_real, t_unl, t_h, 0.f, t_fake, t_mse};
+    for (int i = 0; i < 6; ++i) {
+      const float sum = i == 3 ? bal : block_sum_k(v[i], red);
+      if (threadIdx.x == 0) terms[i] = sum;
+    }
+  }
+}
+
+// true_fake_kernel for k classes
+__global__ void __launch_bounds__(64 * KW) true_fake_k_kernel(const float* __restrict__ unl, int ld_u, int n_unl, const float* __restrict__ fake,
+                                                             int ld_f, int n_fake, int k, float w_unl, float w_fake, float* __restrict__ d_unl,
+                                                             int ld_du, int acc_unl, float* __restrict__ d_fake, int ld_df, int acc_fake,
+                                                             float* __restrict__ loss) {
+  __shared__ float red[KW];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nch = (k + 63) >> 6;
+  float l[KCH], p[KCH], lse, t_u = 0.f, t_f = 0.f;
+  for (int pass = 0; pass < 2; ++pass) {
+    const int n = pass == 0 ? n_unl : n_fake;
+    const float* src = pass == 0 ? unl : fake;
+    const int ld = pass == 0 ? ld_u : ld_f, ldo = pass == 0 ? ld_du : ld_df, accum = pass == 0 ? acc_unl : acc_fake;
+    float* dst = pass == 0 ? d_unl : d_fake;
+    for (int r = wv; r < n; r += KW) {
+      softmax_row(src + (int64_t)r * ld, k, nch, lane, l, p, &lse);
+      float coef;
+      if (pass == 0) { if (lane == 0) t_u += (-0.5f * lse + 0.5f * softplus(lse)) / n; coef = w_unl * (-0.5f + 0.5f * sigm(lse)) / n; }
+      else { if (lane == 0) t_f += 0.5f * softplus(lse) / n; coef = w_fake * 0.5f * sigm(lse) / n; }
+      float* o = dst + (int64_t)r * ldo;
+#pragma unroll
+      for (int c = 0; c < KCH; ++c) {
+        const int j = c * 64 + lane;
+        if (c < nch && j < k) o[j] = (accum ? o[j] : 0.f) + coef * p[c];
+      }
+      if (!accum) for (int j = k + lane; j < ldo; j += 64) o[j] = 0.f;
+    }
+  }
+  t_u = block_sum_k(t_u, red);
+  t_f = block_sum_k(t_f, red);
+  if (threadIdx.x == 0) { loss[0] = w_unl * t_u + w_fake * t_f; loss[1] = t_u; loss[2] = t_f; }
+}
+
+// softmax_ce_kernel for k classes
+__global__ void __launch_bounds__(64 * KW) softmax_ce_k_kernel(const float* __restrict__ z, int ld, const float* __restrict__ y, int n, int k, float w,
+                                                              float* __restrict__ dz, int ld_d, int acc, float* __restrict__ loss) {
+  __shared__ float red[KW];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nch = (k + 63) >> 6;
+  float l[KCH], p[KCH], lse, t = 0.f;
+  for (int r = wv; r < n; r += KW) {
+    softmax_row(z + (int64_t)r * ld, k, nch, lane, l, p, &lse);
+    const float* yr = y + (int64_t)r * k;
+    float ysum, yl;
+    label_dots(yr, k, nch, lane, l, &ysum, &yl);
+    if (lane == 0) t += (lse * ysum - yl) / n;
+    if (dz) {
+      float* o = dz + (int64_t)r * ld_d;
+#pragma unroll
+      for (int c = 0; c < KCH; ++c) {
+        const int j = c * 64 + lane;
+        if (c < nch && j < k) o[j] = (acc ? o[j] : 0.f) + w * (p[c] * ysum - yr[j]) / n;
+      }
+      if (!acc) for (int j = k + lane; j < ld_d; j += 64) o[j] = 0.f;
+    }
+  }
+  t = block_sum_k(t, red);
+  if (threadIdx.x == 0) { loss[0] = w * t; loss[1] = t; }
+}
+
+// entropy_terms_kernel for k classes
+__global__ void __launch_bounds__(64 * KW) entropy_terms_k_kernel(const float* __restrict__ z, int ld, int n, int k, float w_h, float w_bal,
+                                                                 float* __restrict__ dz, int ld_d, int acc, float* __restrict__ loss) {
+  __shared__ float red[KW];
+  __shared__ float qp[KW][KMAX];
+  __shared__ float q[KMAX];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nch = (k + 63) >> 6;
+  class_marginals(z, ld, n, k, nch, qp, q);
+  const float bal = balance_entropy(q, k, red);
+  float l[KCH], p[KCH], lse, t_h = 0.f;
+  for (int r = wv; r < n; r += KW) {
+    softmax_row(z + (int64_t)r * ld, k, nch, lane, l, p, &lse);
+    float pl = 0.f, pdq = 0.f;
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) {
+      const int j = c * 64 + lane;
+      if (c < nch && j < k) { pl += p[c] * l[c]; pdq += p[c] * (-1.f / (k * (q[j] + 1e-12f)) / n); }
+    }
+    pl = tgd::wave_sum(pl);
+    pdq = tgd::wave_sum(pdq);
+    if (lane == 0) t_h += (lse - pl) / n;
+    if (dz) {
+      float* o = dz + (int64_t)r * ld_d;
+#pragma unroll
+      for (int c = 0; c < KCH; ++c) {
+        const int j = c * 64 + lane;
+        if (c < nch && j < k)
+          o[j] = (acc ? o[j] : 0.f) + w_h * (p[c] - p[c] * (1.f + l[c] - pl)) / n + w_bal * p[c] * (-1.f / (k * (q[j] + 1e-12f)) / n - pdq);
+      }
+      if (!acc) for (int j = k + lane; j < ld_d; j += 64) o[j] = 0.f;
+    }
+  }
+  t_h = block_sum_k(t_h, red);
+  if (threadIdx.x == 0) { loss[0] = w_h * t_h + w_bal * bal; loss[1] = t_h; loss[2] = bal; }
+}
+
 // counters[0] += #(argmax logits == argmax labels), counters[1] += n     (tf.metrics.accuracy, Train_goodGAN.py:428-447)
 __global__ void __launch_bounds__(256) accuracy_kernel(const float* __restrict__ logits, int ld, const float* __restrict__ labels, int n, int k,
                                                        float* __restrict__ counters) {
@@ -417,12 +700,18 @@ __global__ void __launch_bounds__(256) accuracy_kernel(const float* __restrict__
 
 }  // namespace
 
-#define LOSS_LAUNCH(kern, ...)                                               \
+#define LOSS_LAUNCH_T(kern, threads, ...)                                    \
   hipStream_t s__ = tg::as_stream(stream);                                   \
   tg::ProfScope prof__(tg::PC_LOSS, 0, 0, s__);                              \
-  hipLaunchKernelGGL(kern, dim3(1), dim3(256), 0, s__, __VA_ARGS__);         \
+  hipLaunchKernelGGL(kern, dim3(1), dim3(threads), 0, s__, __VA_ARGS__);     \
   TG_CHECK_LAUNCH(#kern);                                                    \
   return TG_OK;
+#define LOSS_LAUNCH(kern, ...) LOSS_LAUNCH_T(kern, 256, __VA_ARGS__)
+#define LOSS_LAUNCH_K(kern, ...) LOSS_LAUNCH_T(kern, 64 * KW, __VA_ARGS__)
+
+// the class count of a general-K head
+#define REQUIRE_K(name, k)                                                                                                          \
+  TG_REQUIRE((k) >= 2 && (k) <= KMAX, name ": k = %d classes is outside the supported range 2 <= k <= %d", (int)(k), KMAX)
 
 extern "C" {
 
@@ -463,12 +752,53 @@ int tg_c_loss_terms_f32(const float* c_logits, int ld, int n_real, int n_unl, in
               ld_d, loss, terms)
 }
 
+int tg_c_loss_k_f32(const float* c_logits, int ld, int n_real, int n_unl, int n_rep, int n_fake, int k, const float* y_real, const float* y_fake,
+                    const float* d_unl_logits, int ld_dunl, const float* lambdas, float* dlogits, int ld_d, float* loss, void* stream) {
+  if (k == KC)
+    return tg_c_loss_f32(c_logits, ld, n_real, n_unl, n_rep, n_fake, y_real, y_fake, d_unl_logits, ld_dunl, lambdas, dlogits, ld_d, loss, stream);
+  REQUIRE_K("c_loss_k", k);
+  TG_REQUIRE(c_logits && y_real && y_fake && d_unl_logits && lambdas && dlogits && loss, "c_loss_k: null buffer");
+  TG_REQUIRE(n_real > 0 && n_unl > 0 && n_fake > 0 && (n_rep == 0 || n_rep == n_unl) && ld >= k && ld_d >= k, "c_loss_k: bad sizes");
+  const CW w{1.f, 0.005f, 1e-6f, 1e-3f, 0.f, 0.f};
+  LOSS_LAUNCH_K(c_loss_k_kernel, c_logits, ld, n_real, n_unl, n_rep, n_fake, k, y_real, y_fake, d_unl_logits, ld_dunl, lambdas, w, dlogits, ld_d,
+                loss, (float*)nullptr)
+}
+
+int tg_c_loss_terms_k_f32(const float* c_logits, int ld, int n_real, int n_unl, int n_rep, int n_fake, int k, const float* y_real,
+                          const float* y_fake, const float* d_unl_logits, int ld_dunl, const float* weights, float* dlogits, int ld_d, float* loss,
+                          float* terms, void* stream) {
+  if (k == KC)
+    return tg_c_loss_terms_f32(c_logits, ld, n_real, n_unl, n_rep, n_fake, y_real, y_fake, d_unl_logits, ld_dunl, weights, dlogits, ld_d, loss,
+                               terms, stream);
+  REQUIRE_K("c_loss_terms_k", k);
+  TG_REQUIRE(c_logits && y_real && weights && dlogits && loss, "c_loss_terms_k: null buffer");
+  TG_REQUIRE(n_real > 0 && n_unl > 0 && n_fake >= 0 && (n_rep == 0 || n_rep == n_unl) && ld >= k && ld_d >= k, "c_loss_terms_k: bad sizes");
+  TG_REQUIRE(n_fake == 0 || y_fake, "c_loss_terms_k: y_fake is NULL with %d generated rows", n_fake);
+  TG_REQUIRE(d_unl_logits || weights[1] == 0.f, "c_loss_terms_k: d_unl_logits is NULL but the C-fools-D weight is %g", (double)weights[1]);
+  const CW w{weights[0], weights[1], weights[2], weights[3], weights[4], weights[5]};
+  LOSS_LAUNCH_K(c_loss_k_kernel, c_logits, ld, n_real, n_unl, n_rep, n_fake, k, y_real, y_fake, d_unl_logits, ld_dunl, (const float*)nullptr, w,
+                dlogits, ld_d, loss, terms)
+}
+
 int tg_true_fake_loss_f32(const float* unl_logits, int ld_u, int n_unl, const float* fake_logits, int ld_f, int n_fake, float w_unl, float w_fake,
                           float* d_unl, int ld_du, int accumulate_unl, float* d_fake, int ld_df, int accumulate_fake, float* loss, void* stream) {
   TG_REQUIRE(unl_logits && fake_logits && d_unl && d_fake && loss, "true_fake_loss: null buffer");
   TG_REQUIRE(n_unl > 0 && n_fake > 0 && ld_u >= KC && ld_f >= KC && ld_du >= KC && ld_df >= KC, "true_fake_loss: bad sizes");
   LOSS_LAUNCH(true_fake_kernel, unl_logits, ld_u, n_unl, fake_logits, ld_f, n_fake, w_unl, w_fake, d_unl, ld_du, accumulate_unl, d_fake, ld_df,
               accumulate_fake, loss)
+}
+
+int tg_true_fake_loss_k_f32(const float* unl_logits, int ld_u, int n_unl, const float* fake_logits, int ld_f, int n_fake, int k, float w_unl,
+                            float w_fake, float* d_unl, int ld_du, int accumulate_unl, float* d_fake, int ld_df, int accumulate_fake, float* loss,
+                            void* stream) {
+  if (k == KC)
+    return tg_true_fake_loss_f32(unl_logits, ld_u, n_unl, fake_logits, ld_f, n_fake, w_unl, w_fake, d_unl, ld_du, accumulate_unl, d_fake, ld_df,
+                                 accumulate_fake, loss, stream);
+  REQUIRE_K("true_fake_loss_k", k);
+  TG_REQUIRE(unl_logits && fake_logits && d_unl && d_fake && loss, "true_fake_loss_k: null buffer");
+  TG_REQUIRE(n_unl > 0 && n_fake > 0 && ld_u >= k && ld_f >= k && ld_du >= k && ld_df >= k, "true_fake_loss_k: bad sizes");
+  LOSS_LAUNCH_K(true_fake_k_kernel, unl_logits, ld_u, n_unl, fake_logits, ld_f, n_fake, k, w_unl, w_fake, d_unl, ld_du, accumulate_unl, d_fake,
+                ld_df, accumulate_fake, loss)
 }
 
 int tg_sqdiff_rows_loss_f32(const float* a, int ld_a, const float* b, int ld_b, int n, int k, float w, float* da, int ld_da, int accumulate_a,
@@ -492,8 +822,10 @@ int tg_pull_away_f32(const float* f, int n, int c, int masked, float* scratch, f
 
 int tg_softmax_ce_f32(const float* logits, int ld, const float* labels, int n, int k, float w, float* dlogits, int ld_d, int accumulate, float* loss,
                       void* stream) {
-  TG_REQUIRE(logits && labels && loss && n > 0 && k == KC && ld >= KC && (!dlogits || ld_d >= KC), "softmax_ce: bad args (k must be %d)", KC);
-  LOSS_LAUNCH(softmax_ce_kernel, logits, ld, labels, n, w, dlogits, ld_d, accumulate, loss)
+  REQUIRE_K("softmax_ce", k);
+  TG_REQUIRE(logits && labels && loss && n > 0 && ld >= k && (!dlogits || ld_d >= k), "softmax_ce: bad args");
+  if (k == KC) { LOSS_LAUNCH(softmax_ce_kernel, logits, ld, labels, n, w, dlogits, ld_d, accumulate, loss) }
+  LOSS_LAUNCH_K(softmax_ce_k_kernel, logits, ld, labels, n, k, w, dlogits, ld_d, accumulate, loss)
 }
 
 int tg_bce_logits_f32(const float* logits, int ld, const float* labels, int ld_y, float label, int n, int c, float w, float* dlogits, int ld_d,
@@ -504,8 +836,10 @@ int tg_bce_logits_f32(const float* logits, int ld, const float* labels, int ld_y
 
 int tg_entropy_terms_f32(const float* logits, int ld, int n, int k, float w_h, float w_bal, float* dlogits, int ld_d, int accumulate, float* loss,
                          void* stream) {
-  TG_REQUIRE(logits && loss && n > 0 && k == KC && ld >= KC && (!dlogits || ld_d >= KC), "entropy_terms: bad args (k must be %d)", KC);
-  LOSS_LAUNCH(entropy_terms_kernel, logits, ld, n, w_h, w_bal, dlogits, ld_d, accumulate, loss)
+  REQUIRE_K("entropy_terms", k);
+  TG_REQUIRE(logits && loss && n > 0 && ld >= k && (!dlogits || ld_d >= k), "entropy_terms: bad args");
+  if (k == KC) { LOSS_LAUNCH(entropy_terms_kernel, logits, ld, n, w_h, w_bal, dlogits, ld_d, accumulate, loss) }
+  LOSS_LAUNCH_K(entropy_terms_k_kernel, logits, ld, n, k, w_h, w_bal, dlogits, ld_d, accumulate, loss)
 }
 
 int tg_accuracy_count_f32(const float* logits, int ld, const float* labels, int n, int k, float* counters, void* stream) {

@@ -8,6 +8,8 @@
     python tools/bench_config.py --config svhn       the same in fp32
     python tools/bench_config.py --config mnist      MNIST 28x28x1, Good_GAN mnist (configs[0] shape)
     python tools/bench_config.py --config cifar10[-bf16]   the bench.py workload (Good_GAN_cifar10, synthetic ZCA), fp32 / bf16 operands
+    python tools/bench_config.py --config cifar100   the CIFAR-10 networks and step with 100 classes (Training/Train_goodGAN._main_training_cifar100)
+    --num-classes K                                  config.NUM_CLASSES (2..1024; default 100 for cifar100, 10 otherwise, the rows as they always were)
     --loss wgan_gp                                   any fp32 configuration trained with config.LOSS = 'WGAN_GP' (the gradient penalty in the
                                                      D-update); the default --loss gan is the step above, with exactly the output it always had
 
@@ -42,10 +44,11 @@ SHAPES = {   # name: (data, H, C, B_G, L_C, U_C, L_D, U_D, mfma dtype, lambda_1,
     'mnist': ('mnist', 28, 1, 100, 100, 100, 20, 80, 'f32', 0.1, 1e-3, 3e-4),
     'cifar10': ('cifar10', 32, 3, 100, 50, 50, 20, 80, 'f32', 0.3, 3e-4, 3e-3),
     'cifar10-bf16': ('cifar10', 32, 3, 100, 50, 50, 20, 80, 'bf16', 0.3, 3e-4, 3e-3),
+    'cifar100': ('cifar100', 32, 3, 100, 50, 50, 20, 80, 'f32', 0.3, 3e-4, 3e-3),
 }
 
 
-def make_config(name='stress64', loss='gan'):
+def make_config(name='stress64', loss='gan', num_classes=None):
     from config import Config
     data, hw, ch, bg, lc, uc, ld, ud, prec, lam, lr, clr = SHAPES[name]
 
@@ -63,7 +66,7 @@ def make_config(name='stress64', loss='gan'):
         IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = hw, hw, ch
         FAKE_G_LAMBDA = lam
         Z_DIM = 100
-        NUM_CLASSES = 10
+        NUM_CLASSES = num_classes if num_classes is not None else (100 if data == 'cifar100' else 10)
         MINIBATCH_DIS = False
         LEARNING_RATE = lr
         CLA_LEARNINIG_RATE = clr
@@ -86,18 +89,19 @@ def main():
     ap.add_argument('--steps', type=int, default=60)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--loss', choices=('gan', 'wgan_gp'), default='gan')
+    ap.add_argument('--num-classes', type=int, default=None, help='config.NUM_CLASSES (default: 100 for cifar100, else 10)')
     args = ap.parse_args()
     import torch
     from tg import lib
     from Training.Train_goodGAN import Train
     if args.config == 'stress64':
         from Model.Good_GAN_stress64 import Good_GAN_stress64 as Model
-    elif args.config.startswith('cifar10'):
+    elif args.config.startswith('cifar10'):                               # cifar10, cifar10-bf16, cifar100
         from Model.Good_GAN_cifar10 import Good_GAN_cifar10 as Model
     else:
         from Model.Good_GAN import Good_GAN as Model
 
-    cfg = make_config(args.config, args.loss)
+    cfg = make_config(args.config, args.loss, args.num_classes)
     if args.config.startswith('cifar10'):
         q, _ = np.linalg.qr(np.random.default_rng(4321).standard_normal((3072, 3072)))      # SURVEY §8d synthetic whitening
         cfg.ZCA = (np.zeros(3072, np.float32), q.astype(np.float32))
@@ -108,7 +112,8 @@ def main():
     rng = np.random.default_rng(1234)
     lo = 0.0 if cfg.DATA_NAME == 'mnist' else -1.0
     img = lambda n: rng.uniform(lo, 1, (n, cfg.IMAGE_HEIGHT, cfg.IMAGE_WIDTH, cfg.CHANNEL)).astype(np.float32)
-    oh = lambda n: np.eye(10, dtype=np.float32)[rng.integers(0, 10, n)]
+    k = cfg.NUM_CLASSES
+    oh = lambda n: np.eye(k, dtype=np.float32)[rng.integers(0, k, n)]
     tr.feed(dict(x_l_c=img(cfg.BATCH_SIZE_L_C), y_l_c=oh(cfg.BATCH_SIZE_L_C), x_l_d=img(cfg.BATCH_SIZE_L_D), y_l_d=oh(cfg.BATCH_SIZE_L_D),
                  x_u_d=img(cfg.BATCH_SIZE_U_D), x_u_c=img(cfg.BATCH_SIZE_U_C)))
 
@@ -175,7 +180,8 @@ def main():
     mem = torch.cuda.max_memory_allocated() / 2 ** 30
     print(json.dumps({"workload": "%s: synthetic %dx%dx%d, B_G/L_C/U_C/L_D/U_D=%d/%d/%d/%d/%d, %s D+G+C step, MFMA operands %s" % (
                           args.config, cfg.IMAGE_HEIGHT, cfg.IMAGE_WIDTH, cfg.CHANNEL, cfg.BATCH_SIZE_G, cfg.BATCH_SIZE_L_C, cfg.BATCH_SIZE_U_C,
-                          cfg.BATCH_SIZE_L_D, cfg.BATCH_SIZE_U_D, Model.__name__, cfg.MFMA_DTYPE) + (", WGAN-GP loss" if args.loss == 'wgan_gp' else ""),
+                          cfg.BATCH_SIZE_L_D, cfg.BATCH_SIZE_U_D, Model.__name__, cfg.MFMA_DTYPE) + (", WGAN-GP loss" if args.loss == 'wgan_gp' else "")
+                          + (", %d classes" % k if k != 10 else ""),
                       "act_dtype": cfg.ACT_DTYPE, "bf16_act_edges": tr.bf16_act_edges,
                       "ms_per_step": round(dt * 1e3, 3), "images_per_sec": round(cfg.BATCH_SIZE_G / dt, 1), "steps": args.steps, "hbm_gib_allocated": round(mem, 2),
                       "host_issue_ms_per_step": round(t_issue_free * 1e3, 3), "host_issue_ms_per_step_queue_full": round(t_issue * 1e3, 3),
