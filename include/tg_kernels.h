@@ -497,6 +497,11 @@ int tg_onehot_i32_f32(const int32_t* labels, float* out, int64_t n, int k, void*
 int tg_add_f32(float* dst, const float* a, const float* b, int64_t n, void* stream);
 /* tf.one_hot(tf.argmax(logits,1)) (Good_GAN_cifar10.py:232,237,259,270); out [n][k]. */
 int tg_argmax_onehot_f32(const float* logits, int ld, int n, int k, float* out, void* stream);
+/* ZCA fit of the CIFAR classifiers (Model/Good_GAN_cifar10.py cifar10_ZCA.fit; the constants the reference loads at
+ * Model/Good_GAN_cifar10.py:289-290): gram[d*d] += sum_n x'_n x'_n^T and colsum[d] += sum_n x'_n with x' = x - 128, over x: n rows of d
+ * uint8, contiguous.  Both triangles of gram are written.  Exact for any n: int64 outputs, int32 partial sums over at most 131071 rows,
+ * added with int64 atomics (the result does not depend on their order).  n = 0 is a no-op. */
+int tg_gram_u8_i64(const uint8_t* x, int64_t n, int d, int64_t* gram, int64_t* colsum, void* stream);
 
 /* ---- loss heads: value + d/dlogits in one launch (Training/train_base.py:113-154) ---------------- */
 /* rows [real | fake | unl]: d_loss = BCE(real,1) + .5 BCE(fake,0) + .5 BCE(unl,0). */

@@ -11,6 +11,7 @@ reference file.  Differences forced by eager execution:
   * `segments=` (extension) batches several applications of C or D into one call: identical maths,
     since D has no batch statistics and C's mean-only BN is computed per segment.
 """
+import math
 import os
 
 import numpy as np
@@ -383,18 +384,175 @@ def _onehot_act(logits, k):
     return Act(ops.argmax_onehot(logits, k), logits.n, 1, 1, k, k)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Fitting the ZCA constants from the training split (config.ZCA = 'fit').  The reference loads them from
+# DATA_DIR/<data>_zca_{mean,mat}.npy (:289-290) but neither it nor this package had code that makes them.
+# ---------------------------------------------------------------------------------------------------------------------
+
+# Regularisation of the whitening, mat = U diag((s + eps)^-1/2) U^T.  [UNVERIFIED] the value of the ZCA class of the improved-GAN /
+# Triple-GAN code lineage, recalled from memory: the reference repository holds no fitting code.
+ZCA_EPS = 1e-5
+ZCA_DATA = ('cifar10', 'cifar100')        # the DATA_NAMEs whose classifier sees ZCA-whitened inputs
+ZCA_CHUNK = 16384                         # images per staging buffer of the fit (50 MB of CIFAR bytes)
+# n G' - S' S'^T is exact in int64 while n^2 2^14 <= 2^63 - 1 (|x'| <= 128, so |G'| <= n 2^14 and |S'_i S'_j| <= n^2 2^14)
+ZCA_N_MAX = math.isqrt((2 ** 63 - 1) >> 14)
+
+
+def zca_prefix(config):
+    """'cifar100' for CIFAR-100 (cifar100_zca_*.npy), else 'cifar10'."""
+    return "cifar100" if getattr(config, 'DATA_NAME', None) == "cifar100" else "cifar10"
+
+
+def zca_paths(config):
+    """(mean, mat) file paths the reference loads (:289-290)."""
+    pre = os.path.join(config.DATA_DIR, zca_prefix(config))
+    return pre + "_zca_mean.npy", pre + "_zca_mat.npy"
+
+
+def zca_constants(n, colsum, gram, eps=ZCA_EPS, timings=None):
+    """Host derivation (float64, no device) of the ZCA constants from the exact integer moments of n images x (uint8) with x' = x - 128:
+    colsum S' = sum x', gram G' = sum x' x'^T.  The images the classifier sees are x/255*2-1 = (2x'+1)/255 (cifar10Dataset.py:60), so
+        mean = (2 S'/n + 1) / 255,   cov = 4/255^2 (n G' - S' S'^T) / n^2      (numerator exact in int64 for n <= ZCA_N_MAX)
+    and mat = U diag((s + eps)^-1/2) U^T over eigh(cov) with the eigenvalues s clipped at 0 (n < d leaves a null space).
+    Returns float64 (mean [d], mat [d, d]) in the flatten order of the images (NHWC)."""
+    import time
+    n = int(n)
+    if not 0 < n <= ZCA_N_MAX:
+        raise ValueError("ZCA fit: %d images; the integer derivation is exact for 1..%d" % (n, ZCA_N_MAX))
+    s1 = np.asarray(colsum, np.int64).reshape(-1)
+    d = s1.size
+    g = np.asarray(gram, np.int64).reshape(d, d)
+    mean = (2.0 * s1 / n + 1.0) / 255.0
+    num = n * g - np.outer(s1, s1)                                   # n^2 cov(x'), exact
+    cov = num.astype(np.float64) * (4.0 / (255.0 ** 2)) / (float(n) * float(n))
+    t0 = time.perf_counter()
+    s, u = np.linalg.eigh(cov)
+    t1 = time.perf_counter()
+    s = np.maximum(s, 0.0)
+    mat = (u * (s + eps) ** -0.5) @ u.T
+    mat = 0.5 * (mat + mat.T)                                        # symmetric to the last bit
+    if timings is not None:
+        timings['eigh'] = timings.get('eigh', 0.0) + (t1 - t0)
+        timings['mat'] = timings.get('mat', 0.0) + (time.perf_counter() - t1)
+    return mean, mat
+
+
+def zca_training_files(dataset):
+    """The record files of the training split of a TFRecord dataset, each once: input_from_tfrecord_filename() returns the labelled file
+    twice ([labelled for D, labelled for C, unlabelled]).  The test split is not opened."""
+    from Input_Pipeline.tfrecordDataset import tfrecordDataset
+    from tg import lib
+    if not isinstance(dataset, tfrecordDataset) or dataset.UNIT_RANGE:
+        raise lib.TgError("ZCA = 'fit' needs a training split of uint8 TFRecords in [-1, 1] scaling (a tfrecordDataset such as "
+                          "cifar10Dataset); %s has none" % type(dataset).__name__)
+    if dataset.subset != 'train':
+        raise lib.TgError("ZCA = 'fit' reads the training split only, got subset %r" % (dataset.subset,))
+    out = []
+    for rec in dataset.input_from_tfrecord_filename():
+        if all(rec is not r for r in out):
+            out.append(rec)
+    return out
+
+
+def zca_training_chunks(dataset, rows=ZCA_CHUNK):
+    """(RecordFile, record indices) pieces of at most `rows` records that cover every training record exactly once."""
+    for rec in zca_training_files(dataset):
+        for s in range(0, len(rec), rows):
+            yield rec, np.arange(s, min(s + rows, len(rec)), dtype=np.int64)
+
+
+def write_zca_files(config, mean, mat):
+    """Write (mean, mat) as float32 to zca_paths(config), each atomically (temporary file in the same directory, then os.replace); the
+    mat file last, so a reader that finds both finds complete ones.  lib.TgError naming the path if it cannot be written."""
+    import tempfile
+    from tg import lib
+    for path, arr in zip(zca_paths(config), (mean, mat)):
+        tmp = None
+        try:
+            fd, tmp = tempfile.mkstemp(dir=os.path.dirname(path) or '.', prefix='.' + os.path.basename(path), suffix='.tmp')
+            with os.fdopen(fd, 'wb') as f:
+                np.save(f, np.asarray(arr, np.float32))
+            os.replace(tmp, path)
+            tmp = None
+        except OSError as e:
+            raise lib.TgError("ZCA = 'fit': cannot write %s (%s)" % (path, e))
+        finally:
+            if tmp is not None and os.path.exists(tmp):
+                os.remove(tmp)
+
+
 class cifar10_ZCA():
     """:287-299: (flatten(x) - mean) @ mat.  Constants come from DATA_DIR/cifar10_zca_{mean,mat}.npy as in the
     reference; when the files are absent (they are not part of the reference repository) `config.ZCA` may
-    supply (mean, mat) arrays, e.g. the synthetic orthogonal matrix of SURVEY §8d."""
+    supply (mean, mat) arrays, e.g. the synthetic orthogonal matrix of SURVEY §8d, or the ones cifar10_ZCA.fit
+    computes (config.ZCA = 'fit', resolved by Training/Train_goodGAN.Train.train)."""
+
+    @staticmethod
+    def fit(dataset, eps=ZCA_EPS, chunk=ZCA_CHUNK, timings=None):
+        """ZCA constants of the training split of `dataset` (a tfrecordDataset, subset 'train') -> float32 (mean [d], mat [d, d]).
+        Every training record is decoded once into pinned uint8 staging (two buffers: decoding chunk k+1 overlaps the copy and the
+        Gram launch of chunk k, the event discipline of tfrecordDataset._to_device), copied to the device and accumulated by
+        tg_gram_u8_i64 into exact int64 (S', G'); those come back once and zca_constants derives the constants on the host.
+        timings: a dict to receive the wall seconds of each phase (decode, h2d, gram, d2h, eigh, mat); with it every device phase is
+        synchronised on its own, so the phases are measured one after the other instead of overlapped."""
+        import time
+        import torch
+        from tg import lib
+        from tg.runtime import ctx
+        cx = ctx()
+        files = [r for r in zca_training_files(dataset) if len(r)]
+        shapes = {r.shape for r in files}
+        if len(shapes) != 1:
+            raise lib.TgError("ZCA = 'fit': the training files hold images of shapes %s (one shape needed, none if empty)" % sorted(shapes))
+        d = int(np.prod(shapes.pop()))
+        stream = torch.cuda.current_stream(cx.device)
+        T = timings
+
+        def tick(key, t0, sync=False):
+            if T is None:
+                return
+            if sync:
+                torch.cuda.synchronize(cx.device)
+            T[key] = T.get(key, 0.0) + time.perf_counter() - t0
+
+        staging = [torch.empty(chunk * d, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        labels = np.empty(chunk, np.int32)
+        dev = [torch.empty(chunk * d, dtype=torch.uint8, device=cx.device) for _ in range(2)]
+        gram = torch.zeros(d * d, dtype=torch.int64, device=cx.device)
+        colsum = torch.zeros(d, dtype=torch.int64, device=cx.device)
+        events, n = [None, None], 0
+        for k, (rec, idx) in enumerate(zca_training_chunks(dataset, chunk)):
+            s, m = k & 1, len(idx)
+            if events[s] is not None:                    # the copy out of this staging buffer (two chunks ago) has run
+                events[s].synchronize()
+            t0 = time.perf_counter()
+            rec.gather(idx, staging[s].numpy(), labels, n_threads=4)
+            tick('decode', t0)
+            t0 = time.perf_counter()
+            dev[s][:m * d].copy_(staging[s][:m * d], non_blocking=True)
+            events[s] = torch.cuda.Event()
+            events[s].record(stream)
+            tick('h2d', t0, sync=True)
+            t0 = time.perf_counter()
+            lib.call('tg_gram_u8_i64', lib.ptr(dev[s]), m, d, lib.ptr(gram), lib.ptr(colsum), cx.stream)
+            tick('gram', t0, sync=True)
+            n += m
+        t0 = time.perf_counter()
+        g, s1 = gram.cpu().numpy(), colsum.cpu().numpy()
+        tick('d2h', t0)
+        mean, mat = zca_constants(n, s1, g, eps, timings)
+        return mean.astype(np.float32), mat.astype(np.float32)
 
     def __init__(self, config):
         cx = ctx()
         zc = getattr(config, 'ZCA', None)
+        if isinstance(zc, str):
+            from tg import lib
+            raise lib.TgError("config.ZCA = %r is resolved by Train.train (Training/Train_goodGAN.py) before the model whitens" % (zc,))
         if zc is None:
-            pre = "cifar100" if getattr(config, 'DATA_NAME', None) == "cifar100" else "cifar10"      # cifar100_zca_*.npy for CIFAR-100
-            m = np.load(os.path.join(config.DATA_DIR, pre + "_zca_mean.npy"))
-            mat = np.load(os.path.join(config.DATA_DIR, pre + "_zca_mat.npy"))
+            m_path, mat_path = zca_paths(config)                     # cifar100_zca_*.npy for CIFAR-100
+            m = np.load(m_path)
+            mat = np.load(mat_path)
         else:
             m, mat = zc
         m = np.asarray(m, np.float32).reshape(-1)

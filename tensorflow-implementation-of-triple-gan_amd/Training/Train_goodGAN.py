@@ -80,6 +80,29 @@ def check_num_classes(config):
     return int(k)
 
 
+def check_zca(config, Dataset=None):
+    """config.ZCA: None (the reference's DATA_DIR/<data>_zca_*.npy files), (mean, mat) arrays, or 'fit' (fitted from the
+    training split by Train.train and written to those files).  Needs no device.  ValueError for any other string; lib.TgError when
+    'fit' meets a model without ZCA whitening (DATA_NAME not cifar10 / cifar100: MNIST, SVHN, stress64) or a Dataset (class or instance)
+    that is not a uint8 TFRecord source in [-1, 1] scaling, e.g. the default syntheticDataset."""
+    zc = getattr(config, 'ZCA', None)
+    if not isinstance(zc, str):
+        return zc
+    if zc != 'fit':
+        raise ValueError("ZCA must be None, (mean, mat) arrays or 'fit', got %r" % (zc,))
+    from Model.Good_GAN_cifar10 import ZCA_DATA
+    if getattr(config, 'DATA_NAME', None) not in ZCA_DATA:
+        raise lib.TgError("ZCA = 'fit' applies to the ZCA-whitened classifiers of %s; DATA_NAME %r has no ZCA whitening"
+                          % (' / '.join(ZCA_DATA), getattr(config, 'DATA_NAME', None)))
+    if Dataset is not None:
+        from Input_Pipeline.tfrecordDataset import tfrecordDataset
+        cls = Dataset if isinstance(Dataset, type) else type(Dataset)
+        if not issubclass(cls, tfrecordDataset) or cls.UNIT_RANGE:
+            raise lib.TgError("ZCA = 'fit' needs a training split of uint8 TFRecords (a tfrecordDataset such as cifar10Dataset); %s has "
+                              "none" % cls.__name__)
+    return zc
+
+
 class Train(Train_base):
     def __init__(self, config, log_dir, save_dir, **kwargs):
         super(Train, self).__init__()
@@ -115,6 +138,7 @@ class Train(Train_base):
         self.iteration = 0
         self._exposed = None             # [(mark before, mark after)] of the waits for gradient buckets while measure_exposed(True)
         self._label_override = {}        # see label_override()
+        self.zca_source = None           # config.ZCA = 'fit' resolved by train(): 'files' | 'fit' (rank 0) | 'broadcast' (other ranks)
         self.summary_train = self.summary_val = None
         if getattr(config, 'SUMMARY', False) and log_dir and self.rank == 0:          # :37-41
             from Training.Summary import Summary
@@ -645,6 +669,45 @@ class Train(Train_base):
             out = self.model.good_sampler(cx.from_numpy(sample_z, key='smp:z'), cx.from_numpy(sample_y, key='smp:y'))
             return out.numpy().reshape([-1] + list(self.config.IMAGE_DIM))
 
+    def _resolve_zca(self, dataset_train):
+        """config.ZCA = 'fit' -> (mean, mat) float32 arrays, before the model first whitens.  Rank 0 loads
+        DATA_DIR/<data>_zca_{mean,mat}.npy when both exist (the reference's path, no refit), else fits them from the training split
+        (Model/Good_GAN_cifar10.cifar10_ZCA.fit) and writes them; with data parallelism the other ranks receive rank 0's constants
+        (tg.dist.broadcast_), so every replica holds the same bits and there is exactly one writer."""
+        c = self.config
+        if not isinstance(getattr(c, 'ZCA', None), str):
+            return
+        check_zca(c, dataset_train)
+        from Model.Good_GAN_cifar10 import cifar10_ZCA, write_zca_files, zca_paths
+        d = int(np.prod(c.IMAGE_DIM))
+        mean = mat = None
+        if self.rank == 0:
+            m_path, mat_path = zca_paths(c)
+            if os.path.exists(m_path) and os.path.exists(mat_path):
+                mean, mat = np.load(m_path), np.load(mat_path)
+                self.zca_source = 'files'
+            else:
+                ddir = os.path.dirname(m_path) or '.'
+                if not os.access(ddir, os.W_OK):
+                    raise lib.TgError("ZCA = 'fit': %s is not writable (the fitted constants go to %s)" % (ddir, m_path))
+                mean, mat = cifar10_ZCA.fit(dataset_train)
+                write_zca_files(c, mean, mat)
+                self.zca_source = 'fit'
+            mean = np.asarray(mean, np.float32).reshape(-1)
+            mat = np.asarray(mat, np.float32)
+            if mean.shape != (d,) or mat.shape != (d, d):
+                raise lib.TgError("ZCA constants of shapes %s / %s do not match images of %d values" % (mean.shape, mat.shape, d))
+        if tgdist.active():
+            flat = torch.empty(d + d * d, dtype=torch.float32, device=self.cx.device)
+            if self.rank == 0:
+                flat.copy_(torch.from_numpy(np.concatenate([mean, mat.reshape(-1)])))
+            tgdist.broadcast_(flat)
+            if self.rank != 0:
+                host = flat.cpu().numpy()
+                mean, mat = host[:d].copy(), host[d:].reshape(d, d).copy()
+                self.zca_source = 'broadcast'
+        c.ZCA = (mean, mat)
+
     # ------------------------------------------------------------------ the reference's entry point
     def train(self, Dataset, Model, sample_y):
         """:43-381.  Dataset(data_dir, config, num_label, subset, use_augmentation).inputpipline_train_val(val)
@@ -653,6 +716,7 @@ class Train(Train_base):
         c = self.config
         dataset_train = Dataset(c.DATA_DIR, c, c.NUM_LABEL, 'train', True)
         dataset_val = Dataset(c.DATA_DIR, c, c.NUM_LABEL, 'test', False)
+        self._resolve_zca(dataset_train)
         init_op_train, init_op_val, NNIO = dataset_train.inputpipline_train_val(dataset_val)
         self._build_train_graph(Model)
         sample_z = np.random.uniform(low=-1.0, high=1.0, size=(c.SAMPLE_SIZE, c.Z_DIM)).astype(np.float32)   # :130
@@ -760,6 +824,7 @@ def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
     tmp_config.SAMPLE_DIR = os.path.join(_root_dir(), "Training", tmp_config.SAMPLE_DIR)
     if tmp_config.NUM_LABEL < 1000:
         tmp_config.PRE_TRAIN = True                                    # :537-538,614-615
+    check_zca(tmp_config, Dataset or syntheticDataset)                 # --zca fit: before any device work
     tmp_config.display()
     training = Train(tmp_config, tmp_config.LOG_DIR, tmp_config.WEIGHT_DIR, comments=comments + tmp_config.config_str())
     sample_y = np.eye(tmp_config.NUM_CLASSES, dtype=np.float32)[np.arange(tmp_config.SAMPLE_SIZE) % tmp_config.NUM_CLASSES]
@@ -804,7 +869,8 @@ def _main_training_svhn(FLAGS=None, Dataset=None, epochs=None):
 
 
 def _main_training_cifar10(FLAGS=None, Dataset=None, epochs=None):
-    """:551-626.  config.ZCA must carry (mean, mat) when DATA_DIR holds no cifar10_zca_*.npy."""
+    """:551-626.  config.ZCA must carry (mean, mat) when DATA_DIR holds no cifar10_zca_*.npy, or be 'fit' (--zca fit, with a TFRecord
+    Dataset): fitted from the training split and written there."""
     from config import Config
     from Model.Good_GAN_cifar10 import Good_GAN_cifar10 as Model
 
@@ -846,7 +912,7 @@ def _main_training_cifar10(FLAGS=None, Dataset=None, epochs=None):
 def _main_training_cifar100(FLAGS=None, Dataset=None, epochs=None):
     """CIFAR-100 (not an entry point of the reference): the networks and algorithm of _main_training_cifar10 with NUM_CLASSES = 100, so the
     classifier heads run the general-K kernels (csrc/loss.hip).  config.ZCA must carry (mean, mat) when DATA_DIR holds no
-    cifar100_zca_*.npy; without either, the synthetic whitening of the CIFAR-10 entry point."""
+    cifar100_zca_*.npy, or be 'fit' as for CIFAR-10; without either, the synthetic whitening of the CIFAR-10 entry point."""
     from config import Config
     from Model.Good_GAN_cifar10 import Good_GAN_cifar10 as Model
 

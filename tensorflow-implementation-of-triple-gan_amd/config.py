@@ -56,7 +56,8 @@ class Config(object):
                              # 'plan': that two-stream launch sequence recorded once per solver run and re-issued natively (tg_plan_replay,
                              # include/tg_plan.h) - no interpreter on the launch path;
                              # 'graph': hipGraph replay (single chain); 'eager': eager launches on one stream
-    ZCA = None               # (mean, mat) arrays when DATA_DIR holds no cifar10_zca_*.npy
+    ZCA = None               # (mean, mat) arrays when DATA_DIR holds no cifar10_zca_*.npy; 'fit' (--zca fit): fitted from the training
+                             # TFRecords by Train.train and written to those files, or loaded from them when present
     LOSS = 'GAN'             # the loss of the three solver runs: 'GAN' (_loss_GAN, the reference's training loss) or 'WGAN_GP' (its
                              # _loss_WGAN_GP with the gradient penalty, wired into the step as DESIGN §9.1 decides; fp32 MFMA operands, no
                              # minibatch discrimination, BATCH_SIZE_L_D + BATCH_SIZE_U_D == BATCH_SIZE_G — Training/Train_goodGAN.check_loss)
