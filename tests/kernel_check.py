@@ -1,4 +1,4 @@
-"""Shared checks of the per-kernel float64 tests (tests/test_gpu_elementwise.py, _prep.py, _norm_finalize.py, _loss_heads.py, _gemm_tiles.py),
+"""Shared checks of the per-kernel float64 tests (tests/test_gpu_elementwise.py, _prep.py, _norm_finalize.py, _loss_heads.py, _gemm_tiles.py, _halo_tiles.py),
 and the float64 oracle of an implicit-GEMM descriptor (igemm_ref64, on the device).
 
 Every output a test reads is allocated by `guarded`: the buffer is followed by GUARD floats holding a fixed bit pattern, and the output
@@ -210,9 +210,10 @@ def igemm_filter(wf, d, tap):
     return wf.as_strided((d.c_out, d.ld_in), (d.w_sn, 1), int(d.tapw[tap]) * d.w_st)
 
 
-def igemm_ref64(descs, x, wf):
+def igemm_ref64(descs, x, wf, last_k=32):
     """float64 accumulators of every descriptor: [(acc, sum|a||b|, the last K-tile's share of acc)], each [M, c_out].  The last K-tile is
-    channels [ld_in - 32, ld_in) of the descriptor's last tap."""
+    channels [ld_in - last_k, ld_in) of the descriptor's last tap (32: the generic kernels' K-tile; the halo kernels' channel chunk is 64
+    with bf16 operands)."""
     out = []
     for d in descs:
         acc = sab = last = None
@@ -221,7 +222,7 @@ def igemm_ref64(descs, x, wf):
             p, s = a @ w.T, a.abs() @ w.abs().T
             acc = p if acc is None else acc + p
             sab = s if sab is None else sab + s
-        last = a[:, -32:] @ w[:, -32:].T
+        last = a[:, -last_k:] @ w[:, -last_k:].T
         out.append((acc, sab, last))
     return out
 

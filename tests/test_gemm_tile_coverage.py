@@ -2,7 +2,7 @@
 
 The dispatch lines of csrc/igemm.hip (launch_igemm<BM, BN, ...> / launch_wgrad<CT, NT, ...>) name the tile instantiations the generic
 kernels can run.  Every dispatched igemm tile x operand type x schedule (uncut / cut along K) x epilogue family (plain, colsum, actsum,
-bnstat) must be reached by a case of IGEMM_CASES, as tg_igemm_tile and tg_igemm_workspace_bytes evaluate it, or be listed in UNREACHABLE
+bnstat, bnbwdstat) must be reached by a case of IGEMM_CASES, as tg_igemm_tile and tg_igemm_workspace_bytes evaluate it, or be listed in UNREACHABLE
 with the reason the cost model can never pick it; every dispatched wgrad tile must be reached by a case of WGRAD_CASES (tg_wgrad_tile) in
 both operand types.  A tile added to the dispatch, or a case that stops reaching what it names, fails here."""
 import os

@@ -19,7 +19,8 @@ Checks (tests/kernel_check.py, tests/test_gpu_igemm.py):
     1-Lipschitz, so the bound of the accumulator carries over; tanhf adds its own few ulp (0.5 in units of the bound);
   * cut schedules: the launch with scratch, twice, is bit-identical, and the launch without scratch (one workgroup per tile) meets the
     same float64 bound;
-  * column sums (and sums of squares) against float64 sums of the STORED outputs, at the same bound of the sum of |terms|;
+  * column sums (and sums of squares; bnbwdstat: the sums of dy and of dy * x) against float64 sums of the STORED outputs, at the same bound
+    of the sum of |terms|;
   * negative controls: the bound rejects the reference without its last K-tile (32 channels of one tap), and, for the filter gradient,
     without its last 32-pixel tile.
 
@@ -37,7 +38,7 @@ from oracle import tf_ops as T
 pytestmark = pytest.mark.gpu
 
 F32, BF16 = 'f32', 'bf16'
-FAMILIES = ('plain', 'colsum', 'actsum', 'bnstat')
+FAMILIES = ('plain', 'colsum', 'actsum', 'bnstat', 'bnbwdstat')
 
 
 def _c(id, family, prec, op, args, tile, cut, segs=None, act=None, ld_out=None, n_store=None, live=None):
@@ -76,7 +77,7 @@ IGEMM_CASES = [
 ]
 
 
-# the column-sum families (tg_igemm_colsum_*, tg_igemm_actsum_*, tg_igemm_bnstat_*) share one tile rule: every application segment has at least
+# the column-sum families (tg_igemm_colsum_*, tg_igemm_actsum_*, tg_igemm_bnstat_*, tg_igemm_bnbwdstat_*) share one tile rule: every application segment has at least
 # BM rows, so a tile straddles at most one boundary.  Per tile, operand type and schedule one shape, with a segment boundary inside a tile
 # and a segment of exactly BM rows: (tile, prec, cut, op, args, segs, live)
 _SEG_SHAPES = [
@@ -97,10 +98,11 @@ _SEG_SHAPES = [
     ((128, 128), BF16, False, 'dense', (12750, 64, 256), [128, 6000, 6622], 250),
     ((128, 128), BF16, True, 'conv', SVHN, [128, 6336, 6336], None),
 ]
-_FAMILY_ACTS = {'colsum': [None], 'actsum': ['lrelu', 'relu'], 'bnstat': ['lrelu', 'relu', None]}      # bnstat: the layer's own; actsum: act' of yact
+_FAMILY_ACTS = {'colsum': [None], 'actsum': ['lrelu', 'relu'], 'bnstat': ['lrelu', 'relu', None], 'bnbwdstat': [None]}      # bnstat: the layer's own; actsum: act' of yact
+# (bnbwdstat: the stored value is the raw accumulator dy, no bias, no activation; its second sum is of dy * x, x from kc.y_for)
 IGEMM_CASES += [_c('%s-%dx%d-%s%s' % (fam, t[0], t[1], prec, '-cut' if cut else ''), fam, prec, op, args, t, cut, segs=segs,
                    act=_FAMILY_ACTS[fam][i % len(_FAMILY_ACTS[fam])], live=live)
-                for fam in ('colsum', 'actsum', 'bnstat') for i, (t, prec, cut, op, args, segs, live) in enumerate(_SEG_SHAPES)]
+                for fam in ('colsum', 'actsum', 'bnstat', 'bnbwdstat') for i, (t, prec, cut, op, args, segs, live) in enumerate(_SEG_SHAPES)]
 
 # filter gradient (tg_wgrad_*): tile (CT, NT) = (tg::wgrad_tile(ld_in), tg::wgrad_tile(c_out)), every instantiation, 160 and 288 channels on
 # 64-wide tiles whose last one overhangs.  (id, (CT, NT), (n, h, w, ld_in, c_out, k, stride, pad), ld_dy)
@@ -258,9 +260,9 @@ def test_igemm_tile_against_float64(case):
     ns = len(segs) if segs else 0
     sa = (C.c_int32 * ns)(*segs) if segs else None
     yact = None
-    if fam == 'actsum':
+    if fam in ('actsum', 'bnbwdstat'):              # actsum: the activation output y; bnbwdstat: the batch norm's input x (both at the output's addresses)
         yact = kc.dev(kc.y_for(rng, out_shape, case['act']))
-    n_sums = {'plain': 0, 'colsum': ns * d0.c_out, 'actsum': ns * d0.c_out, 'bnstat': 8 * ns * 2 * d0.c_out}[fam]
+    n_sums = {'plain': 0, 'colsum': ns * d0.c_out, 'actsum': ns * d0.c_out, 'bnstat': 8 * ns * 2 * d0.c_out, 'bnbwdstat': 8 * ns * 2 * d0.c_out}[fam]
 
     def launch(scratch):
         g = kc.guarded(n_out)
@@ -276,6 +278,8 @@ def test_igemm_tile_against_float64(case):
         elif fam == 'actsum':
             lib.call_igemm('tg_igemm_actsum_' + prec, d0, lib.ptr(xd), lib.ptr(wd), lib.ptr(yact), lib.ACT[case['act']], float(kc.ALPHA), g.ptr, sa, ns, sp,
                            0, st, scratch=scratch)
+        elif fam == 'bnbwdstat':
+            lib.call_igemm('tg_igemm_bnbwdstat_' + prec, d0, lib.ptr(xd), lib.ptr(wd), lib.ptr(yact), g.ptr, sa, ns, sp, 0, st, scratch=scratch)
         else:
             lib.call_igemm('tg_igemm_bnstat_' + prec, d0, lib.ptr(xd), lib.ptr(wd), lib.ptr(bd), g.ptr, sa, ns, sp, 0, st, scratch=scratch)
         g.check_guard()
@@ -315,6 +319,14 @@ def test_igemm_tile_against_float64(case):
             for k, sq in ((0, False), (1, True)):
                 r, a = _seg_sums(rows, segs, sq)
                 close(s[0, :, k, :ns_], r, a, what + (' sums of squares' if sq else ' sums'))
+                assert (s[0, :, k, ns_:] == 0).all()
+        elif fam == 'bnbwdstat':                     # S0 = sum dy, S1 = sum dy * x
+            s = s.view(8, ns, 2, d0.c_out)
+            assert (s[1:] == 0).all(), "%s: replicas 1..7 of the statistics buffer are not zero" % what
+            xr = yact[..., :ns_].reshape(M, ns_).double()
+            for k, v, nm in ((0, rows, ' sums of dy'), (1, rows.double() * xr, ' sums of dy * x')):
+                r, a = _seg_sums(v, segs)
+                close(s[0, :, k, :ns_], r, a, what + nm)
                 assert (s[0, :, k, ns_:] == 0).all()
         else:
             s = s.view(ns, d0.c_out)

@@ -23,30 +23,10 @@ RUNTIME_NAMED = {
                            "f32 / bf16 parametrised; name built from the precision"),
     "tg_igemm_multi_bf16": ("test_gpu_igemm.py::test_cut_long_parities_of_a_transposed_conv_launch", "'tg_igemm_multi_' + prec",
                             "f32 / bf16 parametrised; name built from the precision"),
-    "tg_igemm_colsum_f32": ("test_gpu_kernels.py::test_fused_mean_only_batch_norm_forward_backward", "'tg_igemm_colsum_' + prec",
-                            "f32 / bf16 parametrised; name built from the precision"),
-    "tg_igemm_colsum_bf16": ("test_gpu_kernels.py::test_fused_mean_only_batch_norm_forward_backward", "'tg_igemm_colsum_' + prec",
-                             "f32 / bf16 parametrised; name built from the precision"),
-    "tg_igemm_actsum_f32": ("test_gpu_igemm.py::test_cut_tiles_with_column_sums_and_activation_gradient", "'tg_igemm_actsum_' + prec",
-                            "f32 / bf16 parametrised; name built from the precision"),
-    "tg_igemm_actsum_bf16": ("test_gpu_igemm.py::test_cut_tiles_with_column_sums_and_activation_gradient", "'tg_igemm_actsum_' + prec",
-                             "f32 / bf16 parametrised; name built from the precision"),
-    "tg_igemm_bnstat_f32": ("test_gpu_kernels.py::test_batch_norm_statistics_in_the_convolution_epilogue", "'tg_igemm_bnstat_' + prec",
-                            "f32 / bf16 parametrised; name built from the precision"),
-    "tg_igemm_bnstat_bf16": ("test_gpu_kernels.py::test_batch_norm_statistics_in_the_convolution_epilogue", "'tg_igemm_bnstat_' + prec",
-                             "f32 / bf16 parametrised; name built from the precision"),
-    "tg_igemm_bnbwdstat_f32": ("test_gpu_kernels.py::test_batch_norm_backward_statistics_in_the_epilogue_of_the_launch_that_produces_dy",
-                               "'tg_igemm_bnbwdstat_' + prec", "f32 / bf16 parametrised; name built from the precision"),
-    "tg_igemm_bnbwdstat_bf16": ("test_gpu_kernels.py::test_batch_norm_backward_statistics_in_the_epilogue_of_the_launch_that_produces_dy",
-                                "'tg_igemm_bnbwdstat_' + prec", "f32 / bf16 parametrised; name built from the precision"),
     "tg_igemm_labels_f32": ("test_gpu_igemm.py::test_conv_writes_the_cond_concat_behind_it", '"tg_igemm_labels_" + prec',
                             "f32 / bf16 parametrised; name built from the precision"),
     "tg_igemm_labels_bf16": ("test_gpu_igemm.py::test_conv_writes_the_cond_concat_behind_it", '"tg_igemm_labels_" + prec',
                              "f32 / bf16 parametrised; name built from the precision"),
-    "tg_wgrad_f32": ("test_gpu_igemm.py::test_conv_fwd_dgrad_wgrad", '"tg_wgrad_" + prec',
-                     "f32 / bf16 parametrised; name built from the precision"),
-    "tg_wgrad_bf16": ("test_gpu_igemm.py::test_conv_fwd_dgrad_wgrad", '"tg_wgrad_" + prec',
-                      "f32 / bf16 parametrised; name built from the precision"),
 }
 
 # host functions whose names end like a kernel's but launch nothing
