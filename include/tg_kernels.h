@@ -493,6 +493,13 @@ int tg_splitk_reduce_f32(const float* part, const float* bias, float* out, int l
  * (scale 2, shift -1 for SVHN / CIFAR-10; scale 1, shift 0 for MNIST, mnistDataset.py:65), and tf.one_hot(label, k). */
 int tg_u8_affine_f32(const uint8_t* src, float* dst, int64_t n, float scale, float shift, void* stream);
 int tg_onehot_i32_f32(const int32_t* labels, float* out, int64_t n, int k, void* stream);
+/* the training augmentation fused into that tail (config.AUGMENT; the reference's pre_processing hook, cifar10Dataset.py:72-74).  src, dst
+ * [n][h][w][c].  Image i draws r = Philox4x32-10(counter (i, stream_id, lo32(count), hi32(count)), key (lo32(seed), hi32(seed))) and is
+ * shifted by dy = ((u64)r.x*(2S+1) >> 32) - S, dx = ((u64)r.y*(2S+1) >> 32) - S with reflect padding (S = max_shift, 0..min(h,w)-1),
+ * then flipped horizontally when flip && (r.z >> 31):  dst[i,y,x,ch] = float(src[i, refl(y+dy), refl(xf+dx), ch])/255 * scale + shift,
+ * xf = flipped ? w-1-x : x.  S = 0 without flip is tg_u8_affine_f32 bit for bit. */
+int tg_u8_augment_f32(const uint8_t* src, float* dst, int n, int h, int w, int c, float scale, float shift, int max_shift, int flip, int64_t seed,
+                      uint32_t stream_id, int64_t count, void* stream);
 /* dst = a + b (dst may alias a or b): sums the per-application gradient buffers of a network applied several times. */
 int tg_add_f32(float* dst, const float* a, const float* b, int64_t n, void* stream);
 /* tf.one_hot(tf.argmax(logits,1)) (Good_GAN_cifar10.py:232,237,259,270); out [n][k]. */

@@ -9,3 +9,5 @@ class cifar10Dataset(tfrecordDataset):
     TRAIN_SIZE = 50000
     CHANNELS = 3
     UNIT_RANGE = False
+    AUG_SHIFT = 2
+    AUG_FLIP = True

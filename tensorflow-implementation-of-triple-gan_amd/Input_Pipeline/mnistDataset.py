@@ -9,3 +9,5 @@ class mnistDataset(tfrecordDataset):
     TRAIN_SIZE = 60000
     CHANNELS = 1
     UNIT_RANGE = True
+    AUG_SHIFT = 2
+    AUG_FLIP = False             # flipped digits are other digits

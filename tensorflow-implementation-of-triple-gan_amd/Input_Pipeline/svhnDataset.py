@@ -9,3 +9,5 @@ class svhnDataset(tfrecordDataset):
     TRAIN_SIZE = 73257
     CHANNELS = 3
     UNIT_RANGE = False
+    AUG_SHIFT = 2
+    AUG_FLIP = False             # flipped digits are other digits

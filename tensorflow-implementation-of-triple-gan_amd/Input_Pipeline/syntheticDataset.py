@@ -23,6 +23,10 @@ class _NNIO(object):
 
 class syntheticDataset(object):
     def __init__(self, data_dir, config, num_label, subset, use_augmentation=False, seed=1234, val_size=1000):
+        if subset == 'train' and use_augmentation and getattr(config, 'AUGMENT', False):
+            from tg import lib
+            raise lib.TgError("AUGMENT needs a training split of uint8 TFRecords (a tfrecordDataset such as cifar10Dataset); "
+                              "syntheticDataset has no real images to augment")
         self.config, self.subset, self.seed = config, subset, seed
         c = config
         lo = 0.0 if c.DATA_NAME == 'mnist' else -1.0

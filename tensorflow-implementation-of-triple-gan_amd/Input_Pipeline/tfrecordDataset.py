@@ -9,6 +9,9 @@
   .shuffle(MIN_QUEUE_EXAMPLES + 30*BATCH_SIZE).repeat(n)   :76-82   ShuffleStream: the same streaming-buffer algorithm on record indices
   .batch(bs).prefetch(5*bs)                 :84-87         Batcher + a background thread that stays `PREFETCH` batches ahead
   iterators / initializers                  :96-137        init_op_train() / init_op_val() restart the streams
+  .map(pre_processing) "do augmentation"    cifar10Dataset.py:72-74 (a no-op there)   config.AUGMENT: random shift (reflect padding)
+                                                           and horizontal flip of every training batch, fused into the device tail
+                                                           (tg_u8_augment_f32; augment_indices + _to_host: the same in NumPy)
 
 Batch protocol (SURVEY §8a T1 — the reference's three pipelines disagree with its placeholders, the build fixes one):
 three training streams — labelled for C (L_C), labelled for D (L_D), unlabelled (U_D + U_C, sliced as x_u[:U_D], x_u[U_D:]
@@ -47,6 +50,37 @@ class ShuffleStream(object):
                     buf[j] = buf[-1]
                     buf.pop()
             epoch += 1
+
+
+def philox4x32(ctr, key):
+    """Philox4x32-10 (Random123; csrc/tg_device.h philox): ctr = four uint32 arrays (or ints) of one shape, key = two ints -> the four
+    output words, uint64 arrays holding 32-bit values."""
+    m = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (np.asarray(v, np.uint64) & m for v in ctr)
+    k0, k1 = np.uint64(key[0] & 0xFFFFFFFF), np.uint64(key[1] & 0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = c0 * np.uint64(0xD2511F53), c2 * np.uint64(0xCD9E8D57)
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m, (k1 + np.uint64(0xBB67AE85)) & m
+    return c0, c1, c2, c3
+
+
+def augment_indices(n, h, w, max_shift, flip, seed, stream_id, count):
+    """source rows [n, h] and columns [n, w] of the augmentation of a batch of n images (tg_u8_augment_f32): image i draws
+    r = Philox4x32-10(counter (i, stream_id, lo32(count), hi32(count)), key (lo32(seed), hi32(seed))), is shifted by
+    dy, dx = (r.x, r.y) * (2S+1) >> 32, minus S, with reflect padding, and flipped horizontally when flip and r.z >> 31."""
+    seed, count = int(seed) & (2 ** 64 - 1), int(count) & (2 ** 64 - 1)
+    i = np.arange(n, dtype=np.uint64)
+    rx, ry, rz, _ = philox4x32((i, stream_id, count & 0xFFFFFFFF, count >> 32), (seed & 0xFFFFFFFF, seed >> 32))
+    span = np.uint64(2 * max_shift + 1)
+    dy = ((rx * span) >> np.uint64(32)).astype(np.int64) - max_shift
+    dx = ((ry * span) >> np.uint64(32)).astype(np.int64) - max_shift
+    flipped = (rz >> np.uint64(31)).astype(bool) & bool(flip)
+
+    def reflect(p, size):
+        return np.where(p < 0, -p, np.where(p >= size, 2 * size - 2 - p, p))
+    x = np.arange(w)
+    return reflect(np.arange(h)[None, :] + dy[:, None], h), reflect(np.where(flipped[:, None], w - 1 - x, x) + dx[:, None], w)
 
 
 def _batches(stream, batch_size):
@@ -151,6 +185,8 @@ class tfrecordDataset(object):
     TRAIN_SIZE = None
     CHANNELS = 3
     UNIT_RANGE = False          # True: x/255 (mnistDataset.py:65); False: x/255*2-1
+    AUG_SHIFT = 2               # config.AUGMENT: random shift of every training image by up to this many pixels (reflect padding)
+    AUG_FLIP = False            # config.AUGMENT: horizontal flip with probability 1/2 (natural images; not digits)
     PREFETCH = 5                # batches (the reference prefetches batch_size*5 elements, :86)
     DECODE_THREADS = 1          # one thread decodes ~0.9 M CIFAR records/s; spawning helpers only pays for large batches
 
@@ -163,6 +199,7 @@ class tfrecordDataset(object):
         self.train_size = self.TRAIN_SIZE
         self.seed = (1234 if seed is None else seed) + 1000 * getattr(config, 'RANK', 0)
         self._streams = None
+        self._aug_counts = [0, 0, 0, 0]      # batches augmented so far per stream id (0: records of the per-record parser path)
 
     # ---- files ----------------------------------------------------------------------------------
     def get_filenames(self):                                                     # :23-31
@@ -191,7 +228,13 @@ class tfrecordDataset(object):
         return image, onehot
 
     def pre_processing(self, image, label):                                      # :72-74 (a no-op in the reference)
-        return image, label
+        """config.AUGMENT: the training augmentation of one decoded record (a batch of one image of stream 0, counted per record)."""
+        aug = self._aug_draw(0)
+        if aug is None:
+            return image, label
+        h, w, _ = image.shape
+        ys, xs = augment_indices(1, h, w, self.AUG_SHIFT, self.AUG_FLIP, self.seed, *aug)
+        return image[ys[0][:, None], xs[0][None, :]], label
 
     def shuffle_and_repeat(self, dataset, repeat=1, seed=0):                     # :76-82
         return ShuffleStream(len(dataset), self.config.MIN_QUEUE_EXAMPLES + 30 * self.config.BATCH_SIZE, repeat, self.seed + seed)
@@ -199,9 +242,20 @@ class tfrecordDataset(object):
     def batch(self, dataset, batch_size):                                        # :84-87
         return _batches(dataset, batch_size)
 
+    # ---- augmentation (config.AUGMENT) -------------------------------------------------
+    def _aug_draw(self, stream_id):
+        """(stream_id, count) of the next batch of that stream when the training augmentation is on (config.AUGMENT on a Dataset built
+        with use_augmentation), else None.  The count runs from the Dataset's creation, across epochs."""
+        if not (self.use_augmentation and getattr(self.config, 'AUGMENT', False)):
+            return None
+        count = self._aug_counts[stream_id]
+        self._aug_counts[stream_id] += 1
+        return stream_id, count
+
     # ---- device tail ----------------------------------------------------------------------------
-    def _to_device(self, images_u8, labels_i32, want_labels=True, slot=None):
-        """uint8 [n,H,W,C] / int32 [n] host arrays -> (Act float32 scaled, Act one-hot) on the GPU."""
+    def _to_device(self, images_u8, labels_i32, want_labels=True, slot=None, aug=None):
+        """uint8 [n,H,W,C] / int32 [n] host arrays -> (Act float32 scaled, Act one-hot) on the GPU; aug = (stream_id, count): augmented
+        (tg_u8_augment_f32) in the same pass."""
         import torch
         from tg import lib
         from tg.runtime import Act, ctx
@@ -210,7 +264,11 @@ class tfrecordDataset(object):
         xu = torch.from_numpy(images_u8).to(cx.device, non_blocking=True)
         x = torch.empty(n * h * w * c, dtype=torch.float32, device=cx.device)
         scale, shift = (1.0, 0.0) if self.UNIT_RANGE else (2.0, -1.0)
-        lib.call('tg_u8_affine_f32', lib.ptr(xu), lib.ptr(x), xu.numel(), scale, shift, cx.stream)
+        if aug is None:
+            lib.call('tg_u8_affine_f32', lib.ptr(xu), lib.ptr(x), xu.numel(), scale, shift, cx.stream)
+        else:
+            lib.call('tg_u8_augment_f32', lib.ptr(xu), lib.ptr(x), n, h, w, c, scale, shift, self.AUG_SHIFT, int(self.AUG_FLIP),
+                     self.seed & (2 ** 64 - 1), aug[0], aug[1] & (2 ** 64 - 1), cx.stream)
         xa, ya = Act(x, n, h, w, c, c), None
         if want_labels:
             k = self.config.NUM_CLASSES
@@ -223,8 +281,12 @@ class tfrecordDataset(object):
             slot.event.record(torch.cuda.current_stream(cx.device))
         return xa, ya
 
-    def _to_host(self, images_u8, labels_i32):
-        """the same tail in NumPy (no GPU: tests, tools)."""
+    def _to_host(self, images_u8, labels_i32, aug=None):
+        """the same tail in NumPy (no GPU: tests, tools), bit for bit."""
+        if aug is not None:
+            n, h, w, _ = images_u8.shape
+            ys, xs = augment_indices(n, h, w, self.AUG_SHIFT, self.AUG_FLIP, self.seed, *aug)
+            images_u8 = images_u8[np.arange(n)[:, None, None], ys[:, :, None], xs[:, None, :]]
         x = images_u8.astype(np.float32)
         x = x / 255 if self.UNIT_RANGE else x / 255 * 2 - 1
         return x, np.eye(self.config.NUM_CLASSES, dtype=np.float32)[labels_i32]
@@ -233,10 +295,11 @@ class tfrecordDataset(object):
         import torch
         return bool(getattr(self.config, 'PIPELINE_DEVICE', True)) and torch.cuda.is_available()
 
-    def _finish(self, slot, want_labels=True):
+    def _finish(self, slot, stream_id, want_labels=True):
+        aug = self._aug_draw(stream_id)
         if self._on_device():
-            return self._to_device(slot.images, slot.labels, want_labels, slot)
-        return self._to_host(slot.images.copy(), slot.labels.copy())
+            return self._to_device(slot.images, slot.labels, want_labels, slot, aug)
+        return self._to_host(slot.images.copy(), slot.labels.copy(), aug)
 
     # ---- pipelines ------------------------------------------------------------------------------
     def _start_train(self):
@@ -259,9 +322,9 @@ class tfrecordDataset(object):
         if any(g is None for g in got) or got[2].n < c.BATCH_SIZE_U_D + c.BATCH_SIZE_U_C:
             raise StopIteration("unlabelled stream exhausted (config.REPEAT epochs)")
         b = {}
-        b['x_l_c'], b['y_l_c'] = self._finish(got[0])
-        b['x_l_d'], b['y_l_d'] = self._finish(got[1])
-        xu, _ = self._finish(got[2], want_labels=False)
+        b['x_l_c'], b['y_l_c'] = self._finish(got[0], 1)                          # stream ids: those of the shuffle seeds
+        b['x_l_d'], b['y_l_d'] = self._finish(got[1], 2)
+        xu, _ = self._finish(got[2], 3, want_labels=False)
         if isinstance(xu, np.ndarray):
             b['x_u_d'], b['x_u_c'] = xu[:c.BATCH_SIZE_U_D], xu[c.BATCH_SIZE_U_D:]
         else:

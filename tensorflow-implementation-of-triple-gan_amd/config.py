@@ -58,6 +58,7 @@ class Config(object):
                              # 'graph': hipGraph replay (single chain); 'eager': eager launches on one stream
     ZCA = None               # (mean, mat) arrays when DATA_DIR holds no cifar10_zca_*.npy; 'fit' (--zca fit): fitted from the training
                              # TFRecords by Train.train and written to those files, or loaded from them when present
+    AUGMENT = False          # True (--augment): random shift and flip of every training batch, fused into the input pipeline
     LOSS = 'GAN'             # the loss of the three solver runs: 'GAN' (_loss_GAN, the reference's training loss) or 'WGAN_GP' (its
                              # _loss_WGAN_GP with the gradient penalty, wired into the step as DESIGN §9.1 decides; fp32 MFMA operands, no
                              # minibatch discrimination, BATCH_SIZE_L_D + BATCH_SIZE_U_D == BATCH_SIZE_G — Training/Train_goodGAN.check_loss)

@@ -4,21 +4,12 @@
 // Training/Train_goodGAN.py:234-239.  The (seed, step) pair lives in DEVICE memory: a captured hipGraph
 // draws fresh numbers on every replay after tg_rng_advance.  counter = (index/4, stream_id, step), key = seed.
 #include "tg_common.h"
+#include "tg_device.h"
 
 namespace {
 
-struct u4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ u4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return u4{c0, c1, c2, c3};
-}
+using tgd::u4;
+using tgd::philox;
 
 __device__ __forceinline__ float u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }   // (0,1)
 

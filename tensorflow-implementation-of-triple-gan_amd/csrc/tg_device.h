@@ -1,4 +1,4 @@
-// Device-side helpers shared by the elementwise / norm kernels.
+// Device-side helpers shared by the elementwise / norm / rng kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/tg_kernels.h"
@@ -26,6 +26,21 @@ __device__ __forceinline__ float act_grad(float y, int a, float alpha) {
     case TG_ACT_SOFTPLUS: return 1.f - expf(-y);             // y = log(1+e^x) -> sigmoid(x) = 1 - e^-y
     default: return 1.f;
   }
+}
+
+struct u4 { uint32_t x, y, z, w; };
+
+// Philox4x32-10 (Random123): counter (c0..c3), key (k0, k1).  Shared by the step's draws (rng.hip) and the input augmentation
+// (elementwise.hip).
+__device__ __forceinline__ u4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return u4{c0, c1, c2, c3};
 }
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Input-pipeline throughput: TFRecord open (mmap + index + CRC-32C of every record), threaded tf.Example
 decode into pinned staging, host-to-device copy + on-device scaling / one-hot.  Synthetic CIFAR-10-shaped records written
-with tg_tfrecord_write.  Prints one JSON line.  The step consumes 200 real images per 100 nominal images: at the bench
+with tg_tfrecord_write.  Prints one JSON line.  --augment: the same with config.AUGMENT (the training streams shifted / flipped in
+the device tail, tg_u8_augment_f32).  The step consumes 200 real images per 100 nominal images: at the bench
 rate (5 600 images/s/GPU, 8 GPUs) a node needs ~90 000 decoded images/s."""
 import json
 import os
@@ -17,13 +18,17 @@ import numpy as np  # noqa: E402
 
 
 def main():
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--augment', action='store_true', help='config.AUGMENT: augment the three training streams (DESIGN §9.4)')
+    args = ap.parse_args()
     import torch
     from tg import io as tgio
     from config import Config
     from Input_Pipeline.cifar10Dataset import cifar10Dataset
     n_lab, n_unl, n_test = 4000, 46000, 1000
     rng = np.random.default_rng(0)
-    out = {}
+    out = dict(augment=args.augment)
     with tempfile.TemporaryDirectory() as d:
         os.makedirs(os.path.join(d, 'Tfrecord'))
 
@@ -42,6 +47,7 @@ def main():
             TRAIN_SIZE = 46000
             EPOCHS = 1
         cfg = Cfg()
+        cfg.AUGMENT = args.augment
         tr = cifar10Dataset(d, cfg, n_lab, 'train', True)
         te = cifar10Dataset(d, cfg, n_lab, 'test', False)
         t0 = time.perf_counter()
