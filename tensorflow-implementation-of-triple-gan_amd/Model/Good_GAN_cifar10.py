@@ -18,7 +18,7 @@ import numpy as np
 
 from Model import model_base
 from Model import nn
-from tg import ops
+from tg import grad_penalty, ops
 from tg.runtime import ParamStore, ctx
 
 
@@ -61,6 +61,8 @@ class Good_GAN_cifar10(model_base.NN_Base):
         self.config = config
         self._create_variables(getattr(config, 'SEED', 0))
         self._zca = None
+        # (sweep body, layer rows, head) of the discriminator for the gradient penalty
+        self._gp = (grad_penalty.conv_sweeps, [grad_penalty.plain(*row) for row in self.D_CONVS], grad_penalty.plain('lin', 1))
 
     # ------------------------------------------------------------------ variables
     @classmethod
@@ -179,124 +181,9 @@ class Good_GAN_cifar10(model_base.NN_Base):
         return (self._sigmoid_no_grad(h3) if want_prob else None), h3
 
     def discriminator_gradient_penalty(self, real, fake, y, weight=1.0, in_step=False):
-        """gp and d gp / d theta_D of the reference's _gradient_penalty (Training/train_base.py:598-620) on this discriminator:
-        x = real + alpha (fake - real) with alpha ~ U[0,1) per image, gx = d sum(logits) / dx, s = sqrt(reduce_sum(gx^2, axis=1)) (axis 1
-        of NHWC is H), gp = mean((s - 1)^2).  real, fake: Act [N,H,W,3]; y: label Act [N,NUM_CLASSES].  Returns (weight * gp as a
-        1-element device tensor, weight * d gp / d theta_D as a flat buffer laid out like the discriminator's ParamStore.g, valid until
-        the next call).  ParamStore.g is not touched.
-
-        With its dropout masks fixed the network is piecewise linear in x, so gp's parameter gradient needs no second-order machinery
-        (DESIGN §9.1): four sweeps over D_CONVS, all on the implicit-GEMM launches —
-          1. forward with the stored activations y_k (their signs are lrelu'),
-          2. input-gradient sweep seeded with 1 per image, keeping each layer's pre-activation gradient dpre_k,
-          3. tg_grad_penalty_f32 (slopes, gp, r = d gp / d gx), then a tangent forward from r: cond-concat with zero labels, the
-             convolution without its bias, * lrelu'(y_k) * dropout mask (tg_actgrad_f32),
-          4. d gp / dW_k = wgrad(tangent input of layer k, dpre_k); d gp / d w_lin = sum over images of the pooled tangent; biases 0.
-        Dropout masks and alpha are drawn in their own RNG scope 'GP' ('alpha', 'drop0', 'drop1', ...); buffers live under the phase
-        'wgan_gp', apart from every buffer a recorded launch plan or graph of the trainer names.  in_step=True (the trainer's D-update with
-        config.LOSS = 'WGAN_GP'): the same sweeps inside the caller's solver run (Context.detached) — no phase of their own, buffers and
-        draws at call sites of the caller's phase, so that its launch plan or graph records them."""
-        from tg import geom, lib
-        from tg.lib import ACT
-        from tg.runtime import pad32
-        cx = ctx()
-        if cx.mfma_dtype != 'f32':
-            raise lib.TgError("discriminator_gradient_penalty: fp32 MFMA path only (MFMA_DTYPE %r): the penalty differentiates a gradient, "
-                              "and bf16-rounded operands in the four sweeps are not pinned to a reference" % (cx.mfma_dtype,))
-        n, H, W, c0 = real.n, real.h, real.w, real.c
-        if (fake.n, fake.h, fake.w, fake.c) != (n, H, W, c0) or y.n != n:
-            raise lib.TgError("discriminator_gradient_penalty: real %s, fake %s and labels [%d] must have the same batch and image shape"
-                              % ((n, H, W, c0), (fake.n, fake.h, fake.w, fake.c), y.n))
-        if y.ld != y.c or getattr(real, 'dtype', 'f32') != 'f32' or getattr(fake, 'dtype', 'f32') != 'f32':
-            raise lib.TgError("discriminator_gradient_penalty: dense fp32 labels and images expected")
-        st = cx.stores['discriminator']
-        ncls, keep, lre = y.c, 0.8, ACT['lrelu']
-        var = lambda nm, leaf: st.value('discriminator/%s/%s/%s' % (nm, nm, leaf))
-        igemm = lambda name, *args: lib.call(name, *ops.igemm_scratch(cx, name, args, False))
-        P = lambda t: None if t is None else lib.ptr(t)
-        grad = cx.scratch('gpgrad', st.n_p) if in_step else cx.ws('wgan_gp:grad', st.n_p)
-        with (cx.detached() if in_step else cx.phase_scope('wgan_gp', record=False)), cx.rng_scoped('GP'):
-            s = cx.stream
-            lib.call('tg_fill_f32', lib.ptr(grad), 0.0, st.n_p, s)
-            zlab = cx.scratch('zlab', n * ncls)
-            lib.call('tg_fill_f32', lib.ptr(zlab), 0.0, n * ncls, s)
-            alpha = cx.rng.uniform(cx, 'alpha', n, 0.0, 1.0)
-            x = cx.new_act(n, H, W, c0, c0)
-            lib.call('tg_wgan_interp_f32', real.ptr, real.ld, fake.ptr, fake.ld, lib.ptr(alpha), x.ptr, x.ld, n, H * W, c0, s)
-            m0 = cx.rng.keep_mask(cx, cx.next_rng_name('drop'), n * H * W * c0, keep)
-            # ---- sweep 1: forward, keeping every layer's input, activation and filter layouts
-            L = []
-            src, mask = x, m0
-            for name, cout, stride, drop in self.D_CONVS:
-                c_in = src.c + ncls
-                ci_p, co_p = pad32(c_in), pad32(cout)
-                a = cx.new_act(n, src.h, src.w, c_in, ci_p)
-                lib.call('tg_cond_concat_f32', src.ptr, src.ld, src.c, P(mask), src.c, 1.0 / keep if mask is not None else 1.0, y.ptr, ncls,
-                         a.ptr, ci_p, n, src.h * src.w, s)
-                w_oti, w_hwio = cx.scratch('woti', co_p * 9 * ci_p), cx.scratch('whwio', 9 * ci_p * co_p)
-                lib.call('tg_filter_prep_f32', lib.ptr(var(name, 'kernel')), None, None, 9, c_in, cout, ci_p, co_p, lib.ptr(w_hwio), lib.ptr(w_oti),
-                         9 * ci_p, ci_p, s)
-                d = geom.conv_fwd(n, a.h, a.w, ci_p, co_p, 3, stride, 'SAME', act='lrelu', alpha=0.2)
-                yk = cx.new_act(n, d.h_out, d.w_out, cout, co_p)
-                igemm('tg_igemm_f32', d, a.ptr, lib.ptr(w_oti), lib.ptr(var(name, 'bias')), yk.ptr, s)
-                mask = cx.rng.keep_mask(cx, cx.next_rng_name('drop'), yk.rows * cout, keep) if drop else None
-                L.append(dict(name=name, stride=stride, a=a, y=yk, w_oti=w_oti, w_hwio=w_hwio, mask=mask))
-                src = yk
-            if L[-1]['mask'] is not None:
-                raise lib.TgError("discriminator_gradient_penalty: a dropout behind the last convolution is not supported")
-            # ---- sweep 2: d sum(logits) / dx; dpre_k = gradient at layer k's pre-activation
-            last = L[-1]['y']
-            cl, hw = last.c, last.h * last.w
-            dp = cx.scratch('dp', n * pad32(cl))
-            lib.call('tg_copy2d_f32', lib.ptr(st.value('discriminator/lin/lin/kernel')), 0, lib.ptr(dp), pad32(cl), n, cl, s)    # w_lin per row
-            dpre = cx.new_act(n, last.h, last.w, cl, last.ld)
-            lib.call('tg_gavgpool_bwd_f32', lib.ptr(dp), pad32(cl), last.ptr, last.ld, dpre.ptr, dpre.ld, n, hw, cl, lre, 0.2, s)
-            for k in range(len(L) - 1, -1, -1):
-                Lk = L[k]
-                Lk['dpre'] = dpre
-                a = Lk['a']
-                da = cx.new_act(n, a.h, a.w, a.c, a.ld)
-                dds = lib.desc_array(geom.conv_dgrad(n, a.h, a.w, a.ld, dpre.ld, 3, Lk['stride'], 'SAME', ld_out=a.ld, n_store=a.ld))
-                igemm('tg_igemm_multi_f32', dds, len(dds), dpre.ptr, lib.ptr(Lk['w_hwio']), None, da.ptr, s)
-                if k > 0:
-                    prev = L[k - 1]
-                    yp, mp = prev['y'], prev['mask']
-                    dpre = cx.new_act(n, yp.h, yp.w, yp.c, yp.ld)
-                    lib.call('tg_actgrad_f32', da.ptr, da.ld, yp.ptr, yp.ld, P(mp), yp.c, 1.0 / keep if mp is not None else 1.0, dpre.ptr, dpre.ld,
-                             yp.rows, yp.c, lre, 0.2, s)
-            gx = cx.new_act(n, H, W, c0, pad32(c0))
-            lib.call('tg_actgrad_f32', da.ptr, da.ld, None, 0, lib.ptr(m0), c0, 1.0 / keep, gx.ptr, gx.ld, gx.rows, c0, 0, 0.0, s)
-            # ---- sweep 3: the penalty, then the tangent forward from r = weight * d gp / d gx
-            r = cx.new_act(n, H, W, c0, gx.ld)
-            partials = cx.scratch('gpp', 2 * ((n * W * r.ld + 255) // 256))
-            gp = cx.scratch('gp', 4)
-            lib.call('tg_grad_penalty_f32', gx.ptr, gx.ld, n, H, W, c0, float(weight), r.ptr, r.ld, lib.ptr(partials), lib.ptr(gp), s)
-            src, mask = r, m0
-            for Lk in L:
-                a, yk = Lk['a'], Lk['y']
-                ta = cx.new_act(n, a.h, a.w, a.c, a.ld)
-                lib.call('tg_cond_concat_f32', src.ptr, src.ld, src.c, P(mask), src.c, 1.0 / keep if mask is not None else 1.0, lib.ptr(zlab), ncls,
-                         ta.ptr, ta.ld, n, a.h * a.w, s)
-                d = geom.conv_fwd(n, a.h, a.w, a.ld, yk.ld, 3, Lk['stride'], 'SAME')
-                tz = cx.new_act(n, yk.h, yk.w, yk.c, yk.ld)
-                igemm('tg_igemm_f32', d, ta.ptr, lib.ptr(Lk['w_oti']), None, tz.ptr, s)
-                mk = Lk['mask']
-                th = cx.new_act(n, yk.h, yk.w, yk.c, yk.ld)
-                lib.call('tg_actgrad_f32', tz.ptr, tz.ld, yk.ptr, yk.ld, P(mk), yk.c, 1.0 / keep if mk is not None else 1.0, th.ptr, th.ld, yk.rows,
-                         yk.c, lre, 0.2, s)
-                # ---- sweep 4 (per layer): d gp / dW_k = wgrad(tangent input, dpre_k)
-                kname = 'discriminator/%s/%s/kernel' % (Lk['name'], Lk['name'])
-                off = st.offset(kname)
-                desc = geom.conv_wgrad(n, a.h, a.w, a.ld, yk.ld, 3, Lk['stride'], 'SAME')
-                ops.filter_grad(desc, ta.t, Lk['dpre'].t, 9, a.c, yk.c, grad[off:off + 9 * a.c * yk.c], defer=False)
-                src, mask = th, None
-            tp = cx.new_act(n, 1, 1, cl + ncls, pad32(cl + ncls))
-            lib.call('tg_gavgpool_concat_f32', src.ptr, src.ld, cl, lib.ptr(zlab), ncls, tp.ptr, tp.ld, n, hw, s)
-            off = st.offset('discriminator/lin/lin/kernel')
-            ops.colstats(0, tp.t, tp.ld, None, 0, n, cl + ncls, [n], s1=grad[off:off + cl + ncls])
-        self.last_gp_state = dict(x=x, alpha=alpha, masks=[m0] + [Lk['mask'] for Lk in L if Lk['mask'] is not None],
-                                  acts=[Lk['y'] for Lk in L], gx=gx, r=r)
-        return gp[0:1], grad
+        """weight * gp and weight * d gp / d theta_D of the WGAN-GP gradient penalty on this discriminator: tg/grad_penalty.py (contract,
+        the four sweeps, in_step) over D_CONVS and the dense head.  real, fake: Act [N,H,W,3]; y: label Act [N,NUM_CLASSES]."""
+        return grad_penalty.penalty(self, *self._gp, real, fake, y, weight, in_step)
 
     def _sigmoid_no_grad(self, logits):
         """tf.nn.sigmoid(logits) as an output: no loss of the reference differentiates through it (they all take the logits)."""

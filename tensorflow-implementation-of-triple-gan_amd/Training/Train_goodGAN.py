@@ -24,7 +24,7 @@ import torch
 
 from Training.train_base import Train_base
 from tg import dist as tgdist
-from tg import lib, ops
+from tg import grad_penalty, lib, ops
 from tg.batching import concat_acts
 from tg.runtime import Act, Context, PhiloxRNG, ctx, set_context
 
@@ -53,13 +53,7 @@ def check_loss(config):
         raise ValueError("LOSS must be one of %s, got %r" % (', '.join(repr(v) for v in LOSSES), loss))
     if loss != 'WGAN_GP':
         return loss
-    if getattr(config, 'MFMA_DTYPE', 'f32') == 'bf16':
-        raise lib.TgError("LOSS = 'WGAN_GP' needs MFMA_DTYPE = 'f32' (got 'bf16', which ACT_DTYPE = %r also needs): the gradient penalty "
-                          "differentiates a gradient, and its sweeps are pinned to a reference on the fp32 path only"
-                          % (getattr(config, 'ACT_DTYPE', 'f32'),))
-    if getattr(config, 'MINIBATCH_DIS', False):
-        raise lib.TgError("LOSS = 'WGAN_GP' does not support MINIBATCH_DIS = True: minibatch discrimination couples the images of a batch, so "
-                          "the discriminator is not piecewise linear in one image")
+    grad_penalty.check_supported("LOSS = 'WGAN_GP'", getattr(config, 'MFMA_DTYPE', 'f32'), getattr(config, 'MINIBATCH_DIS', False))
     l_d, u_d, b_g = (getattr(config, k, None) for k in ('BATCH_SIZE_L_D', 'BATCH_SIZE_U_D', 'BATCH_SIZE_G'))
     if l_d is None or u_d is None or b_g is None or l_d + u_d != b_g:
         raise lib.TgError("LOSS = 'WGAN_GP' needs BATCH_SIZE_L_D + BATCH_SIZE_U_D == BATCH_SIZE_G (got %r + %r, %r): the penalty "
@@ -632,7 +626,6 @@ class Train(Train_base):
         if self.loss_kind == 'WGAN_GP':
             m = self.model
             if X is None:
-                from tg.batching import concat_acts
                 X = concat_acts([m.as_image(self.x_l_d_ph), m.as_image(self.x_u_d_ph)])
             return self._loss_WGAN_GP_step(m.as_image(G), D, C, X, Y, Lambda, discriminator or m.discriminator)
         return self._loss_GAN(D, C, Y, Lambda)

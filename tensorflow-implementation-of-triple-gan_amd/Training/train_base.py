@@ -325,8 +325,8 @@ class Train_base(object):
 
     # ---- WGAN-GP (train_base.py:576-620) --------------------------------------------------------------------------------------------
     # The penalty differentiates the discriminator's input gradient; with its dropout masks and noise fixed the network is piecewise linear
-    # in the image, so the model computes d gp / d theta_D with four first-order sweeps (Model/Good_GAN_cifar10.py and Model/Good_GAN.py:
-    # discriminator_gradient_penalty).  It goes to a flat buffer laid out like the discriminator's ParamStore.g, `self.last_gp_grad`, never into store.g
+    # in the image, so d gp / d theta_D takes four first-order sweeps (tg/grad_penalty.py, which a model's discriminator_gradient_penalty
+    # hands its layer table).  It goes to a flat buffer laid out like the discriminator's ParamStore.g, `self.last_gp_grad`, never into store.g
     # (the caller's D backward owns that, and its filter-gradient launches overwrite); `_add_gp_grad()` adds it once that backward ran.
 
     @staticmethod
