@@ -207,7 +207,8 @@ int tg_conv3x3_packed_wgrad_f32(const float* x, int ld_x, int c_in, const float*
 /* Backward pass of a 5x5 / stride-2 / 'same' transposed convolution with c_out <= 4 output channels (the generator's image layer,
  * Model/Good_GAN_cifar10.py:55-57, Model/modle_base.py:246-259) as K-PACKED fp32 MFMA products (contraction index = the (tap, channel)
  * pair: 75 for three channels) — the generic tiles pad 3 channels to 32 and do ten times the layer's arithmetic.  dy: gradient at the layer's pre-activation output [n, 2h, 2w, ld_dy] (c_out channels used); x: the layer input
- * [n, h, w, ld_x] (ci_p = channel-padded width, a multiple of 32, <= 256; 16 | w, w <= 32, 4 | h).
+ * [n, h, w, ld_x] (ci_p = channel-padded width, a multiple of 32, <= 256; 16 | w, w <= 32, 4 | h; ld_x >= ci_p, 4 | ld_x, 16-byte aligned:
+ * the filter gradient reads x rows as 16-byte units).
  *   dgrad: dx[n,i,j,ci] = sum_{ky,kx,co} dy[n, 2i+ky-1, 2j+kx-1, co] * W[ky,kx,co,ci], W = the [5,5,Cout,Cin] variable itself, times
  *          scale_a[co] when not NULL (weight norm: tg_wn_scale_tab_f32); all ci_p channels of dx are written (zeros beyond c_in).
  *   wgrad: dw[25][c_out][c_in] = sum_{n,i,j} dy[n, 2i+ky-1, 2j+kx-1, co] * x[n,i,j,ci] — the layout of the [5,5,Cout,Cin] variable;
@@ -628,12 +629,21 @@ int tg_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, const f
 int tg_ema_f32(float* shadow, const float* p, int64_t n, float decay, void* stream);
 
 /* ---- RNG (Philox4x32-10; state = device {seed, step}) -------------------------------------------- */
+/* Element e of a draw is word e % 4 of the block with counter (lo32(e / 4), hi32(e / 4), stream_id, lo32(step)) and key (lo32(seed),
+ * hi32(seed) ^ hi32(step)); a one-hot row r takes class (word 0 * k) >> 32 of the block with counter (r, 0, stream_id, lo32(step)).
+ * A word x becomes u = ((x >> 8) + 0.5f) * 2^-24 in fp32: in (0, 1], exactly 1.0 for the one word value x >> 8 == 0xFFFFFF (the sum rounds up).
+ *   uniform:   lo + (hi - lo) * min(u, 1 - 2^-24) in fp32 (multiply, then add).  In [lo, hi) for (lo, hi) = (-1, 1) and (0, 1); for a general
+ *              range the fp32 rounding of the sum can return hi itself (2 + 3 u rounds to 5 at the largest u), so the contract there is [lo, hi].
+ *   keep_mask: min(u, 1 - 2^-24) < keep_prob ? 1 : 0 (keep_prob = 1 keeps everything).
+ *   normal:    Box-Muller on the word pairs (x, y) and (z, w), stddev * sqrt(-2 ln u0) * (cos, sin)(2 pi u1), on the unclamped u (u0 = 1 gives the
+ *              pair (0, 0)): the values of a seeded run's noise are what they have always been.
+ * tests/rng_reference.py restates all of it; tests/test_gpu_rng.py holds the kernels to it value by value. */
 int tg_rng_uniform_f32(float* out, int64_t n, float lo, float hi, const uint64_t* state, uint32_t stream_id, void* stream);
 int tg_rng_keep_mask_f32(float* out, int64_t n, float keep_prob, const uint64_t* state, uint32_t stream_id, void* stream);
 int tg_rng_normal_f32(float* out, int64_t n, float stddev, const uint64_t* state, uint32_t stream_id, void* stream);
 int tg_rng_onehot_f32(float* out, int rows, int k, const uint64_t* state, uint32_t stream_id, void* stream);
 int tg_rng_advance(uint64_t* state, void* stream);
-/* Up to 16 of the draws above in ONE launch (all random inputs of a solver run): mode 0 uniform [a,b), 1 keep-mask with probability a,
+/* Up to 16 of the draws above in ONE launch (all random inputs of a solver run): mode 0 uniform from a to b (as tg_rng_uniform_f32), 1 keep-mask with probability a,
  * 2 normal(0,a), 3 one-hot of a classes per row (n = rows).  Bit-identical to the single calls (same counters). */
 typedef struct tg_rng_job {
   float* out;

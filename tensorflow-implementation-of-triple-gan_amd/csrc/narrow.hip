@@ -273,8 +273,8 @@ extern "C" int tg_deconv5x5s2_narrow_dgrad_f32(const float* dy, int ld_dy, const
 extern "C" int tg_deconv5x5s2_narrow_wgrad_f32(const float* dy, int ld_dy, const float* x, int ld_x, int n, int h, int w, int c_out, int c_in, int ci_p,
                                                float* workspace, float* dw, void* stream) {
   TG_REQUIRE(dy && x && workspace && dw, "deconv5x5s2_narrow_wgrad: null buffer");
-  TG_REQUIRE(shape_ok(n, h, w, c_out, ci_p) && ld_dy >= c_out && ld_x >= ci_p && c_in >= 1 && c_in <= ci_p, "deconv5x5s2_narrow_wgrad: unsupported shape n=%d h=%d w=%d c_out=%d c_in=%d ci_p=%d",
-             n, h, w, c_out, c_in, ci_p);
+  TG_REQUIRE(shape_ok(n, h, w, c_out, ci_p) && ld_dy >= c_out && ld_x >= ci_p && ld_x % 4 == 0 && c_in >= 1 && c_in <= ci_p,
+             "deconv5x5s2_narrow_wgrad: unsupported shape n=%d h=%d w=%d c_out=%d c_in=%d ci_p=%d ld_x=%d", n, h, w, c_out, c_in, ci_p, ld_x);   // x rows are read as 16-byte units
   hipStream_t s = tg::as_stream(stream);
   tg::ProfScope prof(tg::PC_WGRAD, 2.0 * n * h * w * ci_p * TAPS * c_out, 4.0 * ((double)n * h * w * ci_p + (double)n * 4 * h * w * c_out), s, "narrow deconv wgrad");
   const int blocks = n * (h / RB);

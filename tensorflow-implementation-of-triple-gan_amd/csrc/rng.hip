@@ -11,7 +11,13 @@ namespace {
 using tgd::u4;
 using tgd::philox;
 
-__device__ __forceinline__ float u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }   // (0,1)
+// (0,1]: the centre of the word's 2^-24 bin, in fp32.  k + 0.5f is not representable for k >= 2^23 and rounds to even, so x >> 8 == 0xFFFFFF
+// gives exactly 1.0f (one word value in 2^24).  The normal draw takes it as it is (ln 1 = 0: radius 0, a plain sample; the angle 2 pi is as
+// good as 0), so seeded runs, which are mostly noise, keep every value they ever had.
+__device__ __forceinline__ float u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+// (0,1): the same clamped to the largest fp32 below 1 (0x3F7FFFFF = 1 - 2^-24) for the draws whose contract needs u < 1 — uniform [lo,hi) and the
+// keep-mask (keep_prob = 1 keeps everything).  Only the word above changes its value.
+__device__ __forceinline__ float u01_open(uint32_t x) { return fminf(u01(x), 0.99999994f); }
 
 // mode 0: uniform [lo,hi); 1: bernoulli keep-mask (1 with prob a); 2: normal(0, a); 3: one-hot of k=a classes per row
 __global__ void __launch_bounds__(256) rng_kernel(float* __restrict__ out, int64_t n, int mode, float a, float b, const uint64_t* __restrict__ state,
@@ -28,7 +34,7 @@ __global__ void __launch_bounds__(256) rng_kernel(float* __restrict__ out, int64
       sincosf(6.283185307179586f * u01(r.w), &s1, &c1);
       v[0] = a * r0 * c0; v[1] = a * r0 * s0; v[2] = a * r1 * c1; v[3] = a * r1 * s1;
     } else {
-      const float u[4] = {u01(r.x), u01(r.y), u01(r.z), u01(r.w)};
+      const float u[4] = {u01_open(r.x), u01_open(r.y), u01_open(r.z), u01_open(r.w)};
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = mode == 0 ? a + (b - a) * u[k] : (u[k] < a ? 1.f : 0.f);
     }
@@ -75,7 +81,7 @@ __global__ void __launch_bounds__(256) rng_multi_kernel(RngJobs js, const uint64
       sincosf(6.283185307179586f * u01(r.w), &s1, &c1);
       v[0] = a * r0 * c0; v[1] = a * r0 * s0; v[2] = a * r1 * c1; v[3] = a * r1 * s1;
     } else {
-      const float u[4] = {u01(r.x), u01(r.y), u01(r.z), u01(r.w)};
+      const float u[4] = {u01_open(r.x), u01_open(r.y), u01_open(r.z), u01_open(r.w)};
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = J.mode == 0 ? a + (b - a) * u[k] : (u[k] < a ? 1.f : 0.f);
     }

@@ -1,4 +1,5 @@
-"""Shared checks of the per-kernel float64 tests (tests/test_gpu_elementwise.py, _prep.py, _norm_finalize.py, _loss_heads.py, _gemm_tiles.py, _halo_tiles.py),
+"""Shared checks of the per-kernel float64 tests (tests/test_gpu_elementwise.py, _prep.py, _norm_finalize.py, _loss_heads.py, _gemm_tiles.py, _halo_tiles.py,
+_packed_tiles.py, _rng.py),
 and the float64 oracle of an implicit-GEMM descriptor (igemm_ref64, on the device).
 
 Every output a test reads is allocated by `guarded`: the buffer is followed by GUARD floats holding a fixed bit pattern, and the output
