@@ -24,7 +24,7 @@ import torch
 
 from Training.train_base import Train_base
 from tg import dist as tgdist
-from tg import grad_penalty, lib, ops
+from tg import executor, grad_penalty, lib, ops
 from tg.batching import concat_acts
 from tg.runtime import Act, Context, PhiloxRNG, ctx, set_context
 
@@ -125,12 +125,10 @@ class Train(Train_base):
         self.hyper = torch.zeros(4, dtype=torch.float32, device=cx.device)       # lr, cla_lr, lambda_1, lambda_2
         self.loss_dev = torch.zeros(3, dtype=torch.float32, device=cx.device)    # d_loss, g_loss, c_loss
         self.model = None
-        self._graphs = None
+        self.executor = executor.StepExecutor(cx)        # how an iteration is launched, and every graph / launch plan it replays
+        self._refusal_warned = False
         self._rest = {}                  # solver run -> (unexecuted head of its backward tape, call-site counter): bucketed backward passes
-        self._warm = False
-        self._warm_keys = set()
         self.iteration = 0
-        self._exposed = None             # [(mark before, mark after)] of the waits for gradient buckets while measure_exposed(True)
         self._label_override = {}        # see label_override()
         self.zca_source = None           # config.ZCA = 'fit' resolved by train(): 'files' | 'fit' (rank 0) | 'broadcast' (other ranks)
         self.summary_train = self.summary_val = None
@@ -394,201 +392,46 @@ class Train(Train_base):
                 cx.rng.onehot(cx, 'y', self.y_g_ph.n, self.config.NUM_CLASSES, out=self.y_g_ph.t)
 
     def train_iteration(self, pre_train=False, use_graph=None):
-        """D-update, G-update, C-update on the current placeholder contents (:266-276).  No host sync."""
-        cx = self.cx
-        mode = getattr(self.config, 'EXEC_MODE', 'auto')
-        key = 'pre' if pre_train else 'full'
+        """D-update, G-update, C-update on the current placeholder contents (:266-276), launched the way tg.executor.resolve_launch reads
+        out of config.EXEC_MODE / USE_HIP_GRAPH.  No host sync."""
+        ex, key = self.executor, 'pre' if pre_train else 'full'
         if use_graph is None:
             use_graph = getattr(self.config, 'USE_HIP_GRAPH', None)
-        replayable = isinstance(cx.rng, PhiloxRNG)        # injected draws (parity tests) are host-fed per iteration: nothing to replay
-        if mode == 'auto':
-            if use_graph is None and replayable and tgdist.graphs_allowed():
-                mode = self._auto_mode(key)               # 'plan' or 'graph': the measured faster one for this workload on this host
-            elif use_graph is None and replayable:
-                mode = 'plan'                             # torch's RCCL process group forbids captures (tg/dist.py): plans are plain launches
-            else:
-                mode = 'overlap' if not use_graph else 'graph'
-        if use_graph is None:
-            use_graph = mode == 'graph'
-        use_graph = use_graph and replayable
-        use_plan = mode == 'plan' and replayable and not use_graph
-        if use_graph and not tgdist.graphs_allowed():          # torch's RCCL process group: its watchdog cannot coexist with a capture
-            if not getattr(self, '_warned_eager', False) and self.rank == 0:
+        how, refused = executor.resolve_launch(getattr(self.config, 'EXEC_MODE', 'auto'), use_graph, isinstance(self.cx.rng, PhiloxRNG),
+                                               tgdist.graphs_allowed(), ex.replay[key].auto.next)
+        if refused and not self._refusal_warned:          # torch's RCCL process group: its watchdog cannot coexist with a capture
+            self._refusal_warned = True
+            if self.rank == 0:
                 print("tg: backend %r cannot run beside hipGraph capture (tg/dist.py) - launching eagerly; "
                       "use TG_DIST_BACKEND=rccl-direct for graphs" % tgdist.backend_name(), flush=True)
-            self._warned_eager = True
-            use_graph = False
-        if (use_graph or use_plan) and any(v is not None for v in self._label_override.values()):
+        if how in ('graph', 'plan') and any(v is not None for v in self._label_override.values()):
             raise lib.TgError("label_override() is a test hook of eager launches: a replayed graph / launch plan would not see it")
         segs = self._segments(pre_train)
-        if self._graphs is None:
-            self._graphs = {}
-        graphs = self._graphs.setdefault(key, [None] * len(segs))
-        if use_graph and key in self._warm_keys and any(g is None for g in graphs):
-            self._capture(segs, graphs, key)
-        plans = self.__dict__.setdefault('_plans', {}).setdefault(key, [None] * len(segs)) if use_plan else None
-        # a segment's plan is recorded while it runs eagerly in the SECOND two-stream iteration of its kind (the first one allocates the
-        # buffers and records the multi-launch plans of the RNG / filter preparation / statistics arena) and replayed from then on
-        plan_ready = use_plan and ('plan', key) in self._warm_keys
-        pending = []
-        cx.prep_cache = {}                              # filter layouts stay valid between a network's optimiser steps
-        cx.plan_tag = key
-        # second-stream overlap (Context.wgrad_on_side): only beside eager launches — a captured graph with cross-stream edges replays slower
-        # than the single chain on ROCm 7.2 (measured rounds 1 and 3), so graph replay stays one chain
-        side_was = cx.wgrad_side
-        on = (not use_graph) and mode in ('overlap', 'auto', 'plan')
-        cx.wgrad_side = on
-        try:
-            for i, (fn, grads, wait) in enumerate(segs):
-                if wait:                                    # this segment opens with an optimiser step: its network's buckets must be in
-                    mark = self._mark() if (self._exposed is not None and pending) else None
-                    for wk in pending:
-                        tgdist.wait_(wk)
-                    if mark is not None:
-                        self._exposed.append((mark, self._mark()))
-                    pending = []
-                if use_graph and graphs[i] is not None:
-                    lib.call('tg_graph_launch', graphs[i], cx.stream)
-                elif use_plan and plans[i] is not None:
-                    plans[i].replay()
-                elif plan_ready:
-                    plans[i] = self._record_plan(fn)
-                else:
-                    fn()
-                if grads is not None and tgdist.active():
-                    pending.append(tgdist.allreduce_sum_async_(grads))
-        finally:
-            cx.prep_cache = None
-            cx.join_wgrad_side()
-            cx.wgrad_side = side_was
-        self._warm = True
-        self._warm_keys.add(key)       # graphs of a mode are captured from its SECOND iteration on: the first one allocates its buffers eagerly
-        if on and not use_graph:
-            self._warm_keys.add(('plan', key))       # one two-stream iteration has run: its events and side-stream workspaces exist
+        if how == 'graph':
+            ex.capture(segs, key)                         # from the second iteration of this key on, whatever has no graph yet
+        ex.run(segs, key, how)
         self.iteration += 1
 
-    def _record_plan(self, fn):
-        """run segment `fn` eagerly on the two streams while every launch and event operation is appended to a native launch plan
-        (tg/plan.py, include/tg_plan.h); returns the plan.  Buffers may not be born during the recording (the plan holds addresses), and
-        the stores are frozen like under a captured graph."""
-        from tg.plan import Plan
-        cx = self.cx
-        for st in cx.stores.values():
-            st.frozen = True
-        plan = Plan([cx.torch_stream.cuda_stream, cx.side_stream.cuda_stream])
-        was = cx.capturing
-        cx.capturing = True
-        try:
-            with plan.recording():
-                fn()
-        finally:
-            cx.capturing = was
-        return plan
-
-    # ---- EXEC_MODE = 'auto': which way of launching is faster for THIS workload on THIS host is measured, not assumed
-    AUTO_TIMED = 5                     # timed iterations per block
-    AUTO_SETTLE = 3                    # untimed iterations in front of each timed block (allocations, lazily loaded code objects, recorded launch plans)
-    AUTO_BLOCKS = 3                    # blocks per candidate, alternating: a candidate's time is its FASTEST block
-    AUTO_ITERS = 2 * AUTO_BLOCKS * (AUTO_SETTLE + AUTO_TIMED) + 1
-
-    def _auto_mode(self, key):
-        """Both candidates compute the same numbers; which is faster depends on the workload: the CIFAR-10 / SVHN steps (15 ms of large
-        kernels) gain 2.5 - 4 % from the second-stream overlap that only eager launches can have, the MNIST step (2.7 ms in ~300 launches of
-        a few microseconds) is bound by the host's launch rate when launched eagerly (4.1 ms) and needs graph replay.  Schedule per graph
-        key: AUTO_BLOCKS x [overlap block, graph block], a block = AUTO_SETTLE untimed + AUTO_TIMED timed iterations (the first graph block
-        captures); a candidate's time is its fastest block — the first block of a fresh process on a fresh machine measures page-ins of
-        library code, not the candidate (seen: 28 ms for a 14.6 ms step) — then the faster candidate for good.  Costs two device
-        synchronisations per block in the first AUTO_ITERS iterations, none afterwards."""
-        st = self.__dict__.setdefault('_auto', {}).setdefault(key, dict(n=0, t0=None, t={'plan': [], 'graph': []}, pick=None))
-        if st['pick'] is not None:
-            return st['pick']
-        S, N, B = self.AUTO_SETTLE, self.AUTO_TIMED, self.AUTO_BLOCKS
-        n = st['n']
-        st['n'] = n + 1
-        now = lambda: (torch.cuda.synchronize(), time.perf_counter())[1]
-        b, k = divmod(n, S + N)
-        mode = 'plan' if b % 2 == 0 else 'graph'
-        if k == 0 and b > 0:                                # the previous block ends here
-            st['t']['graph' if mode == 'plan' else 'plan'].append((now() - st['t0']) / N)
-        if b == 2 * B:
-            # replicas decide together (every rank reaches this point in the same iteration): the slowest rank's time per candidate
-            st['pick'], st['best'] = tgdist.decide_together(dict(plan=min(st['t']['plan']), graph=min(st['t']['graph'])), self.cx.device)
-            return st['pick']
-        if k == S:
-            st['t0'] = now()
-        return mode
+    # ---- thin views of self.executor (tg/executor.py), under the names bench.py, tools/ and the tests use
+    AUTO_TIMED, AUTO_SETTLE, AUTO_BLOCKS, AUTO_ITERS = executor.AUTO_TIMED, executor.AUTO_SETTLE, executor.AUTO_BLOCKS, executor.AUTO_ITERS
 
     def exec_mode_chosen(self, key='full'):
         """(mode, {candidate: seconds per iteration}) of EXEC_MODE = 'auto' once decided, else (None, partial timings)."""
-        st = getattr(self, '_auto', {}).get(key)
-        if st is None:
-            return None, {}
-        return st['pick'], (dict(st['best']) if 'best' in st else {k: min(v) for k, v in st['t'].items() if v})
+        return self.executor.replay[key].auto.chosen()
 
-    # ---- how much of the gradient exchange is NOT hidden behind the backward pass (bench.py `exchange_exposed_ms`)
-    def _mark(self):
-        """a point of the launch stream's timeline: a timing event on a GPU (the waits are stream-side, the host does not block),
-        the host clock otherwise (gloo's wait blocks the host)."""
-        if self.cx.device.type == 'cuda':
-            e = torch.cuda.Event(enable_timing=True)
-            e.record(torch.cuda.current_stream())
-            return e
-        return time.perf_counter()
+    @property
+    def _auto(self):
+        """{key: {'t': {candidate: [seconds per iteration of each timed block]}}} of the keys whose measurement has begun (bench.py's
+        `exec_mode_blocks_ms` reads it under this name)."""
+        return {key: {'t': st.auto.times} for key, st in self.executor.replay.items() if st.auto.n}
 
     def measure_exposed(self, on=True):
         """start (or stop) bracketing every wait for a network's gradient buckets in train_iteration."""
-        self._exposed = [] if on else None
+        self.executor.measure_exposed(on)
 
     def exposed_ms(self):
-        """total time the launch stream spent stalled in those waits since measure_exposed(True) — the exchange time the backward
-        pass did not hide.  Synchronises the device."""
-        if not self._exposed:
-            return 0.0
-        if isinstance(self._exposed[0][0], float):
-            return 1e3 * sum(b - a for a, b in self._exposed)
-        torch.cuda.synchronize()
-        return float(sum(a.elapsed_time(b) for a, b in self._exposed))
-
-    def _capture(self, segs, graphs, key):
-        """Record every segment of one iteration as a hipGraph — all of them back to back, nothing launched and no collective issued
-        in between.  Only reached when tg.dist.graphs_allowed(): the exchange backends used with graphs (rccl-direct, gloo) have no
-        thread that touches HIP events behind the trainer's back, so a capture cannot be disturbed (tg/dist.py docstring)."""
-        import ctypes as C
-        import gc
-        cx = self.cx
-        cx.prep_cache = {}
-        cx.plan_tag = key
-        for st in cx.stores.values():
-            st.frozen = True                     # the graphs hold these buffers' addresses: ParamStore.extend must not re-allocate them
-        # No garbage collection inside a capture window.  A collector pass can free a PINNED host tensor of an earlier owner (an input
-        # pipeline's staging slots): torch's caching host allocator then records an event on every stream the tensor was copied on — torch
-        # hands out streams from a pool of 32, so in a long-lived process that can be THIS trainer's capturing stream — and its next query of
-        # that captured event fails with "operation not permitted when stream is capturing", which invalidates the capture (every later
-        # launch: "operation failed due to a previous error during capture").  Seen once in a full test session (round 4); mechanism
-        # reproduced in tools/micro/capture_pinned_free.py.
-        gc_was = gc.isenabled()
-        if not os.environ.get('TG_DEBUG_CAPTURE_GC'):      # (test hook: leave the collector running, to show what the guard is for)
-            gc.collect()
-            gc.disable()
-        try:
-            for i, (fn, _grads, _wait) in enumerate(segs):
-                if graphs[i] is not None:
-                    continue
-                lib.call('tg_graph_begin_capture', cx.stream)
-                cx.capturing = True
-                try:
-                    if os.environ.get('TG_DEBUG_CAPTURE_SLEEP'):          # test hook: widen the capture window
-                        time.sleep(float(os.environ['TG_DEBUG_CAPTURE_SLEEP']))
-                    fn()
-                finally:
-                    cx.capturing = False
-                    h = C.c_void_p()
-                    lib.call('tg_graph_end_capture', cx.stream, C.byref(h))
-                graphs[i] = h
-        finally:
-            cx.prep_cache = None
-            if gc_was:
-                gc.enable()
+        """total time the launch stream spent stalled in those waits since measure_exposed(True).  Synchronises the device."""
+        return self.executor.exposed_ms()
 
     def losses(self):
         """(d_loss, g_loss, c_loss) of the last iteration — a device->host sync; call sparingly."""

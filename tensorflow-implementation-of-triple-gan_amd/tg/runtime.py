@@ -100,7 +100,7 @@ class ParamStore(object):
         self._narrow()
         self.step = torch.zeros(1, dtype=torch.int32, device=device)
         self.ema = None
-        self.frozen = False          # set by Train._capture: a hipGraph holds this store's device pointers, re-allocation is an error
+        self.frozen = False          # set by tg.executor.StepExecutor: a hipGraph or a launch plan holds this store's device pointers, re-allocation is an error
 
     def _narrow(self):
         f = self._full
@@ -299,7 +299,7 @@ class PhiloxRNG(object):
 
 
 class Context(object):
-    capturing = False                                 # a hipGraph capture is open on the launch stream (Train._capture)
+    capturing = False                                 # a hipGraph capture is open on the launch stream (tg.executor.StepExecutor.capture)
     _wgrad_side_pending = False                       # launches on the second stream not yet joined (wgrad_on_side)
     detached_draws = False                            # inside Context.detached
 

@@ -25,14 +25,14 @@ def run(use_graph, steps=4, sizes=SMALL, _holder=None, **over):
         tr.train_iteration()
         losses.append(tr.losses())
     params = {net: st.p.detach().cpu().numpy().copy() for net, st in tr.cx.stores.items()}
-    graphs = tr._graphs
+    graphs = {key: st.graphs for key, st in tr.executor.replay.items()}
     return losses, params, graphs
 
 
 def test_graph_replay_equals_eager():
     l_e, p_e, g_e = run(False)
     l_g, p_g, g_g = run(True)
-    assert all(h is None for h in g_e['full']) and all(h is not None for h in g_g['full'])   # the graphs were really used
+    assert g_e['full'] and all(h is None for h in g_e['full']) and g_g['full'] and all(h is not None for h in g_g['full'])   # the graphs were really used
     assert l_e == l_g
     for net in p_e:
         np.testing.assert_array_equal(p_e[net], p_g[net])
@@ -48,7 +48,7 @@ def test_graph_replay_equals_eager_at_the_benchmark_sizes():
     l_e, p_e, _ = run(False, 3, sizes)
     l_g, p_g, g_g = run(True, 3, sizes)
     l_h, p_h, _ = run(True, 3, sizes)
-    assert all(h is not None for h in g_g['full'])
+    assert g_g['full'] and all(h is not None for h in g_g['full'])
     assert l_e == l_g == l_h and all(np.isfinite(v) for l in l_g for v in l)
     for net in p_e:
         np.testing.assert_array_equal(p_e[net], p_g[net])
@@ -65,7 +65,7 @@ def test_graph_replay_equals_eager_with_bf16_operands_at_the_benchmark_sizes():
     l_e, p_e, _ = run(False, 3, sizes, MFMA_DTYPE='bf16')
     assert lib.call('tg_conv3x3_launches') - halo0 >= 3 * 20          # the halo kernels really ran (27+ launches per iteration)
     l_g, p_g, g_g = run(True, 3, sizes, MFMA_DTYPE='bf16')
-    assert all(h is not None for h in g_g['full'])
+    assert g_g['full'] and all(h is not None for h in g_g['full'])
     assert l_e == l_g and all(np.isfinite(v) for l in l_g for v in l)
     for net in p_e:
         np.testing.assert_array_equal(p_e[net], p_g[net])
@@ -80,8 +80,8 @@ def test_plan_replay_equals_eager_at_the_benchmark_sizes(dtype):
     l_e, p_e, _ = run(False, 5, sizes, MFMA_DTYPE=dtype)
     tr_holder = {}
     l_p, p_p, _ = run(None, 5, sizes, MFMA_DTYPE=dtype, EXEC_MODE='plan', _holder=tr_holder)
-    plans = tr_holder['tr']._plans['full']
-    assert all(p is not None for p in plans) and sum(p.launches for p in plans) > 200, [p and p.launches for p in plans]
+    plans = tr_holder['tr'].executor.replay['full'].plans
+    assert plans and all(p is not None for p in plans) and sum(p.launches for p in plans) > 200, [p and p.launches for p in plans]
     assert l_e == l_p and all(np.isfinite(v) for l in l_p for v in l)
     for net in p_e:
         np.testing.assert_array_equal(p_e[net], p_p[net])
@@ -106,21 +106,22 @@ def test_execution_modes_compute_the_same_numbers_and_auto_decides():
             tr.train_iteration()
             losses.append(tr.losses())
         params = {net: st.p.detach().cpu().numpy().copy() for net, st in tr.cx.stores.items()}
-        used_graphs = tr._graphs is not None and all(h is not None for h in tr._graphs.get('full', [None]))
+        st = tr.executor.replay['full']
+        used_graphs = bool(st.graphs) and all(h is not None for h in st.graphs)
         pick, timings = tr.exec_mode_chosen()
         if mode == 'auto':
             assert pick in ('plan', 'graph') and set(timings) == {'plan', 'graph'} and all(t > 0 for t in timings.values()), (pick, timings)
             assert used_graphs          # the graph candidate was captured and timed
-            assert all(p is not None for p in tr._plans['full'])          # and so was the plan candidate
+            assert st.plans and all(p is not None for p in st.plans)          # and so was the plan candidate
         else:
             assert pick is None
             assert used_graphs == (mode == 'graph')
             if mode == 'plan':          # every segment recorded in the second iteration and replayed natively from the third on
-                plans = tr._plans['full']
-                assert all(p is not None for p in plans) and sum(p.launches for p in plans) > 100, [p and p.launches for p in plans]
+                plans = st.plans
+                assert plans and all(p is not None for p in plans) and sum(p.launches for p in plans) > 100, [p and p.launches for p in plans]
                 assert sum(len(p) - p.launches for p in plans) >= 4          # the cross-stream events of the overlap are part of the plans
             else:
-                assert not getattr(tr, '_plans', {})
+                assert all(p is None for s in tr.executor.replay.values() for p in s.plans)
         if ref is None:
             ref = (losses, params)
         else:
@@ -191,7 +192,7 @@ def test_launch_plan_api_on_two_streams_and_its_error_report():
 
 
 def test_capture_survives_the_garbage_of_earlier_owners():
-    """Train._capture keeps Python's garbage collector out of the capture window: a collector pass can free pinned host tensors of earlier
+    """tg.executor.StepExecutor.capture keeps Python's garbage collector out of the capture window: a collector pass can free pinned host tensors of earlier
     owners, torch's host allocator then records and queries an event on the streams they were copied on — if that is the capturing stream
     (torch's stream pool wraps around after 32) the capture is invalidated (tools/micro/capture_pinned_free.py shows the mechanism).  Here
     cyclic garbage holding streams, events, device and pinned tensors waits for collection and the collector is set to run every few
@@ -211,7 +212,7 @@ def test_capture_survives_the_garbage_of_earlier_owners():
         l_g, p_g, g_g = run(True, steps=3)
     finally:
         gc.set_threshold(*old)
-    assert all(h is not None for h in g_g['full'])
+    assert g_g['full'] and all(h is not None for h in g_g['full'])
     assert l_g == l_ref
     for net in p_ref:
         np.testing.assert_array_equal(p_ref[net], p_g[net])

@@ -38,7 +38,7 @@ t = tgdist.max_over_ranks(1.25, tr.cx.device)
 torch.cuda.synchronize()
 backend = torch.distributed.get_backend() if torch.distributed.is_initialized() else ('rccl-direct' if tgdist._direct is not None else None)
 out = dict(active=tgdist.active(), backend=backend, t=t, rccl_ranks=tgdist.rccl_ranks(), pick=tr.exec_mode_chosen()[0],
-           graphs=any(g is not None for g in (tr._graphs or {{}}).get('full', [])),
+           graphs=any(g is not None for g in tr.executor.replay['full'].graphs),
            losses=tr.losses(), p={{k: st.p.cpu().numpy() for k, st in tr.cx.stores.items()}})
 torch.save(out, {out!r})
 tgdist.shutdown()

@@ -91,7 +91,8 @@ def test_stress64_at_its_stated_batch_sizes_properties():
             assert torch.isfinite(s.p).all() and (s.p != before[k]).any(), k
         runs[graph] = (losses, {k: s.p.detach().cpu().numpy().copy() for k, s in tr.cx.stores.items()})
         if graph:
-            assert all(g is not None for g in tr._graphs['full'])
+            graphs = tr.executor.replay['full'].graphs
+            assert graphs and all(g is not None for g in graphs)
     assert runs[True][0] == runs[False][0]
     for k in runs[False][1]:
         np.testing.assert_array_equal(runs[True][1][k], runs[False][1][k], err_msg=k)

@@ -123,7 +123,7 @@ def test_param_store_layout_and_roundtrip():
 
 def test_param_store_growth_keeps_pointers_inside_the_reserve_and_refuses_to_move_captured_buffers():
     """advisor (round 2): variables appended within the reserve keep every device pointer; beyond it the buffers move, which is an
-    error once a hipGraph has captured them (ParamStore.frozen, set by Train._capture)."""
+    error once a hipGraph has captured them (ParamStore.frozen, set by tg.executor.StepExecutor.capture)."""
     import torch
     from tg import lib
     from tg.runtime import ParamStore

@@ -41,7 +41,7 @@ class Store(object):
         self.p = t
 same = bench.replicas_identical(dict(a=Store(torch.arange(1000, dtype=torch.float32) * 0.37), b=Store(torch.ones(33))), 'cpu')
 differ = bench.replicas_identical(dict(a=Store(torch.arange(1000, dtype=torch.float32) * 0.37 + (1e-7 if rank else 0.0))), 'cpu')
-# the execution-mode decision of EXEC_MODE = 'auto' (Train._auto_mode -> tg.dist.decide_together): locally every rank but the last finds
+# the execution-mode decision of EXEC_MODE = 'auto' (tg.executor.AutoMode -> tg.dist.decide_together): locally every rank but the last finds
 # 'plan' faster; the last rank's plan time is the slowest of all -> every replica must take 'graph', with the same timings
 local = dict(plan=14.5e-3 + (2e-3 if rank == world - 1 else 0.0), graph=15.0e-3 + 1e-5 * rank)
 pick, worst = tgdist.decide_together(local, 'cpu')

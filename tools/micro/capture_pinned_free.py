@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Mechanism behind Train._capture's garbage-collection guard (round 4): freeing a PINNED host tensor that was used for an asynchronous copy on
+"""Mechanism behind tg.executor.StepExecutor.capture's garbage-collection guard (round 4): freeing a PINNED host tensor that was used for an asynchronous copy on
 stream S makes torch's caching host allocator record an event on S; if S is capturing, that event is a captured one and the allocator's next
 query of it (at the next pinned allocation, from any owner) fails with hipErrorCapturedEvent and invalidates the capture — every later launch
 of the capture reports "operation failed due to a previous error during capture".  Measured: the free alone is harmless, free + allocation
