@@ -625,6 +625,16 @@ int tg_accuracy_count_f32(const float* logits, int ld, const float* labels, int 
  * g is multiplied by grad_scale (1/world_size after a sum all-reduce). */
 int tg_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2, float eps, int* step_dev,
                 float grad_scale, void* stream);
+/* tf.train.MomentumOptimizer, use_nesterov = False (Training/train_base.py:86-89) over a flat buffer: accum = accum*momentum + g;
+ * p -= lr*accum.  Arguments: values, gradients, the `momentum` slot (zero-initialised), element count, lr (DEVICE scalar, read at
+ * launch), momentum, grad_scale (g is multiplied by it first: 1/world_size after a sum all-reduce).  No step count.  20 B / parameter. */
+int tg_momentum_f32(float* p, const float* g, float* accum, int64_t n, const float* lr_dev, float momentum, float grad_scale, void* stream);
+/* tf.train.RMSPropOptimizer, centered = False (Training/train_base.py:99-105) over a flat buffer: rms += (g*g - rms)*(1 - decay);
+ * mom = mom*momentum + (g*lr)/sqrt(rms + eps); p -= mom — eps INSIDE the root.  Arguments: values, gradients, the `rms` slot (initialised
+ * to ONES by the caller), the `momentum` slot (zeros), element count, lr (DEVICE scalar), decay, momentum, eps, grad_scale (as above).
+ * No step count.  28 B / parameter. */
+int tg_rmsprop_f32(float* p, const float* g, float* rms, float* mom, int64_t n, const float* lr_dev, float decay, float momentum, float eps,
+                   float grad_scale, void* stream);
 /* shadow -= (1-decay)*(shadow - p) (tf.train.ExponentialMovingAverage, Training/Train_goodGAN.py:101-103). */
 int tg_ema_f32(float* shadow, const float* p, int64_t n, float decay, void* stream);
 

@@ -7,8 +7,12 @@ TensorFlow name, in ONE file `model_<epoch>.ckpt.npz` (so `_findfilename`'s name
     <variable>                               trainable values, pop_mean / moving statistics     (tf.GraphKeys.GLOBAL_VARIABLES)
     <variable>/Adam_optimizer                Adam first-moment slot  m                          (train_base.py:91-97) [UNVERIFIED-TF slot naming]
     <variable>/Adam_optimizer_1              Adam second-moment slot v
+    <variable>/Momentum                      momentum SGD's accumulator (m)      — a network trained with config.OPTIMIZER 'momentum' 
+    <variable>/RMSProp_optimizer             RMSProp's rms slot (v)              — a network trained with 'rmsprop'; the slot keys of a
+    <variable>/RMSProp_optimizer_1           RMSProp's momentum slot (m)           network follow ITS optimiser, in TensorFlow's slot order
     <variable>/ExponentialMovingAverage      EMA shadow of the classifier variables             (Train_goodGAN.py:101-103)
-    tg/adam_step/<network>                   step count t of that network's optimiser (TF keeps beta1_power = beta1^t, beta2_power)
+    tg/adam_step/<network>                   step count t of that network's optimiser (TF keeps beta1_power = beta1^t, beta2_power); in every
+                                             file, simply not advanced by momentum SGD and RMSProp, which keep no count
     tg/rng_state                             Philox (seed, step) of the writing rank — TF's graph-level seeds have no equivalent.  On
                                              restore every rank takes the STEP and keeps its own seed (replicas draw different
                                              z / y / masks / noise: config.SEED + 7919 * rank, Train.__init__)
@@ -23,6 +27,24 @@ from datetime import datetime, timedelta, timezone as _tz
 import numpy as np
 
 ADAM_M, ADAM_V, EMA = '/Adam_optimizer', '/Adam_optimizer_1', '/ExponentialMovingAverage'
+# optimiser of a network (ParamStore.optimizer) -> [(key suffix, slot buffer)] in the order tf.train.Saver() numbers the slots
+SLOT_KEYS = {'adam': [(ADAM_M, 'm'), (ADAM_V, 'v')],
+             'momentum': [('/Momentum', 'm')],
+             'rmsprop': [('/RMSProp_optimizer', 'v'), ('/RMSProp_optimizer_1', 'm')]}
+
+
+def _slots(st):
+    return SLOT_KEYS[getattr(st, 'optimizer', 'adam')]
+
+
+def _written_under(st, d):
+    """the optimiser whose slot keys the checkpoint `d` holds for the first trainable variable of store `st` (None: no slots at all)."""
+    nm = next((n for n, _s, t in st.specs if t), None)
+    if nm is not None:
+        for kind, slots in SLOT_KEYS.items():
+            if nm + slots[0][0] in d:
+                return kind
+    return None
 
 
 def _eastern_now():
@@ -44,8 +66,8 @@ def state_dict(stores, rng=None, epoch=0):
         for nm, _shape, trainable in st.specs:
             out[nm] = st.get(nm)
             if trainable:
-                out[nm + ADAM_M] = st.get(nm, 'm')
-                out[nm + ADAM_V] = st.get(nm, 'v')
+                for suffix, which in _slots(st):
+                    out[nm + suffix] = st.get(nm, which)
                 if st.ema is not None:
                     out[nm + EMA] = st.get(nm, 'ema')
         out['tg/adam_step/' + net] = st.step.detach().cpu().numpy().astype(np.int64)
@@ -59,14 +81,22 @@ def load_state_dict(stores, d, rng=None, strict=True, keep_seed=False):
     """keep_seed: restore only the RNG's step counter (data-parallel resume: the file holds rank 0's seed)."""
     import torch
     missing = []
+    for net, st in stores.items():                   # before anything is copied: another optimiser's slots mean something else, and a
+        now, was = getattr(st, 'optimizer', 'adam'), _written_under(st, d)        # zero-filled rms would silently step by lr*g/1e-5
+        if was is not None and was != now:
+            raise KeyError("checkpoint holds the %s slots of network %r, which now trains with %s: restore it under config.OPTIMIZER %r "
+                           "for that network" % (was, net, now, was))
     for net, st in stores.items():
+        now = getattr(st, 'optimizer', 'adam')
         for nm, _shape, trainable in st.specs:
-            keys = [(nm, None)] + ([(nm + ADAM_M, 'm'), (nm + ADAM_V, 'v')] if trainable else [])
+            keys = [(nm, None)] + ([(nm + suffix, which) for suffix, which in _slots(st)] if trainable else [])
             if trainable and st.ema is not None:
                 keys.append((nm + EMA, 'ema'))
             for key, which in keys:
                 if key not in d:
                     missing.append(key)
+                    if which in ('m', 'v') and now != 'adam':    # (strict=False) a slot the file does not supply starts where the optimiser
+                        st._slice(getattr(st, which), nm).fill_(st.slot_init[which])     # starts it: RMSProp's rms at 1, never at 0
                     continue
                 a = np.ascontiguousarray(d[key], np.float32).reshape(-1)
                 dst = st.value(nm) if which is None else st._slice(getattr(st, which), nm)

@@ -61,6 +61,29 @@ def check_loss(config):
     return loss
 
 
+OPTIMIZERS = ('adam', 'rmsprop', 'momentum')
+
+
+def check_optimizer(config):
+    """config.OPTIMIZER ('adam' default | 'rmsprop' | 'momentum', or a 3-tuple of them for the (D, G, C) networks) -> the
+    normalised triple (d, g, c).  Needs no device.  ValueError for an unknown name, a tuple that does not have three entries, or any
+    other type."""
+    opt = getattr(config, 'OPTIMIZER', 'adam')
+    names = ', '.join(repr(v) for v in OPTIMIZERS)
+    if isinstance(opt, str):
+        triple = (opt,) * 3
+    elif isinstance(opt, (tuple, list)):
+        if len(opt) != 3:
+            raise ValueError("OPTIMIZER as a tuple names the optimisers of (D, G, C): three of %s, got %d entries: %r" % (names, len(opt), opt))
+        triple = tuple(opt)
+    else:
+        raise ValueError("OPTIMIZER must be one of %s or a 3-tuple (D, G, C) of them, got %r" % (names, opt))
+    for v in triple:
+        if not isinstance(v, str) or v not in OPTIMIZERS:
+            raise ValueError("OPTIMIZER must be one of %s or a 3-tuple (D, G, C) of them, got %r" % (names, opt))
+    return triple
+
+
 NUM_CLASSES_RANGE = (2, 1024)
 
 
@@ -119,6 +142,7 @@ class Train(Train_base):
         cx.act_dtype = check_act_dtype(config)
         check_num_classes(config)
         self.loss_kind = check_loss(config)          # 'GAN' | 'WGAN_GP': the loss heads of the three solver runs
+        self.optimizer_kinds = check_optimizer(config)     # (D, G, C), each 'adam' | 'rmsprop' | 'momentum' 
         self._gp_w = self._gp_grad = None            # WGAN-GP: the D-update's weighted penalty and its parameter gradient (device)
         cx.bf16_act_layers = set()
         # device-resident hyper-parameters (the reference's lr_ph / cla_lr_ph / lambda placeholders, :30-31,416-420)
@@ -163,10 +187,13 @@ class Train(Train_base):
         self.x_u_c_ph = ph('x_u_c', c.BATCH_SIZE_U_C, dims)
         self.model = Model(c)
         st = cx.stores
-        # three Adam optimisers (:85-87): G and D share lr_ph / config.BETA1, C uses cla_lr_ph / 0.5
-        self.d_optimizer = self._Adam_optimizer(self.hyper[0:1], c.BETA1)
-        self.g_optimizer = self._Adam_optimizer(self.hyper[0:1], c.BETA1)
-        self.c_optimizer = self._Adam_optimizer(self.hyper[1:2], 0.5)
+        # three optimisers, Adam unless config.OPTIMIZER says otherwise (:85-87): G and D share lr_ph / config.BETA1, C uses cla_lr_ph / 0.5
+        kd, kg, kc = self.optimizer_kinds
+        self.d_optimizer = self._make_optimizer(kd, self.hyper[0:1], c.BETA1)
+        self.g_optimizer = self._make_optimizer(kg, self.hyper[0:1], c.BETA1)
+        self.c_optimizer = self._make_optimizer(kc, self.hyper[1:2], 0.5)
+        for opt, net in ((self.d_optimizer, 'discriminator'), (self.g_optimizer, 'good_generator'), (self.c_optimizer, 'classifier')):
+            opt.bind(st[net])                    # the store's slots start where this optimiser's do (RMSProp: rms = 1), now and when they grow
         self.set_hyper(c.LEARNING_RATE, getattr(c, 'CLA_LEARNINIG_RATE', c.LEARNING_RATE), 0.0, 0.0)
         if tgdist.active():                      # identical initial weights on every replica
             for s in st.values():
@@ -176,6 +203,15 @@ class Train(Train_base):
         PH = [self.z_g_ph, self.y_g_ph, self.x_l_c_ph, self.y_l_c_ph, self.x_l_d_ph, self.y_l_d_ph, self.x_u_d_ph,
               self.x_u_c_ph, True, self.hyper[2:4]]
         return PH, self.model
+
+    def _make_optimizer(self, kind, lr_dev, beta1):
+        """one network's optimiser on the device learning rate `lr_dev`: Adam(beta1), RMSProp (decay 0.9, momentum 0, as the reference's
+        factory) or momentum SGD (config.MOMENTUM)."""
+        if kind == 'adam':
+            return self._Adam_optimizer(lr_dev, beta1)
+        if kind == 'rmsprop':
+            return self._RMSProp_optimizer(lr_dev)
+        return self._SGD_w_Momentum_optimizer(lr_dev, float(getattr(self.config, 'MOMENTUM', 0.9)))
 
     def set_hyper(self, lr=None, cla_lr=None, lambda_1=None, lambda_2=None):
         vals = self.hyper.detach().cpu().numpy()

@@ -6,7 +6,8 @@ single-launch kernels (tg_d_loss_f32 / tg_g_loss_f32 / tg_c_loss_f32) that also 
 logits' gradient buffers.  The helper methods it is written with in the reference — `_entropy`, `_balance_entropy` (:43-57),
 `_softmax_cross_entropy_loss_w_logits`, `_sigmoid_cross_entopy_w_logits` (:75-84), `_accuracy_metric` (:107) — keep their names and
 argument order as stand-alone single-launch heads.  `_Adam_optimizer` (:91-97) returns the TF-form Adam configuration applied by
-tg_adam_f32 over a network's flat buffers; `_train_op` applies it.
+tg_adam_f32 over a network's flat buffers; `_SGD_w_Momentum_optimizer` (:86-89) and `_RMSProp_optimizer` (:99-105) return the other two
+(tg_momentum_f32, tg_rmsprop_f32; config.OPTIMIZER); `_train_op` applies whichever it is handed.
 
 Eager-mode conventions: a loss value is a 1-element DEVICE tensor (float(t) synchronises); every head also leaves d(value)/d(logits)
 in `logits.grad` — written when the tensor has no gradient yet, ADDED when it has, so a loss summed from several heads accumulates
@@ -43,14 +44,59 @@ class StreamingAccuracy(object):
 
 class AdamOptimizer(object):
     """tf.train.AdamOptimizer(learning_rate, beta1, beta2=0.999, epsilon=1e-8); lr is a DEVICE scalar."""
+    kind = 'adam'
 
     def __init__(self, lr_dev, beta1, beta2=0.999, epsilon=1e-8, name='Adam_optimizer'):
         self.lr_dev, self.beta1, self.beta2, self.epsilon, self.name = lr_dev, beta1, beta2, epsilon, name
+
+    def bind(self, store):
+        """`store` is trained by this optimiser from here on: both slots start at zero (a fresh store's already do and are left alone)."""
+        store.optimizer = self.kind
+        for which, v in store.slot_init.items():
+            if v != 0.0:
+                store.init_slot(which, 0.0)
 
     def apply(self, store, grad_scale=1.0):
         cx = ctx()
         lib.call('tg_adam_f32', lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.m), lib.ptr(store.v), store.n_p,
                  lib.ptr(self.lr_dev), self.beta1, self.beta2, self.epsilon, lib.ptr(store.step), grad_scale, cx.stream)
+
+
+class MomentumOptimizer(object):
+    """tf.train.MomentumOptimizer(learning_rate, momentum), use_nesterov=False: accum = accum*momentum + g; p -= lr*accum [UNVERIFIED-TF].
+    lr is a DEVICE scalar; store.m is the `momentum` slot (zeros), store.v is not touched; no step count."""
+    kind = 'momentum'
+
+    def __init__(self, lr_dev, momentum, name='Momentum'):
+        self.lr_dev, self.momentum, self.name = lr_dev, momentum, name
+
+    def bind(self, store):
+        store.optimizer = self.kind
+        store.init_slot('m', 0.0)
+
+    def apply(self, store, grad_scale=1.0):
+        lib.call('tg_momentum_f32', lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.m), store.n_p, lib.ptr(self.lr_dev), self.momentum,
+                 grad_scale, ctx().stream)
+
+
+class RMSPropOptimizer(object):
+    """tf.train.RMSPropOptimizer(learning_rate, decay=0.9, momentum=0.0, epsilon=1e-10, centered=False): ms += (g^2 - ms)(1 - decay);
+    mom = mom*momentum + (g*lr)/sqrt(ms + epsilon); p -= mom [UNVERIFIED-TF].  lr is a DEVICE scalar; store.v is the `rms` slot, which
+    starts at ONE (bind() sees to it wherever the store's buffers come to exist), store.m the `momentum` slot (zeros, kept even with
+    momentum 0 as TensorFlow keeps it); no step count."""
+    kind = 'rmsprop'
+
+    def __init__(self, lr_dev, decay=0.9, momentum=0.0, epsilon=1e-10, name='RMSProp_optimizer'):
+        self.lr_dev, self.decay, self.momentum, self.epsilon, self.name = lr_dev, decay, momentum, epsilon, name
+
+    def bind(self, store):
+        store.optimizer = self.kind
+        store.init_slot('m', 0.0)
+        store.init_slot('v', 1.0)
+
+    def apply(self, store, grad_scale=1.0):
+        lib.call('tg_rmsprop_f32', lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.v), lib.ptr(store.m), store.n_p, lib.ptr(self.lr_dev),
+                 self.decay, self.momentum, self.epsilon, grad_scale, ctx().stream)
 
 
 class Train_base(object):
@@ -119,6 +165,14 @@ class Train_base(object):
 
     def _Adam_optimizer(self, lr, beta1, name='Adam_optimizer'):
         return AdamOptimizer(lr, beta1, name=name)
+
+    def _SGD_w_Momentum_optimizer(self, lr, momentum):
+        """train_base.py:86-89."""
+        return MomentumOptimizer(lr, momentum)
+
+    def _RMSProp_optimizer(self, lr, name='RMSProp_optimizer'):
+        """train_base.py:99-105 (decay 0.9)."""
+        return RMSPropOptimizer(lr, decay=0.9, name=name)
 
     def _train_op(self, optimizer, store, grad_scale=1.0):
         """optimizer.minimize(loss, var_list) (train_base.py:64-68): the gradients are already in store.g."""

@@ -62,6 +62,10 @@ class Config(object):
     LOSS = 'GAN'             # the loss of the three solver runs: 'GAN' (_loss_GAN, the reference's training loss) or 'WGAN_GP' (its
                              # _loss_WGAN_GP with the gradient penalty, wired into the step as DESIGN §9.1 decides; fp32 MFMA operands, no
                              # minibatch discrimination, BATCH_SIZE_L_D + BATCH_SIZE_U_D == BATCH_SIZE_G — Training/Train_goodGAN.check_loss)
+    OPTIMIZER = 'adam'       # the optimiser of the three networks: 'adam' (the reference's training choice), 'rmsprop' (its _RMSProp_optimizer:
+                             # decay 0.9, momentum 0, epsilon 1e-10) or 'momentum' (its _SGD_w_Momentum_optimizer with MOMENTUM), or a 3-tuple
+                             # (D, G, C) of them (--optimizer NAME sets all three; Training/Train_goodGAN.check_optimizer)
+    MOMENTUM = 0.9           # the momentum of OPTIMIZER 'momentum' only (RMSProp keeps the reference's momentum 0)
     MFMA_DTYPE = 'f32'       # 'bf16': conv/deconv/dense operands rounded to bf16 inside the MFMA kernels (fp32 accumulate)
     ACT_DTYPE = 'f32'        # 'bf16' (needs MFMA_DTYPE = 'bf16', else ValueError): the training-mode batch norms whose only reader is a
                              # bf16-operand 3x3 convolution store their output as bf16 (the SVHN classifier's c_h0_bn0/bn1, c_h1_bn0/bn1) —
@@ -78,7 +82,7 @@ class Config(object):
         for a in dir(self):
             if not a.startswith("__") and not callable(getattr(self, a)):
                 v = getattr(self, a)
-                print("{:30} {}".format(a, v if not isinstance(v, tuple) else '<arrays>'))
+                print("{:30} {}".format(a, '<arrays>' if isinstance(v, tuple) and not all(isinstance(e, str) for e in v) else v))
         print("\n")
 
     def config_str(self):
@@ -86,6 +90,6 @@ class Config(object):
         for a in dir(self):
             if not a.startswith("__") and not callable(getattr(self, a)):
                 v = getattr(self, a)
-                s += "{:30} {}".format(a, v if not isinstance(v, tuple) else '<arrays>')
+                s += "{:30} {}".format(a, '<arrays>' if isinstance(v, tuple) and not all(isinstance(e, str) for e in v) else v)
                 s += "\n"
         return s

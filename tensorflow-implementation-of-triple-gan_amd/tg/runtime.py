@@ -74,8 +74,10 @@ class Act(object):
 
 class ParamStore(object):
     """One network's variables in flat fp32 device buffers: `p` (trainable values), `g` (gradients),
-    `m`, `v` (Adam slots), `s` (non-trainable state: pop_mean, BN moving statistics).  Offsets are
-    32-float aligned; the padding stays zero (zero gradient => Adam leaves it at zero)."""
+    `m`, `v` (optimiser slots: Adam's moments; momentum SGD's accumulator in `m`; RMSProp's momentum in `m` and rms in `v`), `s`
+    (non-trainable state: pop_mean, BN moving statistics).  Offsets are 32-float aligned; the padding of p / g / m stays zero (zero
+    gradient => every optimiser leaves the value at zero).  A slot buffer starts at `slot_init[slot]` — 0 unless init_slot() says
+    otherwise (RMSProp's rms starts at 1) — wherever it comes to exist: at construction, in the reserve, and when extend() re-allocates."""
 
     def __init__(self, name, specs, device, capacity=0):
         """capacity: floats reserved per buffer beyond what `specs` need (stores that grow through Context.get_variable: variables
@@ -98,6 +100,8 @@ class ParamStore(object):
         # p / g / m / v / s are the LIVE prefixes of the reserved buffers (one Adam / all-reduce launch covers exactly n_p floats)
         self._full = {k: z(cap_s if k == 's' else cap_p) for k in ('p', 'g', 'm', 'v', 's')}
         self._narrow()
+        self.slot_init = {'m': 0.0, 'v': 0.0}
+        self.optimizer = 'adam'      # which optimiser's slots m / v hold (Training/train_base.py sets it; Training/Saver.py names the keys by it)
         self.step = torch.zeros(1, dtype=torch.int32, device=device)
         self.ema = None
         self.frozen = False          # set by tg.executor.StepExecutor: a hipGraph or a launch plan holds this store's device pointers, re-allocation is an error
@@ -146,6 +150,12 @@ class ParamStore(object):
     def to_dict(self, which='value'):
         return {nm: self.get(nm, which) for nm in self.names(None if which == 'value' else True)}
 
+    def init_slot(self, which, value):
+        """(re)initialise slot buffer `which` ('m' | 'v') to `value`, reserve included, and keep `value` for what extend() allocates."""
+        assert which in self.slot_init, which
+        self.slot_init[which] = float(value)
+        self._full[which].fill_(float(value))
+
     def enable_ema(self):
         self._full['ema'] = self._full['p'].clone()
         self.ema = self._full['ema'][:self.n_p]
@@ -175,7 +185,7 @@ class ParamStore(object):
                     raise lib.TgError("ParamStore %r: variable(s) %s created after a hipGraph captured this store's device pointers and "
                                       "beyond its reserve (%d > %d floats): create every variable before the first Train.train_iteration"
                                       % (self.name, [nm for nm, _, _ in specs], need, buf.numel()))
-                new = torch.zeros(max(need, 2 * buf.numel()), dtype=buf.dtype, device=buf.device)
+                new = torch.full((max(need, 2 * buf.numel()),), self.slot_init.get(k, 0.0), dtype=buf.dtype, device=buf.device)
                 new[:buf.numel()].copy_(buf)
                 self._full[k] = new
         self._narrow()

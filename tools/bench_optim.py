@@ -1,0 +1,64 @@
+#!/usr/bin/env python3
+"""The three optimiser launches alone (csrc/optim.hip; config.OPTIMIZER) on flat buffers the size of the CIFAR-10 networks'
+parameter stores: tg_adam_f32 (28 B / parameter), tg_momentum_f32 (20 B), tg_rmsprop_f32 (28 B).  The three are timed alternately,
+--rounds times each, in one process; prints per network and kernel the fastest and the median round in us per launch, and the
+algorithmic bytes over the fastest time in TB/s (HBM peak 8 TB/s)."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tensorflow-implementation-of-triple-gan_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from tg import geom, lib  # noqa: E402
+from Model.Good_GAN_cifar10 import Good_GAN_cifar10  # noqa: E402
+
+BYTES = {'adam': 28.0, 'momentum': 20.0, 'rmsprop': 28.0}
+
+
+def store_sizes():
+    """floats of each network's flat trainable buffer (ParamStore.n_p: every variable padded to 32 floats)."""
+    return {net: sum(geom.pad32(int(np.prod(shape))) for _n, shape, trainable, _i in specs if trainable)
+            for net, specs in Good_GAN_cifar10.param_specs().items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--iters', type=int, default=2000, help='launches per timed window')
+    args = ap.parse_args()
+    lib.load()
+    st = lib.cur_stream()
+    lr = torch.full((1,), 3e-4, device='cuda')
+    step = torch.zeros(1, dtype=torch.int32, device='cuda')
+    for net, n in store_sizes().items():
+        p, g = torch.randn(n, device='cuda') * 0.05, torch.randn(n, device='cuda') * 1e-2
+        m, v = torch.zeros(n, device='cuda'), torch.ones(n, device='cuda')
+        P = lib.ptr
+        calls = {'adam': lambda: lib.call('tg_adam_f32', P(p), P(g), P(m), P(v), n, P(lr), 0.5, 0.999, 1e-8, P(step), 1.0, st),
+                 'momentum': lambda: lib.call('tg_momentum_f32', P(p), P(g), P(m), n, P(lr), 0.9, 1.0, st),
+                 'rmsprop': lambda: lib.call('tg_rmsprop_f32', P(p), P(g), P(v), P(m), n, P(lr), 0.9, 0.0, 1e-10, 1.0, st)}
+        times = {k: [] for k in calls}
+        for fn in calls.values():
+            for _ in range(50):
+                fn()
+        for _ in range(args.rounds):
+            for k, fn in calls.items():
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(args.iters):
+                    fn()
+                b.record()
+                torch.cuda.synchronize()
+                times[k].append(a.elapsed_time(b) / args.iters * 1e3)
+        for k, t in times.items():
+            best = min(t)
+            print("%-14s %8d floats  %-8s fastest %7.2f us  median %7.2f us  %5.2f TB/s algorithmic (%.0f B/parameter)%s"
+                  % (net, n, k, best, float(np.median(t)), BYTES[k] * n / best / 1e6, BYTES[k],
+                     "  [with its step-count launch]" if k == 'adam' else ""), flush=True)
+
+
+if __name__ == "__main__":
+    main()
