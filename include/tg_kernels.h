@@ -635,6 +635,26 @@ int tg_momentum_f32(float* p, const float* g, float* accum, int64_t n, const flo
  * No step count.  28 B / parameter. */
 int tg_rmsprop_f32(float* p, const float* g, float* rms, float* mom, int64_t n, const float* lr_dev, float decay, float momentum, float eps,
                    float grad_scale, void* stream);
+/* tf.clip_by_global_norm over a flat gradient buffer (config.CLIP_NORM; the hook Training/train_base.py:70-73 leaves open):
+ *   out2[0] = norm   = grad_scale * sqrt(sum_i g[i]^2)      sum and root in fp64, rounded to fp32 once
+ *   out2[1] = factor = clip * min(1/norm, 1/clip)           in fp64 from the fp64 norm, rounded to fp32 once: exactly 1.0f when norm <= clip;
+ *                                                           NaN when the norm is not finite (TensorFlow poisons every gradient then)
+ * g: n floats, 16-byte aligned (not written); clip_dev: DEVICE scalar, read at launch; out2: two DEVICE floats; workspace: caller-owned
+ * scratch of at least tg_grad_norm_workspace_bytes(n) bytes (a host query; < 0 for n <= 0), 16-byte aligned, needs no initialisation and
+ * nothing beyond that size is written.  Two launches (per-workgroup fp64 partial sums, then one workgroup that adds them in index order);
+ * the grid depends on n alone and no atomics are used, so out2 is bit-identical from run to run, on any stream.  4 B / parameter read. */
+int64_t tg_grad_norm_workspace_bytes(int64_t n);
+int tg_grad_norm_clip_f32(const float* g, int64_t n, float grad_scale, const float* clip_dev, float* out2, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+/* tg_adam_f32 / tg_momentum_f32 / tg_rmsprop_f32 on the clipped gradient g_used = (g * grad_scale) * factor_dev[0] (two fp32 roundings, in
+ * this order; factor_dev: DEVICE scalar, out2 + 1 of tg_grad_norm_clip_f32) — the same kernel bodies, so with a factor of 1.0f the results
+ * are those of the unclipped entry points bit for bit. */
+int tg_adam_clip_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2, float eps,
+                     int* step_dev, float grad_scale, const float* factor_dev, void* stream);
+int tg_momentum_clip_f32(float* p, const float* g, float* accum, int64_t n, const float* lr_dev, float momentum, float grad_scale,
+                         const float* factor_dev, void* stream);
+int tg_rmsprop_clip_f32(float* p, const float* g, float* rms, float* mom, int64_t n, const float* lr_dev, float decay, float momentum, float eps,
+                        float grad_scale, const float* factor_dev, void* stream);
 /* shadow -= (1-decay)*(shadow - p) (tf.train.ExponentialMovingAverage, Training/Train_goodGAN.py:101-103). */
 int tg_ema_f32(float* shadow, const float* p, int64_t n, float decay, void* stream);
 

@@ -84,6 +84,30 @@ def check_optimizer(config):
     return triple
 
 
+def check_clip_norm(config):
+    """config.CLIP_NORM (None default | a positive float | a 3-tuple for the (D, G, C) networks of positive floats or None)
+    -> the normalised triple (d, g, c) of floats / None.  Needs no device.  ValueError for zero, a negative number, NaN or infinity, a
+    tuple that does not have three entries, and anything that is not a number."""
+    clip = getattr(config, 'CLIP_NORM', None)
+
+    def one(v):
+        if v is None:
+            return None
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (0.0 < float(v) < float('inf')):
+            raise ValueError("CLIP_NORM must be None, a positive finite number or a 3-tuple (D, G, C) of them, got %r" % (clip,))
+        return float(v)
+
+    if isinstance(clip, (tuple, list)):
+        if len(clip) != 3:
+            raise ValueError("CLIP_NORM as a tuple holds the thresholds of (D, G, C): three positive numbers or None, got %d entries: %r"
+                             % (len(clip), clip))
+        return tuple(one(v) for v in clip)
+    return (one(clip),) * 3
+
+
+NETS = ('discriminator', 'good_generator', 'classifier')      # the order of every (D, G, C) triple
+
+
 NUM_CLASSES_RANGE = (2, 1024)
 
 
@@ -143,6 +167,9 @@ class Train(Train_base):
         check_num_classes(config)
         self.loss_kind = check_loss(config)          # 'GAN' | 'WGAN_GP': the loss heads of the three solver runs
         self.optimizer_kinds = check_optimizer(config)     # (D, G, C), each 'adam' | 'rmsprop' | 'momentum' 
+        self.clip_norms = check_clip_norm(config)          # (D, G, C), each a threshold or None: clip_by_global_norm
+        self.clip_dev = None                         # with a clip: per network [threshold, 0, norm, factor] on the device
+        self._clip_views = {}                        # network -> (threshold, {norm, factor}) views of it (Train_base._clip_state)
         self._gp_w = self._gp_grad = None            # WGAN-GP: the D-update's weighted penalty and its parameter gradient (device)
         cx.bf16_act_layers = set()
         # device-resident hyper-parameters (the reference's lr_ph / cla_lr_ph / lambda placeholders, :30-31,416-420)
@@ -195,6 +222,15 @@ class Train(Train_base):
         for opt, net in ((self.d_optimizer, 'discriminator'), (self.g_optimizer, 'good_generator'), (self.c_optimizer, 'classifier')):
             opt.bind(st[net])                    # the store's slots start where this optimiser's do (RMSProp: rms = 1), now and when they grow
         self.set_hyper(c.LEARNING_RATE, getattr(c, 'CLA_LEARNINIG_RATE', c.LEARNING_RATE), 0.0, 0.0)
+        if any(v is not None for v in self.clip_norms):
+            # thresholds and results live on the device, and the norm's workspace exists before anything records: plans and graphs hold both
+            from Training.train_base import clip_workspace_floats
+            self.clip_dev = torch.zeros(4 * len(NETS), dtype=torch.float32, device=cx.device)
+            for k, (net, v) in enumerate(zip(NETS, self.clip_norms)):
+                if v is not None:
+                    self._clip_views[net] = (self.clip_dev[4 * k:4 * k + 1], self.clip_dev[4 * k + 2:4 * k + 4])
+                    cx.ws('clip:ws:' + net, clip_workspace_floats(st[net]))
+            self.set_clip_norm(*self.clip_norms)
         if tgdist.active():                      # identical initial weights on every replica
             for s in st.values():
                 tgdist.broadcast_(s.p)
@@ -219,6 +255,43 @@ class Train(Train_base):
             if v is not None:
                 vals[i] = v
         self.hyper.copy_(torch.from_numpy(vals))
+
+    def set_clip_norm(self, d=None, g=None, c=None):
+        """new thresholds for the networks given (None keeps one), written to the device like set_hyper: a replayed plan or graph follows.
+        Only a network clipped at build time (config.CLIP_NORM) can be changed — the others' launches hold no clip."""
+        if self.clip_dev is None:
+            if (d, g, c) == (None, None, None):
+                return
+            raise lib.TgError("set_clip_norm: this trainer was built with CLIP_NORM = None; a clip is part of the recorded launches")
+        new = []
+        for net, v in zip(NETS, (d, g, c)):
+            if v is None:
+                continue
+            if net not in self._clip_views:
+                raise lib.TgError("set_clip_norm: network %r was built unclipped (CLIP_NORM = %r)" % (net, self.clip_norms))
+            if not 0.0 < float(v) < float('inf'):
+                raise lib.TgError("set_clip_norm: the threshold of %r must be a positive finite number, got %r" % (net, v))
+            new.append((net, float(v)))
+        for net, v in new:                               # only the threshold elements: {norm, factor} beside them are the kernels'
+            self._clip_views[net][0].fill_(v)
+
+    def grad_norms(self):
+        """{'d': (norm, factor), 'g': ..., 'c': ...} of the last iteration's gradients as floats — ONE device->host copy; None for an
+        unclipped network (and (0, 0) for one whose solver has not run yet).  A NaN factor is a non-finite norm."""
+        if self.clip_dev is None:
+            return dict(d=None, g=None, c=None)
+        vals = self.clip_dev.detach().cpu().numpy()
+        return {key: ((float(vals[4 * k + 2]), float(vals[4 * k + 3])) if net in self._clip_views else None)
+                for k, (key, net) in enumerate(zip('dgc', NETS))}
+
+    def _apply(self, optimizer, net, grad_scale):
+        """the optimiser step of `net`: through _train_op_w_grads with the device threshold when the network is clipped, else _train_op."""
+        st = self.cx.stores[net]
+        views = self._clip_views.get(net)
+        if views is None:
+            self._train_op(optimizer, st, grad_scale)
+        else:
+            self._train_op_w_grads(optimizer, st, grad_scale, clip=views[0])
 
     # ------------------------------------------------------------------ the three solver runs
     def _d_forward_backward(self, split=False):
@@ -337,7 +410,7 @@ class Train(Train_base):
 
     def _c_apply(self):
         st = self.cx.stores['classifier']
-        self._train_op(self.c_optimizer, st, 1.0 / self.world)
+        self._apply(self.c_optimizer, 'classifier', 1.0 / self.world)
         # ema.apply(c_vars) under control-dependency on the C step (:101-103)
         lib.call('tg_ema_f32', lib.ptr(st.ema), lib.ptr(st.p), st.n_p, 0.9999, self.cx.stream)
         self.cx.rng.advance(self.cx)
@@ -371,16 +444,15 @@ class Train(Train_base):
         one hipGraph.  With replicas every backward pass is cut at the model's bucket boundaries: a finished bucket is all-reduced on
         the exchange stream while the next segment (the rest of the backward pass) runs; the optimiser step of a network opens the
         next solver run's first segment and waits for that network's buckets."""
-        st = self.cx.stores
         w = 1.0 / self.world
         if pre_train:                                          # :182-226: pre-training runs c_solver only
             phases = [self._phase_segments('C', 'classifier', self._c_forward_backward)]
         else:
             phases = [self._phase_segments('D', 'discriminator', self._d_forward_backward),
                       self._phase_segments('G', 'good_generator', self._g_forward_backward,
-                                           lambda: self._train_op(self.d_optimizer, st['discriminator'], w)),
+                                           lambda: self._apply(self.d_optimizer, 'discriminator', w)),
                       self._phase_segments('C', 'classifier', self._c_forward_backward,
-                                           lambda: self._train_op(self.g_optimizer, st['good_generator'], w))]
+                                           lambda: self._apply(self.g_optimizer, 'good_generator', w))]
         out = []
         for k, segs in enumerate(phases):
             for j, (fn, grads) in enumerate(segs):
@@ -580,6 +652,10 @@ class Train(Train_base):
                 self.zca_source = 'broadcast'
         c.ZCA = (mean, mat)
 
+    def _norm_tags(self):
+        """the train summary's extra scalars: '<d|g|c>_grad_norm' for every clipped network (none without a clip)."""
+        return tuple(k + '_grad_norm' for k, net in zip('dgc', NETS) if net in self._clip_views)
+
     # ------------------------------------------------------------------ the reference's entry point
     def train(self, Dataset, Model, sample_y):
         """:43-381.  Dataset(data_dir, config, num_label, subset, use_augmentation).inputpipline_train_val(val)
@@ -606,7 +682,7 @@ class Train(Train_base):
             elif self.rank == 0:
                 saver.set_save_path(comments=self.comments)                            # :150
         if self.summary_train is not None and getattr(c, 'SUMMARY_SCALAR', True):      # :105-118
-            self.summary_train.add_summary({'scalar': dict.fromkeys(('g_loss', 'd_loss', 'c_loss', 'train_accuracy'))})
+            self.summary_train.add_summary({'scalar': dict.fromkeys(('g_loss', 'd_loss', 'c_loss', 'train_accuracy') + self._norm_tags())})
             self.summary_val.add_summary({'scalar': dict.fromkeys(('val_accuracy',))})
         history = []
         iters = int(c.TRAIN_SIZE / c.BATCH_SIZE)
@@ -633,7 +709,9 @@ class Train(Train_base):
                        images_per_sec=iters * c.BATCH_SIZE * self.world / dt)
             history.append(rec)
             if self.summary_train is not None:                                         # :293,346
-                self.summary_train.write(dict(g_loss=g_loss, d_loss=d_loss, c_loss=c_loss), epoch + start_epoch)
+                norms = self.grad_norms() if self._norm_tags() else {}                  # the last iteration's, clipped networks only
+                self.summary_train.write(dict(dict(g_loss=g_loss, d_loss=d_loss, c_loss=c_loss),
+                                              **{k + '_grad_norm': v[0] for k, v in norms.items() if v is not None}), epoch + start_epoch)
                 self.summary_val.write(dict(val_accuracy=acc), epoch + start_epoch)
             if saver is not None and self.rank == 0 and epoch % c.SAVE_PER_EPOCH == 0:  # :366-369
                 saver.save(self, 'model_' + str(epoch + start_epoch).zfill(4) + '.ckpt')

@@ -7,7 +7,9 @@ logits' gradient buffers.  The helper methods it is written with in the referenc
 `_softmax_cross_entropy_loss_w_logits`, `_sigmoid_cross_entopy_w_logits` (:75-84), `_accuracy_metric` (:107) — keep their names and
 argument order as stand-alone single-launch heads.  `_Adam_optimizer` (:91-97) returns the TF-form Adam configuration applied by
 tg_adam_f32 over a network's flat buffers; `_SGD_w_Momentum_optimizer` (:86-89) and `_RMSProp_optimizer` (:99-105) return the other two
-(tg_momentum_f32, tg_rmsprop_f32; config.OPTIMIZER); `_train_op` applies whichever it is handed.
+(tg_momentum_f32, tg_rmsprop_f32; config.OPTIMIZER); `_train_op` applies whichever it is handed, and `_train_op_w_grads`
+(:70-73) applies it and hands back the gradients — with `clip`, clipped by their global norm first (tg_grad_norm_clip_f32 and the
+tg_*_clip_f32 optimisers; config.CLIP_NORM).
 
 Eager-mode conventions: a loss value is a 1-element DEVICE tensor (float(t) synchronises); every head also leaves d(value)/d(logits)
 in `logits.grad` — written when the tensor has no gradient yet, ADDED when it has, so a loss summed from several heads accumulates
@@ -56,10 +58,15 @@ class AdamOptimizer(object):
             if v != 0.0:
                 store.init_slot(which, 0.0)
 
-    def apply(self, store, grad_scale=1.0):
+    def apply(self, store, grad_scale=1.0, factor_dev=None):
+        """factor_dev: DEVICE scalar the scaled gradient is multiplied by (the clip factor of tg_grad_norm_clip_f32); None = unclipped."""
         cx = ctx()
-        lib.call('tg_adam_f32', lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.m), lib.ptr(store.v), store.n_p,
-                 lib.ptr(self.lr_dev), self.beta1, self.beta2, self.epsilon, lib.ptr(store.step), grad_scale, cx.stream)
+        args = (lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.m), lib.ptr(store.v), store.n_p,
+                lib.ptr(self.lr_dev), self.beta1, self.beta2, self.epsilon, lib.ptr(store.step), grad_scale)
+        if factor_dev is None:
+            lib.call('tg_adam_f32', *args, cx.stream)
+        else:
+            lib.call('tg_adam_clip_f32', *args, lib.ptr(factor_dev), cx.stream)
 
 
 class MomentumOptimizer(object):
@@ -74,9 +81,12 @@ class MomentumOptimizer(object):
         store.optimizer = self.kind
         store.init_slot('m', 0.0)
 
-    def apply(self, store, grad_scale=1.0):
-        lib.call('tg_momentum_f32', lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.m), store.n_p, lib.ptr(self.lr_dev), self.momentum,
-                 grad_scale, ctx().stream)
+    def apply(self, store, grad_scale=1.0, factor_dev=None):
+        args = (lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.m), store.n_p, lib.ptr(self.lr_dev), self.momentum, grad_scale)
+        if factor_dev is None:
+            lib.call('tg_momentum_f32', *args, ctx().stream)
+        else:
+            lib.call('tg_momentum_clip_f32', *args, lib.ptr(factor_dev), ctx().stream)
 
 
 class RMSPropOptimizer(object):
@@ -94,9 +104,50 @@ class RMSPropOptimizer(object):
         store.init_slot('m', 0.0)
         store.init_slot('v', 1.0)
 
-    def apply(self, store, grad_scale=1.0):
-        lib.call('tg_rmsprop_f32', lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.v), lib.ptr(store.m), store.n_p, lib.ptr(self.lr_dev),
-                 self.decay, self.momentum, self.epsilon, grad_scale, ctx().stream)
+    def apply(self, store, grad_scale=1.0, factor_dev=None):
+        args = (lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.v), lib.ptr(store.m), store.n_p, lib.ptr(self.lr_dev),
+                self.decay, self.momentum, self.epsilon, grad_scale)
+        if factor_dev is None:
+            lib.call('tg_rmsprop_f32', *args, ctx().stream)
+        else:
+            lib.call('tg_rmsprop_clip_f32', *args, lib.ptr(factor_dev), ctx().stream)
+
+
+class GradViews(object):
+    """the `grads` of _train_op_w_grads: {variable name: that variable's slice of store.g}, sliced when asked for (an iteration that does
+    not look at them pays nothing)."""
+
+    def __init__(self, store):
+        self.store = store
+
+    def keys(self):
+        return self.store.names(True)
+
+    def __iter__(self):
+        return iter(self.keys())
+
+    def __len__(self):
+        return len(self.keys())
+
+    def __contains__(self, nm):
+        return nm in self.store.index and self.store.index[nm][0] == 'p'
+
+    def __getitem__(self, nm):
+        if nm not in self:
+            raise KeyError(nm)
+        return self.store.grad(nm)
+
+    def items(self):
+        return [(nm, self[nm]) for nm in self.keys()]
+
+    def values(self):
+        return [self[nm] for nm in self.keys()]
+
+
+def clip_workspace_floats(store):
+    """floats of tg_grad_norm_clip_f32's workspace for `store`, sized for everything the store has reserved: a store that grows within its
+    reserve never regrows the workspace a recorded plan or graph holds."""
+    return (lib.call('tg_grad_norm_workspace_bytes', max(store._full['g'].numel(), 1)) + 3) // 4
 
 
 class Train_base(object):
@@ -178,6 +229,40 @@ class Train_base(object):
         """optimizer.minimize(loss, var_list) (train_base.py:64-68): the gradients are already in store.g."""
         ctx().prep_invalidate(store)
         optimizer.apply(store, grad_scale)
+
+    def _clip_state(self, store):
+        """(threshold, {norm, factor}) device tensors of `store`'s network: the trainer's (Train._build_train_graph lays all three networks'
+        out in one buffer), else a buffer of the context's under the network's name."""
+        views = getattr(self, '_clip_views', {}).get(store.name)
+        if views is not None:
+            return views
+        t = ctx().ws('clip:state:' + store.name, 4)
+        return t[0:1], t[2:4]
+
+    def _train_op_w_grads(self, optimizer, store, grad_scale=1.0, clip=None):
+        """train_base.py:70-73: compute_gradients / apply_gradients -> grads ({variable name: gradient view}; the gradients are already in
+        store.g).  clip: where a TF1 user writes tf.clip_by_global_norm(grads, clip) between the two — None applies the gradients as they
+        are; a positive number, or a 1-element DEVICE tensor holding it (read at launch, so a replayed plan or graph follows it), clips
+        the network's gradients by their global norm [UNVERIFIED-TF]: norm = grad_scale*sqrt(sum g^2), factor = clip*min(1/norm, 1/clip),
+        g_used = (g*grad_scale)*factor.  {norm, factor} stay on the device (_clip_state(store)[1]); store.g is not written."""
+        cx = ctx()
+        cx.prep_invalidate(store)
+        if clip is None:
+            optimizer.apply(store, grad_scale)
+            return GradViews(store)
+        thr, out2 = self._clip_state(store)
+        if isinstance(clip, torch.Tensor):
+            thr = clip
+        else:
+            if not 0.0 < float(clip) < float('inf'):
+                raise lib.TgError("_train_op_w_grads: clip must be a positive finite number or a device scalar, got %r" % (clip,))
+            thr.fill_(float(clip))
+        need = lib.call('tg_grad_norm_workspace_bytes', store.n_p)
+        wsp = cx.ws('clip:ws:' + store.name, max(clip_workspace_floats(store), (need + 3) // 4))
+        lib.call('tg_grad_norm_clip_f32', lib.ptr(store.g), store.n_p, grad_scale, lib.ptr(thr), lib.ptr(out2), lib.ptr(wsp), wsp.numel() * 4,
+                 cx.stream)
+        optimizer.apply(store, grad_scale, out2[1:2])
+        return GradViews(store)
 
     # ---- _loss_GAN split by solver (each writes value + d/dlogits) --------------------------------
     def _d_loss(self, d_logits, n_real, n_fake, n_unl, loss_out):

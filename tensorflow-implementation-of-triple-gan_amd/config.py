@@ -66,6 +66,10 @@ class Config(object):
                              # decay 0.9, momentum 0, epsilon 1e-10) or 'momentum' (its _SGD_w_Momentum_optimizer with MOMENTUM), or a 3-tuple
                              # (D, G, C) of them (--optimizer NAME sets all three; Training/Train_goodGAN.check_optimizer)
     MOMENTUM = 0.9           # the momentum of OPTIMIZER 'momentum' only (RMSProp keeps the reference's momentum 0)
+    CLIP_NORM = None         # clip each network's gradients by their global norm before the optimiser step (tf.clip_by_global_norm where
+                             # the reference's _train_op_w_grads hands out the gradients): None (off — the step is exactly the unclipped one),
+                             # a positive float for all three networks (--clip-norm X), or a 3-tuple (D, G, C) of positive floats / None
+                             # (Training/Train_goodGAN.check_clip_norm)
     MFMA_DTYPE = 'f32'       # 'bf16': conv/deconv/dense operands rounded to bf16 inside the MFMA kernels (fp32 accumulate)
     ACT_DTYPE = 'f32'        # 'bf16' (needs MFMA_DTYPE = 'bf16', else ValueError): the training-mode batch norms whose only reader is a
                              # bf16-operand 3x3 convolution store their output as bf16 (the SVHN classifier's c_h0_bn0/bn1, c_h1_bn0/bn1) —

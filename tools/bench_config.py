@@ -14,6 +14,8 @@
                                                      D-update); the default --loss gan is the step above, with exactly the output it always had
     --optimizer rmsprop|momentum                     any configuration trained with config.OPTIMIZER = NAME for all three networks (DESIGN §9.5);
                                                      the default --optimizer adam is the step above, with exactly the output it always had
+    --clip-norm X                                    any configuration with config.CLIP_NORM = X for all three networks: three
+                                                     global-norm launches and the clipped optimisers; without it the step and the output above
 
 Runs the D+G+C step on synthetic images already resident in HBM, then one instrumented eager iteration with
 per-kernel-class HIP-event timing.  Prints ONE JSON line: ms/step, images/sec and, per kernel class, launches,
@@ -50,7 +52,7 @@ SHAPES = {   # name: (data, H, C, B_G, L_C, U_C, L_D, U_D, mfma dtype, lambda_1,
 }
 
 
-def make_config(name='stress64', loss='gan', num_classes=None, optimizer='adam'):
+def make_config(name='stress64', loss='gan', num_classes=None, optimizer='adam', clip_norm=None):
     from config import Config
     data, hw, ch, bg, lc, uc, ld, ud, prec, lam, lr, clr = SHAPES[name]
 
@@ -82,6 +84,7 @@ def make_config(name='stress64', loss='gan', num_classes=None, optimizer='adam')
         ACT_DTYPE = 'bf16' if name.endswith('-act') else 'f32'
         LOSS = {'gan': 'GAN', 'wgan_gp': 'WGAN_GP'}[loss]
         OPTIMIZER = optimizer
+        CLIP_NORM = clip_norm
 
     return TempConfig()
 
@@ -93,6 +96,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--loss', choices=('gan', 'wgan_gp'), default='gan')
     ap.add_argument('--optimizer', choices=('adam', 'rmsprop', 'momentum'), default='adam', help='config.OPTIMIZER of all three networks')
+    ap.add_argument('--clip-norm', type=float, default=None, help='config.CLIP_NORM of all three networks (default: no clip)')
     ap.add_argument('--num-classes', type=int, default=None, help='config.NUM_CLASSES (default: 100 for cifar100, else 10)')
     args = ap.parse_args()
     import torch
@@ -105,7 +109,7 @@ def main():
     else:
         from Model.Good_GAN import Good_GAN as Model
 
-    cfg = make_config(args.config, args.loss, args.num_classes, args.optimizer)
+    cfg = make_config(args.config, args.loss, args.num_classes, args.optimizer, args.clip_norm)
     if args.config.startswith('cifar10'):
         q, _ = np.linalg.qr(np.random.default_rng(4321).standard_normal((3072, 3072)))      # SURVEY §8d synthetic whitening
         cfg.ZCA = (np.zeros(3072, np.float32), q.astype(np.float32))
@@ -185,7 +189,9 @@ def main():
     print(json.dumps({"workload": "%s: synthetic %dx%dx%d, B_G/L_C/U_C/L_D/U_D=%d/%d/%d/%d/%d, %s D+G+C step, MFMA operands %s" % (
                           args.config, cfg.IMAGE_HEIGHT, cfg.IMAGE_WIDTH, cfg.CHANNEL, cfg.BATCH_SIZE_G, cfg.BATCH_SIZE_L_C, cfg.BATCH_SIZE_U_C,
                           cfg.BATCH_SIZE_L_D, cfg.BATCH_SIZE_U_D, Model.__name__, cfg.MFMA_DTYPE) + (", WGAN-GP loss" if args.loss == 'wgan_gp' else "")
-                          + (", %d classes" % k if k != 10 else "") + (", optimizer %s" % args.optimizer if args.optimizer != 'adam' else ""),
+                          + (", %d classes" % k if k != 10 else "") + (", optimizer %s" % args.optimizer if args.optimizer != 'adam' else "")
+                          + (", clip norm %g" % args.clip_norm if args.clip_norm is not None else ""),
+                      **({"grad_norms_d_g_c": [[round(x, 6) for x in v] for v in tr.grad_norms().values()]} if args.clip_norm is not None else {}),
                       "act_dtype": cfg.ACT_DTYPE, "bf16_act_edges": tr.bf16_act_edges,
                       "ms_per_step": round(dt * 1e3, 3), "images_per_sec": round(cfg.BATCH_SIZE_G / dt, 1), "steps": args.steps, "hbm_gib_allocated": round(mem, 2),
                       "host_issue_ms_per_step": round(t_issue_free * 1e3, 3), "host_issue_ms_per_step_queue_full": round(t_issue * 1e3, 3),
