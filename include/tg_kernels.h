@@ -658,6 +658,32 @@ int tg_rmsprop_clip_f32(float* p, const float* g, float* rms, float* mom, int64_
 /* shadow -= (1-decay)*(shadow - p) (tf.train.ExponentialMovingAverage, Training/Train_goodGAN.py:101-103). */
 int tg_ema_f32(float* shadow, const float* p, int64_t n, float decay, void* stream);
 
+/* ---- summaries ------------------------------------------------------------------------------------ */
+/* tf.summary.histogram over a flat fp32 buffer (config.SUMMARY_HISTOGRAM; Training/Summary.py:54-57 of the reference): per segment, what
+ * tensorflow::histogram::Histogram holds after Add((double)x) for every element (restated in tests/summary_reference.py).
+ *   tg_tf_histogram_limits  HOST: writes TensorFlow's 1 551 bucket limits into limits_out (n must be 1551): v = 1e-12; while v < 1e20
+ *                     {push v; v *= 1.1} in IEEE double (774 values), then DBL_MAX; the table = the negated list reversed, 0.0, the list.
+ *                     The caller copies it to the device once; the kernel compares against it and never recomputes it.
+ *   tg_tf_histogram_f32     x: DEVICE buffer of n floats (not written).  segs: HOST array of nseg {element offset, count} pairs (int64);
+ *                     each must lie inside [0, n) (TG_ERR_INVALID otherwise); what lies between segments is never read.  limits_dev: DEVICE
+ *                     copy of the table.  Outputs (DEVICE, overwritten, not accumulated):
+ *                       counts[nseg][1551]  int64; counts[s][b] = #elements of segment s with upper_bound(limits, (double)x) - limits == b,
+ *                                           exact
+ *                       stats[nseg][8]      double {min, max, num, sum, sum_squares, #NaN, #Inf, 0}; min / max exact, sum / sum_squares
+ *                                           accumulated in fp64 from (double)x.  NaN and +-Inf elements are counted in [5] / [6] and enter
+ *                                           neither the buckets nor any other statistic.  An empty segment: {DBL_MAX, -DBL_MAX, 0, ...}.
+ *                     workspace: caller-owned scratch of at least tg_tf_histogram_workspace_bytes(segs, nseg) bytes (a host query; < 0 for
+ *                     a malformed table), 16-byte aligned, needs no initialisation and nothing beyond that size is written.  nseg = 0 is a
+ *                     no-op.  The launch sequence — one copy of the host-built (segment, chunk) map into the workspace, one memset, one
+ *                     workgroup per chunk of 16 384 elements, one workgroup per segment — depends on the segment table alone; counts are
+ *                     integer atomics, the fp64 sums are added in a fixed order without atomics: every output is bit-identical from run to
+ *                     run, on any stream.  The segment table is read before the call returns.  An eager launch: not for a stream that is
+ *                     being captured. */
+int tg_tf_histogram_limits(double* limits_out, int n);
+int64_t tg_tf_histogram_workspace_bytes(const int64_t* segs, int nseg);
+int tg_tf_histogram_f32(const float* x, int64_t n, const int64_t* segs, int nseg, const double* limits_dev, int64_t* counts, double* stats,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- RNG (Philox4x32-10; state = device {seed, step}) -------------------------------------------- */
 /* Element e of a draw is word e % 4 of the block with counter (lo32(e / 4), hi32(e / 4), stream_id, lo32(step)) and key (lo32(seed),
  * hi32(seed) ^ hi32(step)); a one-hot row r takes class (word 0 * k) >> 32 of the block with counter (r, 0, stream_id, lo32(step)).

@@ -182,6 +182,7 @@ class Train(Train_base):
         self.iteration = 0
         self._label_override = {}        # see label_override()
         self.zca_source = None           # config.ZCA = 'fit' resolved by train(): 'files' | 'fit' (rank 0) | 'broadcast' (other ranks)
+        self._hist_runs = {}             # network -> (store layout key, tg.summary.StoreHistograms): see histograms()
         self.summary_train = self.summary_val = None
         if getattr(config, 'SUMMARY', False) and log_dir and self.rank == 0:          # :37-41
             from Training.Summary import Summary
@@ -652,6 +653,51 @@ class Train(Train_base):
                 self.zca_source = 'broadcast'
         c.ZCA = (mean, mat)
 
+    HISTOGRAM_BUFFERS = {'value': 'p', 'grad': 'g', 'ema': 'ema'}
+
+    def histograms(self, which='value', nets=NETS):
+        """tf.summary.histogram of every trainable variable of the networks `nets`: {TF variable name (as Saver spells it): {min, max, num,
+        sum, sum_squares, limits, counts, nan, inf}} — TensorFlow's 1 551 bucket limits (shared array) and the count of every bucket,
+        uncompressed; nan / inf count the non-finite elements, which are in no bucket and no statistic.
+        which: 'value' (store.p), 'grad' (store.g: the gradient as the last iteration's optimiser READ it — summed over the replicas when
+        there are several, before the 1/world scale and before any clip factor; a network whose solver did not run keeps its last one) or
+        'ema' (the classifier's shadows; networks without one are skipped).
+        One tg_tf_histogram_f32 call and ONE device->host copy per network.  Launched eagerly on the launch stream, outside the replayed
+        step, and it only reads the stores: usable at any time, also while a launch plan or a hipGraph is held."""
+        from tg import summary as tgsum
+        if which not in self.HISTOGRAM_BUFFERS:
+            raise ValueError("histograms: which must be one of %s, got %r" % (', '.join(repr(k) for k in self.HISTOGRAM_BUFFERS), which))
+        if self.cx.capturing or lib._recorder is not None:
+            raise lib.TgError("histograms: called inside a hipGraph capture / launch-plan recording; it is an eager launch beside the step")
+        out = {}
+        for net in nets:
+            st = self.cx.stores[net]
+            buf = getattr(st, self.HISTOGRAM_BUFFERS[which])
+            if buf is None:
+                continue
+            names = st.names(True)
+            key = (len(st.specs), st.n_p)
+            run = self._hist_runs.get(net)
+            if run is None or run[0] != key:
+                run = self._hist_runs[net] = (key, tgsum.StoreHistograms([st.index[nm][1:3] for nm in names], self.cx.device))
+            counts, stats = run[1].run(buf, self.cx.stream)
+            out.update(tgsum.as_dicts(names, counts, stats))
+        return out
+
+    def _register_summaries(self, want_hist, want_img):
+        """the reference's image / histogram keys (Summary.py:37-40) on the train summary, beside the scalars it already holds: the
+        samples as 'generated', every trainable variable of D, G and C under its name and its gradient under 'gradients/<name>'."""
+        c, sm = self.config, self.summary_train
+        kinds = dict(scalar=dict.fromkeys(sm._tags)) if sm._tags else {}
+        if want_img:
+            kinds['image'] = {'generated': None}
+        if want_hist:
+            tags = [nm for net in NETS for nm in self.cx.stores[net].names(True)]
+            kinds['histogram'] = dict.fromkeys(tags + ['gradients/' + nm for nm in tags])
+        sm.add_summary(kinds)
+        if want_img:                                     # (add_summary registers images with the reference's default max_outputs of 2)
+            sm._image_outputs = sm._image_summary(kinds['image'], min(int(getattr(c, 'SUMMARY_IMAGE_MAX_OUTPUTS', 2)), int(c.SAMPLE_SIZE)))
+
     def _norm_tags(self):
         """the train summary's extra scalars: '<d|g|c>_grad_norm' for every clipped network (none without a clip)."""
         return tuple(k + '_grad_norm' for k, net in zip('dgc', NETS) if net in self._clip_views)
@@ -684,6 +730,14 @@ class Train(Train_base):
         if self.summary_train is not None and getattr(c, 'SUMMARY_SCALAR', True):      # :105-118
             self.summary_train.add_summary({'scalar': dict.fromkeys(('g_loss', 'd_loss', 'c_loss', 'train_accuracy') + self._norm_tags())})
             self.summary_val.add_summary({'scalar': dict.fromkeys(('val_accuracy',))})
+        want_hist = self.summary_train is not None and bool(getattr(c, 'SUMMARY_HISTOGRAM', False))
+        want_img = self.summary_train is not None and bool(getattr(c, 'SUMMARY_IMAGE', False))
+        registered = False
+        if sample_y is None and want_img:                                              # no labels handed in: the entry points' cyclic ones
+            sample_y = np.eye(c.NUM_CLASSES, dtype=np.float32)[np.arange(c.SAMPLE_SIZE) % c.NUM_CLASSES]
+            own_sample_y = True
+        else:
+            own_sample_y = False
         history = []
         iters = int(c.TRAIN_SIZE / c.BATCH_SIZE)
         for epoch in range(1, c.EPOCHS + 1):
@@ -708,20 +762,41 @@ class Train(Train_base):
             rec = dict(epoch=epoch + start_epoch, d_loss=d_loss, g_loss=g_loss, c_loss=c_loss, val_accuracy=acc,
                        images_per_sec=iters * c.BATCH_SIZE * self.world / dt)
             history.append(rec)
+            samples = None
             if self.summary_train is not None:                                         # :293,346
                 norms = self.grad_norms() if self._norm_tags() else {}                  # the last iteration's, clipped networks only
+                hists = imgs = None
+                if (want_hist or want_img) and not registered:                         # at the first tail: by now every variable exists
+                    self._register_summaries(want_hist, want_img)
+                    registered = True
+                if want_hist:                                                          # values, and store.g as the last optimiser step read it
+                    hists = self.histograms('value')
+                    hists.update(('gradients/' + nm, h) for nm, h in self.histograms('grad').items())
+                if want_img:                                                           # the epoch's samples (drawn here; the sample grid below reuses them)
+                    # The sampler's batch norms run in training mode (reference :176-202) and move their running statistics.  A run
+                    # without the flag samples only for the sample grid: when there is none, the statistics are put back, so the
+                    # summary leaves every store as it found it.
+                    grid = bool(c.SAMPLE_DIR) and not own_sample_y
+                    kept = None if grid else {net: st.s.clone() for net, st in self.cx.stores.items()}
+                    samples = self.sample(sample_z, sample_y)
+                    if kept is not None:
+                        for net, s_before in kept.items():
+                            self.cx.stores[net].s.copy_(s_before)
+                    imgs = {'generated': samples}
                 self.summary_train.write(dict(dict(g_loss=g_loss, d_loss=d_loss, c_loss=c_loss),
-                                              **{k + '_grad_norm': v[0] for k, v in norms.items() if v is not None}), epoch + start_epoch)
+                                              **{k + '_grad_norm': v[0] for k, v in norms.items() if v is not None}), epoch + start_epoch,
+                                         histograms=hists, images=imgs)
                 self.summary_val.write(dict(val_accuracy=acc), epoch + start_epoch)
             if saver is not None and self.rank == 0 and epoch % c.SAVE_PER_EPOCH == 0:  # :366-369
                 saver.save(self, 'model_' + str(epoch + start_epoch).zfill(4) + '.ckpt')
             if self.rank == 0:
                 print("epoch {epoch}: g_loss {g_loss:.3f} d_loss {d_loss:.3f} c_loss {c_loss:.3f} val_acc {val_accuracy:.4f} "
                       "{images_per_sec:.0f} img/s".format(**rec), flush=True)
-                if c.SAMPLE_DIR and sample_y is not None:
+                if c.SAMPLE_DIR and sample_y is not None and not own_sample_y:
                     from utils import save_images, image_manifold_size
                     os.makedirs(c.SAMPLE_DIR, exist_ok=True)
-                    samples = self.sample(sample_z, sample_y)
+                    if samples is None:
+                        samples = self.sample(sample_z, sample_y)
                     save_images(samples, image_manifold_size(samples.shape[0]),
                                 os.path.join(c.SAMPLE_DIR, 'train_{:02d}.png'.format(epoch + start_epoch)))   # :359-363
         if saver is not None and self.rank == 0 and c.EPOCHS > 0:                      # :378-379 (after all epochs)

@@ -39,8 +39,9 @@ class Config(object):
     SUMMARY = True
     SUMMARY_GRAPH = True
     SUMMARY_SCALAR = True
-    SUMMARY_IMAGE = False
-    SUMMARY_HISTOGRAM = False
+    SUMMARY_IMAGE = False              # True (--summary-image): the epoch's first generator samples as 'generated/image/<i>' 
+    SUMMARY_HISTOGRAM = False          # True (--summary-histogram): every trainable variable and its gradient as a TensorBoard histogram
+                                       # per epoch, binned on the device (Train.histograms)
 
     SAMPLE_DIR = None
     LOG_DIR = None
@@ -70,6 +71,8 @@ class Config(object):
                              # the reference's _train_op_w_grads hands out the gradients): None (off — the step is exactly the unclipped one),
                              # a positive float for all three networks (--clip-norm X), or a 3-tuple (D, G, C) of positive floats / None
                              # (Training/Train_goodGAN.check_clip_norm)
+    SUMMARY_IMAGE_MAX_OUTPUTS = 2      # how many samples SUMMARY_IMAGE writes per epoch (tf.summary.image's max_outputs; the reference's
+                                       # _image_summary default, Training/Summary.py:59), at most SAMPLE_SIZE
     MFMA_DTYPE = 'f32'       # 'bf16': conv/deconv/dense operands rounded to bf16 inside the MFMA kernels (fp32 accumulate)
     ACT_DTYPE = 'f32'        # 'bf16' (needs MFMA_DTYPE = 'bf16', else ValueError): the training-mode batch norms whose only reader is a
                              # bf16-operand 3x3 convolution store their output as bf16 (the SVHN classifier's c_h0_bn0/bn1, c_h1_bn0/bn1) —

@@ -34,9 +34,9 @@ def merge(images, size):
     return grid[:, :, 0] if c == 1 else grid
 
 
-def write_png(path, img):
-    """img: float [H,W] or [H,W,3] in [0,1] -> 8-bit PNG."""
-    a = np.clip(np.asarray(img) * 255.0 + 0.5, 0, 255).astype(np.uint8)
+def png_bytes(a):
+    """a: uint8 [H,W] or [H,W,C] (C in 1, 3, 4) -> the bytes of an 8-bit PNG (filter 0 on every row, zlib level 6)."""
+    a = np.ascontiguousarray(a, np.uint8)
     if a.ndim == 2:
         a = a[:, :, None]
     h, w, c = a.shape
@@ -46,9 +46,14 @@ def write_png(path, img):
     def chunk(tag, data):
         return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
 
+    return (b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, color, 0, 0, 0)) +
+            chunk(b'IDAT', zlib.compress(raw, 6)) + chunk(b'IEND', b''))
+
+
+def write_png(path, img):
+    """img: float [H,W] or [H,W,3] in [0,1] -> 8-bit PNG."""
     with open(path, 'wb') as f:
-        f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, color, 0, 0, 0)) +
-                chunk(b'IDAT', zlib.compress(raw, 6)) + chunk(b'IEND', b''))
+        f.write(png_bytes(np.clip(np.asarray(img) * 255.0 + 0.5, 0, 255).astype(np.uint8)))
 
 
 def save_images(images, size, image_path):
