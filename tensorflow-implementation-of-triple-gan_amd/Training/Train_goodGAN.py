@@ -22,126 +22,14 @@ import time
 import numpy as np
 import torch
 
-from Training.train_base import Train_base
+from config import Config
+from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, check_act_dtype, check_clip_norm, check_loss,  # noqa: F401
+                              check_mfma_dtype, check_num_classes, check_optimizer, check_zca, cla_lr, opt, resolve)
+from Training.train_base import Train_base, clip_workspace_floats
 from tg import dist as tgdist
-from tg import executor, grad_penalty, lib, ops
+from tg import executor, lib, ops
 from tg.batching import concat_acts
 from tg.runtime import Act, Context, PhiloxRNG, ctx, set_context
-
-
-def check_act_dtype(config):
-    """config.ACT_DTYPE ('f32' default | 'bf16') checked against config.MFMA_DTYPE: bf16-stored activations are only the same numbers when
-    every reader rounds its operands to bf16 anyway — with fp32 MFMA operands they would silently stop being the reference's arithmetic."""
-    act = getattr(config, 'ACT_DTYPE', 'f32')
-    if act not in ('f32', 'bf16'):
-        raise ValueError("ACT_DTYPE must be 'f32' or 'bf16', got %r" % (act,))
-    if act == 'bf16' and getattr(config, 'MFMA_DTYPE', 'f32') != 'bf16':
-        raise ValueError("ACT_DTYPE = 'bf16' needs MFMA_DTYPE = 'bf16' (got %r): fp32 products of bf16-stored values would not be the "
-                         "fp32 arithmetic of the reference" % (getattr(config, 'MFMA_DTYPE', 'f32'),))
-    return act
-
-
-LOSSES = ('GAN', 'WGAN_GP')
-
-
-def check_loss(config):
-    """config.LOSS ('GAN' default | 'WGAN_GP': the reference's _loss_WGAN_GP, train_base.py:576-620, in the three-player step).
-    Needs no device.  ValueError for an unknown value; lib.TgError for what the WGAN-GP step cannot run: bf16 MFMA operands (and with them
-    ACT_DTYPE = 'bf16'), minibatch discrimination, and a penalty batch whose real and fake halves differ in size."""
-    loss = getattr(config, 'LOSS', 'GAN')
-    if loss not in LOSSES:
-        raise ValueError("LOSS must be one of %s, got %r" % (', '.join(repr(v) for v in LOSSES), loss))
-    if loss != 'WGAN_GP':
-        return loss
-    grad_penalty.check_supported("LOSS = 'WGAN_GP'", getattr(config, 'MFMA_DTYPE', 'f32'), getattr(config, 'MINIBATCH_DIS', False))
-    l_d, u_d, b_g = (getattr(config, k, None) for k in ('BATCH_SIZE_L_D', 'BATCH_SIZE_U_D', 'BATCH_SIZE_G'))
-    if l_d is None or u_d is None or b_g is None or l_d + u_d != b_g:
-        raise lib.TgError("LOSS = 'WGAN_GP' needs BATCH_SIZE_L_D + BATCH_SIZE_U_D == BATCH_SIZE_G (got %r + %r, %r): the penalty "
-                          "interpolates the discriminator's real images X_P with the generated ones image for image" % (l_d, u_d, b_g))
-    return loss
-
-
-OPTIMIZERS = ('adam', 'rmsprop', 'momentum')
-
-
-def check_optimizer(config):
-    """config.OPTIMIZER ('adam' default | 'rmsprop' | 'momentum', or a 3-tuple of them for the (D, G, C) networks) -> the
-    normalised triple (d, g, c).  Needs no device.  ValueError for an unknown name, a tuple that does not have three entries, or any
-    other type."""
-    opt = getattr(config, 'OPTIMIZER', 'adam')
-    names = ', '.join(repr(v) for v in OPTIMIZERS)
-    if isinstance(opt, str):
-        triple = (opt,) * 3
-    elif isinstance(opt, (tuple, list)):
-        if len(opt) != 3:
-            raise ValueError("OPTIMIZER as a tuple names the optimisers of (D, G, C): three of %s, got %d entries: %r" % (names, len(opt), opt))
-        triple = tuple(opt)
-    else:
-        raise ValueError("OPTIMIZER must be one of %s or a 3-tuple (D, G, C) of them, got %r" % (names, opt))
-    for v in triple:
-        if not isinstance(v, str) or v not in OPTIMIZERS:
-            raise ValueError("OPTIMIZER must be one of %s or a 3-tuple (D, G, C) of them, got %r" % (names, opt))
-    return triple
-
-
-def check_clip_norm(config):
-    """config.CLIP_NORM (None default | a positive float | a 3-tuple for the (D, G, C) networks of positive floats or None)
-    -> the normalised triple (d, g, c) of floats / None.  Needs no device.  ValueError for zero, a negative number, NaN or infinity, a
-    tuple that does not have three entries, and anything that is not a number."""
-    clip = getattr(config, 'CLIP_NORM', None)
-
-    def one(v):
-        if v is None:
-            return None
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (0.0 < float(v) < float('inf')):
-            raise ValueError("CLIP_NORM must be None, a positive finite number or a 3-tuple (D, G, C) of them, got %r" % (clip,))
-        return float(v)
-
-    if isinstance(clip, (tuple, list)):
-        if len(clip) != 3:
-            raise ValueError("CLIP_NORM as a tuple holds the thresholds of (D, G, C): three positive numbers or None, got %d entries: %r"
-                             % (len(clip), clip))
-        return tuple(one(v) for v in clip)
-    return (one(clip),) * 3
-
-
-NETS = ('discriminator', 'good_generator', 'classifier')      # the order of every (D, G, C) triple
-
-
-NUM_CLASSES_RANGE = (2, 1024)
-
-
-def check_num_classes(config):
-    """config.NUM_CLASSES: an int in 2..1024, the range of the classifier's loss heads (csrc/loss.hip; 10 runs the ten-class kernels, any
-    other count the general ones).  Needs no device; ValueError outside it."""
-    k = getattr(config, 'NUM_CLASSES', None)
-    lo, hi = NUM_CLASSES_RANGE
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not lo <= k <= hi:
-        raise ValueError("NUM_CLASSES must be an integer in %d..%d (the classifier's loss heads), got %r" % (lo, hi, k))
-    return int(k)
-
-
-def check_zca(config, Dataset=None):
-    """config.ZCA: None (the reference's DATA_DIR/<data>_zca_*.npy files), (mean, mat) arrays, or 'fit' (fitted from the
-    training split by Train.train and written to those files).  Needs no device.  ValueError for any other string; lib.TgError when
-    'fit' meets a model without ZCA whitening (DATA_NAME not cifar10 / cifar100: MNIST, SVHN, stress64) or a Dataset (class or instance)
-    that is not a uint8 TFRecord source in [-1, 1] scaling, e.g. the default syntheticDataset."""
-    zc = getattr(config, 'ZCA', None)
-    if not isinstance(zc, str):
-        return zc
-    if zc != 'fit':
-        raise ValueError("ZCA must be None, (mean, mat) arrays or 'fit', got %r" % (zc,))
-    from Model.Good_GAN_cifar10 import ZCA_DATA
-    if getattr(config, 'DATA_NAME', None) not in ZCA_DATA:
-        raise lib.TgError("ZCA = 'fit' applies to the ZCA-whitened classifiers of %s; DATA_NAME %r has no ZCA whitening"
-                          % (' / '.join(ZCA_DATA), getattr(config, 'DATA_NAME', None)))
-    if Dataset is not None:
-        from Input_Pipeline.tfrecordDataset import tfrecordDataset
-        cls = Dataset if isinstance(Dataset, type) else type(Dataset)
-        if not issubclass(cls, tfrecordDataset) or cls.UNIT_RANGE:
-            raise lib.TgError("ZCA = 'fit' needs a training split of uint8 TFRecords (a tfrecordDataset such as cifar10Dataset); %s has "
-                              "none" % cls.__name__)
-    return zc
 
 
 class Train(Train_base):
@@ -151,23 +39,19 @@ class Train(Train_base):
         self.save_dir = save_dir
         self.log_dir = log_dir
         self.comments = kwargs.get('comments', '')
+        o = self.options = resolve(config)           # every device-free check, before a device is initialised (Training/options.py)
         self.world, self.rank, self.local_rank = tgdist.init()
         try:
             self.cx = ctx()
         except lib.TgError:
-            self.cx = set_context(Context('cuda:%d' % self.local_rank, seed=getattr(config, 'SEED', 0) + 7919 * self.rank))
+            self.cx = set_context(Context('cuda:%d' % self.local_rank, seed=o.seed + 7919 * self.rank))
         cx = self.cx
-        # 'bf16' = BASELINE.json configs[3] "bf16 MFMA conv path": conv / deconv / dense operands rounded to bf16 inside the
-        # MFMA kernels, fp32 accumulation, fp32 tensors, statistics, master weights and optimiser state
-        cx.mfma_dtype = getattr(config, 'MFMA_DTYPE', 'f32')
-        if cx.mfma_dtype not in ('f32', 'bf16'):
-            raise ValueError("MFMA_DTYPE must be 'f32' or 'bf16', got %r" % (cx.mfma_dtype,))
+        cx.mfma_dtype = o.mfma_dtype                 # 'bf16': the MFMA kernels round their operands to bf16 (options.check_mfma_dtype)
         # 'bf16': the batch norms the model marks store their output as bf16 — same numbers, half the bytes (Context.act_dtype)
-        cx.act_dtype = check_act_dtype(config)
-        check_num_classes(config)
-        self.loss_kind = check_loss(config)          # 'GAN' | 'WGAN_GP': the loss heads of the three solver runs
-        self.optimizer_kinds = check_optimizer(config)     # (D, G, C), each 'adam' | 'rmsprop' | 'momentum' 
-        self.clip_norms = check_clip_norm(config)          # (D, G, C), each a threshold or None: clip_by_global_norm
+        cx.act_dtype = o.act_dtype
+        self.loss_kind = o.loss                      # 'GAN' | 'WGAN_GP': the loss heads of the three solver runs
+        self.optimizer_kinds = o.optimizers          # (D, G, C), each 'adam' | 'rmsprop' | 'momentum' 
+        self.clip_norms = o.clip_norms               # (D, G, C), each a threshold or None: clip_by_global_norm
         self.clip_dev = None                         # with a clip: per network [threshold, 0, norm, factor] on the device
         self._clip_views = {}                        # network -> (threshold, {norm, factor}) views of it (Train_base._clip_state)
         self._gp_w = self._gp_grad = None            # WGAN-GP: the D-update's weighted penalty and its parameter gradient (device)
@@ -178,13 +62,14 @@ class Train(Train_base):
         self.model = None
         self.executor = executor.StepExecutor(cx)        # how an iteration is launched, and every graph / launch plan it replays
         self._refusal_warned = False
+        self._g_saved = None             # the D-update's generator forward pass, kept for the G-update on the same feed
         self._rest = {}                  # solver run -> (unexecuted head of its backward tape, call-site counter): bucketed backward passes
         self.iteration = 0
         self._label_override = {}        # see label_override()
         self.zca_source = None           # config.ZCA = 'fit' resolved by train(): 'files' | 'fit' (rank 0) | 'broadcast' (other ranks)
         self._hist_runs = {}             # network -> (store layout key, tg.summary.StoreHistograms): see histograms()
         self.summary_train = self.summary_val = None
-        if getattr(config, 'SUMMARY', False) and log_dir and self.rank == 0:          # :37-41
+        if o.summary and log_dir and self.rank == 0:          # :37-41
             from Training.Summary import Summary
             self.summary_train = Summary(log_dir, config, log_type='train', log_comments=kwargs.get('comments', ''))
             self.summary_val = Summary(log_dir, config, log_type='val', log_comments=kwargs.get('comments', ''))
@@ -222,10 +107,9 @@ class Train(Train_base):
         self.c_optimizer = self._make_optimizer(kc, self.hyper[1:2], 0.5)
         for opt, net in ((self.d_optimizer, 'discriminator'), (self.g_optimizer, 'good_generator'), (self.c_optimizer, 'classifier')):
             opt.bind(st[net])                    # the store's slots start where this optimiser's do (RMSProp: rms = 1), now and when they grow
-        self.set_hyper(c.LEARNING_RATE, getattr(c, 'CLA_LEARNINIG_RATE', c.LEARNING_RATE), 0.0, 0.0)
+        self.set_hyper(c.LEARNING_RATE, cla_lr(c), 0.0, 0.0)
         if any(v is not None for v in self.clip_norms):
             # thresholds and results live on the device, and the norm's workspace exists before anything records: plans and graphs hold both
-            from Training.train_base import clip_workspace_floats
             self.clip_dev = torch.zeros(4 * len(NETS), dtype=torch.float32, device=cx.device)
             for k, (net, v) in enumerate(zip(NETS, self.clip_norms)):
                 if v is not None:
@@ -248,7 +132,7 @@ class Train(Train_base):
             return self._Adam_optimizer(lr_dev, beta1)
         if kind == 'rmsprop':
             return self._RMSProp_optimizer(lr_dev)
-        return self._SGD_w_Momentum_optimizer(lr_dev, float(getattr(self.config, 'MOMENTUM', 0.9)))
+        return self._SGD_w_Momentum_optimizer(lr_dev, self.options.momentum)
 
     def set_hyper(self, lr=None, cla_lr=None, lambda_1=None, lambda_2=None):
         vals = self.hyper.detach().cpu().numpy()
@@ -338,12 +222,12 @@ class Train(Train_base):
                                   self.loss_dev[0:1])
             else:
                 self._d_loss(d_logits, c.BATCH_SIZE_L_D + c.BATCH_SIZE_U_D, c.BATCH_SIZE_G, c.BATCH_SIZE_U_C, self.loss_dev[0:1])
-            self._rest['D'] = (cx.backward(stop_at_boundary='discriminator' if split else False), cx.counter)
+            self._keep_rest('D', cx.backward(stop_at_boundary='discriminator' if split else False))
 
     def _g_forward_backward(self, split=False):
         cx, m = self.cx, self.model
         with cx.phase_scope('G', train_nets=('good_generator',)):
-            saved = getattr(self, '_g_saved', None)
+            saved = self._g_saved
             if saved is not None:                       # generator forward of the D-update on the same feed and weights
                 G, g_tape, g_replay = saved
                 self._g_saved = None
@@ -360,7 +244,7 @@ class Train(Train_base):
             rest = cx.backward(stop_at_boundary='good_generator' if (split and g_tape is None) else False)
             if g_tape is not None:                      # the discriminator's input gradient is complete: now the kept generator tape
                 rest = cx.run_tape(g_tape, stop_at_boundary='good_generator' if split else False)
-            self._rest['G'] = (rest, cx.counter)
+            self._keep_rest('G', rest)
 
     def _c_forward_backward(self, split=False):
         """split: stop the backward pass at the classifier's last gradient-bucket boundary (the rest runs in _backward_rest)."""
@@ -380,7 +264,7 @@ class Train(Train_base):
                 # CE(y_l_c, C_real) + lambda_2 CE(y_g, C_fake): the unl / rep rows weigh 0 and nothing reads D(x_u_c), so it is not run
                 self._c_logits = c_unl
                 self._wgan_c_head(c_logits, segs[0], sum(segs[1:-1]), G.n, self.y_l_c_ph, self.y_g_ph, self.hyper[2:4], self.loss_dev[2:3])
-                self._rest['C'] = (cx.backward(stop_at_boundary='classifier' if split else False), cx.counter)
+                self._keep_rest('C', cx.backward(stop_at_boundary='classifier' if split else False))
                 return
             k = c.NUM_CLASSES
             oh_c = ops.argmax_onehot(c_unl, k)
@@ -392,15 +276,18 @@ class Train(Train_base):
                 _, d_unl = m.discriminator(self.x_u_c_ph, oh_unl, want_prob=False)
             self._c_loss(c_logits, segs[0], segs[1], segs[1] if rep else 0, G.n, self.y_l_c_ph, self.y_g_ph, d_unl,
                          self.hyper[2:4], self.loss_dev[2:3])
-            self._rest['C'] = (cx.backward(stop_at_boundary='classifier' if split else False), cx.counter)
+            self._keep_rest('C', cx.backward(stop_at_boundary='classifier' if split else False))
+
+    def _keep_rest(self, phase, rest):
+        """the unexecuted head `rest` of solver run `phase`'s backward tape, with the call-site counter _backward_rest resumes it at."""
+        self._rest[phase] = (rest, self.cx.counter)
 
     def _backward_rest(self, phase, net, split):
         """continue the backward pass of solver run `phase` — down to the trained network's next bucket boundary (split) or to its end."""
         rest, counter = self._rest[phase]
         if rest:
             with self.cx.phase_scope(phase, train_nets=(net,), counter=counter):
-                rest = self.cx.run_tape(rest, stop_at_boundary=net if split else False)
-                self._rest[phase] = (rest, self.cx.counter)
+                self._keep_rest(phase, self.cx.run_tape(rest, stop_at_boundary=net if split else False))
 
     def _add_gp_slice(self, sl):
         """WGAN-GP: add the penalty's parameter gradient to the slice `sl` of the discriminator's store.g, once the D backward pass has
@@ -421,7 +308,7 @@ class Train(Train_base):
         variables first); one slice — the whole buffer — without replicas."""
         st = self.cx.stores[net]
         names = getattr(self.model, 'GRAD_BUCKETS', {}).get(net, ())
-        if not tgdist.active() or getattr(self.config, 'NO_GRAD_BUCKETS', False) or not names:
+        if not tgdist.active() or self.options.no_grad_buckets or not names:
             return [st.g]
         offs = [0] + sorted(st.offset(n) for n in names) + [st.n_p]
         return [st.g[offs[i]:offs[i + 1]] for i in range(len(offs) - 2, -1, -1)]
@@ -505,8 +392,8 @@ class Train(Train_base):
         out of config.EXEC_MODE / USE_HIP_GRAPH.  No host sync."""
         ex, key = self.executor, 'pre' if pre_train else 'full'
         if use_graph is None:
-            use_graph = getattr(self.config, 'USE_HIP_GRAPH', None)
-        how, refused = executor.resolve_launch(getattr(self.config, 'EXEC_MODE', 'auto'), use_graph, isinstance(self.cx.rng, PhiloxRNG),
+            use_graph = opt(self.config, 'USE_HIP_GRAPH')
+        how, refused = executor.resolve_launch(opt(self.config, 'EXEC_MODE'), use_graph, isinstance(self.cx.rng, PhiloxRNG),
                                                tgdist.graphs_allowed(), ex.replay[key].auto.next)
         if refused and not self._refusal_warned:          # torch's RCCL process group: its watchdog cannot coexist with a capture
             self._refusal_warned = True
@@ -620,7 +507,7 @@ class Train(Train_base):
         (Model/Good_GAN_cifar10.cifar10_ZCA.fit) and writes them; with data parallelism the other ranks receive rank 0's constants
         (tg.dist.broadcast_), so every replica holds the same bits and there is exactly one writer."""
         c = self.config
-        if not isinstance(getattr(c, 'ZCA', None), str):
+        if not isinstance(opt(c, 'ZCA'), str):
             return
         check_zca(c, dataset_train)
         from Model.Good_GAN_cifar10 import cifar10_ZCA, write_zca_files, zca_paths
@@ -696,7 +583,7 @@ class Train(Train_base):
             kinds['histogram'] = dict.fromkeys(tags + ['gradients/' + nm for nm in tags])
         sm.add_summary(kinds)
         if want_img:                                     # (add_summary registers images with the reference's default max_outputs of 2)
-            sm._image_outputs = sm._image_summary(kinds['image'], min(int(getattr(c, 'SUMMARY_IMAGE_MAX_OUTPUTS', 2)), int(c.SAMPLE_SIZE)))
+            sm._image_outputs = sm._image_summary(kinds['image'], min(self.options.summary_image_max_outputs, int(c.SAMPLE_SIZE)))
 
     def _norm_tags(self):
         """the train summary's extra scalars: '<d|g|c>_grad_norm' for every clipped network (none without a clip)."""
@@ -714,7 +601,7 @@ class Train(Train_base):
         init_op_train, init_op_val, NNIO = dataset_train.inputpipline_train_val(dataset_val)
         self._build_train_graph(Model)
         sample_z = np.random.uniform(low=-1.0, high=1.0, size=(c.SAMPLE_SIZE, c.Z_DIM)).astype(np.float32)   # :130
-        lr, cla_lr = c.LEARNING_RATE, getattr(c, 'CLA_LEARNINIG_RATE', c.LEARNING_RATE)
+        lr, c_lr = c.LEARNING_RATE, cla_lr(c)
         start_epoch = 0
         saver = None
         if self.save_dir:
@@ -724,28 +611,23 @@ class Train(Train_base):
                 start_epoch = saver.restore(self, dir_names=c.RUN, epoch=c.RESTORE_EPOCH)
                 if start_epoch >= 300:
                     lr = lr * 0.995 ** (start_epoch - 300)
-                    cla_lr = cla_lr * 0.99 ** (start_epoch - 300)
+                    c_lr = c_lr * 0.99 ** (start_epoch - 300)
             elif self.rank == 0:
                 saver.set_save_path(comments=self.comments)                            # :150
-        if self.summary_train is not None and getattr(c, 'SUMMARY_SCALAR', True):      # :105-118
+        if self.summary_train is not None and self.options.summary_scalar:             # :105-118
             self.summary_train.add_summary({'scalar': dict.fromkeys(('g_loss', 'd_loss', 'c_loss', 'train_accuracy') + self._norm_tags())})
             self.summary_val.add_summary({'scalar': dict.fromkeys(('val_accuracy',))})
-        want_hist = self.summary_train is not None and bool(getattr(c, 'SUMMARY_HISTOGRAM', False))
-        want_img = self.summary_train is not None and bool(getattr(c, 'SUMMARY_IMAGE', False))
-        registered = False
-        if sample_y is None and want_img:                                              # no labels handed in: the entry points' cyclic ones
-            sample_y = np.eye(c.NUM_CLASSES, dtype=np.float32)[np.arange(c.SAMPLE_SIZE) % c.NUM_CLASSES]
-            own_sample_y = True
-        else:
-            own_sample_y = False
+        grid = bool(c.SAMPLE_DIR) and sample_y is not None                             # the sample grid: only for labels handed in
+        if sample_y is None and self.summary_train is not None and self.options.summary_image:
+            sample_y = np.eye(c.NUM_CLASSES, dtype=np.float32)[np.arange(c.SAMPLE_SIZE) % c.NUM_CLASSES]      # the entry points' cyclic ones
         history = []
         iters = int(c.TRAIN_SIZE / c.BATCH_SIZE)
         for epoch in range(1, c.EPOCHS + 1):
             lambda_1 = c.FAKE_G_LAMBDA if (start_epoch + epoch) > 200 else 0.          # :165
             lambda_2 = (0.5 if epoch > 67 else 0.) if getattr(self.model, 'CONSISTENCY', False) else 0.  # :171
             if start_epoch + epoch >= 300:                                             # :175-177
-                lr, cla_lr = lr * 0.995, cla_lr * 0.99
-            self.set_hyper(lr, cla_lr, lambda_1, lambda_2)
+                lr, c_lr = lr * 0.995, c_lr * 0.99
+            self.set_hyper(lr, c_lr, lambda_1, lambda_2)
             init_op_train()
             pre = bool(c.PRE_TRAIN and (start_epoch + epoch <= 30))                    # :182
             t0 = time.time()
@@ -764,44 +646,51 @@ class Train(Train_base):
             history.append(rec)
             samples = None
             if self.summary_train is not None:                                         # :293,346
-                norms = self.grad_norms() if self._norm_tags() else {}                  # the last iteration's, clipped networks only
-                hists = imgs = None
-                if (want_hist or want_img) and not registered:                         # at the first tail: by now every variable exists
-                    self._register_summaries(want_hist, want_img)
-                    registered = True
-                if want_hist:                                                          # values, and store.g as the last optimiser step read it
-                    hists = self.histograms('value')
-                    hists.update(('gradients/' + nm, h) for nm, h in self.histograms('grad').items())
-                if want_img:                                                           # the epoch's samples (drawn here; the sample grid below reuses them)
-                    # The sampler's batch norms run in training mode (reference :176-202) and move their running statistics.  A run
-                    # without the flag samples only for the sample grid: when there is none, the statistics are put back, so the
-                    # summary leaves every store as it found it.
-                    grid = bool(c.SAMPLE_DIR) and not own_sample_y
-                    kept = None if grid else {net: st.s.clone() for net, st in self.cx.stores.items()}
-                    samples = self.sample(sample_z, sample_y)
-                    if kept is not None:
-                        for net, s_before in kept.items():
-                            self.cx.stores[net].s.copy_(s_before)
-                    imgs = {'generated': samples}
-                self.summary_train.write(dict(dict(g_loss=g_loss, d_loss=d_loss, c_loss=c_loss),
-                                              **{k + '_grad_norm': v[0] for k, v in norms.items() if v is not None}), epoch + start_epoch,
-                                         histograms=hists, images=imgs)
-                self.summary_val.write(dict(val_accuracy=acc), epoch + start_epoch)
+                samples = self._write_epoch_summaries(rec, sample_z, sample_y, grid, first=epoch == 1)
             if saver is not None and self.rank == 0 and epoch % c.SAVE_PER_EPOCH == 0:  # :366-369
                 saver.save(self, 'model_' + str(epoch + start_epoch).zfill(4) + '.ckpt')
             if self.rank == 0:
                 print("epoch {epoch}: g_loss {g_loss:.3f} d_loss {d_loss:.3f} c_loss {c_loss:.3f} val_acc {val_accuracy:.4f} "
                       "{images_per_sec:.0f} img/s".format(**rec), flush=True)
-                if c.SAMPLE_DIR and sample_y is not None and not own_sample_y:
-                    from utils import save_images, image_manifold_size
-                    os.makedirs(c.SAMPLE_DIR, exist_ok=True)
-                    if samples is None:
-                        samples = self.sample(sample_z, sample_y)
-                    save_images(samples, image_manifold_size(samples.shape[0]),
-                                os.path.join(c.SAMPLE_DIR, 'train_{:02d}.png'.format(epoch + start_epoch)))   # :359-363
+                if grid:
+                    self._save_sample_grid(samples if samples is not None else self.sample(sample_z, sample_y), rec['epoch'])
         if saver is not None and self.rank == 0 and c.EPOCHS > 0:                      # :378-379 (after all epochs)
             saver.save(self, 'model_' + str(c.EPOCHS + start_epoch).zfill(4) + '.ckpt')
         return history
+
+    def _write_epoch_summaries(self, rec, sample_z, sample_y, grid, first):
+        """The summaries of one epoch tail (:293,346): the losses and the validation accuracy of `rec`, the last iteration's gradient norms
+        of the clipped networks and, with config.SUMMARY_HISTOGRAM / SUMMARY_IMAGE, the histograms and the epoch's samples — which are
+        returned (None without images) for the sample grid to reuse when one follows (`grid`).  first: this train() call's first tail."""
+        o = self.options
+        norms = self.grad_norms() if self._norm_tags() else {}
+        hists = imgs = samples = None
+        if first and (o.summary_histogram or o.summary_image):                         # at the first tail: by now every variable exists
+            self._register_summaries(o.summary_histogram, o.summary_image)
+        if o.summary_histogram:                                                        # values, and store.g as the last optimiser step read it
+            hists = self.histograms('value')
+            hists.update(('gradients/' + nm, h) for nm, h in self.histograms('grad').items())
+        if o.summary_image:
+            # The sampler's batch norms run in training mode (reference :176-202) and move their running statistics.  A run
+            # without the flag samples only for the sample grid: when there is none, the statistics are put back, so the
+            # summary leaves every store as it found it.
+            kept = None if grid else {net: st.s.clone() for net, st in self.cx.stores.items()}
+            samples = self.sample(sample_z, sample_y)
+            if kept is not None:
+                for net, s_before in kept.items():
+                    self.cx.stores[net].s.copy_(s_before)
+            imgs = {'generated': samples}
+        self.summary_train.write(dict(dict(g_loss=rec['g_loss'], d_loss=rec['d_loss'], c_loss=rec['c_loss']),
+                                      **{k + '_grad_norm': v[0] for k, v in norms.items() if v is not None}), rec['epoch'],
+                                 histograms=hists, images=imgs)
+        self.summary_val.write(dict(val_accuracy=rec['val_accuracy']), rec['epoch'])
+        return samples
+
+    def _save_sample_grid(self, samples, epoch):
+        """:359-363: the epoch's samples as one image, SAMPLE_DIR/train_<epoch>.png."""
+        from utils import save_images, image_manifold_size
+        os.makedirs(self.config.SAMPLE_DIR, exist_ok=True)
+        save_images(samples, image_manifold_size(samples.shape[0]), os.path.join(self.config.SAMPLE_DIR, 'train_{:02d}.png'.format(epoch)))
 
 
 def rampup(epoch):
@@ -839,9 +728,91 @@ def _customize_config(tmp_config, FLAGS):
             setattr(tmp_config, k.upper(), v)
 
 
+class ExperimentConfig(Config):
+    """what the five experiments share; a subclass holds what differs.  The directories are relative to the package root (`_run` roots
+    them at _root_dir() when the experiment is started), SAMPLE_DIR to Training/."""
+    NAME = "Good_GAN"
+    BATCH_SIZE_G = 100
+    BATCH_SIZE_bG = 10
+    BATCH_SIZE_L_C = 50
+    BATCH_SIZE_U_C = 50
+    BATCH_SIZE_L_D = 20                      # [x_l_d | x_u_d] is the discriminator's real batch, as large as the generated one
+    BATCH_SIZE_U_D = 80
+    BATCH_SIZE = BATCH_SIZE_G
+    IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = 32, 32, 3
+    REPEAT = -1
+    Z_DIM = 100
+    NUM_CLASSES = 10
+    MINIBATCH_DIS = False
+    RESTORE = False                          # the reference resumes a run directory that is not in its repository (:588-592)
+    LEARNING_RATE = 3e-4
+    CLA_LEARNINIG_RATE = 3e-3
+    FAKE_G_LAMBDA = 0.3
+    EPOCHS = 1000
+    SAVE_PER_EPOCH = 1
+    VAL_STEP = None
+
+
+class SvhnConfig(ExperimentConfig):
+    DATA_NAME, DATA_DIR, NUM_LABEL = "svhn", "DataSet/svhn", 500
+    BATCH_SIZE_bG = 20
+    FAKE_G_LAMBDA = 0.03
+    CLA_LEARNINIG_RATE = 3e-4
+    TRAIN_SIZE = 73257 - NUM_LABEL
+    SAMPLE_DIR, WEIGHT_DIR, LOG_DIR = "good_GAN_svhn_500", "Training/Weight_svhn", "Training/Log_svhn"
+
+
+class Cifar10Config(ExperimentConfig):
+    DATA_NAME, DATA_DIR, NUM_LABEL = "cifar10", "DataSet/cifar_10", 4000
+    TRAIN_SIZE = 60000 - NUM_LABEL
+    SAMPLE_DIR, WEIGHT_DIR, LOG_DIR = "cifar10_good_GAN_4000", "Training/Weight_cifar10", "Training/Log_cifar10"
+
+
+class Cifar100Config(ExperimentConfig):
+    DATA_NAME, DATA_DIR, NUM_LABEL = "cifar100", "DataSet/cifar_100", 10000
+    NUM_CLASSES = 100
+    TRAIN_SIZE = 50000 - NUM_LABEL
+    SAMPLE_DIR, WEIGHT_DIR, LOG_DIR = "cifar100_good_GAN_10000", "Training/Weight_cifar100", "Training/Log_cifar100"
+
+
+class MnistConfig(ExperimentConfig):
+    DATA_NAME, DATA_DIR, NUM_LABEL = "mnist", "DataSet/mnist", 100
+    BATCH_SIZE_bG = BATCH_SIZE_L_C = BATCH_SIZE_U_C = 100
+    IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = 28, 28, 1
+    FAKE_G_LAMBDA = 0.1
+    LEARNING_RATE = 1e-3
+    CLA_LEARNINIG_RATE = 3e-4
+    TRAIN_SIZE = 60000 - NUM_LABEL
+    SAMPLE_DIR, WEIGHT_DIR, LOG_DIR = "mnist_good_GAN_100", "Training/Weight_mnist", "Training/Log_mnist"
+
+
+class Stress64Config(ExperimentConfig):
+    DATA_NAME, DATA_DIR, NUM_LABEL = "stress64", "DataSet/stress64", 4000
+    BATCH_SIZE_G = 256
+    BATCH_SIZE_L_C = BATCH_SIZE_U_C = 128
+    BATCH_SIZE_L_D, BATCH_SIZE_U_D = 51, 205
+    BATCH_SIZE = BATCH_SIZE_G
+    IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = 64, 64, 3
+    TRAIN_SIZE = 60000 - NUM_LABEL
+    SAMPLE_DIR, WEIGHT_DIR, LOG_DIR = "stress64_good_GAN", "Training/Weight_stress64", "Training/Log_stress64"
+
+
+def _synthetic_zca(tmp_config):
+    """the ZCA-whitened (CIFAR) experiments without whitening constants — config.ZCA is None and DATA_DIR holds no <data>_zca_mat.npy —
+    whiten with a fixed random rotation and a zero mean."""
+    from Model.Good_GAN_cifar10 import ZCA_DATA
+    if tmp_config.DATA_NAME in ZCA_DATA and tmp_config.ZCA is None and not os.path.exists(os.path.join(tmp_config.DATA_DIR, tmp_config.DATA_NAME + "_zca_mat.npy")):
+        d = int(np.prod(tmp_config.IMAGE_DIM))
+        q, _ = np.linalg.qr(np.random.default_rng(4321).standard_normal((d, d)))
+        tmp_config.ZCA = (np.zeros(d, np.float32), q.astype(np.float32))
+
+
 def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
     from Input_Pipeline.syntheticDataset import syntheticDataset
     tmp_config = TempConfig()
+    for k in ('DATA_DIR', 'WEIGHT_DIR', 'LOG_DIR'):
+        setattr(tmp_config, k, os.path.join(_root_dir(), getattr(tmp_config, k)))
+    _synthetic_zca(tmp_config)                                         # a default like the class body's: FLAGS below override it
     if FLAGS:
         _customize_config(tmp_config, FLAGS)
     if epochs is not None:
@@ -858,196 +829,34 @@ def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
 
 def _main_training_svhn(FLAGS=None, Dataset=None, epochs=None):
     """:472-549."""
-    from config import Config
     from Model.Good_GAN import Good_GAN as Model
-
-    class TempConfig(Config):
-        NAME = "Good_GAN"
-        DATA_NAME = "svhn"
-        DATA_DIR = os.path.join(_root_dir(), "DataSet/svhn")
-        NUM_LABEL = 500
-        BATCH_SIZE = 100
-        BATCH_SIZE_G = BATCH_SIZE
-        BATCH_SIZE_bG = 20
-        BATCH_SIZE_L_C = 50
-        BATCH_SIZE_U_C = 50
-        BATCH_SIZE_L_D = 20
-        BATCH_SIZE_U_D = 80
-        IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = 32, 32, 3
-        REPEAT = -1
-        FAKE_G_LAMBDA = 0.03
-        CLA_LEARNINIG_RATE = 3e-4
-        Z_DIM = 100
-        NUM_CLASSES = 10
-        MINIBATCH_DIS = False
-        RESTORE = False
-        LEARNING_RATE = 3e-4
-        EPOCHS = 1000
-        TRAIN_SIZE = 73257 - NUM_LABEL
-        SAVE_PER_EPOCH = 1
-        VAL_STEP = None
-        SAMPLE_DIR = "good_GAN_svhn_500"
-        WEIGHT_DIR = os.path.join(_root_dir(), "Training/Weight_svhn")
-        LOG_DIR = os.path.join(_root_dir(), "Training/Log_svhn")
-
-    return _run(TempConfig, Model, Dataset, FLAGS, "This training is for svhn dataset.", epochs)
+    return _run(SvhnConfig, Model, Dataset, FLAGS, "This training is for svhn dataset.", epochs)
 
 
 def _main_training_cifar10(FLAGS=None, Dataset=None, epochs=None):
     """:551-626.  config.ZCA must carry (mean, mat) when DATA_DIR holds no cifar10_zca_*.npy, or be 'fit' (--zca fit, with a TFRecord
-    Dataset): fitted from the training split and written there."""
-    from config import Config
+    Dataset): fitted from the training split and written there; without either, _synthetic_zca."""
     from Model.Good_GAN_cifar10 import Good_GAN_cifar10 as Model
-
-    class TempConfig(Config):
-        NAME = "Good_GAN"
-        DATA_NAME = "cifar10"
-        DATA_DIR = os.path.join(_root_dir(), "DataSet/cifar_10")
-        NUM_LABEL = 4000
-        BATCH_SIZE_G = 100
-        BATCH_SIZE_bG = 10
-        BATCH_SIZE_L_C = 50
-        BATCH_SIZE_U_C = 50
-        BATCH_SIZE_L_D = 20
-        BATCH_SIZE_U_D = 80
-        BATCH_SIZE = BATCH_SIZE_G
-        IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = 32, 32, 3
-        REPEAT = -1
-        FAKE_G_LAMBDA = 0.3
-        Z_DIM = 100
-        NUM_CLASSES = 10
-        MINIBATCH_DIS = False
-        RESTORE = False                      # the reference resumes a run directory that is not in its repository (:588-592)
-        LEARNING_RATE = 3e-4
-        CLA_LEARNINIG_RATE = 3e-3
-        EPOCHS = 1000
-        TRAIN_SIZE = 60000 - NUM_LABEL
-        SAVE_PER_EPOCH = 1
-        VAL_STEP = None
-        SAMPLE_DIR = "cifar10_good_GAN_4000"
-        WEIGHT_DIR = os.path.join(_root_dir(), "Training/Weight_cifar10")
-        LOG_DIR = os.path.join(_root_dir(), "Training/Log_cifar10")
-
-    if not os.path.exists(os.path.join(TempConfig.DATA_DIR, "cifar10_zca_mat.npy")):
-        q, _ = np.linalg.qr(np.random.default_rng(4321).standard_normal((3072, 3072)))      # SURVEY §8d synthetic whitening
-        TempConfig.ZCA = (np.zeros(3072, np.float32), q.astype(np.float32))
-    return _run(TempConfig, Model, Dataset, FLAGS, "This training is for cifar10 dataset.", epochs)
+    return _run(Cifar10Config, Model, Dataset, FLAGS, "This training is for cifar10 dataset.", epochs)
 
 
 def _main_training_cifar100(FLAGS=None, Dataset=None, epochs=None):
     """CIFAR-100 (not an entry point of the reference): the networks and algorithm of _main_training_cifar10 with NUM_CLASSES = 100, so the
-    classifier heads run the general-K kernels (csrc/loss.hip).  config.ZCA must carry (mean, mat) when DATA_DIR holds no
-    cifar100_zca_*.npy, or be 'fit' as for CIFAR-10; without either, the synthetic whitening of the CIFAR-10 entry point."""
-    from config import Config
+    classifier heads run the general-K kernels (csrc/loss.hip).  ZCA as for CIFAR-10, with cifar100_zca_*.npy."""
     from Model.Good_GAN_cifar10 import Good_GAN_cifar10 as Model
-
-    class TempConfig(Config):
-        NAME = "Good_GAN"
-        DATA_NAME = "cifar100"
-        DATA_DIR = os.path.join(_root_dir(), "DataSet/cifar_100")
-        NUM_LABEL = 10000
-        BATCH_SIZE_G = 100
-        BATCH_SIZE_bG = 10
-        BATCH_SIZE_L_C = 50
-        BATCH_SIZE_U_C = 50
-        BATCH_SIZE_L_D = 20
-        BATCH_SIZE_U_D = 80
-        BATCH_SIZE = BATCH_SIZE_G
-        IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = 32, 32, 3
-        REPEAT = -1
-        FAKE_G_LAMBDA = 0.3
-        Z_DIM = 100
-        NUM_CLASSES = 100
-        MINIBATCH_DIS = False
-        RESTORE = False
-        LEARNING_RATE = 3e-4
-        CLA_LEARNINIG_RATE = 3e-3
-        EPOCHS = 1000
-        TRAIN_SIZE = 50000 - NUM_LABEL
-        SAVE_PER_EPOCH = 1
-        VAL_STEP = None
-        SAMPLE_DIR = "cifar100_good_GAN_10000"
-        WEIGHT_DIR = os.path.join(_root_dir(), "Training/Weight_cifar100")
-        LOG_DIR = os.path.join(_root_dir(), "Training/Log_cifar100")
-
-    if TempConfig.ZCA is None and not os.path.exists(os.path.join(TempConfig.DATA_DIR, "cifar100_zca_mat.npy")):
-        q, _ = np.linalg.qr(np.random.default_rng(4321).standard_normal((3072, 3072)))      # the synthetic whitening of _main_training_cifar10
-        TempConfig.ZCA = (np.zeros(3072, np.float32), q.astype(np.float32))
-    return _run(TempConfig, Model, Dataset, FLAGS, "This training is for cifar100 dataset.", epochs)
+    return _run(Cifar100Config, Model, Dataset, FLAGS, "This training is for cifar100 dataset.", epochs)
 
 
 def _main_training_mnist(FLAGS=None, Dataset=None, epochs=None):
     """:628-705."""
-    from config import Config
     from Model.Good_GAN import Good_GAN as Model
-
-    class TempConfig(Config):
-        NAME = "Good_GAN"
-        DATA_NAME = "mnist"
-        DATA_DIR = os.path.join(_root_dir(), "DataSet/mnist")
-        NUM_LABEL = 100
-        BATCH_SIZE_G = 100
-        BATCH_SIZE_bG = 100
-        BATCH_SIZE_L_C = 100
-        BATCH_SIZE_U_C = 100
-        BATCH_SIZE_L_D = 20
-        BATCH_SIZE_U_D = 80
-        BATCH_SIZE = BATCH_SIZE_G
-        IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = 28, 28, 1
-        REPEAT = -1
-        FAKE_G_LAMBDA = 0.1
-        Z_DIM = 100
-        NUM_CLASSES = 10
-        MINIBATCH_DIS = False
-        RESTORE = False
-        LEARNING_RATE = 1e-3
-        CLA_LEARNINIG_RATE = 3e-4
-        EPOCHS = 1000
-        TRAIN_SIZE = 60000 - NUM_LABEL
-        SAVE_PER_EPOCH = 1
-        VAL_STEP = None
-        SAMPLE_DIR = "mnist_good_GAN_100"
-        WEIGHT_DIR = os.path.join(_root_dir(), "Training/Weight_mnist")
-        LOG_DIR = os.path.join(_root_dir(), "Training/Log_mnist")
-
-    return _run(TempConfig, Model, Dataset, FLAGS, "This training is for mnist dataset.", epochs)
+    return _run(MnistConfig, Model, Dataset, FLAGS, "This training is for mnist dataset.", epochs)
 
 
 def _main_training_stress64(FLAGS=None, Dataset=None, epochs=None):
     """Build-defined 64x64x3 / batch-256 stress configuration (not in the reference)."""
-    from config import Config
     from Model.Good_GAN_stress64 import Good_GAN_stress64 as Model
-
-    class TempConfig(Config):
-        NAME = "Good_GAN"
-        DATA_NAME = "stress64"
-        DATA_DIR = os.path.join(_root_dir(), "DataSet/stress64")
-        NUM_LABEL = 4000
-        BATCH_SIZE_G = 256
-        BATCH_SIZE_bG = 10
-        BATCH_SIZE_L_C = 128
-        BATCH_SIZE_U_C = 128
-        BATCH_SIZE_L_D = 51
-        BATCH_SIZE_U_D = 205
-        BATCH_SIZE = BATCH_SIZE_G
-        IMAGE_HEIGHT, IMAGE_WIDTH, CHANNEL = 64, 64, 3
-        REPEAT = -1
-        FAKE_G_LAMBDA = 0.3
-        Z_DIM = 100
-        NUM_CLASSES = 10
-        MINIBATCH_DIS = False
-        RESTORE = False
-        LEARNING_RATE = 3e-4
-        CLA_LEARNINIG_RATE = 3e-3
-        EPOCHS = 1000
-        TRAIN_SIZE = 60000 - NUM_LABEL
-        SAVE_PER_EPOCH = 1
-        VAL_STEP = None
-        SAMPLE_DIR = "stress64_good_GAN"
-        WEIGHT_DIR = os.path.join(_root_dir(), "Training/Weight_stress64")
-        LOG_DIR = os.path.join(_root_dir(), "Training/Log_stress64")
-
-    return _run(TempConfig, Model, Dataset, FLAGS, "64x64 stress configuration.", epochs)
+    return _run(Stress64Config, Model, Dataset, FLAGS, "64x64 stress configuration.", epochs)
 
 
 if __name__ == "__main__":

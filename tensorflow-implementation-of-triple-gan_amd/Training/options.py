@@ -1,0 +1,165 @@
+"""What the trainer reads out of a config object, resolved once and without a device.
+
+config.Config is the only place a default is written: `opt(config, name)` falls back to it, so a duck-typed config that lacks an
+attribute means what a Config subclass without it means.  The `check_*` functions validate one setting each and return its normalised
+value; `resolve(config)` runs them all and returns the record Train.__init__ fills itself from, before any device is initialised.
+This module imports no torch and opens no device."""
+import collections
+
+import numpy as np
+
+from config import Config
+from tg import lib
+
+
+def opt(config, name):
+    """config.<name>, or the default config.Config declares for it."""
+    return getattr(config, name, getattr(Config, name))
+
+
+def cla_lr(config):
+    """the classifier's learning rate: CLA_LEARNINIG_RATE (the reference's spelling; the experiment configs set it, Config does not declare
+    it), else LEARNING_RATE."""
+    return getattr(config, 'CLA_LEARNINIG_RATE', config.LEARNING_RATE)
+
+
+def check_mfma_dtype(config):
+    """config.MFMA_DTYPE ('f32' default | 'bf16' = BASELINE.json configs[3] "bf16 MFMA conv path": conv / deconv / dense operands rounded
+    to bf16 inside the MFMA kernels, fp32 accumulation, fp32 tensors, statistics, master weights and optimiser state)."""
+    mfma = opt(config, 'MFMA_DTYPE')
+    if mfma not in ('f32', 'bf16'):
+        raise ValueError("MFMA_DTYPE must be 'f32' or 'bf16', got %r" % (mfma,))
+    return mfma
+
+
+def check_act_dtype(config):
+    """config.ACT_DTYPE ('f32' default | 'bf16') checked against config.MFMA_DTYPE: bf16-stored activations are only the same numbers when
+    every reader rounds its operands to bf16 anyway — with fp32 MFMA operands they would silently stop being the reference's arithmetic."""
+    act, mfma = opt(config, 'ACT_DTYPE'), opt(config, 'MFMA_DTYPE')
+    if act not in ('f32', 'bf16'):
+        raise ValueError("ACT_DTYPE must be 'f32' or 'bf16', got %r" % (act,))
+    if act == 'bf16' and mfma != 'bf16':
+        raise ValueError("ACT_DTYPE = 'bf16' needs MFMA_DTYPE = 'bf16' (got %r): fp32 products of bf16-stored values would not be the "
+                         "fp32 arithmetic of the reference" % (mfma,))
+    return act
+
+
+LOSSES = ('GAN', 'WGAN_GP')
+
+
+def check_loss(config):
+    """config.LOSS ('GAN' default | 'WGAN_GP': the reference's _loss_WGAN_GP, train_base.py:576-620, in the three-player step).
+    Needs no device.  ValueError for an unknown value; lib.TgError for what the WGAN-GP step cannot run: bf16 MFMA operands (and with them
+    ACT_DTYPE = 'bf16'), minibatch discrimination, and a penalty batch whose real and fake halves differ in size."""
+    loss = opt(config, 'LOSS')
+    if loss not in LOSSES:
+        raise ValueError("LOSS must be one of %s, got %r" % (', '.join(repr(v) for v in LOSSES), loss))
+    if loss != 'WGAN_GP':
+        return loss
+    from tg import grad_penalty                       # (tg.runtime behind it imports torch: only on this branch)
+    grad_penalty.check_supported("LOSS = 'WGAN_GP'", opt(config, 'MFMA_DTYPE'), opt(config, 'MINIBATCH_DIS'))
+    l_d, u_d, b_g = (getattr(config, k, None) for k in ('BATCH_SIZE_L_D', 'BATCH_SIZE_U_D', 'BATCH_SIZE_G'))
+    if l_d is None or u_d is None or b_g is None or l_d + u_d != b_g:
+        raise lib.TgError("LOSS = 'WGAN_GP' needs BATCH_SIZE_L_D + BATCH_SIZE_U_D == BATCH_SIZE_G (got %r + %r, %r): the penalty "
+                          "interpolates the discriminator's real images X_P with the generated ones image for image" % (l_d, u_d, b_g))
+    return loss
+
+
+OPTIMIZERS = ('adam', 'rmsprop', 'momentum')
+
+
+def check_optimizer(config):
+    """config.OPTIMIZER ('adam' default | 'rmsprop' | 'momentum', or a 3-tuple of them for the (D, G, C) networks) -> the
+    normalised triple (d, g, c).  Needs no device.  ValueError for an unknown name, a tuple that does not have three entries, or any
+    other type."""
+    kind = opt(config, 'OPTIMIZER')
+    names = ', '.join(repr(v) for v in OPTIMIZERS)
+    if isinstance(kind, str):
+        triple = (kind,) * 3
+    elif isinstance(kind, (tuple, list)):
+        if len(kind) != 3:
+            raise ValueError("OPTIMIZER as a tuple names the optimisers of (D, G, C): three of %s, got %d entries: %r" % (names, len(kind), kind))
+        triple = tuple(kind)
+    else:
+        raise ValueError("OPTIMIZER must be one of %s or a 3-tuple (D, G, C) of them, got %r" % (names, kind))
+    for v in triple:
+        if not isinstance(v, str) or v not in OPTIMIZERS:
+            raise ValueError("OPTIMIZER must be one of %s or a 3-tuple (D, G, C) of them, got %r" % (names, kind))
+    return triple
+
+
+def check_clip_norm(config):
+    """config.CLIP_NORM (None default | a positive float | a 3-tuple for the (D, G, C) networks of positive floats or None)
+    -> the normalised triple (d, g, c) of floats / None.  Needs no device.  ValueError for zero, a negative number, NaN or infinity, a
+    tuple that does not have three entries, and anything that is not a number."""
+    clip = opt(config, 'CLIP_NORM')
+
+    def one(v):
+        if v is None:
+            return None
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (0.0 < float(v) < float('inf')):
+            raise ValueError("CLIP_NORM must be None, a positive finite number or a 3-tuple (D, G, C) of them, got %r" % (clip,))
+        return float(v)
+
+    if isinstance(clip, (tuple, list)):
+        if len(clip) != 3:
+            raise ValueError("CLIP_NORM as a tuple holds the thresholds of (D, G, C): three positive numbers or None, got %d entries: %r"
+                             % (len(clip), clip))
+        return tuple(one(v) for v in clip)
+    return (one(clip),) * 3
+
+
+NETS = ('discriminator', 'good_generator', 'classifier')      # the order of every (D, G, C) triple
+
+
+NUM_CLASSES_RANGE = (2, 1024)
+
+
+def check_num_classes(config):
+    """config.NUM_CLASSES: an int in 2..1024, the range of the classifier's loss heads (csrc/loss.hip; 10 runs the ten-class kernels, any
+    other count the general ones).  Needs no device; ValueError outside it."""
+    k = opt(config, 'NUM_CLASSES')
+    lo, hi = NUM_CLASSES_RANGE
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not lo <= k <= hi:
+        raise ValueError("NUM_CLASSES must be an integer in %d..%d (the classifier's loss heads), got %r" % (lo, hi, k))
+    return int(k)
+
+
+def check_zca(config, Dataset=None):
+    """config.ZCA: None (the reference's DATA_DIR/<data>_zca_*.npy files), (mean, mat) arrays, or 'fit' (fitted from the
+    training split by Train.train and written to those files).  Needs no device.  ValueError for any other string; lib.TgError when
+    'fit' meets a model without ZCA whitening (DATA_NAME not cifar10 / cifar100: MNIST, SVHN, stress64) or a Dataset (class or instance)
+    that is not a uint8 TFRecord source in [-1, 1] scaling, e.g. the default syntheticDataset."""
+    zc = opt(config, 'ZCA')
+    if not isinstance(zc, str):
+        return zc
+    if zc != 'fit':
+        raise ValueError("ZCA must be None, (mean, mat) arrays or 'fit', got %r" % (zc,))
+    from Model.Good_GAN_cifar10 import ZCA_DATA
+    if opt(config, 'DATA_NAME') not in ZCA_DATA:
+        raise lib.TgError("ZCA = 'fit' applies to the ZCA-whitened classifiers of %s; DATA_NAME %r has no ZCA whitening"
+                          % (' / '.join(ZCA_DATA), opt(config, 'DATA_NAME')))
+    if Dataset is not None:
+        from Input_Pipeline.tfrecordDataset import tfrecordDataset
+        cls = Dataset if isinstance(Dataset, type) else type(Dataset)
+        if not issubclass(cls, tfrecordDataset) or cls.UNIT_RANGE:
+            raise lib.TgError("ZCA = 'fit' needs a training split of uint8 TFRecords (a tfrecordDataset such as cifar10Dataset); %s has "
+                              "none" % cls.__name__)
+    return zc
+
+
+Options = collections.namedtuple('Options', 'mfma_dtype act_dtype num_classes loss optimizers clip_norms momentum seed no_grad_buckets '
+                                            'summary summary_scalar summary_histogram summary_image summary_image_max_outputs')
+
+
+def resolve(config):
+    """every device-free check of `config`, once -> the Options record of what Train reads with a default (EXEC_MODE / USE_HIP_GRAPH
+    excepted: those stay live, read per iteration).  The string form of ZCA is checked here; against a Dataset, where one is known."""
+    check_zca(config)
+    return Options(mfma_dtype=check_mfma_dtype(config), act_dtype=check_act_dtype(config), num_classes=check_num_classes(config),
+                   loss=check_loss(config), optimizers=check_optimizer(config), clip_norms=check_clip_norm(config),
+                   momentum=float(opt(config, 'MOMENTUM')), seed=opt(config, 'SEED'),
+                   no_grad_buckets=bool(getattr(config, 'NO_GRAD_BUCKETS', False)),      # a debugging switch Config does not declare
+                   summary=bool(opt(config, 'SUMMARY')), summary_scalar=bool(opt(config, 'SUMMARY_SCALAR')),
+                   summary_histogram=bool(opt(config, 'SUMMARY_HISTOGRAM')), summary_image=bool(opt(config, 'SUMMARY_IMAGE')),
+                   summary_image_max_outputs=int(opt(config, 'SUMMARY_IMAGE_MAX_OUTPUTS')))

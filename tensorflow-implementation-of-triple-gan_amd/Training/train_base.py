@@ -15,10 +15,26 @@ Eager-mode conventions: a loss value is a 1-element DEVICE tensor (float(t) sync
 in `logits.grad` — written when the tensor has no gradient yet, ADDED when it has, so a loss summed from several heads accumulates
 its gradient the way TensorFlow's autodiff would; `weight` scales value and gradient.
 """
+import ctypes as C_
+
 import torch
 
 from tg import lib
+from tg.batching import concat_acts
 from tg.runtime import ctx
+
+
+def _launch_update(name, clip_name, args, factor_dev):
+    """launch optimiser kernel `name` on `args`, or its twin `clip_name` with the DEVICE scalar `factor_dev` added."""
+    if factor_dev is None:
+        lib.call(name, *args, ctx().stream)
+    else:
+        lib.call(clip_name, *args, lib.ptr(factor_dev), ctx().stream)
+
+
+def _k_head(name, name_k, k):
+    """(kernel, extra arguments) of a loss head over k classes: K = 10 keeps the ten-class launch `name`, else `name_k` takes k."""
+    return (name, ()) if k == 10 else (name_k, (k,))
 
 
 class StreamingAccuracy(object):
@@ -60,13 +76,9 @@ class AdamOptimizer(object):
 
     def apply(self, store, grad_scale=1.0, factor_dev=None):
         """factor_dev: DEVICE scalar the scaled gradient is multiplied by (the clip factor of tg_grad_norm_clip_f32); None = unclipped."""
-        cx = ctx()
         args = (lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.m), lib.ptr(store.v), store.n_p,
                 lib.ptr(self.lr_dev), self.beta1, self.beta2, self.epsilon, lib.ptr(store.step), grad_scale)
-        if factor_dev is None:
-            lib.call('tg_adam_f32', *args, cx.stream)
-        else:
-            lib.call('tg_adam_clip_f32', *args, lib.ptr(factor_dev), cx.stream)
+        _launch_update('tg_adam_f32', 'tg_adam_clip_f32', args, factor_dev)
 
 
 class MomentumOptimizer(object):
@@ -83,10 +95,7 @@ class MomentumOptimizer(object):
 
     def apply(self, store, grad_scale=1.0, factor_dev=None):
         args = (lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.m), store.n_p, lib.ptr(self.lr_dev), self.momentum, grad_scale)
-        if factor_dev is None:
-            lib.call('tg_momentum_f32', *args, ctx().stream)
-        else:
-            lib.call('tg_momentum_clip_f32', *args, lib.ptr(factor_dev), ctx().stream)
+        _launch_update('tg_momentum_f32', 'tg_momentum_clip_f32', args, factor_dev)
 
 
 class RMSPropOptimizer(object):
@@ -107,10 +116,7 @@ class RMSPropOptimizer(object):
     def apply(self, store, grad_scale=1.0, factor_dev=None):
         args = (lib.ptr(store.p), lib.ptr(store.g), lib.ptr(store.v), lib.ptr(store.m), store.n_p, lib.ptr(self.lr_dev),
                 self.decay, self.momentum, self.epsilon, grad_scale)
-        if factor_dev is None:
-            lib.call('tg_rmsprop_f32', *args, ctx().stream)
-        else:
-            lib.call('tg_rmsprop_clip_f32', *args, lib.ptr(factor_dev), ctx().stream)
+        _launch_update('tg_rmsprop_f32', 'tg_rmsprop_clip_f32', args, factor_dev)
 
 
 class GradViews(object):
@@ -283,26 +289,28 @@ class Train_base(object):
         """c_loss (train_base.py:118,130-152); rows of c_logits [real|unl|unl_rep|fake]."""
         cx = ctx()
         g = cx.new_act(c_logits.n, 1, 1, c_logits.c, c_logits.ld, tag='dl')
-        k = c_logits.c
-        head, kk = ('tg_c_loss_f32', ()) if k == 10 else ('tg_c_loss_k_f32', (k,))       # K = 10 keeps the ten-class launch
+        head, kk = _k_head('tg_c_loss_f32', 'tg_c_loss_k_f32', c_logits.c)
         lib.call(head, c_logits.ptr, c_logits.ld, n_real, n_unl, n_rep, n_fake, *kk, y_l_c.ptr, y_g.ptr,
                  d_unl_logits.ptr, d_unl_logits.ld, lib.ptr(lambdas_dev), g.ptr, g.ld, lib.ptr(loss_out), cx.stream)
         c_logits.grad = g
+
+    @staticmethod
+    def _lambda_dev(Lambda):
+        """Lambda = [lambda_1(, lambda_2)] as the device pair the loss heads read: a device tensor as it is, numbers copied to one."""
+        if isinstance(Lambda, torch.Tensor):
+            return Lambda
+        vals = [float(v) for v in Lambda] + [0.0, 0.0]
+        lam = ctx().scratch('loss_lambda', 2)
+        lam.copy_(torch.tensor(vals[:2], dtype=torch.float32))
+        return lam
 
     def _loss_GAN(self, D, C, Y, Lambda):
         """train_base.py:113-154 on the outputs of Model.forward_pass, the reference's arguments:
         D = [D_real, D_real_logits, D_fake, D_fake_logits, D_unl, D_unl_logits]; C = [C_real_logits, C_unl_logits, C_unl_d_logits,
         C_fake_logits(, C_unl_logits_rep — config.DATA_NAME 'cifar10')]; Y = [y_g, y_l_c]; Lambda = [lambda_1(, lambda_2)] as numbers or
         a device tensor.  Returns (d_loss, g_loss, c_loss), 1-element device tensors."""
-        from tg.batching import concat_acts
-        cx = ctx()
-        loss_out = cx.scratch('loss_gan', 4)
-        if isinstance(Lambda, torch.Tensor):
-            lam = Lambda
-        else:
-            vals = [float(v) for v in Lambda] + [0.0, 0.0]
-            lam = cx.scratch('loss_lambda', 2)
-            lam.copy_(torch.tensor(vals[:2], dtype=torch.float32))
+        loss_out = ctx().scratch('loss_gan', 4)
+        lam = self._lambda_dev(Lambda)
         _, d_real, _, d_fake, _, d_unl = D
         dcat = concat_acts([d_real, d_fake, d_unl])
         self._d_loss(dcat, d_real.n, d_fake.n, d_unl.n, loss_out[0:1])
@@ -327,10 +335,6 @@ class Train_base(object):
     def _variant_terms(self, D, c_real, c_unl, c_rep, c_gfake, c_bfake, c_pert, f_bfake, f_unl, y_l_c, y_g, w6, w_bad, w_pert, pt):
         """runs the term kernels; returns the host array [d, d_real, d_fake, d_unl, gG, c_head, T_real, T_unl, T_H, T_bal, T_gfake, T_mse,
         tf_w, T_bad_unl, T_bfake, sq_w, T_sq, fm, pt]."""
-        import ctypes as C
-        import torch
-        from tg.batching import concat_acts
-        from tg.runtime import Act
         cx = ctx()
         lv = torch.zeros(24, dtype=torch.float32, device=cx.device)
         P = lambda i: lib.ptr(lv[i:])
@@ -352,9 +356,9 @@ class Train_base(object):
         n_rep = c_rep.n if c_rep is not None else 0
         n_gf = c_gfake.n if c_gfake is not None else 0
         k = ccat.c
-        head, kk = ('tg_c_loss_terms_f32', ()) if k == 10 else ('tg_c_loss_terms_k_f32', (k,))
+        head, kk = _k_head('tg_c_loss_terms_f32', 'tg_c_loss_terms_k_f32', k)
         lib.call(head, ccat.ptr, ccat.ld, c_real.n, c_unl.n, n_rep, n_gf, *kk, y_l_c.ptr, y_g.ptr if c_gfake is not None else None,
-                 d_unl.ptr if d_unl is not None else None, d_unl.ld if d_unl is not None else 0, (C.c_float * 6)(*w6), g.ptr, g.ld, P(5), P(6),
+                 d_unl.ptr if d_unl is not None else None, d_unl.ld if d_unl is not None else 0, (C_.c_float * 6)(*w6), g.ptr, g.ld, P(5), P(6),
                  cx.stream)
         ccat.grad = g
         off = 0
@@ -365,7 +369,7 @@ class Train_base(object):
         gb = cx.new_act(c_bfake.n, 1, 1, c_bfake.c, c_bfake.ld, tag='dl')
         unl_rows = ccat.view_rows(c_real.n, c_real.n + c_unl.n)
         assert c_bfake.c == k, (c_bfake.c, k)
-        head = 'tg_true_fake_loss_f32' if k == 10 else 'tg_true_fake_loss_k_f32'
+        head, _ = _k_head('tg_true_fake_loss_f32', 'tg_true_fake_loss_k_f32', k)
         lib.call(head, unl_rows.ptr, ccat.ld, c_unl.n, c_bfake.ptr, c_bfake.ld, c_bfake.n, *kk, w_bad, w_bad, g_unl.ptr, g_unl.ld, 1,
                  gb.ptr, gb.ld, 0, P(12), cx.stream)
         c_bfake.grad = gb
@@ -499,8 +503,6 @@ class Train_base(object):
         Gradients: self.last_d_cat.grad <- d_loss w.r.t. the [real | fake | unl] logits (without the penalty), D_fake_logits.grad <-
         g_loss, the three classifier logit tensors' .grad <- c_loss, and self.last_gp_grad <- 10 d gp / d theta_D (add it to the
         discriminator's store.g after its backward pass: _add_gp_grad)."""
-        import ctypes as C_
-        from tg.batching import concat_acts
         if len(D) == 9:
             _, d_real, _, _, d_fake, _, _, d_unl, _ = D
         elif len(D) == 6:
@@ -523,7 +525,7 @@ class Train_base(object):
         ccat = concat_acts([c_real, c_unl, c_fake])                  # tg_c_loss_terms_f32 rows [real | unl | fake]; the unl terms weigh 0
         gc = cx.new_act(ccat.n, 1, 1, ccat.c, ccat.ld, tag='dl')
         k = ccat.c
-        head, kk = ('tg_c_loss_terms_f32', ()) if k == 10 else ('tg_c_loss_terms_k_f32', (k,))
+        head, kk = _k_head('tg_c_loss_terms_f32', 'tg_c_loss_terms_k_f32', k)
         lib.call(head, ccat.ptr, ccat.ld, c_real.n, c_unl.n, 0, c_fake.n, *kk, Y.ptr, Y.ptr, None, 0,
                  (C_.c_float * 6)(1.0, 0.0, 0.0, 0.0, lam2, 0.0), gc.ptr, gc.ld, P(5), P(6), cx.stream)
         ccat.grad = gc
@@ -575,15 +577,8 @@ class Train_base(object):
         Y = [y_g, y_l_c] (the penalty's labels are y_g); Lambda: device pair or numbers.  Returns (d_loss, g_loss, c_loss), 1-element device
         tensors — the penalty runs in the caller's phase (discriminator_gradient_penalty(in_step=True)); its parameter gradient is left in
         self.last_gp_grad."""
-        from tg.batching import concat_acts
-        cx = ctx()
-        loss_out = cx.scratch('loss_wgan', 4)
-        if isinstance(Lambda, torch.Tensor):
-            lam = Lambda
-        else:
-            vals = [float(v) for v in Lambda] + [0.0, 0.0]
-            lam = cx.scratch('loss_lambda', 2)
-            lam.copy_(torch.tensor(vals[:2], dtype=torch.float32))
+        loss_out = ctx().scratch('loss_wgan', 4)
+        lam = self._lambda_dev(Lambda)
         _, d_real, _, d_fake, _, d_unl = D
         y_g, y_l_c = Y
         gp_w, self.last_gp_grad = self._gp_sweeps(discriminator)(X, G, y_g, self.GP_WEIGHT, in_step=True)

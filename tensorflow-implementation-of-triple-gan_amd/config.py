@@ -1,5 +1,6 @@
 """Base configuration class — same attribute names as the reference's config.py:9-93
-(including its spellings, e.g. CLA_LEARNINIG_RATE is set by the experiment configs)."""
+(including its spellings, e.g. CLA_LEARNINIG_RATE is set by the experiment configs).  The defaults written here are the only ones: the
+trainer reads a config through Training/options.py, which falls back to this class for an attribute a config object lacks."""
 
 
 class Config(object):
