@@ -105,7 +105,7 @@ def _wn_layer(x, num_out, k, pad, stride, nonlinearity, init_scale, init, use_we
     if use_weight_normalization and init:
         # x_init = conv(x, l2_normalize(V)); scale_init*(x_init - m_init)   (nn.py:494-500,545-551) — forward only
         ones = cx.ws('const:ones', max(num_out, 1024))
-        ops._call('tg_fill_f32', ops._p(ones), 1.0, ones.numel(), cx.stream)
+        ops.fill(ones, 1.0)
         with cx.no_record():
             y = ops.conv2d(x, V, None, num_out, k, stride, pad, wn=(ones, None))
             y = ops.moments_normalize(y, init_eps, init_scale)
@@ -182,7 +182,7 @@ def _salimans(x, num_out, k, stride, pad, nonlinearity, init_scale, init, ema, i
     a = _tg_act(nonlinearity)
     if init:
         ones = cx.ws('const:ones', max(num_out, 1024))
-        ops._call('tg_fill_f32', ops._p(ones), 1.0, ones.numel(), cx.stream)
+        ops.fill(ones, 1.0)
         with cx.no_record():
             if transposed:
                 y = ops.deconv2d(x, V, None, num_out, wn=(ones, None))

@@ -91,20 +91,16 @@ def _filter_prep(cx, st, row, t, c_in):
     row (as ops.conv2d(wn=...)), the kernel itself for a plain one."""
     c_out = row.cout
     ci_p, co_p = pad32(c_in), pad32(c_out)
-    scale = None
-    if row.g is not None:
-        scale = cx.scratch('wns', c_out)
-        lib.call('tg_wn_scale_f32', lib.ptr(st.value(row.w)), lib.ptr(st.value(row.g)), t * c_in, c_out, lib.ptr(scale), cx.stream)
+    scale = cx.scratch('wns', c_out) if row.g is not None else None
     w_oti, w_hwio = cx.scratch('woti', co_p * t * ci_p), cx.scratch('whwio', t * ci_p * co_p)
-    lib.call('tg_filter_prep_f32', lib.ptr(st.value(row.w)), lib.ptr(scale), None, t, c_in, c_out, ci_p, co_p, lib.ptr(w_hwio), lib.ptr(w_oti),
-             t * ci_p, ci_p, cx.stream)
+    ops.prep_filter(cx, st.value(row.w), st.value(row.g) if row.g is not None else None, scale, w_oti, w_hwio, t, c_in, c_out, ci_p, co_p)
     return w_oti, w_hwio
 
 
 def _filter_grad(cx, st, grad, row, desc, t_in, dpre, t, c_in):
     """sweep 4 of one layer: dW_eff = wgrad(t_in, dpre) (desc: its geometry; None: the head, dpre = 1 per image, dW_eff = column sums of
     t_in).  A plain row's goes straight to the store offset of its kernel in `grad`; a weight-normalised row's to scratch, then dV, dg
-    (tg_wn_bwd_f32) to the store offsets of .../V and .../g."""
+    (ops.filter_grad_tail: tg_wn_bwd_f32) to the store offsets of .../V and .../g."""
     c_out = row.cout
     ow = st.offset(row.w)
     dw, wn = grad[ow:ow + t * c_in * c_out], None
@@ -116,10 +112,7 @@ def _filter_grad(cx, st, grad, row, desc, t_in, dpre, t, c_in):
         ops.filter_grad(desc, t_in.t, dpre.t, t, c_in, c_out, dw, wn=wn, defer=False)
         return
     ops.colstats(0, t_in.t, t_in.ld, None, 0, t_in.rows, c_in, [t_in.rows], s1=dw)
-    if wn is not None:
-        coef = cx.scratch('coef', 2 * c_out)
-        lib.call('tg_wn_bwd_f32', lib.ptr(dw), lib.ptr(wn[0]), lib.ptr(wn[1]), t * c_in, c_out, lib.ptr(wn[2]), lib.ptr(wn[3]), lib.ptr(coef),
-                 cx.stream)
+    ops.filter_grad_tail(cx, dw, t, c_in, c_out, wn)
 
 
 def _label_copies(cx, y, copies):

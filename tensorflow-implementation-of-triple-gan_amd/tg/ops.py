@@ -2,7 +2,9 @@
 Model/model_base.py compose.  Every function launches tg_* kernels through the C ABI on the
 context's stream and, when a tape is active, records a closure producing the input / variable
 gradients.  Gradient of an activation `a` lives in `a.grad` (an Act of identical layout)."""
+import contextlib
 import ctypes as C
+import types
 
 import torch
 
@@ -10,8 +12,10 @@ from . import geom, lib
 from .lib import ACT
 from .runtime import Act, ctx, pad32, seg_array
 
-_MFMA_F32 = ('tg_igemm_f32', 'tg_igemm_multi_f32', 'tg_igemm_colsum_f32', 'tg_igemm_actsum_f32', 'tg_igemm_bnstat_f32', 'tg_igemm_bnbwdstat_f32', 'tg_wgrad_f32',
-             'tg_igemm_labels_f32')
+_BF16_ENTRY = {'tg_igemm_f32': 'tg_igemm_bf16', 'tg_igemm_multi_f32': 'tg_igemm_multi_bf16', 'tg_igemm_colsum_f32': 'tg_igemm_colsum_bf16',
+               'tg_igemm_actsum_f32': 'tg_igemm_actsum_bf16', 'tg_igemm_bnstat_f32': 'tg_igemm_bnstat_bf16',
+               'tg_igemm_bnbwdstat_f32': 'tg_igemm_bnbwdstat_bf16', 'tg_igemm_labels_f32': 'tg_igemm_labels_bf16', 'tg_wgrad_f32': 'tg_wgrad_bf16'}
+_TAKES_SCRATCH = {n for n in list(_BF16_ENTRY) + list(_BF16_ENTRY.values()) + ['tg_igemm_bf16in_bf16', 'tg_igemm_bnstat_bf16in_bf16'] if 'igemm' in n}
 
 
 def _call(name, *args):
@@ -20,12 +24,10 @@ def _call(name, *args):
     sized by tg_igemm_workspace_bytes — the partial sums of tiles the schedule cuts along K, the packed bf16 filter of the 3x3 kernel —
     one buffer per call site like every other workspace; callers here pass the arguments WITHOUT it."""
     cx = ctx()
-    if name in _MFMA_F32:
-        bf16 = cx.mfma_dtype == 'bf16'
-        if bf16:
-            name = name[:-3] + 'bf16'
-        if not name.startswith('tg_wgrad'):
-            args = igemm_scratch(cx, name, args, bf16)
+    if cx.mfma_dtype == 'bf16':
+        name = _BF16_ENTRY.get(name, name)
+    if name in _TAKES_SCRATCH:
+        args = igemm_scratch(cx, name, args, cx.mfma_dtype == 'bf16')
     return lib.call(name, *args)
 
 
@@ -40,6 +42,11 @@ def _p(t):
     if t is not None and t.dtype == torch.bfloat16:
         raise lib.TgError("a bf16-stored tensor was handed to a launch that reads fp32")
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def fill(t, value):
+    """t[:] = value on the context's stream."""
+    _call('tg_fill_f32', _p(t), float(value), t.numel(), ctx().stream)
 
 
 def require_f32(x, op):
@@ -61,8 +68,7 @@ def _single_consumer(y, gy):
 
 def _segs(x, segments):
     """per-application image counts -> row counts of the batched activation."""
-    if segments is None:
-        segments = [x.n]
+    segments = [x.n] if segments is None else segments
     assert sum(segments) == x.n, (segments, x.n)
     per = x.h * x.w
     return [s * per for s in segments]
@@ -84,6 +90,15 @@ def colstats(mode, a_t, ld_a, b_t, ld_b, rows, c, seg_rows, act=None, alpha=0.2,
     return s1, s2
 
 
+# ------------------------------------------------------------------ filter preparation (MFMA layouts + weight-norm scale)
+
+def prep_filter(cx, kernel, g, scale, w_oti, w_hwio, t, c_in, c_out, ci_p, co_p):
+    """[scale = g/||V||, then] the [scaled] filter as OTI [co_p][t][ci_p] and HWIO [t][ci_p][co_p] (or None) into the caller's buffers, uncached."""
+    if g is not None:
+        _call('tg_wn_scale_f32', _p(kernel), _p(g), t * c_in, c_out, _p(scale), cx.stream)
+    _call('tg_filter_prep_f32', _p(kernel), _p(scale), None, t, c_in, c_out, ci_p, co_p, _p(w_hwio), _p(w_oti), t * ci_p, ci_p, cx.stream)
+
+
 def _run_prep_plan(cx, plan):
     """tg_filter_prep_multi_f32 for the recorded layers that are not prepared yet; every result goes into the cache tagged with the
     scratch count its layer would have consumed, so that call-site numbering stays what it was in the recording pass."""
@@ -99,6 +114,48 @@ def _run_prep_plan(cx, plan):
         cx.prep_cache[j['key']] = (j['scale'], j['w_oti'], j['w_hwio'], j['bump'], cx.phase)
 
 
+def _prepared_filter(cx, kernel, g, t, c_in, c_out, ci_p, co_p, needs_x):
+    """(scale, w_oti, w_hwio) of a convolution's filter.  Inside Train.train_iteration the result is kept per variable until that network's
+    optimiser step: the classifier is prepared once for the D-update's forward passes and the C-update, the discriminator once for the
+    G- and C-updates (Context.prep_cache; None outside train_iteration: no caching); a recorded sequence is prepared by its first layer."""
+    cache = cx.prep_cache
+    key = ('conv', kernel.data_ptr(), g.data_ptr() if g is not None else 0, t, c_in, c_out, ci_p, co_p)
+    ent = cache.get(key) if cache is not None else None
+    if ent is None and cache is not None:
+        plan = cx.prep_plans.get((cx.plan_tag, cx.phase, key))
+        if plan is not None:                               # this layer opens a recorded sequence: prepare all of its layers now
+            _run_prep_plan(cx, plan)
+            ent = cache.get(key)
+    if ent is not None and (ent[2] is not None or not needs_x):
+        if len(ent) > 3:                                   # produced by a plan in this phase: keep the call-site numbering of the
+            if ent[4] == cx.phase:                         # recording pass, in which this layer allocated its own buffers here
+                cx.counter += ent[3]
+            cache[key] = ent[:3]
+        return ent[:3]
+    c_before = cx.counter
+    w_oti = cx.scratch('woti', co_p * t * ci_p)
+    w_hwio = cx.scratch('whwio', t * ci_p * co_p) if (needs_x or cache is not None) else None
+    scale = cx.scratch('wns', c_out) if g is not None else None
+    prep_filter(cx, kernel, g, scale, w_oti, w_hwio, t, c_in, c_out, ci_p, co_p)
+    if cache is not None:
+        cache[key] = (scale, w_oti, w_hwio)
+        if cx._prep_rec is not None and w_hwio is not None:
+            cx._prep_rec.append(dict(key=key, kernel=kernel, g=g, scale=scale, w_oti=w_oti, w_hwio=w_hwio,
+                                     t=t, a=c_in, b=c_out, a_pad=ci_p, b_pad=co_p, bump=cx.counter - c_before))
+    return scale, w_oti, w_hwio
+
+
+# ------------------------------------------------------------------ filter gradient
+
+def filter_grad_tail(cx, dst, t, c_dim, n_dim, wn, slab=None, ns=0, desc=None):
+    """finish a filter gradient NOW: sum the `ns` slabs into dst (slab None: dst holds the sum), then, wn=(v, g, dv, dg), the variables' gradient."""
+    if slab is not None:
+        _call('tg_slab_reduce_f32', _p(slab), ns, t, desc.ld_in, desc.c_out, c_dim, n_dim, _p(dst), cx.stream)
+    if wn is not None:
+        coef = cx.scratch('coef', 2 * n_dim)
+        _call('tg_wn_bwd_f32', _p(dst), _p(wn[0]), _p(wn[1]), t * c_dim, n_dim, _p(wn[2]), _p(wn[3]), _p(coef), cx.stream)
+
+
 def filter_grad(desc, in_act_t, dout_t, t, c_dim, n_dim, dst, wn=None, defer=True, in16=False):
     """dst[t][c_dim][n_dim] = filter gradient via tg_wgrad_f32 slabs + deterministic reduce.
     wn=(v, g, dv, dg): weight-normalised layer — dst is the gradient of the effective filter (scratch), dv / dg the variables'.
@@ -106,47 +163,167 @@ def filter_grad(desc, in_act_t, dout_t, t, c_dim, n_dim, dst, wn=None, defer=Tru
     boundary), where the tails of all layers go out as three launches; the 512-split first convolution keeps its own reduce.
     in16: in_act_t is a bf16-stored activation (tg_wgrad_bf16in_bf16)."""
     cx = ctx()
-
-    def wgrad(slab, ns):
-        if in16:
-            lib.call('tg_wgrad_bf16in_bf16', desc, C.c_void_p(in_act_t.data_ptr()), _p(dout_t), _p(slab), ns, cx.stream)
-        else:
-            _call('tg_wgrad_f32', desc, _p(in_act_t), _p(dout_t), _p(slab), ns, cx.stream)
-
     ns = geom.wgrad_splits(desc, cx.mfma_dtype == 'bf16')      # pixel split and slab size: the library's rule (tg_wgrad_splits[_bf16])
     slab = cx.scratch('slab', geom.wgrad_slab_floats(desc, ns))
     deferred = defer and (cx.tape is not None or cx._phase_depth > 0)
     small = desc.n_img * desc.h_v * desc.w_v * desc.ld_in * desc.c_out * desc.n_taps < (1 << 34)      # < 34 GFLOP: the generic kernel's launches
     wide = ns >= 32 and t * c_dim * n_dim <= 65536
-    if deferred and (small or cx.wgrad_side) and not wide:
-        with cx.wgrad_on_side():                                 # beside the input-gradient chain (Context.wgrad_on_side; joined in flush_tails)
-            wgrad(slab, ns)
-    elif deferred and small and wide:
-        # many splits of a small filter (the discriminator's first layers, the classifier's first): the launch AND its own reduction go to
-        # the second stream, so the input-gradient chain does not wait for them (round 4: they were 0.18 ms of the D-update's launch stream)
-        with cx.wgrad_on_side():
-            wgrad(slab, ns)
-            _call('tg_slab_reduce_f32', _p(slab), ns, t, desc.ld_in, desc.c_out, c_dim, n_dim, _p(dst), cx.stream)
-            if wn is not None:
-                coef = cx.scratch('coef', 2 * n_dim)
-                _call('tg_wn_bwd_f32', _p(dst), _p(wn[0]), _p(wn[1]), t * c_dim, n_dim, _p(wn[2]), _p(wn[3]), _p(coef), cx.stream)
-        return
-    else:
-        wgrad(slab, ns)
-    if deferred and not wide:
-        coef = cx.scratch('coef', 2 * n_dim) if wn is not None else None
-        j = lib.WnJob(slab.data_ptr(), dst.data_ptr(), wn[0].data_ptr() if wn else None, wn[1].data_ptr() if wn else None,
-                      wn[2].data_ptr() if wn else None, wn[3].data_ptr() if wn else None, coef.data_ptr() if wn else None,
-                      ns, t, desc.ld_in, desc.c_out, c_dim, n_dim)
-        cx.tail_jobs.append(j)
-        return
-    _call('tg_slab_reduce_f32', _p(slab), ns, t, desc.ld_in, desc.c_out, c_dim, n_dim, _p(dst), cx.stream)
-    if wn is not None:
-        coef = cx.scratch('coef', 2 * n_dim)
-        _call('tg_wn_bwd_f32', _p(dst), _p(wn[0]), _p(wn[1]), t * c_dim, n_dim, _p(wn[2]), _p(wn[3]), _p(coef), cx.stream)
+    side = deferred and (small if wide else (small or cx.wgrad_side))      # beside the input-gradient chain (Context.wgrad_on_side; joined in flush_tails)
+    with cx.wgrad_on_side() if side else contextlib.nullcontext():
+        src = C.c_void_p(in_act_t.data_ptr()) if in16 else _p(in_act_t)
+        _call('tg_wgrad_bf16in_bf16' if in16 else 'tg_wgrad_f32', desc, src, _p(dout_t), _p(slab), ns, cx.stream)
+        if side and wide:
+            # many splits of a small filter (the discriminator's first layers, the classifier's first): the launch AND its own reduction go to
+            # the second stream, so the input-gradient chain does not wait for them (round 4: they were 0.18 ms of the D-update's launch stream)
+            return filter_grad_tail(cx, dst, t, c_dim, n_dim, wn, slab, ns, desc)
+    if not (deferred and not wide):
+        return filter_grad_tail(cx, dst, t, c_dim, n_dim, wn, slab, ns, desc)
+    coef = cx.scratch('coef', 2 * n_dim) if wn is not None else None
+    cx.tail_jobs.append(lib.WnJob(slab.data_ptr(), dst.data_ptr(), wn[0].data_ptr() if wn else None, wn[1].data_ptr() if wn else None,
+                                  wn[2].data_ptr() if wn else None, wn[3].data_ptr() if wn else None, coef.data_ptr() if wn else None,
+                                  ns, t, desc.ld_in, desc.c_out, c_dim, n_dim))
 
 
 # ------------------------------------------------------------------ conv / dense (plain and weight-normalised)
+
+def _conv_route(cx, L, bn_stats, n_store_ld):
+    """the forward route (_fwd_*) of a conv2d layer: the eligibility predicates, evaluated once (the backward reads L.packed, L.narrow_mobn)"""
+    simple_act = L.act in (None, 'relu', 'lrelu')
+    L.packed = (cx.mfma_dtype != 'bf16' and L.k == 3 and L.stride == 1 and L.padding == 'SAME' and L.wn is None and L.mobn is None and not bn_stats
+                and n_store_ld is None and L.c_out == L.co_p and simple_act and L.c_in <= 16
+                and bool(_call('tg_conv3x3_packed_supported', L.x.n, L.x.h, L.x.w, L.c_in, L.c_out)))
+    if L.narrow_mobn and L.train and L.stride == 1 and geom.colsum_supported(L.d, L.seg_rows):
+        return _fwd_colsum
+    if (bn_stats and L.mobn is None and simple_act and L.c_out == L.co_p == L.ld_out and len(L.seg_rows) <= 8
+            and geom.colsum_supported(L.d, L.seg_rows)):
+        return _fwd_bnstat
+    return _fwd_packed if L.packed else _fwd_labels if L.fuse_cat else _fwd_plain
+
+
+def _fwd_colsum(cx, L):
+    """convolution + per-(application, channel) sums in one launch, then ONE apply pass (mean, +b, activation, pop_mean [, 2x2 pool: returned])"""
+    x, y, seg_rows, c_out = L.x, L.y, L.seg_rows, L.c_out
+    b, b_grad, pop = L.mobn
+    sums, zd = cx.zscratch('cs64', 2 * len(seg_rows) * c_out)     # fp64 accumulators
+    _call('tg_igemm_colsum_f32', L.d, x.ptr, _p(L.w_oti), y.ptr, seg_array(seg_rows), len(seg_rows), _p(sums), zd, cx.stream)
+    if L.pool is not None and y.h % 2 == 0 and y.w % 2 == 0 and all(r % (y.h * y.w) == 0 for r in seg_rows):
+        pooled = cx.new_act(y.n, y.h // 2, y.w // 2, c_out, L.co_p, requires_grad=L.needs_w or L.needs_x)
+        _call('tg_mobn_apply_pool_f32', y.ptr, y.ld, y.n, y.h, y.w, c_out, seg_array(seg_rows), len(seg_rows), _p(sums), _p(b), _p(pop), 0.9, ACT[L.act],
+              L.alpha, pooled.ptr, pooled.ld, _p(L.pool[0]), c_out, L.pool[1], cx.stream)
+        return pooled
+    _call('tg_mobn_apply_f32', y.ptr, y.ld, y.rows, c_out, seg_array(seg_rows), len(seg_rows), _p(sums), _p(b), _p(pop), 0.9, ACT[L.act],
+          L.alpha, cx.stream)
+
+
+def _fwd_bnstat(cx, L):
+    seg_rows = L.seg_rows
+    bsum, zd = cx.zscratch('bn64', 32 * len(seg_rows) * L.c_out)     # the batch norm's buffer: 8 replicas x nseg x 2 x c doubles
+    _call('tg_igemm_bnstat_bf16in_bf16' if L.x16 else 'tg_igemm_bnstat_f32', L.d, L.x.ptr, _p(L.w_oti), _p(L.bias), L.y.ptr, seg_array(seg_rows),
+          len(seg_rows), _p(bsum), zd, cx.stream)
+    L.y.bn_sums = (bsum, tuple(seg_rows))
+
+
+def _fwd_packed(cx, L):
+    """K-packed products straight from the [3,3,Cin,Cout] variable (csrc/packed_conv.hip); with concat the label channels ride along"""
+    x, lab = L.x, L.concat if L.fuse_cat else (None, 0)
+    _call('tg_conv3x3_packed_fwd_f32', x.ptr, x.ld, L.c_in, _p(L.kernel), _p(L.bias), ACT[L.act], L.alpha, _p(lab[0]), lab[1], L.y.ptr, L.ld_out,
+          x.n, x.h, x.w, L.c_out, cx.stream)
+
+
+def _fwd_labels(cx, L):
+    _call('tg_igemm_labels_f32', L.d, L.x.ptr, _p(L.w_oti), _p(L.bias), _p(L.concat[0]), L.concat[1], L.y.ptr, cx.stream)
+
+
+def _fwd_plain(cx, L):
+    _call('tg_igemm_bf16in_bf16' if L.x16 else 'tg_igemm_f32', L.d, L.x.ptr, _p(L.w_oti), (_p(L.bias) if L.mobn is None else None), L.y.ptr, cx.stream)
+
+
+def _mobn_unfused(cx, src, dst, c, seg_rows, b, pop, decay, train, act=None, alpha=0.0):
+    """dst = act(src - mean_seg + b) (training: statistics pass, pop updated) or act(src - pop + b): shift, then one apply pass"""
+    sums = None
+    if train:
+        sums, _ = colstats(0, src.t, src.ld, None, 0, src.rows, c, seg_rows)
+    shift = cx.scratch('shift', len(seg_rows) * c)
+    _call('tg_mobn_finalize_f32', _p(sums), seg_array(seg_rows), len(seg_rows), src.rows, c, _p(b), _p(pop), decay, 1 if train else 0, _p(shift), cx.stream)
+    _call('tg_seg_scale_shift_act_f32', src.ptr, src.ld, dst.ptr, dst.ld, src.rows, c, c, seg_array(seg_rows), len(seg_rows),
+          None, _p(shift), ACT[act], alpha, cx.stream)
+
+
+def _dpre_plain(cx, y, gy, act, alpha, c_out, co_p, bias_grad, head=False):
+    """pre-activation gradient [rows][co_p] of y = act(pre + bias) from gy = y.grad, and the bias gradient (None: not wanted).  gy itself where a
+    batch norm behind the layer already made it that (Act.grad_is_dpre) or — head: conv2d only — the loss head wrote a padded dlogits."""
+    if head and act is None and gy.ld == co_p:
+        if bias_grad is not None:
+            colstats(0, gy.t, co_p, None, 0, y.rows, c_out, [y.rows], s1=bias_grad)
+        return gy.t
+    if y.grad_is_dpre and gy.ld == co_p:
+        return gy.t
+    dpre = cx.scratch('dpre', y.rows * co_p)
+    if bias_grad is not None and co_p <= 1024:
+        zs, zd = cx.zscratch('ab64', 16 * c_out)
+        _call('tg_actgrad_bias_f32', gy.ptr, gy.ld, y.ptr if act else None, y.ld, _p(dpre), co_p, y.rows, c_out, ACT[act], alpha,
+              _p(zs), zd, _p(bias_grad), cx.stream)
+    else:
+        _call('tg_actgrad_f32', gy.ptr, gy.ld, y.ptr if act else None, y.ld, None, 0, 1.0, _p(dpre), co_p, y.rows, c_out,
+              ACT[act], alpha, cx.stream)
+        if bias_grad is not None:
+            colstats(0, dpre, co_p, None, 0, y.rows, c_out, [y.rows], s1=bias_grad)
+    return dpre
+
+
+def _dpre_mobn(cx, L, gy):
+    y, seg_rows, c_out, co_p = L.y, L.seg_rows, L.c_out, L.co_p
+    nseg = len(seg_rows)
+    dpre = cx.scratch('dpre', y.rows * co_p)
+    if y.grad_fused is not None:
+        # the consumer's input-gradient launch already stored t = dy*act'(y) in y.grad and summed its columns per application
+        db = L.mobn[1] if L.needs_w else cx.scratch('db', c_out)
+        _call('tg_mobn_center_f32', gy.ptr, gy.ld, _p(dpre), co_p, y.rows, c_out, seg_array(seg_rows), nseg, _p(y.grad_fused[0]),
+              y.grad_fused[1], _p(db), cx.stream)
+    elif L.narrow_mobn:
+        db = L.mobn[1] if L.needs_w else cx.scratch('db', c_out)
+        sums64, zd = cx.zscratch('bs64', 16 * nseg * c_out)     # 8 replicas x nseg x c doubles
+        _call('tg_mobn_bwd_f32', gy.ptr, gy.ld, y.ptr, y.ld, _p(dpre), co_p, y.rows, c_out, seg_array(seg_rows), nseg,
+              ACT[L.act], L.alpha, _p(sums64), zd, _p(db), cx.stream)
+    else:
+        sums, _ = colstats(2, gy.t, gy.ld, y.t, y.ld, y.rows, c_out, seg_rows, L.act, L.alpha)
+        sh = cx.scratch('bshift', nseg * c_out)
+        db = L.mobn[1] if L.needs_w else cx.scratch('db', c_out)
+        _call('tg_mobn_bwd_finalize_f32', _p(sums), seg_array(seg_rows), nseg, y.rows, c_out, _p(sh), _p(db), cx.stream)
+        _call('tg_seg_actgrad_shift_f32', gy.ptr, gy.ld, y.ptr, y.ld, _p(dpre), co_p, y.rows, c_out, seg_array(seg_rows),
+              nseg, _p(sh), ACT[L.act], L.alpha, cx.stream)
+    return dpre
+
+
+def _input_grad(cx, L, dpre):
+    x, ci_p = L.x, L.ci_p
+    fresh = x.grad is None
+    gx = cx.grad_of(x)
+    dlist = geom.conv_dgrad(x.n, x.h, x.w, ci_p, L.co_p, L.k, L.stride, L.padding, ld_out=gx.ld, n_store=ci_p)
+    takes_over = fresh and len(dlist) == 1 and x.c == ci_p == gx.ld == x.ld
+    sink, bsink = x.grad_sink, x.bn_bwd_sink
+    if sink is not None and takes_over and sum(sink[2]) == x.rows and geom.colsum_supported(dlist[0], sink[2]):
+        # x is the output of a mean-only-BN layer: this launch also applies that layer's activation derivative and sums the
+        # columns per application, so its backward pass needs no statistics pass of its own (tg_mobn_center_f32)
+        nsg = len(sink[2])
+        gsum, zd = cx.zscratch('gs64', 2 * nsg * ci_p)
+        _call('tg_igemm_actsum_f32', dlist[0], _p(dpre), _p(L.w_hwio), x.ptr, ACT[sink[0]], sink[1], gx.ptr, seg_array(sink[2]), nsg,
+              _p(gsum), zd, cx.stream)
+        x.grad_fused = (gsum, 1)
+    elif (bsink is not None and takes_over and bsink[0].ld == gx.ld and len(bsink[1]) <= 8 and sum(bsink[1]) == x.rows
+          and geom.colsum_supported(dlist[0], bsink[1])):
+        # x is a training-mode batch norm's output and this launch is the first to write its gradient: the batch norm's backward
+        # statistics (sum dy, sum dy * its input) are taken in this epilogue; batch_norm_train's backward checks that nothing else
+        # contributed before it trusts them
+        bn_in, segs = bsink
+        bsums, zdb = cx.zscratch('bnb64', 32 * len(segs) * ci_p)
+        _call('tg_igemm_bnbwdstat_f32', dlist[0], _p(dpre), _p(L.w_hwio), bn_in.ptr, gx.ptr, seg_array(segs), len(segs), _p(bsums), zdb, cx.stream)
+        x.bn_bwd_sums = (bsums, gx)
+    else:
+        x.bn_bwd_sums = None                              # a second contribution to that gradient: the sums of the first alone are not the statistics
+        dds = lib.desc_array(dlist)
+        _call('tg_igemm_multi_f32', dds, len(dds), _p(dpre), _p(L.w_hwio), None, gx.ptr, cx.stream)
+
 
 def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=None, mobn=None, segments=None,
            train=True, kernel_grad=None, bias_grad=None, n_store_ld=None, bn_stats=False, concat=None, pool=None):
@@ -168,107 +345,32 @@ def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=N
                     and n_store_ld is None and pool is None):
         raise lib.TgError("conv2d: a bf16-stored input is read by the bf16-operand 3x3 / stride-1 / SAME convolution without weight norm, "
                           "mean-only BN, concat or pooling only (MFMA_DTYPE %r)" % (cx.mfma_dtype,))
-    c_in, ci_p, co_p = x.c, x.ld, pad32(c_out)
-    t = k * k
+    co_p = pad32(c_out)
     needs_w = cx.trains() and kernel_grad is not None
     needs_x = cx.tape is not None and x.requires_grad
-    # MFMA-side filter layouts (+ weight-norm scale).  Inside Train.train_iteration the result is kept per variable until that
-    # network's optimiser step: the classifier is prepared once for the D-update's forward passes and the C-update, the
-    # discriminator once for the G- and C-updates (Context.prep_cache; None outside train_iteration: no caching).
-    key = ('conv', kernel.data_ptr(), wn[0].data_ptr() if wn is not None else 0, t, c_in, c_out, ci_p, co_p)
-    ent = cx.prep_cache.get(key) if cx.prep_cache is not None else None
-    if ent is None and cx.prep_cache is not None:
-        plan = cx.prep_plans.get((cx.plan_tag, cx.phase, key))
-        if plan is not None:                               # this layer opens a recorded sequence: prepare all of its layers now
-            _run_prep_plan(cx, plan)
-            ent = cx.prep_cache.get(key)
-    if ent is not None and (ent[2] is not None or not needs_x):
-        scale, w_oti, w_hwio = ent[:3]
-        if len(ent) > 3:                                   # produced by a plan in this phase: keep the call-site numbering of the
-            if ent[4] == cx.phase:                         # recording pass, in which this layer allocated its own buffers here
-                cx.counter += ent[3]
-            cx.prep_cache[key] = ent[:3]
-    else:
-        scale = None
-        c_before = cx.counter
-        w_oti = cx.scratch('woti', co_p * t * ci_p)
-        w_hwio = cx.scratch('whwio', t * ci_p * co_p) if (needs_x or cx.prep_cache is not None) else None
-        if wn is not None:
-            scale = cx.scratch('wns', c_out)
-            _call('tg_wn_scale_f32', _p(kernel), _p(wn[0]), t * c_in, c_out, _p(scale), cx.stream)
-        _call('tg_filter_prep_f32', _p(kernel), _p(scale), None, t, c_in, c_out, ci_p, co_p, _p(w_hwio), _p(w_oti), t * ci_p, ci_p, cx.stream)
-        if cx.prep_cache is not None:
-            cx.prep_cache[key] = (scale, w_oti, w_hwio)
-            if cx._prep_rec is not None and w_hwio is not None:
-                cx._prep_rec.append(dict(key=key, kernel=kernel, g=wn[0] if wn is not None else None, scale=scale, w_oti=w_oti, w_hwio=w_hwio,
-                                         t=t, a=c_in, b=c_out, a_pad=ci_p, b_pad=co_p, bump=cx.counter - c_before))
-    fuse_cat = (concat is not None and mobn is None and not bn_stats and n_store_ld is None and c_out == co_p)
-    if fuse_cat:
-        n_store, ld_out = c_out, pad32(c_out + concat[1])
-    elif n_store_ld is None:
-        n_store, ld_out = c_out, co_p
-    else:
-        n_store, ld_out = n_store_ld
-    fused_act = act if mobn is None else None
-    d = geom.conv_fwd(x.n, x.h, x.w, ci_p, co_p, k, stride, padding, ld_out=ld_out, n_store=n_store, act=fused_act, alpha=alpha)
-    y = cx.new_act(x.n, d.h_out, d.w_out, c_out, ld_out, requires_grad=needs_w or needs_x)
+    L = types.SimpleNamespace(x=x, x16=x16, kernel=kernel, bias=bias, c_in=x.c, ci_p=x.ld, c_out=c_out, co_p=co_p, k=k, t=k * k, stride=stride,
+                              padding=padding, act=act, alpha=alpha, wn=wn, mobn=mobn, train=train, kernel_grad=kernel_grad, concat=concat,
+                              pool=pool, needs_w=needs_w, needs_x=needs_x)
+    _, L.w_oti, L.w_hwio = _prepared_filter(cx, kernel, wn[0] if wn is not None else None, L.t, L.c_in, c_out, L.ci_p, co_p, needs_x)
+    L.fuse_cat = (concat is not None and mobn is None and not bn_stats and n_store_ld is None and c_out == co_p)
+    n_store, ld_out = (c_out, pad32(c_out + concat[1])) if L.fuse_cat else n_store_ld if n_store_ld is not None else (c_out, co_p)
+    L.ld_out = ld_out
+    L.d = geom.conv_fwd(x.n, x.h, x.w, L.ci_p, co_p, k, stride, padding, ld_out=ld_out, n_store=n_store, act=act if mobn is None else None, alpha=alpha)
+    y = L.y = cx.new_act(x.n, L.d.h_out, L.d.w_out, c_out, ld_out, requires_grad=needs_w or needs_x)
     y.strided_grad_ok = True
-    pooled = None
-    seg_rows = _segs(y, segments)
-    fused = (mobn is not None and train and c_out == co_p and c_out <= 512 and stride == 1 and geom.colsum_supported(d, seg_rows))
-    packed = (cx.mfma_dtype != 'bf16' and k == 3 and stride == 1 and padding == 'SAME' and wn is None and mobn is None and not bn_stats
-              and n_store_ld is None and c_out == co_p and act in (None, 'relu', 'lrelu') and c_in <= 16
-              and bool(_call('tg_conv3x3_packed_supported', x.n, x.h, x.w, c_in, c_out)))
-    if fused:
-        # convolution + per-(application, channel) sums in one launch, then one fused apply pass (mean, +b, activation, pop_mean)
-        b, b_grad, pop = mobn
-        sums, zd = cx.zscratch('cs64', 2 * len(seg_rows) * c_out)     # fp64 accumulators
-        _call('tg_igemm_colsum_f32', d, x.ptr, _p(w_oti), y.ptr, seg_array(seg_rows), len(seg_rows), _p(sums), zd, cx.stream)
-        if pool is not None and y.h % 2 == 0 and y.w % 2 == 0 and all(r % (y.h * y.w) == 0 for r in seg_rows):
-            pooled = cx.new_act(y.n, y.h // 2, y.w // 2, c_out, co_p, requires_grad=needs_w or needs_x)
-            _call('tg_mobn_apply_pool_f32', y.ptr, y.ld, y.n, y.h, y.w, c_out, seg_array(seg_rows), len(seg_rows), _p(sums), _p(b), _p(pop), 0.9, ACT[act],
-                  alpha, pooled.ptr, pooled.ld, _p(pool[0]), c_out, pool[1], cx.stream)
-        else:
-            _call('tg_mobn_apply_f32', y.ptr, y.ld, y.rows, c_out, seg_array(seg_rows), len(seg_rows), _p(sums), _p(b), _p(pop), 0.9, ACT[act],
-                  alpha, cx.stream)
-    elif (bn_stats and mobn is None and act in (None, 'relu', 'lrelu') and c_out == co_p == ld_out and len(seg_rows) <= 8
-          and geom.colsum_supported(d, seg_rows)):
-        bsum, zd = cx.zscratch('bn64', 32 * len(seg_rows) * c_out)     # the batch norm's buffer: 8 replicas x nseg x 2 x c doubles
-        if x16:
-            args = (d, x.ptr, _p(w_oti), _p(bias), y.ptr, seg_array(seg_rows), len(seg_rows), _p(bsum), zd, cx.stream)
-            lib.call('tg_igemm_bnstat_bf16in_bf16', *igemm_scratch(cx, 'tg_igemm_bnstat_bf16in_bf16', args, True))
-        else:
-            _call('tg_igemm_bnstat_f32', d, x.ptr, _p(w_oti), _p(bias), y.ptr, seg_array(seg_rows), len(seg_rows), _p(bsum), zd, cx.stream)
-        y.bn_sums = (bsum, tuple(seg_rows))
-    elif x16:
-        args = (d, x.ptr, _p(w_oti), _p(bias), y.ptr, cx.stream)
-        lib.call('tg_igemm_bf16in_bf16', *igemm_scratch(cx, 'tg_igemm_bf16in_bf16', args, True))
-    elif packed:
-        # K-packed products straight from the [3,3,Cin,Cout] variable (csrc/packed_conv.hip); with concat the label channels ride along
-        _call('tg_conv3x3_packed_fwd_f32', x.ptr, x.ld, c_in, _p(kernel), _p(bias), ACT[act], alpha, _p(concat[0]) if fuse_cat else None,
-              concat[1] if fuse_cat else 0, y.ptr, ld_out, x.n, x.h, x.w, c_out, cx.stream)
-        if fuse_cat:
-            y.labels = (concat[0].data_ptr(), concat[1])
-    elif fuse_cat:
-        _call('tg_igemm_labels_f32', d, x.ptr, _p(w_oti), _p(bias), _p(concat[0]), concat[1], y.ptr, cx.stream)
+    L.seg_rows = _segs(y, segments)
+    # a mean-only-BN layer the fused kernels serve (statistics in an epilogue, one-pass backward)
+    L.narrow_mobn = mobn is not None and c_out == co_p and c_out <= 512 and len(L.seg_rows) <= 8
+    fwd = _conv_route(cx, L, bn_stats, n_store_ld)
+    pooled = fwd(cx, L)
+    if L.fuse_cat:
         y.labels = (concat[0].data_ptr(), concat[1])
-    else:
-        _call('tg_igemm_f32', d, x.ptr, _p(w_oti), (_p(bias) if mobn is None else None), y.ptr, cx.stream)
-    if mobn is not None and not fused:
-        b, b_grad, pop = mobn
-        sums = None
-        if train:
-            sums, _ = colstats(0, y.t, y.ld, None, 0, y.rows, c_out, seg_rows)
-        shift = cx.scratch('shift', len(seg_rows) * c_out)
-        _call('tg_mobn_finalize_f32', _p(sums), seg_array(seg_rows), len(seg_rows), y.rows, c_out, _p(b), _p(pop), 0.9,
-              1 if train else 0, _p(shift), cx.stream)
-        _call('tg_seg_scale_shift_act_f32', y.ptr, y.ld, y.ptr, y.ld, y.rows, c_out, c_out, seg_array(seg_rows), len(seg_rows),
-              None, _p(shift), ACT[act], alpha, cx.stream)
-
+    if mobn is not None and fwd is not _fwd_colsum:
+        _mobn_unfused(cx, y, y, c_out, L.seg_rows, mobn[0], mobn[2], 0.9, train, act, alpha)
     if not (needs_w or needs_x):
         return _pool_after(cx, y, pooled, pool)
-    if mobn is not None and train and act is not None and c_out == co_p and c_out <= 512 and len(seg_rows) <= 8 and ld_out == co_p:
-        y.grad_sink = (act, alpha, tuple(seg_rows))      # see Act.grad_sink
+    if L.narrow_mobn and train and act is not None and ld_out == co_p:
+        y.grad_sink = (act, alpha, tuple(L.seg_rows))      # see Act.grad_sink
     if mobn is None and act in ('relu', 'lrelu') and needs_w and bias_grad is not None and c_out == co_p == ld_out:
         y.bias_sink = (act, alpha, bias_grad)            # a batch norm behind this layer may fold act' and the bias gradient into its backward
 
@@ -276,82 +378,20 @@ def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=N
         gy = y.grad
         assert gy is not None, "conv2d backward: no gradient reached the output"
         _single_consumer(y, gy)
-        if mobn is None and act is None and gy.ld == co_p:
-            dpre = gy.t                                   # the loss head already wrote a padded dlogits
-            if needs_w and bias_grad is not None:
-                colstats(0, dpre, co_p, None, 0, y.rows, c_out, [y.rows], s1=bias_grad)
-        elif mobn is None and y.grad_is_dpre and gy.ld == co_p:
-            dpre = gy.t                                   # the batch norm behind this layer already applied act' and summed the bias gradient
+        if mobn is not None:
+            dpre = _dpre_mobn(cx, L, gy)
         else:
-            dpre = cx.scratch('dpre', y.rows * co_p)
-        if mobn is None and dpre is gy.t:
-            pass
-        elif mobn is not None and y.grad_fused is not None:
-            # the consumer's input-gradient launch already stored t = dy*act'(y) in y.grad and summed its columns per application
-            db = mobn[1] if needs_w else cx.scratch('db', c_out)
-            _call('tg_mobn_center_f32', gy.ptr, gy.ld, _p(dpre), co_p, y.rows, c_out, seg_array(seg_rows), len(seg_rows), _p(y.grad_fused[0]),
-                  y.grad_fused[1], _p(db), cx.stream)
-        elif mobn is not None and c_out == co_p and c_out <= 512 and len(seg_rows) <= 8:
-            db = mobn[1] if needs_w else cx.scratch('db', c_out)
-            sums64, zd = cx.zscratch('bs64', 16 * len(seg_rows) * c_out)     # 8 replicas x nseg x c doubles
-            _call('tg_mobn_bwd_f32', gy.ptr, gy.ld, y.ptr, y.ld, _p(dpre), co_p, y.rows, c_out, seg_array(seg_rows), len(seg_rows),
-                  ACT[act], alpha, _p(sums64), zd, _p(db), cx.stream)
-        elif mobn is not None:
-            sums, _ = colstats(2, gy.t, gy.ld, y.t, y.ld, y.rows, c_out, seg_rows, act, alpha)
-            sh = cx.scratch('bshift', len(seg_rows) * c_out)
-            db = mobn[1] if needs_w else cx.scratch('db', c_out)
-            _call('tg_mobn_bwd_finalize_f32', _p(sums), seg_array(seg_rows), len(seg_rows), y.rows, c_out, _p(sh), _p(db), cx.stream)
-            _call('tg_seg_actgrad_shift_f32', gy.ptr, gy.ld, y.ptr, y.ld, _p(dpre), co_p, y.rows, c_out, seg_array(seg_rows),
-                  len(seg_rows), _p(sh), ACT[act], alpha, cx.stream)
-        elif needs_w and bias_grad is not None and co_p <= 1024:
-            zs, zd = cx.zscratch('ab64', 16 * c_out)
-            _call('tg_actgrad_bias_f32', gy.ptr, gy.ld, y.ptr if act else None, y.ld, _p(dpre), co_p, y.rows, c_out, ACT[act], alpha,
-                  _p(zs), zd, _p(bias_grad), cx.stream)
-        else:
-            _call('tg_actgrad_f32', gy.ptr, gy.ld, y.ptr if act else None, y.ld, None, 0, 1.0, _p(dpre), co_p, y.rows, c_out,
-                  ACT[act], alpha, cx.stream)
-            if needs_w and bias_grad is not None:
-                colstats(0, dpre, co_p, None, 0, y.rows, c_out, [y.rows], s1=bias_grad)
-        if needs_w and packed:
-            pws = cx.scratch('pkws', _call('tg_conv3x3_packed_wgrad_workspace_bytes', x.n, x.h, x.w, c_in, c_out) // 4)
+            dpre = _dpre_plain(cx, y, gy, act, alpha, c_out, co_p, bias_grad if needs_w else None, head=True)
+        if needs_w and L.packed:
+            pws = cx.scratch('pkws', _call('tg_conv3x3_packed_wgrad_workspace_bytes', x.n, x.h, x.w, x.c, c_out) // 4)
             with cx.wgrad_on_side():                      # beside the input-gradient chain; joined in flush_tails
-                _call('tg_conv3x3_packed_wgrad_f32', x.ptr, x.ld, c_in, _p(dpre), co_p, x.n, x.h, x.w, c_out, _p(pws), _p(kernel_grad), cx.stream)
+                _call('tg_conv3x3_packed_wgrad_f32', x.ptr, x.ld, x.c, _p(dpre), co_p, x.n, x.h, x.w, c_out, _p(pws), _p(kernel_grad), cx.stream)
         elif needs_w:
-            dw_desc = geom.conv_wgrad(x.n, x.h, x.w, ci_p, co_p, k, stride, padding)
-            if wn is None:
-                filter_grad(dw_desc, x.t, dpre, t, c_in, c_out, kernel_grad, in16=x16)
-            else:
-                dw = cx.scratch('dw', t * c_in * c_out)
-                filter_grad(dw_desc, x.t, dpre, t, c_in, c_out, dw, wn=(kernel, wn[0], kernel_grad, wn[1]))
+            dw = kernel_grad if wn is None else cx.scratch('dw', L.t * x.c * c_out)
+            filter_grad(geom.conv_wgrad(x.n, x.h, x.w, x.ld, co_p, k, stride, padding), x.t, dpre, L.t, x.c, c_out, dw, in16=x16,
+                        wn=None if wn is None else (kernel, wn[0], kernel_grad, wn[1]))
         if needs_x:
-            fresh = x.grad is None
-            gx = cx.grad_of(x)
-            dlist = geom.conv_dgrad(x.n, x.h, x.w, ci_p, co_p, k, stride, padding, ld_out=gx.ld, n_store=ci_p)
-            sink = x.grad_sink
-            if (sink is not None and fresh and len(dlist) == 1 and x.c == ci_p == gx.ld == x.ld and sum(sink[2]) == x.rows
-                    and geom.colsum_supported(dlist[0], sink[2])):
-                # x is the output of a mean-only-BN layer: this launch also applies that layer's activation derivative and sums the
-                # columns per application, so its backward pass needs no statistics pass of its own (tg_mobn_center_f32)
-                nsg = len(sink[2])
-                gsum, zd = cx.zscratch('gs64', 2 * nsg * ci_p)
-                _call('tg_igemm_actsum_f32', dlist[0], _p(dpre), _p(w_hwio), x.ptr, ACT[sink[0]], sink[1], gx.ptr, seg_array(sink[2]), nsg,
-                      _p(gsum), zd, cx.stream)
-                x.grad_fused = (gsum, 1)
-            elif (x.bn_bwd_sink is not None and fresh and len(dlist) == 1 and x.c == ci_p == gx.ld == x.ld
-                  and x.bn_bwd_sink[0].ld == gx.ld and len(x.bn_bwd_sink[1]) <= 8 and sum(x.bn_bwd_sink[1]) == x.rows
-                  and geom.colsum_supported(dlist[0], x.bn_bwd_sink[1])):
-                # x is a training-mode batch norm's output and this launch is the first to write its gradient: the batch norm's backward
-                # statistics (sum dy, sum dy * its input) are taken in this epilogue; batch_norm_train's backward checks that nothing else
-                # contributed before it trusts them
-                bn_in, segs = x.bn_bwd_sink
-                bsums, zdb = cx.zscratch('bnb64', 32 * len(segs) * ci_p)
-                _call('tg_igemm_bnbwdstat_f32', dlist[0], _p(dpre), _p(w_hwio), bn_in.ptr, gx.ptr, seg_array(segs), len(segs), _p(bsums), zdb, cx.stream)
-                x.bn_bwd_sums = (bsums, gx)
-            else:
-                if x.bn_bwd_sums is not None:
-                    x.bn_bwd_sums = None                  # a second contribution to that gradient: the sums of the first alone are not the statistics
-                dds = lib.desc_array(dlist)
-                _call('tg_igemm_multi_f32', dds, len(dds), _p(dpre), _p(w_hwio), None, gx.ptr, cx.stream)
+            _input_grad(cx, L, dpre)
 
     cx.record(bwd)
     return _pool_after(cx, y, pooled, pool)
@@ -415,35 +455,17 @@ def deconv2d(x, kernel, bias, c_out, act=None, kernel_grad=None, bias_grad=None,
         gy = y.grad
         assert gy is not None
         _single_consumer(y, gy)
-        if y.grad_is_dpre and gy.ld == co_p:
-            dpre = gy.t
-        else:
-            dpre = cx.scratch('dpre', y.rows * co_p)
-        if dpre is gy.t:
-            pass
-        elif needs_w and bias_grad is not None and co_p <= 1024:
-            zs, zd = cx.zscratch('ab64', 16 * c_out)
-            _call('tg_actgrad_bias_f32', gy.ptr, gy.ld, y.ptr if act else None, y.ld, _p(dpre), co_p, y.rows, c_out, ACT[act], 0.2,
-                  _p(zs), zd, _p(bias_grad), cx.stream)
-        else:
-            _call('tg_actgrad_f32', gy.ptr, gy.ld, y.ptr if act else None, y.ld, None, 0, 1.0, _p(dpre), co_p, y.rows, c_out,
-                  ACT[act], 0.2, cx.stream)
-            if needs_w and bias_grad is not None:
-                colstats(0, dpre, co_p, None, 0, y.rows, c_out, [y.rows], s1=bias_grad)
+        dpre = _dpre_plain(cx, y, gy, act, 0.2, c_out, co_p, bias_grad if needs_w else None)
         # the 3-channel image layer: both gradients as K-packed products (csrc/narrow.hip) — the generic tiles would pad 3 channels to 32
         if needs_w:
             dw = kernel_grad if wn is None else cx.scratch('dw', 25 * c_out * c_in)
             if narrow:
                 nws = cx.scratch('nwws', lib.call('tg_deconv5x5s2_narrow_wgrad_workspace_bytes', x.n, x.h, x.w, c_out, ci_p) // 4)
-                if wn is None:
-                    with cx.wgrad_on_side():             # a vector-ALU kernel: beside the input-gradient chain like the other filter gradients
-                        _call('tg_deconv5x5s2_narrow_wgrad_f32', _p(dpre), co_p, x.ptr, x.ld, x.n, x.h, x.w, c_out, c_in, ci_p, _p(nws), _p(dw), cx.stream)
-                else:
+                # a vector-ALU kernel: beside the input-gradient chain like the other filter gradients, unless tg_wn_bwd_tab_f32 consumes it right below
+                with cx.wgrad_on_side() if wn is None else contextlib.nullcontext():
                     _call('tg_deconv5x5s2_narrow_wgrad_f32', _p(dpre), co_p, x.ptr, x.ld, x.n, x.h, x.w, c_out, c_in, ci_p, _p(nws), _p(dw), cx.stream)
-            elif wn is None:
-                filter_grad(geom.deconv_wgrad(x.n, x.h, x.w, co_p, ci_p), dpre, x.t, 25, c_out, c_in, kernel_grad)
-            else:
-                filter_grad(geom.deconv_wgrad(x.n, x.h, x.w, co_p, ci_p), dpre, x.t, 25, c_out, c_in, dw, defer=False)   # consumed right below
+            else:                                        # a weight-normalised layer's dw is consumed right below: no deferred tail
+                filter_grad(geom.deconv_wgrad(x.n, x.h, x.w, co_p, ci_p), dpre, x.t, 25, c_out, c_in, dw, defer=wn is None)
             if wn is not None:
                 _call('tg_wn_bwd_tab_f32', _p(dw), _p(kernel), _p(wn[0]), 25, c_out, c_in, _p(kernel_grad), _p(wn[1]), cx.stream)
         if needs_x:
@@ -470,12 +492,7 @@ def mean_only_batch_norm(x, pop_mean, b, b_grad=None, train=True, decay=0.9, seg
     needs = cx.tape is not None and (x.requires_grad or (cx.trains() and b_grad is not None))
     y = cx.new_act(x.n, x.h, x.w, c, x.ld, requires_grad=needs)
     y.strided_grad_ok = True
-    sums = None
-    if train:
-        sums, _ = colstats(0, x.t, x.ld, None, 0, x.rows, c, seg_rows)
-    shift = cx.scratch('shift', nseg * c)
-    _call('tg_mobn_finalize_f32', _p(sums), seg_array(seg_rows), nseg, x.rows, c, _p(b), _p(pop_mean), decay, 1 if train else 0, _p(shift), cx.stream)
-    _call('tg_seg_scale_shift_act_f32', x.ptr, x.ld, y.ptr, y.ld, x.rows, c, c, seg_array(seg_rows), nseg, None, _p(shift), 0, 0.0, cx.stream)
+    _mobn_unfused(cx, x, y, c, seg_rows, b, pop_mean, decay, train)
     if not needs:
         return y
     want_b = cx.trains() and b_grad is not None
@@ -721,6 +738,12 @@ def global_avgpool_concat(x, y_onehot_t, ncls):
     return out
 
 
+def global_avgpool(x):
+    """tf.reduce_mean(x, axis=[1,2]) (Model/Good_GAN.py:198,346) -> [N,C]: global_avgpool_concat without labels."""
+    require_f32(x, 'global_avgpool')
+    return global_avgpool_concat(x, None, 0)
+
+
 def minibatch_discrimination(x, w, b, num_kernels, dim, w_grad=None, b_grad=None, concat_input=False):
     """NN_Base._minibatch_discrimination (Model/modle_base.py:110-128) on a dense [n, c] activation: A = x @ W (a 1-tap MFMA product),
     f[i,k] = sum_j exp(-|A[i,k,:] - A[j,k,:]|_1) + b[k].  Returns f, or concat([x, f], 1) when concat_input (what the SVHN
@@ -765,9 +788,7 @@ def copy2d(dst_t, ld_d, dst_col, src_t, ld_s, rows, c):
 
 def copy_rows(dst_t, dst_off, src_t, numel):
     """contiguous device copy (batch concatenation along N)."""
-    cx = ctx()
-    numel = int(numel)
-    _call('tg_copy2d_f32', C.c_void_p(src_t.data_ptr()), numel, C.c_void_p(dst_t.data_ptr() + 4 * int(dst_off)), numel, 1, numel, cx.stream)
+    copy2d(dst_t, int(numel), int(dst_off), src_t, int(numel), 1, int(numel))
 
 
 def copy_many(jobs):
@@ -805,20 +826,6 @@ def add_noise(x, noise_t):
             x.grad = y.grad
         cx.record(bwd)
     return y
-
-
-def global_avgpool(x):
-    """tf.reduce_mean(x, axis=[1,2]) (Model/Good_GAN.py:198,346) -> [N,C]."""
-    require_f32(x, 'global_avgpool')
-    cx = ctx()
-    out = cx.new_act(x.n, 1, 1, x.c, pad32(x.c), requires_grad=x.requires_grad)
-    _call('tg_gavgpool_concat_f32', x.ptr, x.ld, x.c, None, 0, out.ptr, out.ld, x.n, x.h * x.w, cx.stream)
-    if cx.tape is not None and x.requires_grad:
-        def bwd():
-            gx = cx.grad_of(x)
-            _call('tg_gavgpool_bwd_f32', out.grad.ptr, out.grad.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.n, x.h * x.w, x.c, 0, 0.0, cx.stream)
-        cx.record(bwd)
-    return out
 
 
 def view(x, h, w, c):
@@ -911,7 +918,7 @@ def moments_normalize(x, eps, init_scale=1.0):
     s2, _ = colstats(4, x.t, x.ld, s1, 0, x.rows, c, [x.rows], alpha=1.0 / x.rows)
     sc, sh, mi = cx.scratch('bnsc', c), cx.scratch('bnsh', c), cx.scratch('bnmi', 2 * c)
     g, b = cx.ws('const:init_scale%g' % init_scale, c), cx.ws('const:zeros', max(c, 1024))
-    _call('tg_fill_f32', _p(g), float(init_scale), c, cx.stream)
+    fill(g, init_scale)
     _call('tg_bn_finalize_f32', _p(s1), _p(s2), x.rows, c, _p(g), _p(b), eps, _p(sc), _p(sh), _p(mi), None, None, 0.0, 0, cx.stream)
     y = cx.new_act(x.n, x.h, x.w, c, x.ld)
     _call('tg_seg_scale_shift_act_f32', x.ptr, x.ld, y.ptr, y.ld, x.rows, c, c, seg_array([x.rows]), 1, _p(sc), _p(sh), 0, 0.0, cx.stream)
