@@ -344,6 +344,17 @@ int tg_colstats_f32(int mode, const float* a, int ld_a, const float* b, int ld_b
 /* y[r][k] = act(x[r][k]*scale[k] + shift[seg(r)][k]) for k < c, 0 for c <= k < c_zero_to (scale may be NULL). */
 int tg_seg_scale_shift_act_f32(const float* x, int ld_x, float* y, int ld_y, int rows, int c, int c_zero_to, const int32_t* seg_rows, int nseg,
                                const float* scale, const float* shift, int act, float alpha, void* stream);
+/* Data-dependent weight-norm initialisation (Salimans & Kingma 2016; Model/nn.py:492-500, Model/modle_base.py:68-71) from the layer's
+ * unit-gain pre-activation t [rows][c] (leading dimension ld_t, any value >= c):
+ *   m[k] = mean_r t[r][k],  v[k] = mean_r (t[r][k] - m[k])^2    two passes, fp64 accumulation in a fixed order (no atomics: bit-identical
+ *                                                               run to run)
+ *   g[k] = fl32(init_scale / sqrt(v[k] + eps)),  b[k] = fl32(-m[k] * g[k])      in fp64 with the ROUNDED g, each rounded once
+ *   y[r][k] = act(g[k]*t[r][k] + b[k]) for k < c (fp32, what the layer computes from then on), 0 for c <= k < c_zero_to <= ld_y.
+ * g, b: the caller's [c] buffers (the parameter store).  y may be t.  workspace: tg_wn_init_workspace_floats(rows, c) floats, 8-byte
+ * aligned.  Five launches. */
+int64_t tg_wn_init_workspace_floats(int rows, int c);
+int tg_wn_init_f32(const float* t, int ld_t, int rows, int c, int c_zero_to, float eps, float init_scale, int act, float alpha,
+                   float* workspace, float* g, float* b, float* y, int ld_y, void* stream);
 /* dx[r][k] = dy[r][k]*act'(yact[r][k]) + shift[seg(r)][k]: backward of mean-only BN + nonlinearity. */
 int tg_seg_actgrad_shift_f32(const float* dy, int ld_dy, const float* yact, int ld_y, float* dx, int ld_dx, int rows, int c,
                              const int32_t* seg_rows, int nseg, const float* shift, int act, float alpha, void* stream);

@@ -146,8 +146,9 @@ class Good_GAN(model_base.NN_Base):
         return None
 
     # ------------------------------------------------------------------ networks
-    def good_generator(self, z, y, reuse=False):
-        """:15-83."""
+    def good_generator(self, z, y, reuse=False, init=False):
+        """:15-83.  init (extension; the reference hard-codes init=False): the weight-normalised output layer assigns its g and b from this
+        batch (data_dependent_init)."""
         cx = ctx()
         with cx.variable_scope('good_generator'):
             zy = ops.cond_concat(z, y.t, y.c)
@@ -156,14 +157,14 @@ class Good_GAN(model_base.NN_Base):
                 h0 = self._batch_norm_contrib(h0, 'gg_bn0', train=True)
                 h1 = self._linear_fc(ops.cond_concat(h0, y.t, y.c), 500, 'gg_h1_lin', activation=self._softplus)
                 h1 = self._batch_norm_contrib(h1, 'gg_bn1', train=True)
-                return self._WN_dense(ops.cond_concat(h1, y.t, y.c), 28 * 28, 'gg_h2_lin', activation=self._sigmoid, narrow=True)
+                return self._WN_dense(ops.cond_concat(h1, y.t, y.c), 28 * 28, 'gg_h2_lin', init=init, activation=self._sigmoid, narrow=True)
             h0 = self._linear_fc(zy, 4 * 4 * 512, 'gg_h0_lin', activation=self._relu)           # relu commutes with the reshape (:40-42)
             h0 = self._batch_norm_contrib(ops.reshape(h0, z.n, 4, 4, 512), 'gg_bn0', train=True)
             h0 = self._deconv2d(self._conv_cond_concat(h0, y), 256, k_w=5, k_h=5, d_w=2, d_h=2, name='gg_dconv0', activation=self._relu)
             h0 = self._batch_norm_contrib(h0, 'gg_bn1', train=True)
             h1 = self._deconv2d(self._conv_cond_concat(h0, y), 128, k_w=5, k_h=5, d_w=2, d_h=2, name='gg_dconv1', activation=self._relu)
             h1 = self._batch_norm_contrib(h1, 'gg_bn2', train=True)
-            return self._WN_deconv2d(self._conv_cond_concat(h1, y), 3, k_w=5, k_h=5, d_w=2, d_h=2, init_scale=0.1, init=False,
+            return self._WN_deconv2d(self._conv_cond_concat(h1, y), 3, k_w=5, k_h=5, d_w=2, d_h=2, init_scale=0.1, init=init,
                                      name='gg_wndconv0', activation=self._tanh, narrow=True)
 
     def good_sampler(self, z, y, reuse=True):
@@ -177,37 +178,38 @@ class Good_GAN(model_base.NN_Base):
         with ctx().no_record():
             return ops.activation(logits, 'sigmoid'), logits
 
-    def discriminator(self, image, y, reuse=False, want_prob=True):
-        """:89-206.  Returns (sigmoid(logits), logits [N,1]); want_prob=False (extension, the trainer's solver runs): (None, logits)."""
+    def discriminator(self, image, y, reuse=False, want_prob=True, init=False):
+        """:89-206.  Returns (sigmoid(logits), logits [N,1]); want_prob=False (extension, the trainer's solver runs): (None, logits).
+        init (extension): every weight-normalised layer assigns its g and b from this batch (data_dependent_init)."""
         cx = ctx()
         lre = self._leaky_relu
         with cx.variable_scope('discriminator'):
             if self.mnist:                                                                     # :93-124
                 h = self._add_noise(self.as_image(image), stddev=0.2)
                 for i in range(5):
-                    h = self._WN_dense(ops.cond_concat(h, y.t, y.c), (1000, 500, 250, 250, 250)[i], 'd_h%d_wndense0' % i, init=False, activation=lre)
+                    h = self._WN_dense(ops.cond_concat(h, y.t, y.c), (1000, 500, 250, 250, 250)[i], 'd_h%d_wndense0' % i, init=init, activation=lre)
                     h = self._add_noise(h, stddev=0.2)
-                return self._d_out(self._WN_dense(ops.cond_concat(h, y.t, y.c), 1, 'd_h5_wndense0', init=False, narrow=True), want_prob)
+                return self._d_out(self._WN_dense(ops.cond_concat(h, y.t, y.c), 1, 'd_h5_wndense0', init=init, narrow=True), want_prob)
             image = self._drop_out(image, 0.2, True, fuse_next=True)                           # :126-165
             # (layers whose output goes straight into the next concat write that concatenation themselves: then_concat, ops.conv2d(concat=...))
-            h0 = self._WN_conv2d(self._conv_cond_concat(image, y), 32, k_h=3, k_w=3, d_h=1, d_w=1, init=False, name="d_h0_wnconv0", activation=lre,
+            h0 = self._WN_conv2d(self._conv_cond_concat(image, y), 32, k_h=3, k_w=3, d_h=1, d_w=1, init=init, name="d_h0_wnconv0", activation=lre,
                                  then_concat=y)
-            h0 = self._WN_conv2d(self._conv_cond_concat(h0, y), 32, k_h=3, k_w=3, d_h=2, d_w=2, init=False, name="d_h0_wnconv1", activation=lre)
+            h0 = self._WN_conv2d(self._conv_cond_concat(h0, y), 32, k_h=3, k_w=3, d_h=2, d_w=2, init=init, name="d_h0_wnconv1", activation=lre)
             h0 = self._drop_out(h0, 0.2, True, fuse_next=True)
-            h1 = self._WN_conv2d(self._conv_cond_concat(h0, y), 64, k_h=3, k_w=3, d_h=1, d_w=1, init=False, name="d_h1_wnconv0", activation=lre,
+            h1 = self._WN_conv2d(self._conv_cond_concat(h0, y), 64, k_h=3, k_w=3, d_h=1, d_w=1, init=init, name="d_h1_wnconv0", activation=lre,
                                  then_concat=y)
-            h1 = self._WN_conv2d(self._conv_cond_concat(h1, y), 64, k_h=3, k_w=3, d_h=2, d_w=2, init=False, name="d_h1_wnconv1", activation=lre)
+            h1 = self._WN_conv2d(self._conv_cond_concat(h1, y), 64, k_h=3, k_w=3, d_h=2, d_w=2, init=init, name="d_h1_wnconv1", activation=lre)
             h1 = self._drop_out(h1, 0.2, True, fuse_next=True)
             y2 = _twice(y)
-            h2 = self._WN_conv2d(self._conv_cond_concat(h1, y), 128, k_h=3, k_w=3, d_h=1, d_w=1, init=False, name="d_h2_wnconv0", activation=lre,
+            h2 = self._WN_conv2d(self._conv_cond_concat(h1, y), 128, k_h=3, k_w=3, d_h=1, d_w=1, init=init, name="d_h2_wnconv0", activation=lre,
                                  then_concat=(y2, 2 * y.c))
             h2 = ops.cond_concat(h2, y2, 2 * y.c)                                               # y is concatenated twice (:151-153)
-            h2 = self._WN_conv2d(h2, 128, k_h=3, k_w=3, d_h=1, d_w=1, init=False, name="d_h2_wnconv1", activation=lre)
+            h2 = self._WN_conv2d(h2, 128, k_h=3, k_w=3, d_h=1, d_w=1, init=init, name="d_h2_wnconv1", activation=lre)
             h3 = ops.global_avgpool_concat(h2, y.t, y.c)                                        # reduce_mean + concat y
             if self.config.MINIBATCH_DIS:                                                      # :159-162 (off in every config of the reference)
                 h3 = self._minibatch_discrimination(h3, 100, concat_input=True)               # f = ...; h3 = tf.concat([h3, f], 1)
                 return self._d_out(self._linear_fc(h3, 1, 'd_h3_lin', narrow=True), want_prob)
-            return self._d_out(self._WN_dense(h3, 1, 'd_h3_wndense', narrow=True), want_prob)
+            return self._d_out(self._WN_dense(h3, 1, 'd_h3_wndense', init=init, narrow=True), want_prob)
 
     # ------------------------------------------------------------------ WGAN-GP
     def discriminator_gradient_penalty(self, real, fake, y, weight=1.0, in_step=False):
@@ -217,8 +219,9 @@ class Good_GAN(model_base.NN_Base):
         discrimination (config.MINIBATCH_DIS) couples the images of a batch and is refused."""
         return grad_penalty.penalty(self, *self._gp, real, fake, y, weight, in_step, minibatch_dis=getattr(self.config, 'MINIBATCH_DIS', False))
 
-    def classifier(self, image, train_ph, reuse=False, segments=None):
-        """:212-350.  Returns (logits [N,10], feature).  `segments` (extension): image counts of the applications batched into
+    def classifier(self, image, train_ph, reuse=False, segments=None, init=False):
+        """:212-350.  init (extension): the two network-in-network layers of the SVHN classifier assign their g and b
+        (data_dependent_init).  Returns (logits [N,10], feature).  `segments` (extension): image counts of the applications batched into
         `image` — the convolutions run once over the whole batch, every batch norm keeps per-application statistics and
         updates its moving statistics application by application (tg_bn_train_f32)."""
         cx = ctx()
@@ -232,13 +235,13 @@ class Good_GAN(model_base.NN_Base):
             return self._batch_norm_contrib(x, name=bname, train=train_ph, segments=segments, bf16_out=bf16_out)
 
         def pool_drop(x, key):
-            mask = cx.rng.keep_mask(cx, key, x.rows // 4 * x.c, 0.5) if train_ph else None
+            mask = cx.rng.keep_mask(cx, key, x.rows // 4 * x.c, 0.5) if (train_ph and not cx.assign_init) else None
             return ops.maxpool2_dropout(x, mask, 2.0)
 
         with cx.variable_scope('classifier'):
             if self.mnist:                                                                         # :216-247
                 img = ops.view(image, 28, 28, 1) if (image.h, image.w) == (1, 1) else image
-                noise = cx.rng.normal(cx, 'noise', img.rows * img.c, 0.3)
+                noise = None if cx.assign_init else cx.rng.normal(cx, 'noise', img.rows * img.c, 0.3)
                 x = ops.im2col3x3_add(img, noise)                    # _add_noise + the 1-channel 3x3 window gathered once
                 x = cbr(x, 'c_h0_conv0', 'c_h0_bn0', 32, k=1)
                 x = pool_drop(x, 'drop1')
@@ -259,11 +262,53 @@ class Good_GAN(model_base.NN_Base):
                 x = cbr(x, 'c_h1_conv2', 'c_h1_bn2', 256)
                 x = pool_drop(x, 'drop2')
                 x = cbr(x, 'c_h2_conv0', 'c_h2_bn0', 512)
-                x = self._batch_norm_contrib(self._nin(x, 256, name='c_h2_nin0', activation=lre), name='c_h2_bn1', train=train_ph, segments=segments)
-                x = self._batch_norm_contrib(self._nin(x, 128, name='c_h2_nin1', activation=lre), name='c_h2_bn2', train=train_ph, segments=segments)
+                x = self._batch_norm_contrib(self._nin(x, 256, name='c_h2_nin0', activation=lre, init=init), name='c_h2_bn1', train=train_ph, segments=segments)
+                x = self._batch_norm_contrib(self._nin(x, 128, name='c_h2_nin1', activation=lre, init=init), name='c_h2_bn2', train=train_ph, segments=segments)
             fm = ops.global_avgpool(x)                                                             # tf.reduce_mean(axis=[1,2])
             h = self._linear_fc(fm, self.config.NUM_CLASSES, 'c_h2_lin')
             return self._batch_norm_contrib(h, name='c_h3_bn0', train=train_ph, segments=segments), fm
+
+    # ------------------------------------------------------------------ data-dependent initialisation
+    @property
+    def WN_INIT_LAYERS(self):
+        """{network: scopes of its weight-normalised layers, in the order the pass initialises them}."""
+        G, D, C = 'good_generator/', 'discriminator/', 'classifier/'
+        if self.mnist:
+            return {'good_generator': (G + 'gg_h2_lin',), 'classifier': (),
+                    'discriminator': tuple(D + 'd_h%d_wndense0' % i for i in range(len(D_MNIST_DENSE) + 1))}
+        head = () if getattr(self.config, 'MINIBATCH_DIS', False) else (D + 'd_h3_wndense',)      # (:159-162: a plain dense head)
+        return {'good_generator': (G + 'gg_wndconv0',), 'classifier': (C + 'c_h2_nin0', C + 'c_h2_nin1'),
+                'discriminator': tuple(D + row[0] for row in D_SVHN_CONVS) + head}
+
+    def data_dependent_init(self, z_g, y_g, x_l_d, y_l_d, x_u_d, x_u_c):
+        """The data-dependent initialisation of every weight-normalised layer, in the order and on the inputs of the
+        reference's `init=True` builds (Good_GAN_cifar10.py:216,243,263; Good_GAN.py itself never asks for one): the generator on
+        (z_g, y_g), the classifier on x_u_c, the discriminator on X_P = [x_l_d; x_u_d] with Y_P = [y_l_d; one_hot(argmax C(x_u_d))] — C's
+        ordinary evaluation-mode forward, after its own init.  A network without such layers is skipped.  Dropout and noise are off and
+        the batch norms in between use batch statistics without moving theirs: only */g and */b change.
+        Returns {network: [scopes of the layers initialised]}; the labels the discriminator saw stay in self.wn_init_labels."""
+        from tg.batching import concat_acts
+        cx, k = ctx(), self.config.NUM_CLASSES
+        layers = self.WN_INIT_LAYERS
+        with cx.assigning_init() as done:
+            with cx.rng_scoped('init/G'):
+                self.good_generator(z_g, y_g, init=True)
+            if layers['classifier']:
+                with cx.rng_scoped('init/C'):
+                    self.classifier(self.as_image(x_u_c), True, init=True)
+        # (the MNIST classifier's input noise is on at evaluation too: its draw must not take a Philox stream id away from the step's)
+        ids = dict(cx.rng.stream_ids) if hasattr(cx.rng, 'stream_ids') else None
+        with cx.no_record(), cx.rng_scoped('init/C_unl_d'):
+            logits, _ = self.classifier(self.as_image(x_u_d), False)
+        if ids is not None:
+            cx.rng.stream_ids = ids
+        oh = Act(ops.argmax_onehot(logits, k), x_u_d.n, 1, 1, k, k)
+        self.wn_init_labels = oh
+        with cx.assigning_init() as done_d:
+            with cx.rng_scoped('init/D'):
+                self.discriminator(concat_acts([self.as_image(x_l_d), self.as_image(x_u_d)]), concat_acts([y_l_d, oh]), want_prob=False, init=True)
+        done = list(done) + list(done_d)
+        return {net: [s for s in done if s.startswith(net + '/')] for net in ('good_generator', 'classifier', 'discriminator')}
 
     def forward_pass(self, z_g, y_g, x_l_c, y_l_c, x_l_d, y_l_d, x_u_d, x_u_c, train):
         """:428-472 (evaluation / tests; the trainer runs per-solver sub-graphs)."""

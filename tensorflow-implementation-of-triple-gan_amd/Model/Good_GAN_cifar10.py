@@ -7,7 +7,8 @@ gfx950 kernels of csrc/ through Model/nn.py and Model/model_base.py.  Line refer
 reference file.  Differences forced by eager execution:
   * tensors are tg.runtime.Act handles, `is_training` is a Python bool;
   * variables are created (with the reference's initialisers) when the Model
-    is constructed — the reference's throw-away `init=True` builds (:216,227,263) only create variables;
+    is constructed — the reference's throw-away `init=True` builds (:216,227,263) only create variables
+    (their g / b assigns are never run); `data_dependent_init` runs them (config.WN_INIT = 'data', DESIGN §9.9);
   * `segments=` (extension) batches several applications of C or D into one call: identical maths,
     since D has no batch statistics and C's mean-only BN is computed per segment.
 """
@@ -201,7 +202,8 @@ class Good_GAN_cifar10(model_base.NN_Base):
             # x = self._add_noise(x, stddev=0.15) followed by conv1_1 (:104-110): with 3 input channels the 3x3 window is
             # gathered once (x + noise -> [N,32,32,27]) and conv1_1 runs as a 1x1 product on it with the same variable V
             # ([3,3,3,128] and [1,1,27,128] are the same bytes)
-            noise = cx.rng.normal(cx, 'noise', inp.rows * inp.c, 0.15)
+            # (the data-dependent initialisation pass draws nothing: Context.assigning_init)
+            noise = None if cx.assign_init else cx.rng.normal(cx, 'noise', inp.rows * inp.c, 0.15)
             x = ops.im2col3x3_add(inp, noise)
             for i, (name, cout, pad, pool) in enumerate(self.C_CONVS):
                 self._bucket_mark('classifier', 'classifier/%s/V' % name)
@@ -219,6 +221,23 @@ class Good_GAN_cifar10(model_base.NN_Base):
             kw['nonlinearity'] = None
             logits = nn.dense_WN(x, num_units=self.config.NUM_CLASSES, name='output_dense', **kw)
         return logits, intermediate_layer
+
+    # ------------------------------------------------------------------ data-dependent initialisation
+    WN_INIT_LAYERS = {'good_generator': (), 'discriminator': (),
+                      'classifier': tuple('classifier/' + n for n, _, _, _ in C_CONVS) + ('classifier/NiN1/NiN1', 'classifier/NiN2/NiN2',
+                                                                                         'classifier/output_dense')}
+
+    def data_dependent_init(self, z_g, y_g, x_l_d, y_l_d, x_u_d, x_u_c):
+        """The reference's `init=True` builds (:216,227,263) with their assigns run: one forward pass per network, layer by
+        layer, each weight-normalised layer setting g <- init_scale / sqrt(var + eps), b <- -mean * g from its unit-gain pre-activation and
+        handing its initialised output on.  Here only the classifier has such layers (on ZCA-whitened x_u_c, :222,227); the generator and
+        the discriminator are skipped.  Input noise and dropout are off: the pass is a function of the variables and the batch, and only
+        */g and */b change.  Returns {network: [scopes of the layers initialised]}."""
+        cx = ctx()
+        with cx.assigning_init() as done:
+            with cx.rng_scoped('init/C'):
+                self.classifier(self.zca().apply(x_u_c), False, init=True)
+        return {net: [s for s in done if s.startswith(net + '/')] for net in ('good_generator', 'classifier', 'discriminator')}
 
     # ------------------------------------------------------------------ whole graph (evaluation / tests)
     CONSISTENCY = True        # forward_pass returns C_unl_logits_rep and _loss_GAN adds lambda_2 * MSE (:232-235, train_base.py:118)

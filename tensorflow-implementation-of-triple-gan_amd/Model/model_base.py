@@ -11,6 +11,10 @@ Extensions (keyword-only, default = reference behaviour): `activation` fuses the
 model applies next into the MFMA kernel's epilogue; `narrow` stores only the logical channels.
 Initialisers are applied when the Model creates its variables (see Good_GAN_cifar10.param_specs),
 so `kernel_initializer` is accepted and ignored here.
+
+`init=True` of the _WN_* layers is the reference's live tf.assign branch (modle_base.py:68-71,103-106,150-153): g and b are assigned
+from the moments of the unit-gain pre-activation (eps 1e-10, init_scale honoured) and the layer's value is computed through them
+(NN_Base._wn_init).  The fused layouts (narrow, then_concat) serve init=False; the init runs through the plain one.
 """
 from tg import ops
 from tg.runtime import ctx
@@ -112,6 +116,10 @@ class NN_Base(object):
         config.ACT_DTYPE = 'bf16' (ops.batch_norm_train(out_bf16=True)); evaluation stays fp32."""
         cx = ctx()
         with cx.variable_scope(name):
+            if train and cx.assign_init:
+                # the data-dependent initialisation pass: batch statistics, moving statistics left as they are (Context.assigning_init)
+                return ops.batch_norm_train(x, cx.var('gamma'), cx.var('beta'), None, None, self._batch_norm_epsilon, self._batch_norm_decay,
+                                            segments=segments)
             if not train:
                 return ops.batch_norm_eval(x, cx.var('gamma'), cx.var('beta'), cx.var('moving_mean'), cx.var('moving_variance'),
                                            self._batch_norm_epsilon)
@@ -121,11 +129,35 @@ class NN_Base(object):
                                         gamma_grad=cx.var_grad('gamma') if tr else None, beta_grad=cx.var_grad('beta') if tr else None,
                                         segments=segments, out_bf16=bf16_out)
 
+    def _wn_init(self, t, init_scale, act, alpha, narrow):
+        """init=True of a _WN_* layer, inside its variable scope: g <- init_scale / sqrt(var(t) + 1e-10), b <- -mean(t) * g assigned from the
+        unit-gain pre-activation t, act(g*t + b) returned (ops.wn_data_init) — in the plain channel-padded layout, or, narrow, copied to
+        the dense one the layer's caller expects.  A then_concat behind the layer is left to the cond_concat that follows."""
+        cx = ctx()
+        y = ops.wn_data_init(t, cx.var('g'), cx.var('b'), 1e-10, init_scale, act, alpha)
+        if cx.assign_init:
+            cx.wn_inited.append(cx.scope_name())
+        if narrow and y.ld != y.c:
+            out = cx.new_act(y.n, y.h, y.w, y.c, y.c)
+            ops.copy2d(out.t, y.c, 0, y.t, y.ld, y.rows, y.c)
+            return out
+        return y
+
+    def _ones(self, n):
+        cx = ctx()
+        ones = cx.ws('const:ones', max(n, 1024))
+        ops.fill(ones, 1.0)
+        return ones
+
     def _WN_dense(self, input_, output_size, scope, init_scale=1.0, init=False, activation=None, narrow=False):
-        """g * (x @ l2_normalize(V,[0])) + b (modle_base.py:50-73; the data-dependent init branch is never taken)."""
+        """g * (x @ l2_normalize(V,[0])) + b (modle_base.py:50-73); init=True assigns g and b first (:68-71, _wn_init)."""
         cx = ctx()
         act, alpha = _act_of(activation)
         with cx.variable_scope(scope):
+            if init:
+                with cx.no_record():
+                    t = ops.conv2d(input_, cx.var('V'), None, output_size, 1, 1, 'SAME', wn=(self._ones(output_size), None))
+                    return self._wn_init(t, init_scale, act, alpha, narrow)
             tr = cx.trains()
             return ops.conv2d(input_, cx.var('V'), cx.var('b'), output_size, 1, 1, 'SAME', act=act, alpha=alpha,
                               wn=(cx.var('g'), cx.var_grad('g') if tr else None), kernel_grad=cx.var_grad('V') if tr else None,
@@ -133,12 +165,16 @@ class NN_Base(object):
 
     def _WN_conv2d(self, input_, output_dim, k_h=5, k_w=5, d_h=2, d_w=2, padding='SAME', init_scale=1.0, init=False, name="conv2d",
                    activation=None, then_concat=None):
-        """g * conv(x, l2_normalize(V,[0,1,2])) + b (modle_base.py:75-108).  then_concat (extension): as in _conv2d — (label tensor, count) or a
-        label Act the _conv_cond_concat / cond_concat right behind this layer appends."""
+        """g * conv(x, l2_normalize(V,[0,1,2])) + b (modle_base.py:75-108); init=True assigns g and b first (:103-106, _wn_init).  then_concat
+        (extension): as in _conv2d — (label tensor, count) or a label Act the _conv_cond_concat / cond_concat right behind this layer appends."""
         assert k_h == k_w and d_h == d_w
         cx = ctx()
         act, alpha = _act_of(activation)
         with cx.variable_scope(name):
+            if init:
+                with cx.no_record():
+                    t = ops.conv2d(input_, cx.var('V'), None, int(output_dim), k_h, d_h, padding, wn=(self._ones(int(output_dim)), None))
+                    return self._wn_init(t, init_scale, act, alpha, False)
             tr = cx.trains()
             return ops.conv2d(input_, cx.var('V'), cx.var('b'), int(output_dim), k_h, d_h, padding, act=act, alpha=alpha,
                               wn=(cx.var('g'), cx.var_grad('g') if tr else None), kernel_grad=cx.var_grad('V') if tr else None,
@@ -147,11 +183,15 @@ class NN_Base(object):
     def _WN_deconv2d(self, input_, output_dim, k_h=3, k_w=3, d_h=2, d_w=2, padding='SAME', init_scale=1.0, init=False, name="deconv2d",
                      activation=None, narrow=False):
         """g * conv2d_transpose(x, l2_normalize(V,[0,1,3])) + b, V [kh,kw,Cout,Cin] (modle_base.py:130-155); 5x5 s2 'SAME' only
-        (the only configuration the reference's models use)."""
+        (the only configuration the reference's models use); init=True assigns g and b first (:150-153, _wn_init)."""
         assert (k_h, k_w, d_h, d_w, padding) == (5, 5, 2, 2, 'SAME')
         cx = ctx()
-        act, _ = _act_of(activation)
+        act, alpha = _act_of(activation)
         with cx.variable_scope(name):
+            if init:
+                with cx.no_record():
+                    t = ops.deconv2d(input_, cx.var('V'), None, int(output_dim), wn=(self._ones(int(output_dim)), None))
+                    return self._wn_init(t, init_scale, act, alpha, narrow)
             tr = cx.trains()
             return ops.deconv2d(input_, cx.var('V'), cx.var('b'), int(output_dim), act=act, kernel_grad=cx.var_grad('V') if tr else None,
                                 bias_grad=cx.var_grad('b') if tr else None, narrow_out=narrow,
@@ -167,9 +207,9 @@ class NN_Base(object):
                                             w_grad=cx.var_grad('w') if tr else None, b_grad=cx.var_grad('b') if tr else None,
                                             concat_input=concat_input)
 
-    def _nin(self, input, num_units, name, activation=None):
+    def _nin(self, input, num_units, name, activation=None, init=False):
         """network-in-network (1x1 conv): reshape + _WN_dense + reshape (modle_base.py:204-209)."""
-        return self._WN_dense(input, num_units, name, activation=activation)
+        return self._WN_dense(input, num_units, name, init=init, activation=activation)
 
     def _conv_cond_concat(self, x, y):
         """Concatenate conditioning vector on feature map axis (modle_base.py:239-244); y: Act [N,ncls]."""
@@ -178,9 +218,9 @@ class NN_Base(object):
     def _drop_out(self, x, rate=0.5, train=False, name=None, fuse_next=False):
         """tf.layers.dropout (modle_base.py:190-191): x*mask/keep with a floor(keep+U) keep-mask.  fuse_next (extension): the
         result goes straight into _conv_cond_concat, which applies the mask in its own launch (ops.scale_mask(defer=True))."""
-        if not train:
-            return x
         cx = ctx()
+        if not train or cx.assign_init:                  # the data-dependent initialisation pass draws nothing (Context.assigning_init)
+            return x
         mask = cx.rng.keep_mask(cx, name or cx.next_rng_name('drop'), x.rows * x.c, 1.0 - rate)
         assert x.ld == x.c
         return ops.scale_mask(x, mask, 1.0 / (1.0 - rate), defer=fuse_next)
@@ -189,5 +229,7 @@ class NN_Base(object):
         """inputs + N(mean, stddev) (modle_base.py:193-202) on a dense activation; the gradient passes through."""
         assert mean == 0.0
         cx = ctx()
+        if cx.assign_init:                               # see _drop_out
+            return inputs
         noise = cx.rng.normal(cx, name or cx.next_rng_name('noise'), inputs.rows * inputs.c, stddev)
         return ops.add_noise(inputs, noise)

@@ -9,8 +9,10 @@ variables come from the active `tg.runtime.Context` under the scope names the re
 
 Differences forced by eager execution: `deterministic` is a Python bool (not a tf.bool tensor): True = evaluation (use the
 running statistics), False = training.  `init=True` (data-dependent initialisation) returns what the reference's init branch returns —
-scale_init * (x - m_init), forward only; its g / b assigns are "created but never run" in the reference (nn.py:497-499) and do not
-exist here.  `ema` of the Salimans layers (variable averages substituted at evaluation, nn.py:98-110) is accepted and must be None.
+scale_init * (x - m_init), forward only: its g / b assigns are "created but never run" in the reference (nn.py:497-499).  Inside
+`ctx().assigning_init()` they ARE run: g <- scale_init and b <- -m_init * scale_init are written to the variables by
+ops.wn_data_init and the layer returns nonlinearity(g*x + b), the same value through the assigned variables.  `ema` of the Salimans
+layers (variable averages substituted at evaluation, nn.py:98-110) is accepted and must be None.
 Extension: `segments` = image counts of the classifier applications batched into one call; mean-only-BN statistics are then per
 application (the models' batching, Training/Train_goodGAN.py of this package).
 """
@@ -80,6 +82,21 @@ def batch_norm_impl(x, is_conv_out=True, deterministic=False, decay=0.9, name='B
                                       scale_grad=cx.var_grad('scale') if tr else None, beta_grad=cx.var_grad('beta') if tr else None)
 
 
+def _data_init(cx, x, V, g, b, num_out, k, stride, pad, init_eps, init_scale, nonlinearity, transposed=False):
+    """init=True inside Context.assigning_init: t = conv(x, V/||V||), then g, b assigned from its moments and nonlinearity(g*t + b) returned
+    (ops.wn_data_init).  eps as the reference writes it: 1e-8 behind a convolution, 1e-10 behind a dense product."""
+    ones = cx.ws('const:ones', max(num_out, 1024))
+    ops.fill(ones, 1.0)
+    if transposed:
+        t = ops.deconv2d(x, V, None, num_out, wn=(ones, None))
+    else:
+        t = ops.conv2d(x, V, None, num_out, k, stride, pad, wn=(ones, None))
+    a = _tg_act(nonlinearity)
+    y = ops.wn_data_init(t, g, b, init_eps, init_scale, *(a or (None, 0.0)))
+    cx.wn_inited.append(cx.scope_name())
+    return y if (a or nonlinearity is None) else nonlinearity(y)
+
+
 def _wn_layer(x, num_out, k, pad, stride, nonlinearity, init_scale, init, use_weight_normalization, use_batch_normalization,
               use_mean_only_batch_normalization, deterministic, segments, init_eps, then_pool=None):
     """body shared by conv2d_WN (k x k) and dense_WN (k = 1 on [n,1,1,c]): every flag combination of nn.py:476-518,529-570.
@@ -102,6 +119,9 @@ def _wn_layer(x, num_out, k, pad, stride, nonlinearity, init_scale, init, use_we
     gr = (lambda leaf: cx.var_grad(leaf)) if trains else (lambda leaf: None)
     a = _tg_act(nonlinearity)
     fuse = dict(act=a[0], alpha=a[1]) if a else {}
+    if use_weight_normalization and init and cx.assign_init:
+        # g.assign(scale_init), b.assign(-m_init * scale_init) as nn.py:498-499 write them, mean-only BN or not (pop_mean is not touched)
+        return _data_init(cx, x, V, g, b, num_out, k, stride, pad, init_eps, init_scale, nonlinearity)
     if use_weight_normalization and init:
         # x_init = conv(x, l2_normalize(V)); scale_init*(x_init - m_init)   (nn.py:494-500,545-551) — forward only
         ones = cx.ws('const:ones', max(num_out, 1024))
@@ -180,6 +200,8 @@ def _salimans(x, num_out, k, stride, pad, nonlinearity, init_scale, init, ema, i
     gr = (lambda leaf: cx.var_grad(leaf)) if trains else (lambda leaf: None)
     g_grad = gr('g') if train_scale else None
     a = _tg_act(nonlinearity)
+    if init and cx.assign_init:                                    # train_scale=False freezes g's gradient, not its initial value
+        return _data_init(cx, x, V, g, b, num_out, k, stride, pad, init_eps, init_scale, nonlinearity, transposed)
     if init:
         ones = cx.ws('const:ones', max(num_out, 1024))
         ops.fill(ones, 1.0)

@@ -24,7 +24,7 @@ import torch
 
 from config import Config
 from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, check_act_dtype, check_clip_norm, check_loss,  # noqa: F401
-                              check_mfma_dtype, check_num_classes, check_optimizer, check_zca, cla_lr, opt, resolve)
+                              check_mfma_dtype, check_num_classes, check_optimizer, check_wn_init, check_zca, cla_lr, opt, resolve)
 from Training.train_base import Train_base, clip_workspace_floats
 from tg import dist as tgdist
 from tg import executor, lib, ops
@@ -66,6 +66,7 @@ class Train(Train_base):
         self._rest = {}                  # solver run -> (unexecuted head of its backward tape, call-site counter): bucketed backward passes
         self.iteration = 0
         self._label_override = {}        # see label_override()
+        self.wn_initialised = None       # {network: layers initialised} once data_dependent_init() has run (config.WN_INIT = 'data')
         self.zca_source = None           # config.ZCA = 'fit' resolved by train(): 'files' | 'fit' (rank 0) | 'broadcast' (other ranks)
         self._hist_runs = {}             # network -> (store layout key, tg.summary.StoreHistograms): see histograms()
         self.summary_train = self.summary_val = None
@@ -387,6 +388,32 @@ class Train(Train_base):
                 cx.rng.uniform(cx, 'z', self.z_g_ph.t.numel(), -1.0, 1.0, out=self.z_g_ph.t)
                 cx.rng.onehot(cx, 'y', self.y_g_ph.n, self.config.NUM_CLASSES, out=self.y_g_ph.t)
 
+    def data_dependent_init(self):
+        """config.WN_INIT = 'data' (DESIGN §9.9): the model's data-dependent initialisation pass, run eagerly on the batch the placeholders
+        hold (feed() + sample_latent()) — every weight-normalised layer's g and b are assigned from that batch, nothing else changes.  Then
+        the classifier's EMA shadows are seeded from the weights again, as at build time.  With replicas every rank runs the pass on its own
+        batch (the ranks stay in lock-step) and rank 0's result is broadcast: the single-process initialisation on rank 0's batch.
+        Happens before anything is recorded, so it works in every EXEC_MODE; lib.TgError once a training iteration has run, or inside a
+        capture / recording.  Returns {network: number of layers initialised} (0 for a network without such layers: it is not run)."""
+        cx = self.cx
+        if self.model is None:
+            raise lib.TgError("data_dependent_init: no model yet (_build_train_graph first)")
+        if cx.capturing or lib._recorder is not None:
+            raise lib.TgError("data_dependent_init: called inside a hipGraph capture / launch-plan recording; it is an eager pass before the step")
+        if self.iteration > 0:
+            raise lib.TgError("data_dependent_init: %d training iteration(s) have run; the initialisation belongs before the first (the optimiser "
+                              "slots, the EMA shadows and any recorded launch already follow the present g and b)" % self.iteration)
+        with cx.phase_scope('wn_init', record=False):
+            done = self.model.data_dependent_init(self.z_g_ph, self.y_g_ph, self.x_l_d_ph, self.y_l_d_ph, self.x_u_d_ph, self.x_u_c_ph)
+        if tgdist.active():
+            for st in cx.stores.values():
+                tgdist.broadcast_(st.p)
+                tgdist.broadcast_(st.s)
+        st = cx.stores['classifier']
+        st.ema.copy_(st.p)
+        self.wn_initialised = {net: len(v) for net, v in done.items()}
+        return dict(self.wn_initialised)
+
     def train_iteration(self, pre_train=False, use_graph=None):
         """D-update, G-update, C-update on the current placeholder contents (:266-276), launched the way tg.executor.resolve_launch reads
         out of config.EXEC_MODE / USE_HIP_GRAPH.  No host sync."""
@@ -604,11 +631,13 @@ class Train(Train_base):
         lr, c_lr = c.LEARNING_RATE, cla_lr(c)
         start_epoch = 0
         saver = None
+        wn_pending = self.options.wn_init == 'data'                                    # a restored run never re-initialises (below)
         if self.save_dir:
             from Training.Saver import Saver
             saver = Saver(self.save_dir)
             if c.RESTORE:                                                              # :140-147
                 start_epoch = saver.restore(self, dir_names=c.RUN, epoch=c.RESTORE_EPOCH)
+                wn_pending = False
                 if start_epoch >= 300:
                     lr = lr * 0.995 ** (start_epoch - 300)
                     c_lr = c_lr * 0.99 ** (start_epoch - 300)
@@ -634,6 +663,9 @@ class Train(Train_base):
             for i in range(iters):
                 self.feed(NNIO.next())
                 self.sample_latent()
+                if wn_pending:                                                         # WN_INIT = 'data': on the first batch, which is
+                    self.data_dependent_init()                                         # then iteration 1 as well
+                    wn_pending = False
                 self.train_iteration(pre_train=pre)
             torch.cuda.synchronize()
             dt = time.time() - t0
@@ -815,6 +847,8 @@ def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
     _synthetic_zca(tmp_config)                                         # a default like the class body's: FLAGS below override it
     if FLAGS:
         _customize_config(tmp_config, FLAGS)
+        if getattr(FLAGS, 'wn_init', None) is not None:                # --wn-init data: Config does not declare WN_INIT, so the hasattr rule
+            tmp_config.WN_INIT = FLAGS.wn_init                         # of _customize_config would drop it (Training/options.check_wn_init)
     if epochs is not None:
         tmp_config.EPOCHS = epochs
     tmp_config.SAMPLE_DIR = os.path.join(_root_dir(), "Training", tmp_config.SAMPLE_DIR)

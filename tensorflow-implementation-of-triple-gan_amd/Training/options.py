@@ -148,15 +148,48 @@ def check_zca(config, Dataset=None):
     return zc
 
 
-Options = collections.namedtuple('Options', 'mfma_dtype act_dtype num_classes loss optimizers clip_norms momentum seed no_grad_buckets '
+WN_INITS = (None, 'data')
+
+
+def check_wn_init(config):
+    """config.WN_INIT: None (default; also when the attribute is absent — config.Config does not declare it) or 'data': the
+    data-dependent initialisation of the weight-normalised layers on the first training batch (DESIGN §9.9).  Needs no device;
+    ValueError for any other value."""
+    v = getattr(config, 'WN_INIT', None)
+    if v is not None and not (isinstance(v, str) and v == 'data'):
+        raise ValueError("WN_INIT must be None or 'data', got %r" % (v,))
+    return v
+
+
+_Fields = collections.namedtuple('Options', 'mfma_dtype act_dtype num_classes loss optimizers clip_norms momentum seed no_grad_buckets '
                                             'summary summary_scalar summary_histogram summary_image summary_image_max_outputs')
+
+
+class Options(_Fields):
+    """the record resolve() returns.  Its tuple fields are the settings config.Config declares a default for (and NO_GRAD_BUCKETS);
+    `wn_init` (check_wn_init: a setting Config deliberately does not declare) is carried as an attribute beside them, so the field
+    list — what _asdict() and unpacking give — stays what it was.  Two records are equal when fields and wn_init are."""
+
+    def __new__(cls, wn_init=None, **fields):
+        self = super(Options, cls).__new__(cls, **fields)
+        self.wn_init = wn_init
+        return self
+
+    def __eq__(self, other):
+        return tuple.__eq__(self, other) and getattr(other, 'wn_init', None) == self.wn_init
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((tuple(self), self.wn_init))
 
 
 def resolve(config):
     """every device-free check of `config`, once -> the Options record of what Train reads with a default (EXEC_MODE / USE_HIP_GRAPH
     excepted: those stay live, read per iteration).  The string form of ZCA is checked here; against a Dataset, where one is known."""
     check_zca(config)
-    return Options(mfma_dtype=check_mfma_dtype(config), act_dtype=check_act_dtype(config), num_classes=check_num_classes(config),
+    return Options(wn_init=check_wn_init(config), mfma_dtype=check_mfma_dtype(config), act_dtype=check_act_dtype(config), num_classes=check_num_classes(config),
                    loss=check_loss(config), optimizers=check_optimizer(config), clip_norms=check_clip_norm(config),
                    momentum=float(opt(config, 'MOMENTUM')), seed=opt(config, 'SEED'),
                    no_grad_buckets=bool(getattr(config, 'NO_GRAD_BUCKETS', False)),      # a debugging switch Config does not declare

@@ -80,6 +80,11 @@ class Config(object):
                              # the bits that convolution would round it to, so the step is bit-identical with half the bytes on those
                              # edges; Train.bf16_act_edges counts them (0 on a model without such an edge: the switch changes nothing)
 
+    # WN_INIT — NOT declared here (the entry configurations' attribute sets are pinned): an instance or subclass may set
+    # WN_INIT = 'data' (--wn-init data) for the data-dependent initialisation of every weight-normalised layer on the first
+    # training batch, g <- init_scale / sqrt(var + eps), b <- -mean * g (Salimans & Kingma 2016; Train.data_dependent_init,
+    # DESIGN §9.9); absent or None: g = 1, b = 0 as created.  Read by Training/options.check_wn_init.
+
     def __init__(self):
         """Set values of computed attributes (config.py:70-73)."""
         self.MIN_QUEUE_EXAMPLES = self.BATCH_SIZE * 3

@@ -880,6 +880,71 @@ int ew_grid(int64_t work) {
   return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
+// ---- data-dependent weight-norm initialisation (tg_wn_init_f32): two passes over t [rows][c], both accumulated in fp64 in a fixed order.
+// Any ld (no 16-byte groups: the layer outputs it reads may be as narrow as one channel); 64 columns x 4 row lanes per workgroup, one
+// workgroup per (64 columns, RCH rows).  PASS 0: part[chunk][k] = sum t; PASS 1: part[chunk][k] = sum (t - mean[k])^2.
+template <int PASS>
+__global__ void __launch_bounds__(256) wn_init_partial(const float* t, int ld, int rows, int c, const double* __restrict__ mean,
+                                                        double* __restrict__ part) {
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + tx;
+  const int r0 = blockIdx.y * RCH, r1 = min(rows, r0 + RCH);
+  double s = 0.;
+  if (col < c) {
+    const double m = PASS ? mean[col] : 0.;
+    for (int r = r0 + ty; r < r1; r += 4) {
+      const double v = (double)t[(int64_t)r * ld + col];
+      if (PASS) {
+        const double d = v - m;
+        s += d * d;
+      } else {
+        s += v;
+      }
+    }
+  }
+  __shared__ double red[4][64];
+  red[ty][tx] = s;
+  __syncthreads();
+  if (ty == 0 && col < c) part[(int64_t)blockIdx.y * c + col] = ((red[0][tx] + red[1][tx]) + red[2][tx]) + red[3][tx];
+}
+
+// the chunks of one column summed by 8 lanes (lane l: chunks l, l+8, ...), then lane 0 adds the 8 in order.  PASS 0: mean; PASS 1: g, b.
+template <int PASS>
+__global__ void __launch_bounds__(256) wn_init_finalize(const double* __restrict__ part, int nchunks, int rows, int c, double* __restrict__ mean,
+                                                         double eps, double init_scale, float* __restrict__ g, float* __restrict__ b) {
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int col = blockIdx.x * 32 + tx;
+  double a = 0.;
+  if (col < c)
+    for (int k = ty; k < nchunks; k += 8) a += part[(int64_t)k * c + col];
+  __shared__ double red[8][32];
+  red[ty][tx] = a;
+  __syncthreads();
+  if (ty == 0 && col < c) {
+    for (int k = 1; k < 8; ++k) a += red[k][tx];
+    if (PASS == 0) {
+      mean[col] = a / (double)rows;
+    } else {
+      const float gf = (float)(init_scale / sqrt(a / (double)rows + eps));
+      g[col] = gf;
+      b[col] = (float)(-mean[col] * (double)gf);        // the assigned (rounded) g: b = assign(-mean * g)
+    }
+  }
+}
+
+// y[r][k] = act(g[k]*t[r][k] + b[k]) for k < c, 0 for c <= k < c_zero_to (y may be t itself: every element is read by the lane that writes it)
+__global__ void __launch_bounds__(256) wn_init_apply(const float* t, int ld_t, float* y, int ld_y, int rows, int c, int c_zero_to,
+                                                      const float* __restrict__ g, const float* __restrict__ b, int act, float alpha) {
+  const int64_t total = (int64_t)rows * c_zero_to;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / c_zero_to;
+    const int k = (int)(i - r * c_zero_to);
+    float v = 0.f;
+    if (k < c) v = tgd::act(g[k] * t[r * ld_t + k] + b[k], act, alpha);
+    y[r * ld_y + k] = v;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1287,6 +1352,38 @@ int tg_bn_bwd_finalize_f32(const float* s_dy, const float* s_dyx, int rows, int 
   tg::ProfScope prof(tg::PC_NORM, 0, 0, s);
   hipLaunchKernelGGL(bn_bwd_finalize, dim3((c + 127) / 128), dim3(128), 0, s, s_dy, s_dyx, rows, c, gamma, mean_inv, abc, dgamma, dbeta);
   TG_CHECK_LAUNCH("bn_bwd_finalize");
+  return TG_OK;
+}
+
+int64_t tg_wn_init_workspace_floats(int rows, int c) {
+  if (rows < 1 || c < 1) return 0;
+  return ((int64_t)(rows + RCH - 1) / RCH + 1) * c * 2;   // fp64: the means [c], then one partial [c] per chunk of RCH rows
+}
+
+int tg_wn_init_f32(const float* t, int ld_t, int rows, int c, int c_zero_to, float eps, float init_scale, int act, float alpha,
+                   float* workspace, float* g, float* b, float* y, int ld_y, void* stream) {
+  TG_REQUIRE(t && workspace && g && b && y, "wn_init: null buffer");
+  TG_REQUIRE(rows > 0 && c > 0, "wn_init: rows=%d c=%d (moments of an empty batch are undefined)", rows, c);
+  TG_REQUIRE(c <= ld_t && c_zero_to >= c && c_zero_to <= ld_y, "wn_init: c=%d c_zero_to=%d ld_t=%d ld_y=%d", c, c_zero_to, ld_t, ld_y);
+  TG_REQUIRE(eps >= 0.f && init_scale == init_scale && eps == eps, "wn_init: eps=%g init_scale=%g", (double)eps, (double)init_scale);
+  TG_REQUIRE((uintptr_t)workspace % 8 == 0, "wn_init: workspace must be 8-byte aligned");
+  const int nchunks = (rows + RCH - 1) / RCH;
+  TG_REQUIRE(nchunks <= 65535, "wn_init: rows=%d exceeds %d", rows, 65535 * RCH);
+  hipStream_t s = tg::as_stream(stream);
+  tg::ProfScope prof(tg::PC_NORM, 0, 4.0 * rows * (3.0 * c + c_zero_to), s);
+  double* mean = reinterpret_cast<double*>(workspace);
+  double* part = mean + c;
+  const dim3 pgrid((c + 63) / 64, nchunks), fgrid((c + 31) / 32);
+  hipLaunchKernelGGL(wn_init_partial<0>, pgrid, dim3(256), 0, s, t, ld_t, rows, c, mean, part);
+  TG_CHECK_LAUNCH("wn_init_partial<0>");
+  hipLaunchKernelGGL(wn_init_finalize<0>, fgrid, dim3(256), 0, s, part, nchunks, rows, c, mean, (double)eps, (double)init_scale, g, b);
+  TG_CHECK_LAUNCH("wn_init_finalize<0>");
+  hipLaunchKernelGGL(wn_init_partial<1>, pgrid, dim3(256), 0, s, t, ld_t, rows, c, mean, part);
+  TG_CHECK_LAUNCH("wn_init_partial<1>");
+  hipLaunchKernelGGL(wn_init_finalize<1>, fgrid, dim3(256), 0, s, part, nchunks, rows, c, mean, (double)eps, (double)init_scale, g, b);
+  TG_CHECK_LAUNCH("wn_init_finalize<1>");
+  hipLaunchKernelGGL(wn_init_apply, dim3(ew_grid((int64_t)rows * c_zero_to)), dim3(256), 0, s, t, ld_t, y, ld_y, rows, c, c_zero_to, g, b, act, alpha);
+  TG_CHECK_LAUNCH("wn_init_apply");
   return TG_OK;
 }
 

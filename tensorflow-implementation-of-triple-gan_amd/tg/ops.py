@@ -923,3 +923,14 @@ def moments_normalize(x, eps, init_scale=1.0):
     y = cx.new_act(x.n, x.h, x.w, c, x.ld)
     _call('tg_seg_scale_shift_act_f32', x.ptr, x.ld, y.ptr, y.ld, x.rows, c, c, seg_array([x.rows]), 1, _p(sc), _p(sh), 0, 0.0, cx.stream)
     return y
+
+
+def wn_data_init(t, g, b, eps, init_scale, act=None, alpha=0.0):
+    """Data-dependent initialisation of a weight-normalised layer (Salimans & Kingma 2016; Model/nn.py:492-500, Model/modle_base.py:68-71)
+    from its unit-gain pre-activation t = conv(x, V/||V||) (the layer's ordinary launch with wn=(ones, None)): with m, v the moments of t
+    over all axes but the last (biased variance, two passes in fp64),  g <- init_scale / sqrt(v + eps),  b <- -m * g  are WRITTEN into the
+    variables' tensors `g`, `b` ([t.c] each), and act(g*t + b) - what the layer evaluates from then on - is returned.  Forward only, recorded
+    nowhere, refused inside a hipGraph capture / launch-plan recording: it runs once, before a step exists.  The launch is tg/wn_init.py's:
+    this module's launches are the ones a recorded step replays (tests/launch_trace.py pins them), and this one never is."""
+    from . import wn_init
+    return wn_init.data_init(t, g, b, eps, init_scale, act, alpha)

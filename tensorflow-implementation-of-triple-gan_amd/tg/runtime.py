@@ -312,6 +312,8 @@ class Context(object):
     capturing = False                                 # a hipGraph capture is open on the launch stream (tg.executor.StepExecutor.capture)
     _wgrad_side_pending = False                       # launches on the second stream not yet joined (wgrad_on_side)
     detached_draws = False                            # inside Context.detached
+    assign_init = False                               # inside Context.assigning_init
+    wn_inited = ()                                    # scope names of the layers initialised inside the open assigning_init scope
 
     def __init__(self, device='cuda:0', seed=0):
         lib.load()                                   # fails loudly when the HIP extension is missing
@@ -560,6 +562,21 @@ class Context(object):
             yield
         finally:
             self.tape = prev
+
+    @contextlib.contextmanager
+    def assigning_init(self):
+        """the data-dependent initialisation pass: inside, init=True of the Model/nn.py layers ASSIGNS g and b
+        (ops.wn_data_init; outside it is the reference's forward-only branch), and the pass is a pure function of the variables and the
+        batch — NN_Base._drop_out / _add_noise and the classifiers' input noise are the identity, batch norms normalise with batch
+        statistics and leave the moving ones alone, nothing is recorded.  Yields the list that collects the initialised layers' scopes."""
+        if self.capturing or lib._recorder is not None:
+            raise lib.TgError("Context.assigning_init: inside a hipGraph capture / launch-plan recording")
+        prev = (self.assign_init, self.wn_inited, self.tape)
+        self.assign_init, self.wn_inited, self.tape = True, [], None
+        try:
+            yield self.wn_inited
+        finally:
+            self.assign_init, self.wn_inited, self.tape = prev
 
     def run_tape(self, tape, stop_at_boundary=False):
         """run a recorded tape in reverse (all of it, or down to its last bucket boundary: see backward); returns the unexecuted head
