@@ -778,7 +778,7 @@ bool conv3x3_bf16_applicable(const tg_igemm_desc* d, int n_desc, const int32_t* 
 }
 
 // A launch of the right shape whose last round is less than 90 % full: the number of LEADING images that make whole rounds — they go to
-// the halo kernel, the few images left to the generic one (igemm_impl splits the launch; 130 images of 32x32: 128 + 2).  0: no such
+// the halo kernel, the few images left to the generic one (igemm_launch cuts the launch; 130 images of 32x32: 128 + 2).  0: no such
 // split (rounds full enough, too few images for one round, or the whole-round prefix is less than 60 % of the launch).
 int conv3x3_bf16_split_images(const tg_igemm_desc* d, int n_desc, const int32_t* seg_rows, int nseg, bool bf16) {
   if (g_policy != 0 || !conv3x3_fits(d, n_desc, seg_rows, nseg, bf16)) return 0;
@@ -798,17 +798,18 @@ int64_t conv3x3_bf16_pack_bytes(const tg_igemm_desc* d, int n_desc) {
   return pack_bytes(d);
 }
 
-int conv3x3_bf16_launch(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, double* colsum,
-                        const int32_t* seg_rows, int nseg, const float* ymul, int ymul_act, float ymul_alpha, uint32_t in_bytes, uint32_t w_bytes,
-                        uint32_t out_bytes, hipStream_t s, bool bf16, void* scratch, int64_t scratch_bytes, int stat2, bool in16) {
-  TG_REQUIRE(!in16 || (bf16 && (colsum == nullptr || stat2 == 1) && ymul == nullptr),
+int conv3x3_bf16_launch(const IgemmCall& c, uint32_t in_bytes, uint32_t w_bytes, uint32_t out_bytes) {
+  const tg_igemm_desc* d = c.descs;
+  const bool bf16 = c.bf16();
+  hipStream_t s = as_stream(c.stream);
+  TG_REQUIRE(!c.in16() || (bf16 && (c.sums == nullptr || c.stat2() == 1) && c.ymul == nullptr),
              "conv3x3: a bf16-stored input is served for the bf16 forward and its batch-norm statistics form only");
   ConvParams p;
-  p.stat2 = stat2;
-  p.in16 = in16 ? 1 : 0;
-  p.in = in; p.w = w; p.bias = bias; p.out = out; p.colsum = colsum; p.ymul = ymul; p.ymul_act = ymul_act; p.ymul_alpha = ymul_alpha;
-  p.nseg = nseg;
-  for (int i = 0; i < 8; ++i) p.seg_rows[i] = (seg_rows && i < nseg) ? seg_rows[i] : 0;
+  p.stat2 = c.stat2();
+  p.in16 = c.in16() ? 1 : 0;
+  p.in = c.in; p.w = c.w; p.bias = c.bias; p.out = c.out; p.colsum = c.sums; p.ymul = c.ymul; p.ymul_act = c.ymul_act; p.ymul_alpha = c.ymul_alpha;
+  p.nseg = c.nseg;
+  for (int i = 0; i < 8; ++i) p.seg_rows[i] = (c.seg_rows && i < c.nseg) ? c.seg_rows[i] : 0;
   p.n_img = d->n_img; p.h = d->h_in; p.ld_in = d->ld_in; p.ld_out = d->ld_out; p.c_out = d->c_out; p.n_store = d->n_store;
   p.act = d->act; p.alpha = d->alpha;
   p.w_sn = d->w_sn; p.w_st = d->w_st;
@@ -818,17 +819,17 @@ int conv3x3_bf16_launch(const tg_igemm_desc* d, const float* in, const float* w,
   p.n_tiles_n = d->c_out / BN;
   p.in_bytes = in_bytes; p.w_bytes = w_bytes; p.out_bytes = out_bytes;
   const auto simple = [](int a) { return a == TG_ACT_NONE || a == TG_ACT_LRELU || a == TG_ACT_RELU; };
-  TG_REQUIRE(ymul == nullptr || simple(ymul_act), "conv3x3: activation %d of the gradient multiplier is not none / relu / leaky relu", ymul_act);
+  TG_REQUIRE(c.ymul == nullptr || simple(c.ymul_act), "conv3x3: activation %d of the gradient multiplier is not none / relu / leaky relu", c.ymul_act);
   p.wpk = nullptr;
   if (bf16) {
     // the bf16 filter goes global -> LDS by LDS-DMA from a packed copy in CALLER-OWNED scratch (size: tg_igemm_workspace_bytes(descs, n_desc, seg_rows, nseg, bf16 = 1));
     // the library allocates nothing, and a launch without the scratch it was told to bring is an error, not a slower kernel
     const int64_t need = pack_bytes(d);
-    TG_REQUIRE(scratch != nullptr && scratch_bytes >= need,
+    TG_REQUIRE(c.scratch != nullptr && c.scratch_bytes >= need,
                "conv3x3 (bf16): this launch needs %lld bytes of scratch for the packed filter, got %lld (query tg_igemm_workspace_bytes(..., bf16 = 1))",
-               (long long)need, (long long)(scratch ? scratch_bytes : 0));
-    TG_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "conv3x3 (bf16): scratch must be 16-byte aligned");
-    p.wpk = scratch;
+               (long long)need, (long long)(c.scratch ? c.scratch_bytes : 0));
+    TG_REQUIRE((reinterpret_cast<uintptr_t>(c.scratch) & 15) == 0, "conv3x3 (bf16): scratch must be 16-byte aligned");
+    p.wpk = c.scratch;
     const int nchunks = d->ld_in / KC;
     const int total = p.n_tiles_n * nchunks * 9 * 1024;        // 16-byte chunks of the packed filter
     hipLaunchKernelGGL(filter_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, p, nchunks, total);

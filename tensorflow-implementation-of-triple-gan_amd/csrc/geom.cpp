@@ -52,7 +52,7 @@ int fill(tg_igemm_desc* d, int n_img, int h_in, int w_in, int ld_in, int h_v, in
 
 namespace tg {
 
-// ---- tile pick of igemm_impl (csrc/igemm.hip) — the quantisation cost model, see the comments there ------------------------------------
+// ---- tile pick of igemm_route (csrc/igemm.hip) — the quantisation cost model, see the comments there ------------------------------------
 bool igemm_pick_tile(const tg_igemm_desc* descs, int n_desc, bool colsum, const int32_t* seg_rows, int nseg, bool bf16, int* bm_out, int* bn_out) {
   struct Cand { int bm, bn; double eff; };
   // No 128 x 64 candidate: it could never win.  Wherever it is allowed, 64 x 64 is too (same BN; a smaller BM passes the segment rule),

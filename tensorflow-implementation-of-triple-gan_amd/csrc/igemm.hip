@@ -1059,85 +1059,98 @@ static void launch_igemm(IgemmParams& p, hipStream_t s, bool bf16) {
   }
 }
 
-// the head / tail cut of a launch of the halo kernel's shape that does not fill whole rounds (conv3x3_bf16.hip): descriptors and segment
-// tables of the two parts.  Returns the head's image count, 0: no cut.
-struct HeadTail { tg_igemm_desc dh, dt; int32_t seg_h[8], seg_t[8]; int nh, nt, k0; };
-static int head_tail(const tg_igemm_desc* descs, int n_desc, const int32_t* seg_rows, int nseg, bool colsum, bool bf16, HeadTail* o) {
-  const int head = tg::conv3x3_bf16_split_images(descs, n_desc, seg_rows, colsum ? nseg : 0, bf16);
-  if (!head) return 0;
-  o->dh = descs[0]; o->dt = descs[0];
-  o->dh.n_img = head;
-  o->dt.n_img = descs[0].n_img - head;
-  const int64_t per_img = (int64_t)descs[0].h_in * descs[0].w_in;
-  o->nh = o->nt = o->k0 = 0;
-  if (colsum) {
-    int64_t left = (int64_t)head * per_img;                   // rows of the head still to hand out
+using tg::IgemmCall;
+
+// ---- the route of a launch: decided once, by igemm_route, for igemm_launch (which executes it) and tg_igemm_workspace_bytes (which
+// returns its scratch_bytes) -----------------------------------------------------------------------------------------------------------------
+//   HEAD_TAIL  a 3x3 layer of the halo kernel's shape whose launch does not fill whole rounds of one workgroup per CU (conv3x3_bf16.hip):
+//              the leading images that do are one launch, the few left over another — disjoint image ranges of the same buffers, the
+//              statistics of both accumulating into the same per-segment accumulators.  Each part is routed as a launch of its own.
+//   WIDEN      a bf16-stored input on images the halo kernel does not take: widened into the front of the scratch, then GENERIC on the rest
+//   HALO       conv3x3_bf16.hip (both operand types); bf16 operands REQUIRE the scratch for the packed filter
+//   GENERIC    igemm_f32_kernel: the cost model's tile (geom.cpp) and the schedule that cuts tiles along K through all the scratch it wants
+enum RouteKind { ROUTE_HEAD_TAIL, ROUTE_WIDEN, ROUTE_HALO, ROUTE_GENERIC };
+struct IgemmRoute {
+  RouteKind kind;
+  int64_t scratch_bytes;                                   // scratch the launch can use
+  int head, nh, nt, k0;                                    // HEAD_TAIL: images of the head, segments of the parts, first segment of the tail
+  tg_igemm_desc dh, dt;
+  int32_t seg_h[8], seg_t[8];
+  int64_t widen_bytes;                                     // WIDEN
+  int bm, bn, nk[MAX_SUB];                                 // WIDEN, GENERIC: tile (0: none fits), K-tiles per sub-problem in kernel order,
+  int64_t tiles;                                           // tiles per sub-problem and the schedule WITH scratch
+  tg::IgemmSched sched;
+};
+
+// nseg = 0: no statistics.  labels: tg_igemm_labels_* (always GENERIC; the size query cannot know and answers as without labels)
+static IgemmRoute igemm_route(const tg_igemm_desc* descs, int n_desc, const int32_t* seg_rows, int nseg, tg::IgemmOperands ops, bool labels) {
+  IgemmRoute r{};
+  const tg_igemm_desc* d = &descs[0];
+  const bool bf16 = ops != tg::IGEMM_F32;
+  r.head = labels ? 0 : tg::conv3x3_bf16_split_images(descs, n_desc, seg_rows, nseg, bf16);
+  if (r.head) {
+    r.kind = ROUTE_HEAD_TAIL;
+    r.dh = r.dt = *d;
+    r.dh.n_img = r.head;
+    r.dt.n_img = d->n_img - r.head;
+    int64_t left = (int64_t)r.head * d->h_in * d->w_in;     // rows of the head still to hand out
     for (int i = 0; i < nseg; ++i) {
-      const int64_t r = seg_rows[i], take = r < left ? r : left;
-      if (take > 0) o->seg_h[o->nh++] = (int32_t)take;
-      if (r - take > 0) {
-        if (o->nt == 0) o->k0 = i;
-        o->seg_t[o->nt++] = (int32_t)(r - take);
+      const int64_t rows = seg_rows[i], take = rows < left ? rows : left;
+      if (take > 0) r.seg_h[r.nh++] = (int32_t)take;
+      if (rows - take > 0) {
+        if (r.nt == 0) r.k0 = i;
+        r.seg_t[r.nt++] = (int32_t)(rows - take);
       }
       left -= take;
     }
+    const int64_t a = igemm_route(&r.dh, 1, r.seg_h, r.nh, ops, false).scratch_bytes, b = igemm_route(&r.dt, 1, r.seg_t, r.nt, ops, false).scratch_bytes;
+    r.scratch_bytes = a > b ? a : b;                        // one after the other
+    return r;
   }
-  return head;
+  if (!labels && tg::conv3x3_bf16_applicable(descs, n_desc, seg_rows, nseg, bf16)) {
+    r.kind = ROUTE_HALO;
+    r.scratch_bytes = bf16 ? tg::conv3x3_bf16_pack_bytes(descs, n_desc) : 0;
+    return r;
+  }
+  r.kind = ops == tg::IGEMM_BF16_IN16 ? ROUTE_WIDEN : ROUTE_GENERIC;
+  r.scratch_bytes = r.widen_bytes = r.kind == ROUTE_WIDEN ? widen_bytes(d) : 0;
+  // tile choice by the quantisation cost model of geom.cpp (tg::igemm_pick_tile; also behind tg_igemm_tile / tg_igemm_colsum_supported)
+  if (!tg::igemm_pick_tile(descs, n_desc, nseg > 0, seg_rows, nseg, bf16, &r.bm, &r.bn)) return r;
+  // work units: tiles of an under-filled launch / of the long sub-problems are cut along K through the caller's scratch
+  int order[MAX_SUB] = {0, 1, 2, 3};
+  tg::igemm_sub_order(descs, n_desc, order);
+  for (int i = 0; i < n_desc; ++i) r.nk[i] = descs[order[i]].n_taps * (d->ld_in / BK);
+  const int64_t M = (int64_t)d->n_img * d->h_v * d->w_v;
+  r.tiles = ((M + r.bm - 1) / r.bm) * ((d->c_out + r.bn - 1) / r.bn);
+  tg::igemm_schedule(n_desc, r.nk, r.tiles, r.bm, r.bn, 2 * tg::halo_compute_units(), true, &r.sched);
+  r.scratch_bytes += r.sched.ws_bytes;
+  return r;
 }
 
-static int igemm_impl(const tg_igemm_desc* descs, int n_desc, const float* in, const float* w, const float* bias, float* out, void* stream,
-                      double* colsum, const int32_t* seg_rows, int nseg, bool bf16 = false, const float* ymul = nullptr, int ymul_act = 0,
-                      float ymul_alpha = 0.f, void* scratch = nullptr, int64_t scratch_bytes = 0, int stat2 = 0, const float* lab = nullptr,
-                      int lab_n = 0, bool in16 = false) {
-  TG_REQUIRE(descs && n_desc >= 1 && n_desc <= MAX_SUB, "igemm: n_desc=%d out of range", n_desc);
-  TG_REQUIRE(in && w && out, "igemm: null buffer");
-  if (lab) {
-    const tg_igemm_desc* e = &descs[0];
-    TG_REQUIRE(n_desc == 1 && !colsum && e->n_group == 0 && e->os_x == 1 && e->os_y == 1 && lab_n >= 1 && (e->n_store & 3) == 0 && (e->ld_out & 3) == 0 &&
-               e->ld_out >= e->n_store + lab_n,
+static int igemm_validate(const IgemmCall& c) {
+  TG_REQUIRE(c.descs && c.n_desc >= 1 && c.n_desc <= MAX_SUB, "igemm: n_desc=%d out of range", c.n_desc);
+  TG_REQUIRE(c.in && c.w && c.out, "igemm: null buffer");
+  if (c.lab) {
+    const tg_igemm_desc* e = &c.descs[0];
+    TG_REQUIRE(c.n_desc == 1 && !c.sums && e->n_group == 0 && e->os_x == 1 && e->os_y == 1 && c.lab_n >= 1 && (e->n_store & 3) == 0 && (e->ld_out & 3) == 0 &&
+               e->ld_out >= e->n_store + c.lab_n,
                "igemm_labels: needs one ungrouped sub-problem with os = 1, 4 | n_store, 4 | ld_out and ld_out >= n_store + n_labels (n_store %d, ld_out %d, n_labels %d)",
-               e->n_store, e->ld_out, lab_n);
+               e->n_store, e->ld_out, c.lab_n);
   }
-  // A 3x3 layer of the halo kernel's shape whose launch does not fill whole rounds of one workgroup per CU (conv3x3_bf16.hip): the leading
-  // images that do go to that kernel, the few left over to the generic one — two launches over disjoint image ranges of the same buffers
-  // (the column sums of both accumulate into the same per-segment accumulators).
-  TG_REQUIRE(!in16 || (bf16 && !lab && !ymul && n_desc == 1), "igemm: a bf16-stored input is served for one bf16 sub-problem without labels / multiplier");
-  HeadTail ht;
-  if (const int head = lab ? 0 : head_tail(descs, n_desc, seg_rows, nseg, colsum != nullptr, bf16, &ht)) {
-    const int64_t per_img = (int64_t)descs[0].h_in * descs[0].w_in;
-    int rc = igemm_impl(&ht.dh, 1, in, w, bias, out, stream, colsum, colsum ? ht.seg_h : nullptr, ht.nh, bf16, ymul, ymul_act, ymul_alpha, scratch, scratch_bytes, stat2,
-                        nullptr, 0, in16);
-    if (rc != TG_OK) return rc;
-    const int64_t o_in = (int64_t)head * per_img * descs[0].ld_in, o_out = (int64_t)head * per_img * descs[0].ld_out;
-    const float* in_t = reinterpret_cast<const float*>(reinterpret_cast<const char*>(in) + o_in * (in16 ? 2 : 4));
-    // (the tail is stream-ordered behind the head: both may use the same scratch)
-    return igemm_impl(&ht.dt, 1, in_t, w, bias, out + o_out, stream, colsum ? colsum + (int64_t)ht.k0 * descs[0].c_out * (stat2 ? 2 : 1) : nullptr,
-                      colsum ? ht.seg_t : nullptr, ht.nt, bf16, ymul ? ymul + o_out : nullptr, ymul_act, ymul_alpha, scratch, scratch_bytes, stat2, nullptr, 0,
-                      in16);
-  }
-  if (in16 && !tg::conv3x3_bf16_applicable(descs, n_desc, seg_rows, colsum ? nseg : 0, bf16)) {
-    // images the halo kernel does not take: widen them into the front of the scratch, the generic kernel's cut tiles use the rest
-    TG_REQUIRE(check_desc(&descs[0]) == TG_OK, "igemm: bad descriptor");
-    const int64_t wb = widen_bytes(&descs[0]);
-    TG_REQUIRE(scratch != nullptr && scratch_bytes >= wb && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0,
-               "igemm (bf16-stored input): this launch needs %lld bytes of 16-byte aligned scratch to widen its input, got %lld (query "
-               "tg_igemm_workspace_bytes(..., bf16 = 2))", (long long)wb, (long long)(scratch ? scratch_bytes : 0));
-    const int64_t n4 = (int64_t)descs[0].n_img * descs[0].h_in * descs[0].w_in * descs[0].ld_in / 4;
-    const int64_t nb = (n4 + 255) / 256;
-    hipLaunchKernelGGL(widen_bf16_kernel, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, tg::as_stream(stream), reinterpret_cast<const uint2*>(in),
-                       static_cast<float4*>(scratch), n4);
-    TG_CHECK_LAUNCH("widen_bf16_kernel");
-    char* rest = static_cast<char*>(scratch) + wb;
-    return igemm_impl(descs, n_desc, static_cast<const float*>(scratch), w, bias, out, stream, colsum, seg_rows, nseg, bf16, ymul, ymul_act, ymul_alpha,
-                      scratch_bytes > wb ? rest : nullptr, scratch_bytes - wb, stat2);
-  }
-  IgemmParams p;
-  p.in = in; p.w = w; p.bias = bias; p.out = out; p.n_sub = n_desc;
-  p.colsum = colsum; p.nseg = nseg;
-  p.ymul = ymul; p.ymul_act = ymul_act; p.ymul_alpha = ymul_alpha;
-  p.stat2 = stat2;
-  p.lab = lab; p.lab_n = lab_n; p.lab_c0 = descs[0].n_store;
-  for (int i = 0; i < 8; ++i) p.seg_rows[i] = (seg_rows && i < nseg) ? seg_rows[i] : 0;
+  TG_REQUIRE(!c.in16() || (c.bf16() && !c.lab && !c.ymul && c.n_desc == 1), "igemm: a bf16-stored input is served for one bf16 sub-problem without labels / multiplier");
+  return TG_OK;
+}
+
+// the kernel's view of the call: checked descriptors in kernel order, the three buffer-descriptor extents, everything but the schedule
+static int igemm_pack(const IgemmCall& c, IgemmParams& p) {
+  const tg_igemm_desc* descs = c.descs;
+  const int n_desc = c.n_desc;
+  p.in = c.in; p.w = c.w; p.bias = c.bias; p.out = c.out; p.n_sub = n_desc;
+  p.colsum = c.sums; p.nseg = c.nseg;
+  p.ymul = c.ymul; p.ymul_act = c.ymul_act; p.ymul_alpha = c.ymul_alpha;
+  p.stat2 = c.stat2();
+  p.lab = c.lab; p.lab_n = c.lab_n; p.lab_c0 = descs[0].n_store;
+  for (int i = 0; i < 8; ++i) p.seg_rows[i] = (c.seg_rows && i < c.nseg) ? c.seg_rows[i] : 0;
   const tg_igemm_desc* d = &descs[0];
   // sub-problems longest first: workgroups are dispatched in index order, so the 9-tap parity of a 5x5 s2 transposed
   // conv starts before the 4-tap one instead of forming the tail
@@ -1177,40 +1190,13 @@ static int igemm_impl(const tg_igemm_desc* descs, int n_desc, const float* in, c
   }
   TG_REQUIRE(out_bytes < 0x7FFFFFF0LL, "igemm: output tensor exceeds the 2 GiB buffer-descriptor range");
   p.out_bytes = (uint32_t)out_bytes;
-  double taps = 0;
-  for (int i = 0; i < n_desc; ++i) taps += descs[i].n_taps;
-  const double flops = 2.0 * p.M * d->c_out * taps * d->ld_in;
-  const double bytes = (in16 ? 2.0 : 4.0) * p.M * d->ld_in + 4.0 * ((double)p.M * d->n_store * n_desc + (double)d->c_out * taps * d->ld_in);
-  hipStream_t s = tg::as_stream(stream);
-  const bool halo = !lab && tg::conv3x3_bf16_applicable(descs, n_desc, seg_rows, colsum ? nseg : 0, bf16);      // the classifier's 3x3 layers: halo-tiled kernel (both operand types)
-  // tile choice by the quantisation cost model of geom.cpp (tg::igemm_pick_tile; also behind tg_igemm_tile / tg_igemm_colsum_supported)
-  int bm = 0, bn = 0;
-  tg::IgemmSched sc;
-  std::memset(&sc, 0, sizeof sc);
-  if (!halo) {
-    TG_REQUIRE(tg::igemm_pick_tile(descs, n_desc, colsum != nullptr, seg_rows, nseg, bf16, &bm, &bn), "igemm: no tile fits c_out=%d with the given segments",
-               d->c_out);
-    // work units: tiles of the last partial round / of an under-filled launch / of the long sub-problems are cut along K when the caller
-    // brought scratch for their partial sums (tg_igemm_workspace_bytes); otherwise one unit per tile
-    p.m_tiles = (p.M + bm - 1) / bm;
-    p.n_tiles = (p.c_out + bn - 1) / bn;
-    int nk[MAX_SUB] = {0, 0, 0, 0};
-    for (int i = 0; i < n_desc; ++i) nk[i] = descs[order[i]].n_taps * (d->ld_in / BK);
-    tg::igemm_schedule(n_desc, nk, (int64_t)p.m_tiles * p.n_tiles, bm, bn, 2 * tg::halo_compute_units(), scratch != nullptr, &sc);
-    if (sc.ws_bytes > scratch_bytes || (reinterpret_cast<uintptr_t>(scratch) & 15))      // less scratch than the cut needs: the one-launch schedule
-      tg::igemm_schedule(n_desc, nk, (int64_t)p.m_tiles * p.n_tiles, bm, bn, 2 * tg::halo_compute_units(), false, &sc);
-  }
-  char desc[128];
-  snprintf(desc, sizeof(desc), "M=%dx%d N=%d K=%gx%d in=%dx%d s=%d os=%d%s tile=%dx%d units=%d fix=%d ks=%d/%d/%d/%d", n_desc, p.M, d->c_out, taps, d->ld_in, d->h_in,
-           d->w_in, d->s_y, d->os_y, bf16 ? " bf16" : "", bm, bn, sc.n_units, sc.n_fix, sc.ks[0], sc.ks[1], sc.ks[2], sc.ks[3]);
-  tg::ProfScope prof(tg::PC_IGEMM, flops, bytes, s, desc);
-  if (halo)
-    return tg::conv3x3_bf16_launch(d, in, w, bias, out, colsum, seg_rows, nseg, ymul, ymul_act, ymul_alpha, in16 ? p.in_bytes / 2 : p.in_bytes, p.w_bytes,
-                                   p.out_bytes, s, bf16, scratch, scratch_bytes, stat2, in16);
+  return TG_OK;
+}
+
+static int launch_generic(IgemmParams& p, const tg::IgemmSched& sc, int bm, int bn, hipStream_t s, bool bf16) {
   p.n_units = sc.n_units; p.n_fix = sc.n_fix; p.nfull = sc.nfull; p.pat_len = sc.pat_len; p.n_pat_split = sc.n_pat_split; p.n_split_sub = sc.n_split_sub;
   for (int i = 0; i < MAX_SUB; ++i) { p.ks[i] = sc.ks[i]; p.split_sub[i] = sc.split_sub[i]; p.first_slot[i] = sc.first_slot[i]; }
   for (int i = 0; i < 16; ++i) { p.pat_sub[i] = sc.pat_sub[i]; p.pat_k[i] = sc.pat_k[i]; p.pat_slot[i] = sc.pat_slot[i]; }
-  p.ws = static_cast<float*>(scratch);
   if (bm == 128 && bn == 128) launch_igemm<128, 128, 2, 2>(p, s, bf16);
   else if (bm == 64 && bn == 128) launch_igemm<64, 128, 2, 2>(p, s, bf16);
   else if (bm == 64 && bn == 64) launch_igemm<64, 64, 2, 2>(p, s, bf16);
@@ -1218,6 +1204,82 @@ static int igemm_impl(const tg_igemm_desc* descs, int n_desc, const float* in, c
   else launch_igemm<128, 32, 4, 1>(p, s, bf16);
   TG_CHECK_LAUNCH("igemm_f32_kernel");
   return TG_OK;
+}
+
+// HALO and GENERIC (and what WIDEN leaves): one kernel over the whole call
+static int igemm_run(const IgemmCall& c, const IgemmRoute& r) {
+  IgemmParams p;
+  int rc = igemm_pack(c, p);
+  if (rc != TG_OK) return rc;
+  const tg_igemm_desc* d = &c.descs[0];
+  const bool halo = r.kind == ROUTE_HALO;                  // the classifier's 3x3 layers: halo-tiled kernel (both operand types)
+  double taps = 0;
+  for (int i = 0; i < c.n_desc; ++i) taps += c.descs[i].n_taps;
+  const double flops = 2.0 * p.M * d->c_out * taps * d->ld_in;
+  const double bytes = (c.in16() ? 2.0 : 4.0) * p.M * d->ld_in + 4.0 * ((double)p.M * d->n_store * c.n_desc + (double)d->c_out * taps * d->ld_in);
+  tg::IgemmSched sc = r.sched;
+  if (!halo) {
+    TG_REQUIRE(r.bm, "igemm: no tile fits c_out=%d with the given segments", d->c_out);
+    p.m_tiles = (p.M + r.bm - 1) / r.bm;
+    p.n_tiles = (p.c_out + r.bn - 1) / r.bn;
+    // no scratch, less than the cut needs, or misaligned: the one-launch schedule (one unit per tile)
+    if (sc.ws_bytes > 0 && (!c.scratch || sc.ws_bytes > c.scratch_bytes || (reinterpret_cast<uintptr_t>(c.scratch) & 15)))
+      tg::igemm_schedule(c.n_desc, r.nk, r.tiles, r.bm, r.bn, 2 * tg::halo_compute_units(), false, &sc);
+  }
+  hipStream_t s = tg::as_stream(c.stream);
+  char desc[128];
+  snprintf(desc, sizeof(desc), "M=%dx%d N=%d K=%gx%d in=%dx%d s=%d os=%d%s tile=%dx%d units=%d fix=%d ks=%d/%d/%d/%d", c.n_desc, p.M, d->c_out, taps, d->ld_in, d->h_in,
+           d->w_in, d->s_y, d->os_y, c.bf16() ? " bf16" : "", r.bm, r.bn, sc.n_units, sc.n_fix, sc.ks[0], sc.ks[1], sc.ks[2], sc.ks[3]);
+  tg::ProfScope prof(tg::PC_IGEMM, flops, bytes, s, desc);
+  if (halo) return tg::conv3x3_bf16_launch(c, c.in16() ? p.in_bytes / 2 : p.in_bytes, p.w_bytes, p.out_bytes);
+  p.ws = static_cast<float*>(c.scratch);
+  return launch_generic(p, sc, r.bm, r.bn, s, c.bf16());
+}
+
+static int igemm_launch(const IgemmCall& c);
+
+static int launch_head_tail(const IgemmCall& c, const IgemmRoute& r) {
+  const tg_igemm_desc* d = &c.descs[0];
+  const int64_t rows = (int64_t)r.head * d->h_in * d->w_in, o_in = rows * d->ld_in, o_out = rows * d->ld_out;
+  IgemmCall h = c, t = c;
+  h.descs = &r.dh; h.seg_rows = r.seg_h; h.nseg = r.nh;
+  int rc = igemm_launch(h);
+  if (rc != TG_OK) return rc;
+  t.descs = &r.dt; t.seg_rows = r.seg_t; t.nseg = r.nt;
+  t.in = reinterpret_cast<const float*>(reinterpret_cast<const char*>(c.in) + o_in * (c.in16() ? 2 : 4));
+  t.out = c.out + o_out;
+  if (c.sums) t.sums = c.sums + (int64_t)r.k0 * d->c_out * (c.stat2() ? 2 : 1);
+  if (c.ymul) t.ymul = c.ymul + o_out;
+  return igemm_launch(t);                                  // (stream-ordered behind the head: both may use the same scratch)
+}
+
+static int launch_widen(const IgemmCall& c, const IgemmRoute& r) {
+  const tg_igemm_desc* d = &c.descs[0];
+  TG_REQUIRE(check_desc(d) == TG_OK, "igemm: bad descriptor");
+  const int64_t wb = r.widen_bytes;
+  TG_REQUIRE(c.scratch != nullptr && c.scratch_bytes >= wb && (reinterpret_cast<uintptr_t>(c.scratch) & 15) == 0,
+             "igemm (bf16-stored input): this launch needs %lld bytes of 16-byte aligned scratch to widen its input, got %lld (query "
+             "tg_igemm_workspace_bytes(..., bf16 = 2))", (long long)wb, (long long)(c.scratch ? c.scratch_bytes : 0));
+  const int64_t n4 = (int64_t)d->n_img * d->h_in * d->w_in * d->ld_in / 4;
+  const int64_t nb = (n4 + 255) / 256;
+  hipLaunchKernelGGL(widen_bf16_kernel, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, tg::as_stream(c.stream), reinterpret_cast<const uint2*>(c.in),
+                     static_cast<float4*>(c.scratch), n4);
+  TG_CHECK_LAUNCH("widen_bf16_kernel");
+  IgemmCall g = c;                                         // the generic kernel on the widened copy, its cut tiles in the rest of the scratch
+  g.in = static_cast<const float*>(c.scratch);
+  g.ops = tg::IGEMM_BF16;
+  g.scratch = c.scratch_bytes > wb ? static_cast<char*>(c.scratch) + wb : nullptr;
+  g.scratch_bytes = c.scratch_bytes - wb;
+  return igemm_run(g, r);
+}
+
+static int igemm_launch(const IgemmCall& c) {
+  int rc = igemm_validate(c);
+  if (rc != TG_OK) return rc;
+  const IgemmRoute r = igemm_route(c.descs, c.n_desc, c.seg_rows, c.sums ? c.nseg : 0, c.ops, c.lab != nullptr);
+  if (r.kind == ROUTE_HEAD_TAIL) return launch_head_tail(c, r);
+  if (r.kind == ROUTE_WIDEN) return launch_widen(c, r);
+  return igemm_run(c, r);
 }
 
 #ifdef TG_STAMP
@@ -1234,97 +1296,38 @@ extern "C" int tg_debug_read_stamps(unsigned long long* out) {
 
 extern "C" int tg_igemm_multi_f32(const tg_igemm_desc* descs, int n_desc, const float* in, const float* w, const float* bias, float* out,
                                   void* scratch, int64_t scratch_bytes, void* stream) {
-  return igemm_impl(descs, n_desc, in, w, bias, out, stream, nullptr, nullptr, 0, false, nullptr, 0, 0.f, scratch, scratch_bytes);
+  return igemm_launch({.descs = descs, .n_desc = n_desc, .in = in, .w = w, .bias = bias, .out = out, .ops = tg::IGEMM_F32, .scratch = scratch,
+                       .scratch_bytes = scratch_bytes, .stream = stream});
+}
+
+extern "C" int tg_igemm_multi_bf16(const tg_igemm_desc* descs, int n_desc, const float* in, const float* w, const float* bias, float* out,
+                                   void* scratch, int64_t scratch_bytes, void* stream) {
+  return igemm_launch({.descs = descs, .n_desc = n_desc, .in = in, .w = w, .bias = bias, .out = out, .ops = tg::IGEMM_BF16, .scratch = scratch,
+                       .scratch_bytes = scratch_bytes, .stream = stream});
 }
 
 extern "C" int tg_igemm_f32(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, void* scratch,
                             int64_t scratch_bytes, void* stream) {
-  return igemm_impl(d, 1, in, w, bias, out, stream, nullptr, nullptr, 0, false, nullptr, 0, 0.f, scratch, scratch_bytes);
+  return tg_igemm_multi_f32(d, 1, in, w, bias, out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int tg_igemm_bf16(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, void* scratch,
+                             int64_t scratch_bytes, void* stream) {
+  return tg_igemm_multi_bf16(d, 1, in, w, bias, out, scratch, scratch_bytes, stream);
 }
 
 extern "C" int tg_igemm_labels_f32(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, const float* labels, int n_labels, float* out,
                                    void* scratch, int64_t scratch_bytes, void* stream) {
   TG_REQUIRE(labels != nullptr, "igemm_labels: null labels");
-  return igemm_impl(d, 1, in, w, bias, out, stream, nullptr, nullptr, 0, false, nullptr, 0, 0.f, scratch, scratch_bytes, 0, labels, n_labels);
+  return igemm_launch({.descs = d, .n_desc = 1, .in = in, .w = w, .bias = bias, .out = out, .ops = tg::IGEMM_F32, .lab = labels, .lab_n = n_labels,
+                       .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream});
 }
 
 extern "C" int tg_igemm_labels_bf16(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, const float* labels, int n_labels, float* out,
                                     void* scratch, int64_t scratch_bytes, void* stream) {
   TG_REQUIRE(labels != nullptr, "igemm_labels: null labels");
-  return igemm_impl(d, 1, in, w, bias, out, stream, nullptr, nullptr, 0, true, nullptr, 0, 0.f, scratch, scratch_bytes, 0, labels, n_labels);
-}
-
-// scratch a launch of these descriptors can use: the larger of the halo kernel's packed bf16 filter (REQUIRED by such a launch) and the
-// partial sums of the tiles the generic kernel's schedule cuts along K (optional: with less the launch runs as one unit per tile);
-// a launch that is cut into a halo head and a generic tail uses the scratch for one after the other.  Mirrors the routing of igemm_impl.
-static int64_t igemm_ws_bytes(const tg_igemm_desc* descs, int n_desc, const int32_t* seg_rows, int nseg, bool bf16, bool in16 = false) {
-  const bool colsum = nseg > 0;
-  HeadTail ht;
-  if (head_tail(descs, n_desc, seg_rows, nseg, colsum, bf16, &ht)) {
-    const int64_t a = igemm_ws_bytes(&ht.dh, 1, colsum ? ht.seg_h : nullptr, ht.nh, bf16, in16);
-    const int64_t b = igemm_ws_bytes(&ht.dt, 1, colsum ? ht.seg_t : nullptr, ht.nt, bf16, in16);
-    return a > b ? a : b;
-  }
-  if (tg::conv3x3_bf16_applicable(descs, n_desc, seg_rows, colsum ? nseg : 0, bf16)) return bf16 ? tg::conv3x3_bf16_pack_bytes(descs, n_desc) : 0;
-  if (in16) return widen_bytes(&descs[0]) + igemm_ws_bytes(descs, n_desc, seg_rows, nseg, bf16, false);      // widened input in front (igemm_impl)
-  int bm = 0, bn = 0;
-  if (!tg::igemm_pick_tile(descs, n_desc, colsum, seg_rows, nseg, bf16, &bm, &bn)) return 0;
-  int order[MAX_SUB] = {0, 1, 2, 3}, nk[MAX_SUB] = {0, 0, 0, 0};
-  tg::igemm_sub_order(descs, n_desc, order);
-  for (int i = 0; i < n_desc; ++i) nk[i] = descs[order[i]].n_taps * (descs[0].ld_in / BK);
-  const int64_t M = (int64_t)descs[0].n_img * descs[0].h_v * descs[0].w_v;
-  tg::IgemmSched sc;
-  tg::igemm_schedule(n_desc, nk, ((M + bm - 1) / bm) * ((descs[0].c_out + bn - 1) / bn), bm, bn, 2 * tg::halo_compute_units(), true, &sc);
-  return sc.ws_bytes;
-}
-
-extern "C" int64_t tg_igemm_workspace_bytes(const tg_igemm_desc* descs, int n_desc, const int32_t* seg_rows, int nseg, int bf16) {
-  if (!descs || n_desc < 1 || n_desc > MAX_SUB || nseg < 0 || nseg > 8 || (nseg > 0 && !seg_rows)) { tg::set_error("igemm_workspace_bytes: bad arguments"); return TG_ERR_INVALID; }
-  for (int i = 0; i < n_desc; ++i)
-    if (descs[i].ld_in <= 0 || descs[i].c_out <= 0 || descs[i].n_taps <= 0 || descs[i].n_taps > TG_MAX_TAPS || descs[i].n_img <= 0) { tg::set_error("igemm_workspace_bytes: bad descriptor"); return TG_ERR_INVALID; }
-  return igemm_ws_bytes(descs, n_desc, seg_rows, nseg, bf16 != 0, bf16 == 2);
-}
-
-static int igemm_colsum_impl(const tg_igemm_desc* d, const float* in, const float* w, float* out, const int32_t* seg_rows, int nseg,
-                             double* colsum, int colsum_zeroed, void* stream, bool bf16, const float* ymul = nullptr, int ymul_act = 0,
-                             float ymul_alpha = 0.f, void* scratch = nullptr, int64_t scratch_bytes = 0) {
-  TG_REQUIRE(d && colsum && seg_rows && nseg >= 1 && nseg <= 8, "igemm_colsum: bad args");
-  TG_REQUIRE(d->n_group == 0, "igemm_colsum: grouped columns are not supported");
-  TG_REQUIRE(d->act == TG_ACT_NONE, "igemm_colsum: the statistics are of the raw convolution output (no activation)");
-  int tot = 0;
-  for (int i = 0; i < nseg; ++i) { TG_REQUIRE(seg_rows[i] >= 32, "igemm_colsum: segment %d has %d rows (need at least one 32-row tile)", i, seg_rows[i]); tot += seg_rows[i]; }
-  TG_REQUIRE(tot == d->n_img * d->h_v * d->w_v, "igemm_colsum: segments sum to %d rows, launch has %d", tot, d->n_img * d->h_v * d->w_v);
-  if (!colsum_zeroed) {
-    hipError_t e = hipMemsetAsync(colsum, 0, sizeof(double) * nseg * d->c_out, tg::as_stream(stream));
-    if (e != hipSuccess) return tg::hip_fail(e, "hipMemsetAsync(colsum)");
-  }
-  return igemm_impl(d, 1, in, w, nullptr, out, stream, colsum, seg_rows, nseg, bf16, ymul, ymul_act, ymul_alpha, scratch, scratch_bytes);
-}
-
-extern "C" int tg_igemm_colsum_f32(const tg_igemm_desc* d, const float* in, const float* w, float* out, const int32_t* seg_rows, int nseg,
-                                   double* colsum, int colsum_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
-  return igemm_colsum_impl(d, in, w, out, seg_rows, nseg, colsum, colsum_zeroed, stream, false, nullptr, 0, 0.f, scratch, scratch_bytes);
-}
-
-extern "C" int tg_igemm_colsum_bf16(const tg_igemm_desc* d, const float* in, const float* w, float* out, const int32_t* seg_rows, int nseg,
-                                    double* colsum, int colsum_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
-  return igemm_colsum_impl(d, in, w, out, seg_rows, nseg, colsum, colsum_zeroed, stream, true, nullptr, 0, 0.f, scratch, scratch_bytes);
-}
-
-// conv + bias + activation whose output feeds a batch norm: the statistics of the ACTIVATED output are taken in the epilogue
-static int igemm_bnstat_impl(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, const int32_t* seg_rows, int nseg,
-                             double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream, bool bf16, bool in16 = false) {
-  TG_REQUIRE(d && sums && seg_rows && nseg >= 1 && nseg <= 8, "igemm_bnstat: bad args");
-  TG_REQUIRE(d->n_group == 0, "igemm_bnstat: grouped columns are not supported");
-  TG_REQUIRE(d->act == TG_ACT_NONE || d->act == TG_ACT_RELU || d->act == TG_ACT_LRELU, "igemm_bnstat: activation %d is not none / relu / leaky relu", d->act);
-  int tot = 0;
-  for (int i = 0; i < nseg; ++i) { TG_REQUIRE(seg_rows[i] >= 32, "igemm_bnstat: segment %d has %d rows (need at least one 32-row tile)", i, seg_rows[i]); tot += seg_rows[i]; }
-  TG_REQUIRE(tot == d->n_img * d->h_v * d->w_v, "igemm_bnstat: segments sum to %d rows, launch has %d", tot, d->n_img * d->h_v * d->w_v);
-  if (!sums_zeroed) {
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * 8 * 2 * nseg * d->c_out, tg::as_stream(stream));      // all eight replicas of the batch norm's buffer
-    if (e != hipSuccess) return tg::hip_fail(e, "hipMemsetAsync(bn statistics)");
-  }
-  return igemm_impl(d, 1, in, w, bias, out, stream, sums, seg_rows, nseg, bf16, nullptr, 0, 0.f, scratch, scratch_bytes, 1, nullptr, 0, in16);
+  return igemm_launch({.descs = d, .n_desc = 1, .in = in, .w = w, .bias = bias, .out = out, .ops = tg::IGEMM_BF16, .lab = labels, .lab_n = n_labels,
+                       .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream});
 }
 
 // the gathered activation is stored as bf16 (include/tg_kernels.h): only layers of the halo kernels' shape
@@ -1337,78 +1340,128 @@ static int require_halo_shape(const tg_igemm_desc* d, const char* what) {
   return TG_OK;
 }
 
-extern "C" int tg_igemm_bnstat_bf16in_bf16(const tg_igemm_desc* d, const void* in, const float* w, const float* bias, float* out, const int32_t* seg_rows,
-                                           int nseg, double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
-  int rc = require_halo_shape(d, "igemm_bnstat_bf16in");
-  if (rc != TG_OK) return rc;
-  return igemm_bnstat_impl(d, static_cast<const float*>(in), w, bias, out, seg_rows, nseg, sums, sums_zeroed, scratch, scratch_bytes, stream, true, true);
-}
-
 extern "C" int tg_igemm_bf16in_bf16(const tg_igemm_desc* d, const void* in, const float* w, const float* bias, float* out, void* scratch,
                                     int64_t scratch_bytes, void* stream) {
   int rc = require_halo_shape(d, "igemm_bf16in");
   if (rc != TG_OK) return rc;
-  return igemm_impl(d, 1, static_cast<const float*>(in), w, bias, out, stream, nullptr, nullptr, 0, true, nullptr, 0, 0.f, scratch, scratch_bytes, 0,
-                    nullptr, 0, true);
+  return igemm_launch({.descs = d, .n_desc = 1, .in = static_cast<const float*>(in), .w = w, .bias = bias, .out = out, .ops = tg::IGEMM_BF16_IN16,
+                       .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream});
 }
 
-extern "C" int tg_igemm_bnstat_f32(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, const int32_t* seg_rows, int nseg,
-                                   double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
-  return igemm_bnstat_impl(d, in, w, bias, out, seg_rows, nseg, sums, sums_zeroed, scratch, scratch_bytes, stream, false);
+// scratch a launch of these descriptors can use: the halo kernel's packed bf16 filter (REQUIRED by such a launch), the widened copy of a
+// bf16-stored input (required) and the partial sums of the tiles the generic kernel's schedule cuts along K (optional); a launch that is
+// cut into a halo head and a generic tail uses the scratch for one after the other.  The launch executes the same igemm_route.
+extern "C" int64_t tg_igemm_workspace_bytes(const tg_igemm_desc* descs, int n_desc, const int32_t* seg_rows, int nseg, int bf16) {
+  if (!descs || n_desc < 1 || n_desc > MAX_SUB || nseg < 0 || nseg > 8 || (nseg > 0 && !seg_rows)) { tg::set_error("igemm_workspace_bytes: bad arguments"); return TG_ERR_INVALID; }
+  for (int i = 0; i < n_desc; ++i)
+    if (descs[i].ld_in <= 0 || descs[i].c_out <= 0 || descs[i].n_taps <= 0 || descs[i].n_taps > TG_MAX_TAPS || descs[i].n_img <= 0) { tg::set_error("igemm_workspace_bytes: bad descriptor"); return TG_ERR_INVALID; }
+  return igemm_route(descs, n_desc, seg_rows, nseg, bf16 == 2 ? tg::IGEMM_BF16_IN16 : bf16 ? tg::IGEMM_BF16 : tg::IGEMM_F32, false).scratch_bytes;
 }
 
-extern "C" int tg_igemm_bnstat_bf16(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, const int32_t* seg_rows, int nseg,
-                                    double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
-  return igemm_bnstat_impl(d, in, w, bias, out, seg_rows, nseg, sums, sums_zeroed, scratch, scratch_bytes, stream, true);
-}
-
-// input gradient (or any conv) whose output dy is consumed by a batch norm's backward pass: that pass's statistics in the epilogue
-static int igemm_bnbwdstat_impl(const tg_igemm_desc* d, const float* in, const float* w, const float* x, float* out, const int32_t* seg_rows, int nseg,
-                                double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream, bool bf16) {
-  TG_REQUIRE(d && sums && x && seg_rows && nseg >= 1 && nseg <= 8, "igemm_bnbwdstat: bad args");
-  TG_REQUIRE(d->n_group == 0 && d->act == TG_ACT_NONE, "igemm_bnbwdstat: grouped columns / a fused activation are not supported");
+// ---- the statistics families ---------------------------------------------------------------------------------------------------------------
+// Common to the three: every application segment holds at least one 32-row tile, the segments add up to the launch's rows, and the
+// n_sums fp64 accumulators are zeroed here unless the caller did.
+static int igemm_stat_launch(const IgemmCall& c, const char* who, int64_t n_sums, int zeroed, const char* memset_what) {
+  const tg_igemm_desc* d = c.descs;
   int tot = 0;
-  for (int i = 0; i < nseg; ++i) { TG_REQUIRE(seg_rows[i] >= 32, "igemm_bnbwdstat: segment %d has %d rows (need at least one 32-row tile)", i, seg_rows[i]); tot += seg_rows[i]; }
-  TG_REQUIRE(tot == d->n_img * d->h_v * d->w_v, "igemm_bnbwdstat: segments sum to %d rows, launch has %d", tot, d->n_img * d->h_v * d->w_v);
-  if (!sums_zeroed) {
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * 8 * 2 * nseg * d->c_out, tg::as_stream(stream));      // all eight replicas of the batch norm's buffer
-    if (e != hipSuccess) return tg::hip_fail(e, "hipMemsetAsync(bn backward statistics)");
+  for (int i = 0; i < c.nseg; ++i) { TG_REQUIRE(c.seg_rows[i] >= 32, "%s: segment %d has %d rows (need at least one 32-row tile)", who, i, c.seg_rows[i]); tot += c.seg_rows[i]; }
+  TG_REQUIRE(tot == d->n_img * d->h_v * d->w_v, "%s: segments sum to %d rows, launch has %d", who, tot, d->n_img * d->h_v * d->w_v);
+  if (!zeroed) {
+    hipError_t e = hipMemsetAsync(c.sums, 0, sizeof(double) * n_sums, tg::as_stream(c.stream));
+    if (e != hipSuccess) return tg::hip_fail(e, memset_what);
   }
-  return igemm_impl(d, 1, in, w, nullptr, out, stream, sums, seg_rows, nseg, bf16, x, TG_ACT_NONE, 0.f, scratch, scratch_bytes, 2);
+  return igemm_launch(c);
 }
 
-extern "C" int tg_igemm_bnbwdstat_f32(const tg_igemm_desc* d, const float* in, const float* w, const float* x, float* out, const int32_t* seg_rows, int nseg,
-                                      double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
-  return igemm_bnbwdstat_impl(d, in, w, x, out, seg_rows, nseg, sums, sums_zeroed, scratch, scratch_bytes, stream, false);
+// column sums of the raw output; with ymul: of out = acc * act'(ymul) (tg_igemm_actsum_*)
+static int igemm_colsum(const IgemmCall& c, int zeroed) {
+  const tg_igemm_desc* d = c.descs;
+  TG_REQUIRE(d && c.sums && c.seg_rows && c.nseg >= 1 && c.nseg <= 8, "igemm_colsum: bad args");
+  TG_REQUIRE(d->n_group == 0, "igemm_colsum: grouped columns are not supported");
+  TG_REQUIRE(d->act == TG_ACT_NONE, "igemm_colsum: the statistics are of the raw convolution output (no activation)");
+  return igemm_stat_launch(c, "igemm_colsum", (int64_t)c.nseg * d->c_out, zeroed, "hipMemsetAsync(colsum)");
 }
 
-extern "C" int tg_igemm_bnbwdstat_bf16(const tg_igemm_desc* d, const float* in, const float* w, const float* x, float* out, const int32_t* seg_rows, int nseg,
-                                       double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
-  return igemm_bnbwdstat_impl(d, in, w, x, out, seg_rows, nseg, sums, sums_zeroed, scratch, scratch_bytes, stream, true);
+extern "C" int tg_igemm_colsum_f32(const tg_igemm_desc* d, const float* in, const float* w, float* out, const int32_t* seg_rows, int nseg,
+                                   double* colsum, int colsum_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
+  return igemm_colsum({.descs = d, .n_desc = 1, .in = in, .w = w, .out = out, .ops = tg::IGEMM_F32, .sums = colsum, .seg_rows = seg_rows, .nseg = nseg,
+                       .stat = tg::IGEMM_STAT_COLSUM, .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream}, colsum_zeroed);
+}
+
+extern "C" int tg_igemm_colsum_bf16(const tg_igemm_desc* d, const float* in, const float* w, float* out, const int32_t* seg_rows, int nseg,
+                                    double* colsum, int colsum_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
+  return igemm_colsum({.descs = d, .n_desc = 1, .in = in, .w = w, .out = out, .ops = tg::IGEMM_BF16, .sums = colsum, .seg_rows = seg_rows, .nseg = nseg,
+                       .stat = tg::IGEMM_STAT_COLSUM, .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream}, colsum_zeroed);
 }
 
 extern "C" int tg_igemm_actsum_f32(const tg_igemm_desc* d, const float* in, const float* w, const float* yact, int act, float alpha, float* out,
                                    const int32_t* seg_rows, int nseg, double* colsum, int colsum_zeroed, void* scratch, int64_t scratch_bytes,
                                    void* stream) {
   TG_REQUIRE(yact != nullptr, "igemm_actsum: yact is NULL");
-  return igemm_colsum_impl(d, in, w, out, seg_rows, nseg, colsum, colsum_zeroed, stream, false, yact, act, alpha, scratch, scratch_bytes);
+  return igemm_colsum({.descs = d, .n_desc = 1, .in = in, .w = w, .out = out, .ops = tg::IGEMM_F32, .sums = colsum, .seg_rows = seg_rows, .nseg = nseg,
+                       .stat = tg::IGEMM_STAT_COLSUM, .ymul = yact, .ymul_act = act, .ymul_alpha = alpha, .scratch = scratch, .scratch_bytes = scratch_bytes,
+                       .stream = stream}, colsum_zeroed);
 }
 
 extern "C" int tg_igemm_actsum_bf16(const tg_igemm_desc* d, const float* in, const float* w, const float* yact, int act, float alpha, float* out,
                                     const int32_t* seg_rows, int nseg, double* colsum, int colsum_zeroed, void* scratch, int64_t scratch_bytes,
                                     void* stream) {
   TG_REQUIRE(yact != nullptr, "igemm_actsum: yact is NULL");
-  return igemm_colsum_impl(d, in, w, out, seg_rows, nseg, colsum, colsum_zeroed, stream, true, yact, act, alpha, scratch, scratch_bytes);
+  return igemm_colsum({.descs = d, .n_desc = 1, .in = in, .w = w, .out = out, .ops = tg::IGEMM_BF16, .sums = colsum, .seg_rows = seg_rows, .nseg = nseg,
+                       .stat = tg::IGEMM_STAT_COLSUM, .ymul = yact, .ymul_act = act, .ymul_alpha = alpha, .scratch = scratch, .scratch_bytes = scratch_bytes,
+                       .stream = stream}, colsum_zeroed);
 }
 
-extern "C" int tg_igemm_multi_bf16(const tg_igemm_desc* descs, int n_desc, const float* in, const float* w, const float* bias, float* out,
-                                   void* scratch, int64_t scratch_bytes, void* stream) {
-  return igemm_impl(descs, n_desc, in, w, bias, out, stream, nullptr, nullptr, 0, true, nullptr, 0, 0.f, scratch, scratch_bytes);
+// conv + bias + activation whose output feeds a batch norm: the statistics of the ACTIVATED output are taken in the epilogue
+static int igemm_bnstat(const IgemmCall& c, int zeroed) {
+  const tg_igemm_desc* d = c.descs;
+  TG_REQUIRE(d && c.sums && c.seg_rows && c.nseg >= 1 && c.nseg <= 8, "igemm_bnstat: bad args");
+  TG_REQUIRE(d->n_group == 0, "igemm_bnstat: grouped columns are not supported");
+  TG_REQUIRE(d->act == TG_ACT_NONE || d->act == TG_ACT_RELU || d->act == TG_ACT_LRELU, "igemm_bnstat: activation %d is not none / relu / leaky relu", d->act);
+  return igemm_stat_launch(c, "igemm_bnstat", (int64_t)8 * 2 * c.nseg * d->c_out, zeroed, "hipMemsetAsync(bn statistics)");      // all eight replicas of the batch norm's buffer
 }
 
-extern "C" int tg_igemm_bf16(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, void* scratch,
-                             int64_t scratch_bytes, void* stream) {
-  return igemm_impl(d, 1, in, w, bias, out, stream, nullptr, nullptr, 0, true, nullptr, 0, 0.f, scratch, scratch_bytes);
+extern "C" int tg_igemm_bnstat_f32(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, const int32_t* seg_rows, int nseg,
+                                   double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
+  return igemm_bnstat({.descs = d, .n_desc = 1, .in = in, .w = w, .bias = bias, .out = out, .ops = tg::IGEMM_F32, .sums = sums, .seg_rows = seg_rows,
+                       .nseg = nseg, .stat = tg::IGEMM_STAT_BN, .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream}, sums_zeroed);
+}
+
+extern "C" int tg_igemm_bnstat_bf16(const tg_igemm_desc* d, const float* in, const float* w, const float* bias, float* out, const int32_t* seg_rows, int nseg,
+                                    double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
+  return igemm_bnstat({.descs = d, .n_desc = 1, .in = in, .w = w, .bias = bias, .out = out, .ops = tg::IGEMM_BF16, .sums = sums, .seg_rows = seg_rows,
+                       .nseg = nseg, .stat = tg::IGEMM_STAT_BN, .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream}, sums_zeroed);
+}
+
+extern "C" int tg_igemm_bnstat_bf16in_bf16(const tg_igemm_desc* d, const void* in, const float* w, const float* bias, float* out, const int32_t* seg_rows,
+                                           int nseg, double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
+  int rc = require_halo_shape(d, "igemm_bnstat_bf16in");
+  if (rc != TG_OK) return rc;
+  return igemm_bnstat({.descs = d, .n_desc = 1, .in = static_cast<const float*>(in), .w = w, .bias = bias, .out = out, .ops = tg::IGEMM_BF16_IN16, .sums = sums,
+                       .seg_rows = seg_rows, .nseg = nseg, .stat = tg::IGEMM_STAT_BN, .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream},
+                      sums_zeroed);
+}
+
+// input gradient (or any conv) whose output dy is consumed by a batch norm's backward pass: that pass's statistics in the epilogue
+static int igemm_bnbwdstat(const IgemmCall& c, int zeroed) {
+  const tg_igemm_desc* d = c.descs;
+  TG_REQUIRE(d && c.sums && c.ymul && c.seg_rows && c.nseg >= 1 && c.nseg <= 8, "igemm_bnbwdstat: bad args");
+  TG_REQUIRE(d->n_group == 0 && d->act == TG_ACT_NONE, "igemm_bnbwdstat: grouped columns / a fused activation are not supported");
+  return igemm_stat_launch(c, "igemm_bnbwdstat", (int64_t)8 * 2 * c.nseg * d->c_out, zeroed, "hipMemsetAsync(bn backward statistics)");
+}
+
+extern "C" int tg_igemm_bnbwdstat_f32(const tg_igemm_desc* d, const float* in, const float* w, const float* x, float* out, const int32_t* seg_rows, int nseg,
+                                      double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
+  return igemm_bnbwdstat({.descs = d, .n_desc = 1, .in = in, .w = w, .out = out, .ops = tg::IGEMM_F32, .sums = sums, .seg_rows = seg_rows, .nseg = nseg,
+                          .stat = tg::IGEMM_STAT_BNBWD, .ymul = x, .ymul_act = TG_ACT_NONE, .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream},
+                         sums_zeroed);
+}
+
+extern "C" int tg_igemm_bnbwdstat_bf16(const tg_igemm_desc* d, const float* in, const float* w, const float* x, float* out, const int32_t* seg_rows, int nseg,
+                                       double* sums, int sums_zeroed, void* scratch, int64_t scratch_bytes, void* stream) {
+  return igemm_bnbwdstat({.descs = d, .n_desc = 1, .in = in, .w = w, .out = out, .ops = tg::IGEMM_BF16, .sums = sums, .seg_rows = seg_rows, .nseg = nseg,
+                          .stat = tg::IGEMM_STAT_BNBWD, .ymul = x, .ymul_act = TG_ACT_NONE, .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream},
+                         sums_zeroed);
 }
 
 template <int CT, int NT, int WC, int WN, int WK>
@@ -1420,29 +1473,38 @@ static void launch_wgrad(WgradParams& p, hipStream_t s, bool bf16) {
   else hipLaunchKernelGGL((wgrad_f32_kernel<CT, NT, WC, WN, WK, false>), dim3(blocks), dim3(256), 0, s, p);
 }
 
-static int wgrad_impl(const tg_igemm_desc* d, const float* in, const float* dout, float* slab, int n_split, void* stream, bool bf16) {
+// in16 (tg_wgrad_bf16in_bf16): the activation is stored as bf16 — always wgrad3x3 (its shape rule without the occupancy rule of the default
+// policy: any n_split is served)
+static int wgrad_impl(const tg_igemm_desc* d, const float* in, const float* dout, float* slab, int n_split, void* stream, bool bf16, bool in16 = false) {
+  const char* who = in16 ? "wgrad_bf16in" : "wgrad";
   int rc = check_desc(d);
   if (rc != TG_OK) return rc;
-  TG_REQUIRE(in && dout && slab, "wgrad: null buffer");
-  TG_REQUIRE(n_split >= 1, "wgrad: n_split=%d", n_split);
-  TG_REQUIRE(d->c_out <= d->ld_out, "wgrad: c_out=%d exceeds ld_out=%d", d->c_out, d->ld_out);
-  TG_REQUIRE(d->n_group == 0, "wgrad: grouped columns are not supported");
+  TG_REQUIRE(in && dout && slab, "%s: null buffer", who);
+  TG_REQUIRE(n_split >= 1, "%s: n_split=%d", who, n_split);
+  if (in16) {
+    TG_REQUIRE(tg::wgrad3x3_applicable(d, n_split, true, 1, tg::halo_compute_units()),
+               "wgrad_bf16in: a bf16-stored input is served for 3x3 / stride-1 / SAME layers of width 16 / 32 / 64 (128 pixels per tile), 32 | ld_in, "
+               "128 | c_out only");
+  } else {
+    TG_REQUIRE(d->c_out <= d->ld_out, "wgrad: c_out=%d exceeds ld_out=%d", d->c_out, d->ld_out);
+    TG_REQUIRE(d->n_group == 0, "wgrad: grouped columns are not supported");
+  }
   WgradParams p{in, dout, slab, *d, 0, n_split, 0, 0, 0, 0, 0};
   p.M = d->n_img * d->h_v * d->w_v;
-  const int64_t ib = (int64_t)d->n_img * d->h_in * d->w_in * d->ld_in * 4, ob = (int64_t)d->n_img * d->h_out * d->w_out * d->ld_out * 4;
-  TG_REQUIRE(ib < 0x7FFFFFF0LL && ob < 0x7FFFFFF0LL, "wgrad: operand exceeds the 2 GiB buffer-descriptor range");
+  const int64_t ib = (int64_t)d->n_img * d->h_in * d->w_in * d->ld_in * (in16 ? 2 : 4), ob = (int64_t)d->n_img * d->h_out * d->w_out * d->ld_out * 4;
+  TG_REQUIRE(ib < 0x7FFFFFF0LL && ob < 0x7FFFFFF0LL, "%s: operand exceeds the 2 GiB buffer-descriptor range", who);
   p.in_bytes = (uint32_t)ib; p.dout_bytes = (uint32_t)ob;
   p.px_per_split = (((p.M + n_split - 1) / n_split) + BK - 1) / BK * BK;
   const double flops = 2.0 * p.M * d->c_out * d->n_taps * d->ld_in;
-  const double bytes = 4.0 * ((double)p.M * d->ld_in + (double)p.M * d->c_out + (double)n_split * d->c_out * d->n_taps * d->ld_in);
+  const double bytes = (in16 ? 2.0 : 4.0) * p.M * d->ld_in + 4.0 * ((double)p.M * d->c_out + (double)n_split * d->c_out * d->n_taps * d->ld_in);
   char desc[96];
-  snprintf(desc, sizeof(desc), "M=%d N=%d K=%dx%d in=%dx%d s=%d split=%d%s", p.M, d->c_out, d->n_taps, d->ld_in, d->h_in, d->w_in, d->s_y, n_split,
-           bf16 ? " bf16" : "");
-  tg::ProfScope prof(tg::PC_WGRAD, flops, bytes, tg::as_stream(stream), desc);
+  if (in16) snprintf(desc, sizeof(desc), "M=%lld N=%d K=%dx%d in=%dx%d split=%d bf16in", (long long)p.M, d->c_out, d->n_taps, d->ld_in, d->h_in, d->w_in, n_split);
+  else snprintf(desc, sizeof(desc), "M=%d N=%d K=%dx%d in=%dx%d s=%d split=%d%s", p.M, d->c_out, d->n_taps, d->ld_in, d->h_in, d->w_in, d->s_y, n_split, bf16 ? " bf16" : "");
   hipStream_t s = tg::as_stream(stream);
-  if (tg::wgrad3x3_applicable(d, n_split, bf16, tg::halo_policy(), tg::halo_compute_units())) {      // the classifier's 3x3 layers: wgrad3x3.hip
+  tg::ProfScope prof(tg::PC_WGRAD, flops, bytes, s, desc);
+  if (in16 || tg::wgrad3x3_applicable(d, n_split, bf16, tg::halo_policy(), tg::halo_compute_units())) {      // the classifier's 3x3 layers: wgrad3x3.hip
     tg::halo_count_launch();
-    return tg::wgrad3x3_launch(d, in, dout, slab, n_split, p.in_bytes, p.dout_bytes, s, bf16);
+    return tg::wgrad3x3_launch(d, in, dout, slab, n_split, p.in_bytes, p.dout_bytes, s, bf16, in16);
   }
   // channel tiles: tg::wgrad_tile (geom.cpp; tg_wgrad_splits sizes the pixel split with the same rule)
   const int ct = tg::wgrad_tile(d->ld_in), nt = tg::wgrad_tile(d->c_out);
@@ -1467,23 +1529,6 @@ extern "C" int tg_wgrad_bf16(const tg_igemm_desc* d, const float* in, const floa
   return wgrad_impl(d, in, dout, slab, n_split, stream, true);
 }
 
-// bf16-stored activation: always wgrad3x3 (its shape rule without the occupancy rule of the default policy — any n_split is served)
 extern "C" int tg_wgrad_bf16in_bf16(const tg_igemm_desc* d, const void* in, const float* dout, float* slab, int n_split, void* stream) {
-  int rc = check_desc(d);
-  if (rc != TG_OK) return rc;
-  TG_REQUIRE(in && dout && slab, "wgrad_bf16in: null buffer");
-  TG_REQUIRE(n_split >= 1, "wgrad_bf16in: n_split=%d", n_split);
-  TG_REQUIRE(tg::wgrad3x3_applicable(d, n_split, true, 1, tg::halo_compute_units()),
-             "wgrad_bf16in: a bf16-stored input is served for 3x3 / stride-1 / SAME layers of width 16 / 32 / 64 (128 pixels per tile), 32 | ld_in, "
-             "128 | c_out only");
-  const int64_t ib = (int64_t)d->n_img * d->h_in * d->w_in * d->ld_in * 2, ob = (int64_t)d->n_img * d->h_out * d->w_out * d->ld_out * 4;
-  TG_REQUIRE(ib < 0x7FFFFFF0LL && ob < 0x7FFFFFF0LL, "wgrad_bf16in: operand exceeds the 2 GiB buffer-descriptor range");
-  const int64_t M = (int64_t)d->n_img * d->h_v * d->w_v;
-  char desc[96];
-  snprintf(desc, sizeof(desc), "M=%lld N=%d K=%dx%d in=%dx%d split=%d bf16in", (long long)M, d->c_out, d->n_taps, d->ld_in, d->h_in, d->w_in, n_split);
-  hipStream_t s = tg::as_stream(stream);
-  tg::ProfScope prof(tg::PC_WGRAD, 2.0 * M * d->c_out * d->n_taps * d->ld_in,
-                     2.0 * M * d->ld_in + 4.0 * M * d->c_out + 4.0 * n_split * d->c_out * d->n_taps * d->ld_in, s, desc);
-  tg::halo_count_launch();
-  return tg::wgrad3x3_launch(d, static_cast<const float*>(in), dout, slab, n_split, (uint32_t)ib, (uint32_t)ob, s, true, true);
+  return wgrad_impl(d, static_cast<const float*>(in), dout, slab, n_split, stream, true, true);
 }

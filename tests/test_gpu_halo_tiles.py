@@ -12,7 +12,7 @@ regimes appear: one tile per workgroup, an odd number (3) of tiles on every work
 they started on), and a last round that is partly empty; each case asserts its regime at run time.
 
 Every launch runs under tg_conv3x3_policy(1) (the halo kernels wherever the layer applies), except the ROUTING cases, which run under the
-default policy 0 with image counts that make igemm_impl cut the launch into a halo head and a generic tail.  Checks per case
+default policy 0 with image counts that make igemm_launch cut the launch into a halo head and a generic tail.  Checks per case
 (tests/kernel_check.py, tests/test_gpu_gemm_tiles.py):
   * tg_conv3x3_launches moves by exactly 1: the halo kernel ran;
   * outputs and sums come from kernel_check.guarded (NaN-filled, guard behind): every owned element is written, channels in
