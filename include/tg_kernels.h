@@ -694,8 +694,23 @@ int tg_tf_histogram_limits(double* limits_out, int n);
 int64_t tg_tf_histogram_workspace_bytes(const int64_t* segs, int nseg);
 int tg_tf_histogram_f32(const float* x, int64_t n, const int64_t* segs, int nseg, const double* limits_dev, int64_t* counts, double* stats,
                         void* workspace, int64_t workspace_bytes, void* stream);
+/* First and second moments of an fp32 feature matrix, in fp64 (Train.sample_metrics: the Fréchet distance between classifier features,
+ * DESIGN §9.10).  f: DEVICE [n][ld] floats, of which columns 0..c-1 are read and columns c..ld-1 never are (they may hold anything).
+ *   sum[k]       += sum_r (double)f[r][k]                      (DEVICE, c doubles)
+ *   gram[a*c+b]  += sum_r (double)f[r][a] * (double)f[r][b]    (DEVICE, c*c doubles; both triangles written, exactly equal)
+ * ACCUMULATED into the caller's buffers, which the caller zeroes before the first call.  Every fp32 x fp32 product is exact in fp64, so
+ * the only rounding is that of the fp64 additions, and those run in a fixed order: launch 1 leaves one partial per (row range, 32 x 32
+ * block of the upper triangle) in the workspace, each added in row order; launch 2 adds an element's partials in range order and
+ * accumulates — no floating-point atomics, the grid a function of (n, c) alone, so the outputs are bit-identical from run to run, on
+ * any stream.  1 <= c <= 512, ld >= c, n >= 0 (TG_ERR_INVALID otherwise); n = 0 is a no-op (no launch; the pointers may be NULL).
+ * workspace: caller-owned scratch of at least tg_feature_moments_workspace_bytes(n, c) bytes (a host query; 0 for n = 0, < 0 for a bad
+ * n or c; a smaller workspace is TG_ERR_INVALID), 16-byte aligned, needs no initialisation, nothing beyond that size is written.
+ * 2 n c^2 FLOP on the fp64 VALU. */
+int64_t tg_feature_moments_workspace_bytes(int n, int c);
+int tg_feature_moments_f32(const float* f, int ld, int n, int c, double* sum, double* gram, void* workspace, int64_t workspace_bytes,
+                           void* stream);
 
-/* ---- RNG (Philox4x32-10; state = device {seed, step}) -------------------------------------------- */
+/* ---- RNG(Philox4x32-10; state = device {seed, step}) -------------------------------------------- */
 /* Element e of a draw is word e % 4 of the block with counter (lo32(e / 4), hi32(e / 4), stream_id, lo32(step)) and key (lo32(seed),
  * hi32(seed) ^ hi32(step)); a one-hot row r takes class (word 0 * k) >> 32 of the block with counter (r, 0, stream_id, lo32(step)).
  * A word x becomes u = ((x >> 8) + 0.5f) * 2^-24 in fp32: in (0, 1], exactly 1.0 for the one word value x >> 8 == 0xFFFFFF (the sum rounds up).

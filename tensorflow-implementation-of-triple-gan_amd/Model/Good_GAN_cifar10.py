@@ -193,8 +193,13 @@ class Good_GAN_cifar10(model_base.NN_Base):
 
     def classifier(self, inp, is_training, init=False, reuse=False, getter=None, segments=None):
         """:101-174.  inp: Act [N,32,32,3] (ZCA-whitened).  Returns (logits Act [N,10], feature Act [N,128]).
-        The Gaussian input noise is always on (also at evaluation, :104); dropout only when training."""
+        The Gaussian input noise is always on (also at evaluation, :104); dropout only when training.
+        getter: the reference's custom_getter hook (:101-102; it never passes one).  Any truthy value selects the averaged weights: every
+        trainable variable reads as its EMA shadow, pop_mean as it is (Context.reading_shadows) — forward only, outside the step."""
         cx = ctx()
+        if getter:
+            with cx.reading_shadows('classifier'):
+                return self.classifier(inp, is_training, init=init, reuse=reuse, getter=None, segments=segments)
         kw = dict(init=init, use_weight_normalization=True, use_batch_normalization=False,
                   use_mean_only_batch_normalization=True, deterministic=not is_training, nonlinearity=self.leakyReLu,
                   segments=segments)

@@ -15,6 +15,7 @@ RNG step) live in device memory.  Applications of one network inside a solver ru
 application).  Data-parallel replicas (one process per GPU) sum-all-reduce the trained network's flat gradient
 buffer over RCCL after each backward (tg/dist.py); the reference has no multi-device path.
 """
+import contextlib
 import math
 import os
 import time
@@ -23,8 +24,8 @@ import numpy as np
 import torch
 
 from config import Config
-from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, check_act_dtype, check_clip_norm, check_loss,  # noqa: F401
-                              check_mfma_dtype, check_num_classes, check_optimizer, check_wn_init, check_zca, cla_lr, opt, resolve)
+from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, check_act_dtype, check_clip_norm, check_eval_ema, check_loss,  # noqa: F401
+                              check_mfma_dtype, check_num_classes, check_optimizer, check_sample_metrics, check_wn_init, check_zca, cla_lr, opt, resolve)
 from Training.train_base import Train_base, clip_workspace_floats
 from tg import dist as tgdist
 from tg import executor, lib, ops
@@ -68,6 +69,7 @@ class Train(Train_base):
         self._label_override = {}        # see label_override()
         self.wn_initialised = None       # {network: layers initialised} once data_dependent_init() has run (config.WN_INIT = 'data')
         self.zca_source = None           # config.ZCA = 'fit' resolved by train(): 'files' | 'fit' (rank 0) | 'broadcast' (other ranks)
+        self._metric_latents = None      # (z, y) host arrays of sample_metrics(), drawn once per trainer from config.SEED
         self._hist_runs = {}             # network -> (store layout key, tg.summary.StoreHistograms): see histograms()
         self.summary_train = self.summary_val = None
         if o.summary and log_dir and self.rank == 0:          # :37-41
@@ -496,13 +498,21 @@ class Train(Train_base):
             return self._loss_WGAN_GP_step(m.as_image(G), D, C, X, Y, Lambda, discriminator or m.discriminator)
         return self._loss_GAN(D, C, Y, Lambda)
 
-    def evaluate(self, batches):
+    def _classifier_weights(self, ema):
+        """the weights a forward-only classifier pass reads: the variables, or (ema) their EMA shadows — Context.reading_shadows."""
+        return self.cx.reading_shadows('classifier') if ema else contextlib.nullcontext()
+
+    def evaluate(self, batches, ema=False):
         """streaming accuracy of argmax C_real_logits vs argmax y over test batches with train=False (:295-351, :428-447).
-        batches: iterable of (x [n,h,w,c], y onehot [n,k]) host arrays.  Returns accuracy."""
+        batches: iterable of (x [n,h,w,c], y onehot [n,k]) host arrays.  Returns accuracy.
+        ema: evaluate the averaged classifier — every trainable variable read from its EMA shadow (ParamStore.ema: decay 0.9999 per
+        C-update, no bias correction), pop_mean / batch-norm moving statistics from the store as they are: what the reference's getter
+        (nn.py:98-110) would have returned had it been passed, since ema.apply covered c_vars only.  The pass leaves no
+        trace: it writes no store, draws from the Philox state without advancing it, and runs outside every prepared-filter cache."""
         cx, m = self.cx, self.model
         metric = None
         for x, y in batches:
-            with cx.phase_scope('val', record=False):
+            with cx.phase_scope('val', record=False), self._classifier_weights(ema):
                 xa = cx.from_numpy(x, key='val:x')
                 ya = cx.from_numpy(y, key='val:y')
                 if m.zca() is not None:
@@ -511,6 +521,87 @@ class Train(Train_base):
                     logits, _ = m.classifier(xa, False)
                 metric = self._accuracy_metric(ya, logits, metric)[0]        # what _metric (:428-447) counts; its one-hot prediction output is not needed here
         return float(metric) if metric is not None else 0.0
+
+    def _sample_latents(self, n_batches):
+        """(z [n_batches * B, Z_DIM], y one-hot of class i % NUM_CLASSES) of sample_metrics: drawn once per trainer from a RandomState
+        of its own seeded by config.SEED (NumPy's global state and the device Philox state are not touched), the same every epoch.  A
+        longer request extends the draw; its head stays what it was."""
+        c = self.config
+        rows = n_batches * c.BATCH_SIZE_G
+        if self._metric_latents is None or self._metric_latents[0].shape[0] < rows:
+            rs = np.random.RandomState((int(self.options.seed) * 1000003 + 0x5A17) % (1 << 32))
+            z = rs.uniform(low=-1.0, high=1.0, size=(rows, c.Z_DIM)).astype(np.float32)
+            y = np.eye(c.NUM_CLASSES, dtype=np.float32)[np.arange(rows) % c.NUM_CLASSES]
+            self._metric_latents = (z, y)
+        z, y = self._metric_latents
+        return z[:rows], y[:rows]
+
+    def sample_metrics(self, batches, n_samples, ema=False):
+        """Score the generator with the run's own classifier -> dict(val_accuracy, g_class_accuracy, frechet_distance,
+        n_real, n_fake).
+        Real side: ONE pass over `batches` exactly as evaluate makes it (raw weights, or the shadows with `ema`), which yields
+        val_accuracy and the moments of the pooled feature `fm` (the classifier's second return value).
+        Generated side: ceil(n_samples / BATCH_SIZE_G) batches of BATCH_SIZE_G fixed latents (_sample_latents; the generator's batch
+        norms use batch statistics, so the batch size is part of the definition) through good_sampler, as_image, the model's ZCA and
+        classifier(x, False); the first n_samples are scored.  g_class_accuracy: the share whose arg-max is the class asked for
+        (tg_accuracy_count_f32).  frechet_distance: tg.metrics.frechet_distance between the two Gaussians fitted to the features
+        (tg_feature_moments_f32 in fp64 on the device, the c x c algebra on the host); NaN with fewer than two rows on either side.
+        The sampler's batch norms move their running statistics: every store's `s` is put back afterwards, and nothing else is
+        written — weights, shadows, optimiser slots, step counters and the Philox state are what they were.  The pass runs under
+        phases of its own ('metrics', 'metrics_g': unrecorded, buffer keys of their own), so no buffer a launch plan or graph names
+        is touched.  Synchronises the device."""
+        from tg import metrics as tgm
+        cx, m, c = self.cx, self.model, self.config
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError("sample_metrics: n_samples must be a positive integer, got %r" % (n_samples,))
+        if cx.capturing or lib._recorder is not None:
+            raise lib.TgError("sample_metrics: called inside a hipGraph capture / launch-plan recording; it is an eager pass beside the step")
+        B = int(c.BATCH_SIZE_G)
+        n_batches = -(-n_samples // B)
+        z, y = self._sample_latents(n_batches)
+        kept = {net: st.s.clone() for net, st in cx.stores.items()}
+        real = fake = None
+        try:
+            acc_real = None
+            for xb, yb in batches:                                   # (the moments are sized by the first feature seen)
+                with cx.phase_scope('metrics', record=False), self._classifier_weights(ema):
+                    xa = cx.from_numpy(xb, key='metrics:x')
+                    ya = cx.from_numpy(yb, key='metrics:y')
+                    if m.zca() is not None:
+                        xa = m.zca().apply(m.as_image(xa))
+                    # the input noise is drawn under evaluate's Philox stream id: ids are handed out in order of first use, and a pass that
+                    # registered one of its own would shift those of a solver run that first runs later (the full step after pre-training)
+                    with cx.rng_scoped('val/C'):
+                        logits, fm = m.classifier(xa, False)
+                    acc_real = self._accuracy_metric(ya, logits, acc_real)[0]
+                    if real is None:
+                        real = tgm.FeatureMoments(fm.c, cx.device)
+                    real.add(fm, cx.stream)
+            acc_fake = None
+            for k in range(n_batches):
+                take = min(B, n_samples - k * B)
+                with cx.phase_scope('metrics_g', record=False), self._classifier_weights(ema):
+                    za = cx.from_numpy(z[k * B:(k + 1) * B], key='metrics:z')
+                    yg = cx.from_numpy(y[k * B:(k + 1) * B], key='metrics:y_g')
+                    xg = m.as_image(m.good_sampler(za, yg))
+                    if m.zca() is not None:
+                        xg = m.zca().apply(xg)
+                    with cx.rng_scoped('val/C'):
+                        logits, fm = m.classifier(xg, False)
+                    acc_fake = self._accuracy_metric(yg.view_rows(0, take), logits.view_rows(0, take), acc_fake)[0]
+                    if fake is None:
+                        fake = tgm.FeatureMoments(fm.c, cx.device)
+                    fake.add(fm.view_rows(0, take), cx.stream)
+            n_real, mu_r, cov_r = real.result() if real is not None else (0, None, None)
+            n_fake, mu_f, cov_f = fake.result()
+            fd = tgm.frechet_distance(mu_r, cov_r, mu_f, cov_f) if n_real >= 2 and n_fake >= 2 else float('nan')
+            out = dict(val_accuracy=float(acc_real) if acc_real is not None else 0.0, g_class_accuracy=float(acc_fake),
+                       frechet_distance=fd, n_real=int(n_real), n_fake=int(n_fake))
+        finally:
+            for net, s_before in kept.items():
+                cx.stores[net].s.copy_(s_before)
+        return out
 
     def sync_running_state(self):
         """Replicas keep their own running statistics (pop_mean, batch-norm moving mean / variance) and EMA shadows while
@@ -616,6 +707,29 @@ class Train(Train_base):
         """the train summary's extra scalars: '<d|g|c>_grad_norm' for every clipped network (none without a clip)."""
         return tuple(k + '_grad_norm' for k, net in zip('dgc', NETS) if net in self._clip_views)
 
+    def _tail_metric_tags(self):
+        """the epoch tail's extra records and val-summary scalars, in order: 'val_accuracy_ema' with config.EVAL_EMA, 'g_class_accuracy'
+        and 'frechet_distance' with config.SAMPLE_METRICS (none with both off)."""
+        o = self.options
+        return (('val_accuracy_ema',) if o.eval_ema else ()) + (('g_class_accuracy', 'frechet_distance') if o.sample_metrics else ())
+
+    def _tail_metrics(self, NNIO, init_op_val):
+        """{tag: value} of _tail_metric_tags() for this epoch tail, after sync_running_state: every replica computes the same numbers
+        from the same averaged state, the same validation split and the same latents — no collective.  With both settings on, the
+        averaged accuracy comes out of the metrics pass itself (its real side is evaluate's pass with the shadows): the split is run
+        once for both."""
+        o, out = self.options, {}
+        if o.sample_metrics:
+            init_op_val()
+            sm = self.sample_metrics(NNIO.val_batches(), o.sample_metrics, ema=o.eval_ema)
+            if o.eval_ema:
+                out['val_accuracy_ema'] = sm['val_accuracy']
+            out['g_class_accuracy'], out['frechet_distance'] = sm['g_class_accuracy'], sm['frechet_distance']
+        elif o.eval_ema:
+            init_op_val()
+            out['val_accuracy_ema'] = self.evaluate(NNIO.val_batches(), ema=True)
+        return out
+
     # ------------------------------------------------------------------ the reference's entry point
     def train(self, Dataset, Model, sample_y):
         """:43-381.  Dataset(data_dir, config, num_label, subset, use_augmentation).inputpipline_train_val(val)
@@ -645,7 +759,7 @@ class Train(Train_base):
                 saver.set_save_path(comments=self.comments)                            # :150
         if self.summary_train is not None and self.options.summary_scalar:             # :105-118
             self.summary_train.add_summary({'scalar': dict.fromkeys(('g_loss', 'd_loss', 'c_loss', 'train_accuracy') + self._norm_tags())})
-            self.summary_val.add_summary({'scalar': dict.fromkeys(('val_accuracy',))})
+            self.summary_val.add_summary({'scalar': dict.fromkeys(('val_accuracy',) + self._tail_metric_tags())})
         grid = bool(c.SAMPLE_DIR) and sample_y is not None                             # the sample grid: only for labels handed in
         if sample_y is None and self.summary_train is not None and self.options.summary_image:
             sample_y = np.eye(c.NUM_CLASSES, dtype=np.float32)[np.arange(c.SAMPLE_SIZE) % c.NUM_CLASSES]      # the entry points' cyclic ones
@@ -675,6 +789,8 @@ class Train(Train_base):
             acc = self.evaluate(NNIO.val_batches())
             rec = dict(epoch=epoch + start_epoch, d_loss=d_loss, g_loss=g_loss, c_loss=c_loss, val_accuracy=acc,
                        images_per_sec=iters * c.BATCH_SIZE * self.world / dt)
+            extra = self._tail_metrics(NNIO, init_op_val)                              # EVAL_EMA / SAMPLE_METRICS: {} with both off
+            rec.update(extra)
             history.append(rec)
             samples = None
             if self.summary_train is not None:                                         # :293,346
@@ -683,7 +799,7 @@ class Train(Train_base):
                 saver.save(self, 'model_' + str(epoch + start_epoch).zfill(4) + '.ckpt')
             if self.rank == 0:
                 print("epoch {epoch}: g_loss {g_loss:.3f} d_loss {d_loss:.3f} c_loss {c_loss:.3f} val_acc {val_accuracy:.4f} "
-                      "{images_per_sec:.0f} img/s".format(**rec), flush=True)
+                      "{images_per_sec:.0f} img/s".format(**rec) + "".join(" %s %.4f" % (k, rec[k]) for k in extra), flush=True)
                 if grid:
                     self._save_sample_grid(samples if samples is not None else self.sample(sample_z, sample_y), rec['epoch'])
         if saver is not None and self.rank == 0 and c.EPOCHS > 0:                      # :378-379 (after all epochs)
@@ -715,7 +831,7 @@ class Train(Train_base):
         self.summary_train.write(dict(dict(g_loss=rec['g_loss'], d_loss=rec['d_loss'], c_loss=rec['c_loss']),
                                       **{k + '_grad_norm': v[0] for k, v in norms.items() if v is not None}), rec['epoch'],
                                  histograms=hists, images=imgs)
-        self.summary_val.write(dict(val_accuracy=rec['val_accuracy']), rec['epoch'])
+        self.summary_val.write(dict(dict(val_accuracy=rec['val_accuracy']), **{k: rec[k] for k in self._tail_metric_tags()}), rec['epoch'])
         return samples
 
     def _save_sample_grid(self, samples, epoch):
@@ -849,6 +965,10 @@ def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
         _customize_config(tmp_config, FLAGS)
         if getattr(FLAGS, 'wn_init', None) is not None:                # --wn-init data: Config does not declare WN_INIT, so the hasattr rule
             tmp_config.WN_INIT = FLAGS.wn_init                         # of _customize_config would drop it (Training/options.check_wn_init)
+        if getattr(FLAGS, 'eval_ema', None) is not None:               # --eval-ema, --sample-metrics N: likewise undeclared
+            tmp_config.EVAL_EMA = FLAGS.eval_ema                       # (Training/options.check_eval_ema, check_sample_metrics)
+        if getattr(FLAGS, 'sample_metrics', None) is not None:
+            tmp_config.SAMPLE_METRICS = FLAGS.sample_metrics
     if epochs is not None:
         tmp_config.EPOCHS = epochs
     tmp_config.SAMPLE_DIR = os.path.join(_root_dir(), "Training", tmp_config.SAMPLE_DIR)

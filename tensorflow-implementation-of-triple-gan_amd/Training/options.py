@@ -161,35 +161,66 @@ def check_wn_init(config):
     return v
 
 
+def check_eval_ema(config):
+    """config.EVAL_EMA: off (default; also when the attribute is absent — config.Config does not declare it) or on: the epoch tail also
+    evaluates the classifier's averaged weights and records `val_accuracy_ema` (Train.evaluate(ema=True)).  -> bool.
+    Needs no device; ValueError for anything but None, a bool or 0 / 1."""
+    v = getattr(config, 'EVAL_EMA', None)
+    if v is None:
+        return False
+    if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and v in (0, 1)):
+        return bool(v)
+    raise ValueError("EVAL_EMA must be None, True or False, got %r" % (v,))
+
+
+def check_sample_metrics(config):
+    """config.SAMPLE_METRICS: None (default; also when the attribute is absent — config.Config does not declare it) or a positive int N:
+    the epoch tail scores N generated samples with the run's own classifier and records `g_class_accuracy` and `frechet_distance`
+    (Train.sample_metrics).  -> None or int.  Needs no device; ValueError for zero, a negative number, a bool, a float
+    or any other type."""
+    v = getattr(config, 'SAMPLE_METRICS', None)
+    if v is None:
+        return None
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+        raise ValueError("SAMPLE_METRICS must be None or a positive integer (how many samples to score), got %r" % (v,))
+    return int(v)
+
+
 _Fields = collections.namedtuple('Options', 'mfma_dtype act_dtype num_classes loss optimizers clip_norms momentum seed no_grad_buckets '
                                             'summary summary_scalar summary_histogram summary_image summary_image_max_outputs')
 
 
 class Options(_Fields):
     """the record resolve() returns.  Its tuple fields are the settings config.Config declares a default for (and NO_GRAD_BUCKETS);
-    `wn_init` (check_wn_init: a setting Config deliberately does not declare) is carried as an attribute beside them, so the field
-    list — what _asdict() and unpacking give — stays what it was.  Two records are equal when fields and wn_init are."""
+    `wn_init`, `eval_ema` and `sample_metrics` (check_wn_init, check_eval_ema, check_sample_metrics: settings Config deliberately does
+    not declare) are carried as attributes beside them, so the field list — what _asdict() and unpacking give — stays what it was.
+    Two records are equal when the fields and these attributes are."""
+    EXTRAS = ('wn_init', 'eval_ema', 'sample_metrics')
 
-    def __new__(cls, wn_init=None, **fields):
+    def __new__(cls, wn_init=None, eval_ema=False, sample_metrics=None, **fields):
         self = super(Options, cls).__new__(cls, **fields)
-        self.wn_init = wn_init
+        self.wn_init, self.eval_ema, self.sample_metrics = wn_init, eval_ema, sample_metrics
         return self
 
+    def _extras(self):
+        return tuple(getattr(self, k) for k in self.EXTRAS)
+
     def __eq__(self, other):
-        return tuple.__eq__(self, other) and getattr(other, 'wn_init', None) == self.wn_init
+        return tuple.__eq__(self, other) and tuple(getattr(other, k, d) for k, d in zip(self.EXTRAS, (None, False, None))) == self._extras()
 
     def __ne__(self, other):
         return not self == other
 
     def __hash__(self):
-        return hash((tuple(self), self.wn_init))
+        return hash((tuple(self),) + self._extras())
 
 
 def resolve(config):
     """every device-free check of `config`, once -> the Options record of what Train reads with a default (EXEC_MODE / USE_HIP_GRAPH
     excepted: those stay live, read per iteration).  The string form of ZCA is checked here; against a Dataset, where one is known."""
     check_zca(config)
-    return Options(wn_init=check_wn_init(config), mfma_dtype=check_mfma_dtype(config), act_dtype=check_act_dtype(config), num_classes=check_num_classes(config),
+    return Options(wn_init=check_wn_init(config), eval_ema=check_eval_ema(config), sample_metrics=check_sample_metrics(config),
+                   mfma_dtype=check_mfma_dtype(config), act_dtype=check_act_dtype(config), num_classes=check_num_classes(config),
                    loss=check_loss(config), optimizers=check_optimizer(config), clip_norms=check_clip_norm(config),
                    momentum=float(opt(config, 'MOMENTUM')), seed=opt(config, 'SEED'),
                    no_grad_buckets=bool(getattr(config, 'NO_GRAD_BUCKETS', False)),      # a debugging switch Config does not declare

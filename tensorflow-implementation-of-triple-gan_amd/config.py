@@ -85,6 +85,15 @@ class Config(object):
     # training batch, g <- init_scale / sqrt(var + eps), b <- -mean * g (Salimans & Kingma 2016; Train.data_dependent_init,
     # DESIGN §9.9); absent or None: g = 1, b = 0 as created.  Read by Training/options.check_wn_init.
 
+    # EVAL_EMA, SAMPLE_METRICS — NOT declared here either, for the same reason; an instance or subclass may set
+    #   EVAL_EMA = True (--eval-ema): the epoch tail also evaluates the classifier's averaged weights (the EMA shadows, decay 0.9999
+    #     without bias correction: they lag the weights by roughly 1e4 iterations) and records `val_accuracy_ema`;
+    #   SAMPLE_METRICS = N (--sample-metrics N), a positive int: the epoch tail scores N generated samples with the run's own
+    #     classifier — `g_class_accuracy`, the share classified as the class they were asked for, and `frechet_distance` between the
+    #     classifier features of the validation split and of the samples (with the averaged weights when EVAL_EMA is on).  The
+    #     extractor moves with training: compare generators under one classifier, not epochs (Train.sample_metrics).
+    # Absent, None or False: the epoch tail is what it was.  Read by Training/options.check_eval_ema / check_sample_metrics.
+
     def __init__(self):
         """Set values of computed attributes (config.py:70-73)."""
         self.MIN_QUEUE_EXAMPLES = self.BATCH_SIZE * 3

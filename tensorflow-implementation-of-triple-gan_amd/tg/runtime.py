@@ -104,6 +104,7 @@ class ParamStore(object):
         self.optimizer = 'adam'      # which optimiser's slots m / v hold (Training/train_base.py sets it; Training/Saver.py names the keys by it)
         self.step = torch.zeros(1, dtype=torch.int32, device=device)
         self.ema = None
+        self.read_ema = False        # inside Context.reading_shadows: value() hands out the EMA shadow of a trainable variable
         self.frozen = False          # set by tg.executor.StepExecutor: a hipGraph or a launch plan holds this store's device pointers, re-allocation is an error
 
     def _narrow(self):
@@ -120,8 +121,9 @@ class ParamStore(object):
         return buf[off:off + n]
 
     def value(self, nm):
+        """the variable's tensor; inside Context.reading_shadows a trainable variable's EMA shadow instead (non-trainable state as it is)."""
         kind = self.index[nm][0]
-        return self._slice(self.p if kind == 'p' else self.s, nm)
+        return self._slice((self.ema if self.read_ema else self.p) if kind == 'p' else self.s, nm)
 
     def grad(self, nm):
         assert self.index[nm][0] == 'p', nm
@@ -131,7 +133,7 @@ class ParamStore(object):
         return self.index[nm][3]
 
     def set(self, nm, array):
-        v = self.value(nm)
+        v = self._slice(self.p if self.index[nm][0] == 'p' else self.s, nm)         # the variable itself, never its shadow
         a = np.ascontiguousarray(array, np.float32).reshape(-1)
         assert a.size == v.numel(), (nm, a.size, v.numel())
         v.copy_(torch.from_numpy(a))
@@ -577,6 +579,27 @@ class Context(object):
             yield self.wn_inited
         finally:
             self.assign_init, self.wn_inited, self.tape = prev
+
+    @contextlib.contextmanager
+    def reading_shadows(self, net='classifier'):
+        """the reference's `custom_getter` over ema.average (nn.py:98-110, Train_goodGAN.py:100-103): inside, every trainable variable of
+        network `net` reads as its EMA shadow (ParamStore.value) and its non-trainable state — pop_mean, batch-norm moving statistics,
+        which ema.apply did not cover — as it is.  A forward-only evaluation pass outside the training step: nothing is recorded on a
+        tape, and no prepared-filter cache exists here (Context.prep_cache is None outside Train.train_iteration), so nothing made from
+        the shadows outlives the pass and nothing made from the raw weights is served to it.  lib.TgError inside a training iteration,
+        a hipGraph capture or a launch-plan recording, and for a network without shadows.  Re-entrant."""
+        st = self.stores[net]
+        if st.ema is None:
+            raise lib.TgError("reading_shadows: network %r keeps no EMA shadows" % (net,))
+        if self.capturing or lib._recorder is not None or self.prep_cache is not None:
+            raise lib.TgError("reading_shadows: inside a training iteration, a hipGraph capture or a launch-plan recording; the averaged "
+                              "weights are for evaluation passes outside the step")
+        prev = (st.read_ema, self.tape)
+        st.read_ema, self.tape = True, None
+        try:
+            yield st
+        finally:
+            st.read_ema, self.tape = prev
 
     def run_tape(self, tape, stop_at_boundary=False):
         """run a recorded tape in reverse (all of it, or down to its last bucket boundary: see backward); returns the unexecuted head

@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""Restore a run's checkpoint and print its generated-sample metrics (Train.sample_metrics): the validation accuracy, the
+class-conditional accuracy of N generated samples and the Fréchet distance between the classifier features of the validation split and
+of the samples — with the raw weights, or with the classifier's averaged weights (--ema).  The extractor is the checkpoint's own
+classifier: distances compare generators scored by ONE classifier, not checkpoints of different epochs.
+
+    python tools/sample_metrics.py --experiment mnist [--weight-dir DIR] [--run Run_...] [--epoch N] [--samples 10000] [--ema]
+                                   [--data-dir DIR]
+
+--weight-dir defaults to the experiment's WEIGHT_DIR (Training/Weight_<data>), --run to its latest Run_* directory, --epoch to that
+run's last checkpoint.  Without --data-dir the validation split is the synthetic one the entry points train on; with it, the
+experiment's TFRecord test split under DIR.  The classifiers' input noise is drawn from the restored Philox state under THIS process's
+stream ids (handed out in order of first use), so an accuracy agrees with the one the run printed to within that noise, not bit for
+bit.  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "tensorflow-implementation-of-triple-gan_amd")
+for p in (ROOT, PKG):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+EXPERIMENTS = ('mnist', 'svhn', 'cifar10', 'cifar100', 'stress64')
+
+
+def build(experiment, weight_dir=None, data_dir=None, seed=None):
+    """(trainer with its model built, config, Dataset class) of one of the entry points' experiments, nothing trained or restored."""
+    from Training import Train_goodGAN as TG
+    cfg = {'mnist': TG.MnistConfig, 'svhn': TG.SvhnConfig, 'cifar10': TG.Cifar10Config, 'cifar100': TG.Cifar100Config,
+           'stress64': TG.Stress64Config}[experiment]()
+    for k in ('DATA_DIR', 'WEIGHT_DIR', 'LOG_DIR'):
+        setattr(cfg, k, os.path.join(TG._root_dir(), getattr(cfg, k)))
+    if weight_dir is not None:
+        cfg.WEIGHT_DIR = weight_dir
+    if seed is not None:
+        cfg.SEED = seed
+    cfg.SUMMARY = False
+    if data_dir is not None:
+        import importlib
+        cfg.DATA_DIR = data_dir
+        Dataset = getattr(importlib.import_module('Input_Pipeline.%sDataset' % experiment), experiment + 'Dataset')
+    else:
+        from Input_Pipeline.syntheticDataset import syntheticDataset as Dataset
+    TG._synthetic_zca(cfg)
+    if experiment in ('mnist', 'svhn'):
+        from Model.Good_GAN import Good_GAN as Model
+    elif experiment == 'stress64':
+        from Model.Good_GAN_stress64 import Good_GAN_stress64 as Model
+    else:
+        from Model.Good_GAN_cifar10 import Good_GAN_cifar10 as Model
+    tr = TG.Train(cfg, None, None)
+    tr._build_train_graph(Model)
+    return tr, cfg, Dataset
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    ap.add_argument('--experiment', choices=EXPERIMENTS, required=True)
+    ap.add_argument('--weight-dir', help="the directory that holds the run's Run_* directories (default: the experiment's WEIGHT_DIR)")
+    ap.add_argument('--run', help='the Run_* directory to restore (default: the latest)')
+    ap.add_argument('--epoch', type=int, help="the checkpoint's epoch (default: the run's last)")
+    ap.add_argument('--samples', type=int, default=10000, help='generated samples to score')
+    ap.add_argument('--ema', action='store_true', help="score with the classifier's averaged weights (the EMA shadows)")
+    ap.add_argument('--data-dir', help="DATA_DIR of the experiment's TFRecords (default: the synthetic validation split)")
+    a = ap.parse_args()
+    from Training.Saver import Saver
+    tr, cfg, Dataset = build(a.experiment, a.weight_dir, a.data_dir)
+    epoch = Saver(cfg.WEIGHT_DIR).restore(tr, dir_names=a.run, epoch=a.epoch)
+    train = Dataset(cfg.DATA_DIR, cfg, cfg.NUM_LABEL, 'train', False)
+    val = Dataset(cfg.DATA_DIR, cfg, cfg.NUM_LABEL, 'test', False)
+    _, init_op_val, NNIO = train.inputpipline_train_val(val)
+    init_op_val()
+    out = tr.sample_metrics(NNIO.val_batches(), a.samples, ema=a.ema)
+    print(json.dumps(dict(out, experiment=a.experiment, epoch=int(epoch), ema=bool(a.ema), samples=int(a.samples),
+                          weight_dir=cfg.WEIGHT_DIR, run=a.run)))
+
+
+if __name__ == '__main__':
+    main()
