@@ -709,6 +709,34 @@ int tg_tf_histogram_f32(const float* x, int64_t n, const int64_t* segs, int nseg
 int64_t tg_feature_moments_workspace_bytes(int n, int c);
 int tg_feature_moments_f32(const float* f, int ld, int n, int c, double* sum, double* gram, void* workspace, int64_t workspace_bytes,
                            void* stream);
+/* k-nearest-neighbour distances on fp32 feature rows (precision / recall / density / coverage of generated samples,
+ * tg.metrics.manifold_metrics).  The distance is part of the interface: for rows a, b of width c,
+ *   d2(a, b) = the fp32 value of  acc = 0; for ch = 0 .. c-1: d = a[ch] - b[ch]; p = d * d; acc = acc + p
+ * every operation rounded to fp32, one accumulator, ascending channels, no contraction (no fma).  The terms are non-negative, so d2 is
+ * within (c + 3) 2^-24 of the exact value, relative, whatever offset the features share; the chain is fixed, so every output below is
+ * reproducible bit for bit (tests/manifold_reference.py restates it in NumPy).
+ *   tg_knn_self_f32        x: DEVICE [n][ld].  out_d2[i*k + t], t = 0..k-1: the k smallest d2(x_i, x_j) over j != i, ascending (DEVICE, n*k
+ *                          floats).  The row itself is left out by INDEX, not by value: a duplicated row contributes a 0.  n >= k + 1.
+ *   tg_manifold_query_f32  q: DEVICE [m][ld_q], r: DEVICE [n][ld_r], r2: DEVICE n floats or NULL.  For every query row i over all n rows of r:
+ *                            count[i]  = #{ j : d2(q_i, r_j) <= r2[j] }   (DEVICE, m int32; with r2 == NULL count is not written and may be NULL)
+ *                            nn_d2[i]  = min_j d2(q_i, r_j)               (DEVICE, m floats)
+ *                            nn_idx[i] = the lowest j attaining it        (DEVICE, m int32)
+ *                          m, n >= 1.
+ * Both: columns c..ld-1 are never read (they may hold anything); 1 <= c <= 512, 1 <= k <= 16, ld >= c; anything else, a NULL pointer
+ * (r2 / count as above excepted) or a workspace smaller than the query's answer is TG_ERR_INVALID before any launch.  A 256-thread
+ * workgroup owns a 64 x 64 tile of (query, reference) pairs, 16 independent chains per thread, channel chunks of both row tiles staged
+ * in LDS; the reference rows are cut into ranges (the grid over query tiles alone would not fill the device) and each (query, range)
+ * leaves its partial — the k smallest; the minimum with its index and the count — in the workspace, which a finishing launch merges
+ * in range order.  No floating-point atomics, the grid a function of the shapes alone: bit-identical from run to run, on any stream.
+ * Behaviour on non-finite features is unspecified apart from staying in bounds.
+ * workspace: caller-owned scratch of at least tg_knn_self_workspace_bytes(n, k) / tg_manifold_query_workspace_bytes(m, n) bytes (host
+ * queries; < 0 for a bad argument), 16-byte aligned, needs no initialisation, nothing beyond that size is written.
+ * 3 c operations per pair on the fp32 VALU: 3 n^2 c (self), 3 m n c (query). */
+int64_t tg_knn_self_workspace_bytes(int n, int k);
+int tg_knn_self_f32(const float* x, int ld, int n, int c, int k, float* out_d2, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t tg_manifold_query_workspace_bytes(int m, int n);
+int tg_manifold_query_f32(const float* q, int ld_q, int m, const float* r, int ld_r, int n, int c, const float* r2, int32_t* count,
+                          float* nn_d2, int32_t* nn_idx, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- RNG(Philox4x32-10; state = device {seed, step}) -------------------------------------------- */
 /* Element e of a draw is word e % 4 of the block with counter (lo32(e / 4), hi32(e / 4), stream_id, lo32(step)) and key (lo32(seed),

@@ -25,7 +25,8 @@ import torch
 
 from config import Config
 from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, check_act_dtype, check_clip_norm, check_eval_ema, check_loss,  # noqa: F401
-                              check_mfma_dtype, check_num_classes, check_optimizer, check_sample_metrics, check_wn_init, check_zca, cla_lr, opt, resolve)
+                              check_mfma_dtype, check_num_classes, check_optimizer, check_sample_manifold_k, check_sample_metrics, check_wn_init,
+                              check_zca, cla_lr, opt, resolve)
 from Training.train_base import Train_base, clip_workspace_floats
 from tg import dist as tgdist
 from tg import executor, lib, ops
@@ -549,7 +550,26 @@ class Train(Train_base):
         The sampler's batch norms move their running statistics: every store's `s` is put back afterwards, and nothing else is
         written — weights, shadows, optimiser slots, step counters and the Philox state are what they were.  The pass runs under
         phases of its own ('metrics', 'metrics_g': unrecorded, buffer keys of their own), so no buffer a launch plan or graph names
-        is touched.  Synchronises the device."""
+        is touched.  Synchronises the device.
+        sample_manifold_metrics is this pass with the k-nearest-neighbour metrics on top."""
+        return self._sample_metrics_pass(batches, n_samples, ema, None)[0]
+
+    def sample_manifold_metrics(self, batches, n_samples, manifold_k, ema=False, return_banks=False):
+        """sample_metrics plus the k-nearest-neighbour manifold metrics -> its five keys, then `precision`, `recall`,
+        `density` and `coverage`.  manifold_k: the k of the radii, 1..16 (tg.metrics.check_k).
+        The same two passes also keep their feature rows — every real one, the first n_samples generated ones — in a
+        tg.metrics.FeatureBank each, and tg.metrics.manifold_metrics (tg_knn_self_f32 and tg_manifold_query_f32, twice each) turns the
+        banks into the four numbers.  They are NaN, and the kernels are not called, when a side's moment sums are not finite (a
+        diverged run) or a side has fewer than k + 1 rows.  The banks are buffers of their own and the kernels write nothing else:
+        what sample_metrics says about the trainer's state holds unchanged.
+        return_banks: return (result, (real bank, fake bank)) — the rows that were scored — instead of the result alone."""
+        from tg import metrics as tgm
+        manifold_k = tgm.check_k(manifold_k, 'sample_manifold_metrics: manifold_k')
+        out, banks = self._sample_metrics_pass(batches, n_samples, ema, manifold_k)
+        return (out, banks) if return_banks else out
+
+    def _sample_metrics_pass(self, batches, n_samples, ema, manifold_k):
+        """the pass behind sample_metrics (manifold_k None) and sample_manifold_metrics -> (result, (real bank, fake bank) or None)."""
         from tg import metrics as tgm
         cx, m, c = self.cx, self.model, self.config
         n_samples = int(n_samples)
@@ -561,7 +581,7 @@ class Train(Train_base):
         n_batches = -(-n_samples // B)
         z, y = self._sample_latents(n_batches)
         kept = {net: st.s.clone() for net, st in cx.stores.items()}
-        real = fake = None
+        real = fake = bank_real = bank_fake = None
         try:
             acc_real = None
             for xb, yb in batches:                                   # (the moments are sized by the first feature seen)
@@ -578,6 +598,9 @@ class Train(Train_base):
                     if real is None:
                         real = tgm.FeatureMoments(fm.c, cx.device)
                     real.add(fm, cx.stream)
+                    if manifold_k is not None:
+                        bank_real = bank_real or tgm.FeatureBank(fm.c, cx.device)
+                        bank_real.add(fm, cx.stream)
             acc_fake = None
             for k in range(n_batches):
                 take = min(B, n_samples - k * B)
@@ -593,15 +616,23 @@ class Train(Train_base):
                     if fake is None:
                         fake = tgm.FeatureMoments(fm.c, cx.device)
                     fake.add(fm.view_rows(0, take), cx.stream)
-            n_real, mu_r, cov_r = real.result() if real is not None else (0, None, None)
-            n_fake, mu_f, cov_f = fake.result()
+                    if manifold_k is not None:
+                        bank_fake = bank_fake or tgm.FeatureBank(fm.c, cx.device)
+                        bank_fake.add(fm.view_rows(0, take), cx.stream)
+            (n_real, sum_r, gram_r), (n_fake, sum_f, gram_f) = real.sums() if real is not None else (0, None, None), fake.sums()
+            mu_r, cov_r = tgm.mean_cov(n_real, sum_r, gram_r) if real is not None else (None, None)
+            mu_f, cov_f = tgm.mean_cov(n_fake, sum_f, gram_f)
             fd = tgm.frechet_distance(mu_r, cov_r, mu_f, cov_f) if n_real >= 2 and n_fake >= 2 else float('nan')
             out = dict(val_accuracy=float(acc_real) if acc_real is not None else 0.0, g_class_accuracy=float(acc_fake),
                        frechet_distance=fd, n_real=int(n_real), n_fake=int(n_fake))
+            if manifold_k is not None:
+                finite = real is not None and all(bool(np.isfinite(a).all()) for a in (sum_r, gram_r, sum_f, gram_f))
+                out.update(tgm.manifold_metrics(bank_real, bank_fake, manifold_k, cx.stream) if finite
+                           else dict.fromkeys(tgm.MANIFOLD_KEYS, float('nan')))
         finally:
             for net, s_before in kept.items():
                 cx.stores[net].s.copy_(s_before)
-        return out
+        return out, (None if manifold_k is None else (bank_real, bank_fake))
 
     def sync_running_state(self):
         """Replicas keep their own running statistics (pop_mean, batch-norm moving mean / variance) and EMA shadows while
@@ -709,9 +740,12 @@ class Train(Train_base):
 
     def _tail_metric_tags(self):
         """the epoch tail's extra records and val-summary scalars, in order: 'val_accuracy_ema' with config.EVAL_EMA, 'g_class_accuracy'
-        and 'frechet_distance' with config.SAMPLE_METRICS (none with both off)."""
+        and 'frechet_distance' with config.SAMPLE_METRICS, then 'precision', 'recall', 'density' and 'coverage' with
+        config.SAMPLE_MANIFOLD_K (none with all off)."""
+        from tg import metrics as tgm
         o = self.options
-        return (('val_accuracy_ema',) if o.eval_ema else ()) + (('g_class_accuracy', 'frechet_distance') if o.sample_metrics else ())
+        return ((('val_accuracy_ema',) if o.eval_ema else ()) + (('g_class_accuracy', 'frechet_distance') if o.sample_metrics else ())
+                + (tgm.MANIFOLD_KEYS if o.sample_metrics and o.sample_manifold_k else ()))
 
     def _tail_metrics(self, NNIO, init_op_val):
         """{tag: value} of _tail_metric_tags() for this epoch tail, after sync_running_state: every replica computes the same numbers
@@ -721,10 +755,16 @@ class Train(Train_base):
         o, out = self.options, {}
         if o.sample_metrics:
             init_op_val()
-            sm = self.sample_metrics(NNIO.val_batches(), o.sample_metrics, ema=o.eval_ema)
+            if o.sample_manifold_k:
+                sm = self.sample_manifold_metrics(NNIO.val_batches(), o.sample_metrics, o.sample_manifold_k, ema=o.eval_ema)
+            else:
+                sm = self.sample_metrics(NNIO.val_batches(), o.sample_metrics, ema=o.eval_ema)
             if o.eval_ema:
                 out['val_accuracy_ema'] = sm['val_accuracy']
             out['g_class_accuracy'], out['frechet_distance'] = sm['g_class_accuracy'], sm['frechet_distance']
+            if o.sample_manifold_k:                                                     # SAMPLE_MANIFOLD_K: the same pass, four more numbers
+                from tg import metrics as tgm
+                out.update((k, sm[k]) for k in tgm.MANIFOLD_KEYS)
         elif o.eval_ema:
             init_op_val()
             out['val_accuracy_ema'] = self.evaluate(NNIO.val_batches(), ema=True)
@@ -969,6 +1009,8 @@ def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
             tmp_config.EVAL_EMA = FLAGS.eval_ema                       # (Training/options.check_eval_ema, check_sample_metrics)
         if getattr(FLAGS, 'sample_metrics', None) is not None:
             tmp_config.SAMPLE_METRICS = FLAGS.sample_metrics
+        if getattr(FLAGS, 'sample_manifold_k', None) is not None:      # --sample-manifold-k K (check_sample_manifold_k; flag objects
+            tmp_config.SAMPLE_MANIFOLD_K = FLAGS.sample_manifold_k     # without the attribute are common: getattr with a default)
     if epochs is not None:
         tmp_config.EPOCHS = epochs
     tmp_config.SAMPLE_DIR = os.path.join(_root_dir(), "Training", tmp_config.SAMPLE_DIR)

@@ -186,27 +186,43 @@ def check_sample_metrics(config):
     return int(v)
 
 
+def check_sample_manifold_k(config):
+    """config.SAMPLE_MANIFOLD_K: None (default; also when the attribute is absent — config.Config does not declare it) or an int k in
+    1..16: the epoch tail's sample metrics also record the k-nearest-neighbour `precision`, `recall`, `density` and `coverage` of the
+    generated samples (Train.sample_manifold_metrics; k = 3 in Kynkäänniemi et al. 2019).  -> None or int.  Needs no
+    device; ValueError for what tg.metrics.check_k refuses (a value outside 1..16, a bool, a float, any other type) and when set
+    without SAMPLE_METRICS (the numbers come out of that pass)."""
+    from tg.metrics import check_k                                    # (device-free: the module touches torch only inside its classes)
+    v = getattr(config, 'SAMPLE_MANIFOLD_K', None)
+    if v is None:
+        return None
+    v = check_k(v, 'SAMPLE_MANIFOLD_K')
+    if check_sample_metrics(config) is None:
+        raise ValueError("SAMPLE_MANIFOLD_K = %r needs SAMPLE_METRICS = N: the sample-metrics pass computes the manifold metrics" % (v,))
+    return v
+
+
 _Fields = collections.namedtuple('Options', 'mfma_dtype act_dtype num_classes loss optimizers clip_norms momentum seed no_grad_buckets '
                                             'summary summary_scalar summary_histogram summary_image summary_image_max_outputs')
 
 
 class Options(_Fields):
     """the record resolve() returns.  Its tuple fields are the settings config.Config declares a default for (and NO_GRAD_BUCKETS);
-    `wn_init`, `eval_ema` and `sample_metrics` (check_wn_init, check_eval_ema, check_sample_metrics: settings Config deliberately does
-    not declare) are carried as attributes beside them, so the field list — what _asdict() and unpacking give — stays what it was.
-    Two records are equal when the fields and these attributes are."""
-    EXTRAS = ('wn_init', 'eval_ema', 'sample_metrics')
+    `wn_init`, `eval_ema`, `sample_metrics` and `sample_manifold_k` (check_wn_init, check_eval_ema, check_sample_metrics,
+    check_sample_manifold_k: settings Config deliberately does not declare) are carried as attributes beside them, so the field
+    list — what _asdict() and unpacking give — stays what it was.  Two records are equal when the fields and these attributes are."""
+    EXTRAS = ('wn_init', 'eval_ema', 'sample_metrics', 'sample_manifold_k')
 
-    def __new__(cls, wn_init=None, eval_ema=False, sample_metrics=None, **fields):
+    def __new__(cls, wn_init=None, eval_ema=False, sample_metrics=None, sample_manifold_k=None, **fields):
         self = super(Options, cls).__new__(cls, **fields)
-        self.wn_init, self.eval_ema, self.sample_metrics = wn_init, eval_ema, sample_metrics
+        self.wn_init, self.eval_ema, self.sample_metrics, self.sample_manifold_k = wn_init, eval_ema, sample_metrics, sample_manifold_k
         return self
 
     def _extras(self):
         return tuple(getattr(self, k) for k in self.EXTRAS)
 
     def __eq__(self, other):
-        return tuple.__eq__(self, other) and tuple(getattr(other, k, d) for k, d in zip(self.EXTRAS, (None, False, None))) == self._extras()
+        return tuple.__eq__(self, other) and tuple(getattr(other, k, d) for k, d in zip(self.EXTRAS, (None, False, None, None))) == self._extras()
 
     def __ne__(self, other):
         return not self == other
@@ -220,6 +236,7 @@ def resolve(config):
     excepted: those stay live, read per iteration).  The string form of ZCA is checked here; against a Dataset, where one is known."""
     check_zca(config)
     return Options(wn_init=check_wn_init(config), eval_ema=check_eval_ema(config), sample_metrics=check_sample_metrics(config),
+                   sample_manifold_k=check_sample_manifold_k(config),
                    mfma_dtype=check_mfma_dtype(config), act_dtype=check_act_dtype(config), num_classes=check_num_classes(config),
                    loss=check_loss(config), optimizers=check_optimizer(config), clip_norms=check_clip_norm(config),
                    momentum=float(opt(config, 'MOMENTUM')), seed=opt(config, 'SEED'),

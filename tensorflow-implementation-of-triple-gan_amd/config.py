@@ -92,7 +92,11 @@ class Config(object):
     #     classifier — `g_class_accuracy`, the share classified as the class they were asked for, and `frechet_distance` between the
     #     classifier features of the validation split and of the samples (with the averaged weights when EVAL_EMA is on).  The
     #     extractor moves with training: compare generators under one classifier, not epochs (Train.sample_metrics).
-    # Absent, None or False: the epoch tail is what it was.  Read by Training/options.check_eval_ema / check_sample_metrics.
+    #   SAMPLE_MANIFOLD_K = k (--sample-manifold-k k), an int in 1..16, with SAMPLE_METRICS: the same pass also records the
+    #     k-nearest-neighbour `precision`, `recall`, `density` and `coverage` of the samples against the validation split (k = 3 in
+    #     Kynkäänniemi et al. 2019; tg_knn_self_f32 / tg_manifold_query_f32).  The radii depend on k and on both counts.
+    # Absent, None or False: the epoch tail is what it was.  Read by Training/options.check_eval_ema / check_sample_metrics /
+    # check_sample_manifold_k.
 
     def __init__(self):
         """Set values of computed attributes (config.py:70-73)."""

@@ -1,14 +1,17 @@
-"""Generated-sample metrics on classifier features (Train.sample_metrics, DESIGN §9.10): the host side of tg_feature_moments_f32
-(include/tg_kernels.h, csrc/moments.hip) and the Fréchet distance between two Gaussians in NumPy float64.
+"""Generated-sample metrics on classifier features (Train.sample_metrics, DESIGN §9.10, §9.11): the host side of tg_feature_moments_f32
+(include/tg_kernels.h, csrc/moments.hip) and the Fréchet distance between two Gaussians in NumPy float64; the host side of
+tg_knn_self_f32 / tg_manifold_query_f32 (csrc/knn.hip) and the k-nearest-neighbour precision, recall, density and coverage.
 
 The device adds up a feature matrix's column sums and Gram matrix in fp64, batch after batch; the host turns them into a mean and a
 covariance once, at the end, and takes the distance — c x c eigenproblems, no scipy.  Importable without a device: torch and the HIP
-library are touched only by FeatureMoments."""
+library are touched only by FeatureMoments, FeatureBank and manifold_metrics."""
 import numpy as np
 
 from . import lib
 
-MAX_FEATURES = 512          # tg_feature_moments_f32 accepts 1 <= c <= 512
+MAX_FEATURES = 512          # tg_feature_moments_f32, tg_knn_self_f32 and tg_manifold_query_f32 accept 1 <= c <= 512
+MAX_K = 16                  # tg_knn_self_f32 accepts 1 <= k <= 16
+MANIFOLD_KEYS = ('precision', 'recall', 'density', 'coverage')
 
 
 def mean_cov(n, total, gram):
@@ -84,3 +87,124 @@ class FeatureMoments(object):
         """(n, mean, cov) — mean_cov of what has been added."""
         n, total, gram = self.sums()
         return (n,) + mean_cov(n, total, gram)
+
+
+def check_k(k, what='k'):
+    """the k of the k-nearest-neighbour radii: an int in 1..MAX_K (what tg_knn_self_f32 accepts), not a bool -> int.  ValueError
+    otherwise, naming `what`.  The one check of it: options.check_sample_manifold_k, Train.sample_manifold_metrics and
+    manifold_metrics all come here."""
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_K:
+        raise ValueError("%s must be an integer in 1..%d, got %r" % (what, MAX_K, k))
+    return int(k)
+
+
+class FeatureBank(object):
+    """the [n, c] fp32 feature rows of a pass, dense on `device`, for the k-nearest-neighbour kernels: add() is one tg_copy2d_f32 launch
+    behind the rows already there.  The buffer grows by re-allocation (doubling), which a hipGraph capture or a launch-plan recording
+    must not see: add() refuses to run inside one."""
+
+    def __init__(self, c, device):
+        if not 1 <= int(c) <= MAX_FEATURES:
+            raise ValueError("FeatureBank: c must be in 1..%d, got %r" % (MAX_FEATURES, c))
+        self.c, self.device, self.n = int(c), device, 0
+        self.buf = None
+
+    def reset(self):
+        self.n = 0
+        return self
+
+    def _reserve(self, rows):
+        import torch
+        have = 0 if self.buf is None else self.buf.numel() // self.c
+        if rows <= have:
+            return
+        grown = torch.empty(max(rows, 2 * have, 256) * self.c, dtype=torch.float32, device=self.device)
+        if self.n:
+            grown[:self.n * self.c].copy_(self.buf[:self.n * self.c])
+        self.buf = grown
+
+    def add(self, act, stream=None):
+        """act: an Act whose logical shape is [n, c] (h = w = 1), channel stride ld >= c; its padding columns are not copied."""
+        import torch
+        if act.h != 1 or act.w != 1 or act.c != self.c or act.dtype != 'f32':
+            raise lib.TgError("FeatureBank.add: an fp32 [n, %d] feature is needed, got [%d, %d, %d, %d] %s" % (self.c, act.n, act.h, act.w, act.c, act.dtype))
+        if lib._recorder is not None or torch.cuda.is_current_stream_capturing():
+            raise lib.TgError("FeatureBank.add: called inside a hipGraph capture / launch-plan recording; the bank re-allocates as it grows")
+        if act.n == 0:
+            return self
+        self._reserve(self.n + act.n)
+        if stream is None:
+            stream = lib.cur_stream()
+        lib.call('tg_copy2d_f32', act.ptr, act.ld, lib.ptr(self.buf[self.n * self.c:]), self.c, act.n, self.c, stream)
+        self.n += act.n
+        return self
+
+    def rows(self):
+        """the [n, c] device tensor of what has been added (a view of the buffer)."""
+        import torch
+        if self.buf is None:
+            return torch.empty((0, self.c), dtype=torch.float32, device=self.device)
+        return self.buf[:self.n * self.c].view(self.n, self.c)
+
+    def numpy(self):
+        """the rows as a host [n, c] float32 array (synchronises)."""
+        return self.rows().cpu().numpy().copy()
+
+
+def knn_self(x, k, stream=None):
+    """x: [n, c] dense fp32 device tensor -> [n, k] device tensor of tg_knn_self_f32: every row's k smallest squared distances to the
+    other rows, ascending."""
+    import torch
+    n, c = x.shape
+    need = lib.call('tg_knn_self_workspace_bytes', n, k)
+    work = torch.empty(max((need + 3) // 4, 4), dtype=torch.float32, device=x.device)
+    out = torch.empty((n, k), dtype=torch.float32, device=x.device)
+    lib.call('tg_knn_self_f32', lib.ptr(x), c, n, c, k, lib.ptr(out), lib.ptr(work), work.numel() * 4, lib.cur_stream() if stream is None else stream)
+    return out
+
+
+def manifold_query(q, r, r2=None, stream=None):
+    """q [m, c], r [n, c] dense fp32 device tensors, r2 [n] or None -> (count int32 [m] or None, nn_d2 [m], nn_idx int32 [m]) device
+    tensors of tg_manifold_query_f32."""
+    import torch
+    (m, c), n = q.shape, r.shape[0]
+    need = lib.call('tg_manifold_query_workspace_bytes', m, n)
+    work = torch.empty(max((need + 3) // 4, 4), dtype=torch.float32, device=q.device)
+    count = None if r2 is None else torch.empty(m, dtype=torch.int32, device=q.device)
+    nn_d2 = torch.empty(m, dtype=torch.float32, device=q.device)
+    nn_idx = torch.empty(m, dtype=torch.int32, device=q.device)
+    lib.call('tg_manifold_query_f32', lib.ptr(q), c, m, lib.ptr(r), c, n, c, lib.ptr(r2), lib.ptr(count), lib.ptr(nn_d2), lib.ptr(nn_idx),
+             lib.ptr(work), work.numel() * 4, lib.cur_stream() if stream is None else stream)
+    return count, nn_d2, nn_idx
+
+
+def manifold_from_counts(k, n_fake, count_fr, count_rf, nn_rf, r2_real):
+    """{precision, recall, density, coverage} from the query outputs, reduced in float64 on the host: count_fr [n_fake] the reals whose
+    ball holds fake i, count_rf [n_real] the fakes whose ball holds real j, nn_rf [n_real] real j's squared distance to its nearest fake,
+    r2_real [n_real] the reals' squared radii."""
+    count_fr, count_rf = np.asarray(count_fr), np.asarray(count_rf)
+    return dict(precision=float(np.mean(count_fr > 0)), recall=float(np.mean(count_rf > 0)),
+                density=float(count_fr.astype(np.float64).sum() / (float(k) * n_fake)),
+                coverage=float(np.mean(np.asarray(nn_rf) <= np.asarray(r2_real))))
+
+
+def manifold_metrics(real_bank, fake_bank, k, stream=None):
+    """k-nearest-neighbour precision and recall (Kynkäänniemi et al. 2019) and density and coverage (Naeem et al. 2020) of the fake
+    bank's rows against the real bank's.  A row's ball has the squared radius of its k-th nearest other row of its own
+    side (tg_knn_self_f32, twice); fake -> real and real -> fake queries (tg_manifold_query_f32, twice) count the balls a row falls in:
+      precision  the share of fakes inside some real ball          recall    the share of reals inside some fake ball
+      density    the real balls a fake falls in, over k, averaged   coverage  the share of reals whose nearest fake is inside their own ball
+    Every distance is the fp32 chain of include/tg_kernels.h, so the four numbers are reproducible exactly.  All NaN when either side
+    has fewer than k + 1 rows (no launch).  stream: the stream the four launches go to — the current torch stream (the default), or one
+    ordered with it: the buffers are allocated and the results copied back on the current torch stream.  Synchronises."""
+    k = check_k(k, 'manifold_metrics: k')
+    if real_bank.c != fake_bank.c:
+        raise ValueError("manifold_metrics: the banks hold features of different widths (%d, %d)" % (real_bank.c, fake_bank.c))
+    if real_bank.n < k + 1 or fake_bank.n < k + 1:
+        return dict.fromkeys(MANIFOLD_KEYS, float('nan'))
+    real, fake = real_bank.rows(), fake_bank.rows()
+    r2_real = knn_self(real, k, stream)[:, k - 1].contiguous()
+    r2_fake = knn_self(fake, k, stream)[:, k - 1].contiguous()
+    count_fr, _, _ = manifold_query(fake, real, r2_real, stream)
+    count_rf, nn_rf, _ = manifold_query(real, fake, r2_fake, stream)
+    return manifold_from_counts(k, fake_bank.n, count_fr.cpu().numpy(), count_rf.cpu().numpy(), nn_rf.cpu().numpy(), r2_real.cpu().numpy())
