@@ -362,6 +362,9 @@ int tg_seg_actgrad_shift_f32(const float* dy, int ld_dy, const float* yact, int 
  * (1-decay)*mean_s sequentially over s; eval (train = 0): shift[s][k] = b[k] - pop_mean[k]. */
 int tg_mobn_finalize_f32(const float* sums, const int32_t* seg_rows, int nseg, int rows, int c, const float* b, float* pop_mean, float decay,
                          int train, float* shift, void* stream);
+/* Host only: the number of replicas of an fp64 statistics accumulator (8) — the leading dimension of every `sums` / `dsum` scratch below
+ * that is described as "8 replicas", and the n_repl of tg_mobn_center_f32 for sums that tg_maxpool2_bwd_actsum_f32 left behind. */
+int tg_stats_replicas(void);
 /* fused tail of mean-only BN on x (in place): y = act(x - mean_seg + b) with mean_seg = sums[seg]/rows_seg (sums from
  * tg_igemm_colsum_f32; training: pop_mean <- decay*pop_mean + (1-decay)*mean_seg sequentially over the segments), or
  * y = act(x - pop_mean + b) when sums is NULL (evaluation).  c <= 512, c % 4 == 0. */

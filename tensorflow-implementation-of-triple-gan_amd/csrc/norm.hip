@@ -6,6 +6,16 @@
 //  * generic building blocks (shapes the fused paths do not take, evaluation mode): per-(segment, channel) column sums with a
 //    deterministic two-stage reduction, finalisers, shift/scale + activation passes.
 //
+// Each mechanism of the fused paths is defined once:
+//   colsum_tail      the end of every statistics workgroup: per-thread partials -> LDS -> lane 0 of each column group adds the other
+//                    row lanes in lane order -> one fp64 atomicAdd per column into replica (workgroup % REPL);
+//   repl_total       the replicas of one accumulator entry added in replica order (bn_repl, mobn_bwd_shift, repl_finalize);
+//   mobn_fwd_shift   the forward shift b - mean in LDS + the pop_mean chain (mobn_apply, mobn_apply_pool);
+//   mobn_bwd_shift   the backward shift -mean(t) in LDS + db (mobn_bwd_apply, mobn_center);
+//   seg_moments      mean and clamped biased variance of a segment from S0 / S1, in fp64;
+//   bn_moving_chain  the moving-statistics update over the segments (bn_train_apply, bn_moving_update: bit-identical by construction);
+//   bn_chunk / seg_chunks, stats_chunk   which rows a workgroup owns (device) / how many workgroups that makes and how long a chunk is (host).
+//
 // Access pattern: rows are NHWC pixels, channels contiguous; every lane moves 16 B (float4), a block's 32
 // column-groups cover 512 contiguous bytes per row, 8 rows in flight per pass.
 #include "tg_common.h"
@@ -50,6 +60,77 @@ __device__ __forceinline__ bool bn_chunk(const SegTable& st, int chunk, int bid,
   return false;
 }
 
+// The end of a statistics workgroup (256 threads).  Thread t holds K partial sums acc[] of column group t % cgn, summed over the rows of
+// row lane t / cgn: K = 4 one sum per column, K = 8 two (acc[4..7] is the second).  Lane 0 of each column group adds the lanes
+// 1 .. lanes-1 in that order, then one fp64 atomicAdd per column (column < c only) into replica blockIdx.x % REPL of the accumulator
+// sums[REPL][nslot][K/4][c], slot `slot`, columns c0 + 4 * group ...  T is the type the partials are held, exchanged and added in.
+// Threads with t / cgn >= lanes (256 is no multiple of cgn) take no part: their acc[] is stored and never read.
+template <typename T, int K>
+__device__ __forceinline__ void colsum_tail(T (&acc)[K], int cgn, int lanes, double* __restrict__ sums, int nslot, int slot, int c, int c0) {
+  static_assert(K == 4 || K == 8, "one or two sums of four columns");
+  __shared__ T red[256 * K];
+  const int cg = threadIdx.x % cgn, rl = threadIdx.x / cgn;
+#pragma unroll
+  for (int k = 0; k < K; ++k) red[threadIdx.x * K + k] = acc[k];
+  __syncthreads();
+  if (rl == 0) {
+#pragma unroll(128 / (K * sizeof(T)))                      // 32 registers of LDS reads in flight whatever T and K (more costs bn_sums a wave per SIMD)
+    for (int l = 1; l < lanes; ++l)
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] += red[(l * cgn + cg) * K + k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int col = c0 + cg * 4 + k;
+      if (col < c) {
+        double* o = sums + (((int64_t)(blockIdx.x % REPL) * nslot + slot) * (K / 4)) * c + col;
+        atomicAdd(o, (double)acc[k]);
+        if constexpr (K == 8) atomicAdd(o + c, (double)acc[4 + k]);
+      }
+    }
+  }
+}
+
+// one accumulator entry added over its replicas r = 0 .. n_repl-1, in that order: sums[r * stride + offset]
+__device__ __forceinline__ double repl_total(const double* __restrict__ sums, int n_repl, int64_t stride, int64_t offset) {
+  double t = 0.;
+  for (int r = 0; r < n_repl; ++r) t += sums[r * stride + offset];
+  return t;
+}
+
+// Forward mean-only BN, start of an apply workgroup: shift[k] = b[k] - sums[seg][k] / rows_seg (training) or b[k] - pop[k]
+// (evaluation: sums = NULL) into LDS; workgroup 0 applies the sequential pop_mean updates.  Ends with the barrier.
+__device__ __forceinline__ void mobn_fwd_shift(float* shift, const SegTable& st, int seg, int c, const double* __restrict__ sums,
+                                               const float* __restrict__ b, float* __restrict__ pop, float decay) {
+  for (int k = threadIdx.x; k < c; k += 256) {
+    const float bb = b ? b[k] : 0.f;
+    shift[k] = sums ? bb - (float)(sums[(int64_t)seg * c + k] / (double)st.rows[seg]) : bb - pop[k];
+  }
+  if (blockIdx.x == 0 && sums) {
+    for (int k = threadIdx.x; k < c; k += 256) {
+      float pm = pop[k];
+      for (int s = 0; s < st.nseg; ++s) pm = pm * decay + (float)(sums[(int64_t)s * c + k] / (double)st.rows[s]) * (1.f - decay);
+      pop[k] = pm;
+    }
+  }
+  __syncthreads();
+}
+
+// Backward mean-only BN, start of an apply workgroup: shift[k] = -(sum of t over the segment) / rows_seg into LDS from
+// sums[n_repl][nseg][c]; workgroup 0 writes db[k] = the sum over all segments, in segment order.  Ends with the barrier.
+__device__ __forceinline__ void mobn_bwd_shift(float* shift, const SegTable& st, int seg, int c, const double* __restrict__ sums, int n_repl,
+                                               float* __restrict__ db) {
+  const int64_t stride = (int64_t)st.nseg * c;
+  for (int k = threadIdx.x; k < c; k += 256) shift[k] = -(float)(repl_total(sums, n_repl, stride, (int64_t)seg * c + k) / (double)st.rows[seg]);
+  if (blockIdx.x == 0 && db) {
+    for (int k = threadIdx.x; k < c; k += 256) {
+      double t = 0.;
+      for (int s = 0; s < st.nseg; ++s) t += repl_total(sums, n_repl, stride, (int64_t)s * c + k);
+      db[k] = (float)t;
+    }
+  }
+  __syncthreads();
+}
+
 // mode: 0 SUM(a) ; 1 SUM(a), SUM(a^2) ; 2 SUM(a*act'(b)) ; 3 SUM(a), SUM(a*b) ;
 // 4 SUM((a-mu)^2) with mu[c] = b[c]*alpha (b = per-channel sums of a previous mode-0 pass, alpha = 1/rows)
 struct d4 { double x, y, z, w; };
@@ -60,17 +141,8 @@ struct d4 { double x, y, z, w; };
 template <int MODE>
 __global__ void __launch_bounds__(256) colstats_stage1(const float* __restrict__ a, const float* __restrict__ b, int ld_a, int ld_b,
                                                         int c4, SegTable st, int act, float alpha, double* __restrict__ part, int c_pad) {
-  // locate this block's chunk: (segment, row range)
-  int ch = blockIdx.y, seg = 0, base = 0;
-  for (; seg < st.nseg; ++seg) {
-    int n = (st.rows[seg] + RCH - 1) / RCH;
-    if (ch < n) break;
-    ch -= n;
-    base += st.rows[seg];
-  }
-  if (seg >= st.nseg) return;
-  const int r0 = base + ch * RCH;
-  const int r1 = min(base + st.rows[seg], r0 + RCH);
+  int seg, r0, r1;
+  if (!bn_chunk(st, RCH, blockIdx.y, &seg, &r0, &r1)) return;
   const int cg = blockIdx.x * 32 + (threadIdx.x & 31);   // float4 column group
   const int ry = threadIdx.x >> 5;
   d4 s1 = {0, 0, 0, 0}, s2 = {0, 0, 0, 0};
@@ -233,18 +305,7 @@ __global__ void __launch_bounds__(256) mobn_apply(float* __restrict__ x, int ld,
   __shared__ float shift[512];
   int seg, r0, r1;
   if (!bn_chunk(st, 32, blockIdx.x, &seg, &r0, &r1)) return;
-  for (int k = threadIdx.x; k < c; k += 256) {
-    const float bb = b ? b[k] : 0.f;
-    shift[k] = sums ? bb - (float)(sums[(int64_t)seg * c + k] / (double)st.rows[seg]) : bb - pop[k];
-  }
-  if (blockIdx.x == 0 && sums) {
-    for (int k = threadIdx.x; k < c; k += 256) {
-      float pm = pop[k];
-      for (int s = 0; s < st.nseg; ++s) pm = pm * decay + (float)(sums[(int64_t)s * c + k] / (double)st.rows[s]) * (1.f - decay);
-      pop[k] = pm;
-    }
-  }
-  __syncthreads();
+  mobn_fwd_shift(shift, st, seg, c, sums, b, pop, decay);
   const int c4 = c >> 2;
   const int rows_here = r1 - r0;
   for (int i = threadIdx.x; i < rows_here * c4; i += 256) {
@@ -273,18 +334,7 @@ __global__ void __launch_bounds__(256) mobn_apply_pool(float* __restrict__ x, in
   int seg = 0;
   int64_t acc_rows = st.rows[0];
   while (seg < st.nseg - 1 && row0 >= acc_rows) acc_rows += st.rows[++seg];
-  for (int k = threadIdx.x; k < c; k += 256) {
-    const float bb = b ? b[k] : 0.f;
-    shift[k] = sums ? bb - (float)(sums[(int64_t)seg * c + k] / (double)st.rows[seg]) : bb - pop[k];
-  }
-  if (blockIdx.x == 0 && sums) {
-    for (int k = threadIdx.x; k < c; k += 256) {
-      float pm = pop[k];
-      for (int s = 0; s < st.nseg; ++s) pm = pm * decay + (float)(sums[(int64_t)s * c + k] / (double)st.rows[s]) * (1.f - decay);
-      pop[k] = pm;
-    }
-  }
-  __syncthreads();
+  mobn_fwd_shift(shift, st, seg, c, sums, b, pop, decay);
   const int c4 = c >> 2;
   for (int i = threadIdx.x; i < wo * c4; i += 256) {
     const int ox = i / c4, cg = i - ox * c4;
@@ -323,33 +373,16 @@ __global__ void __launch_bounds__(256) mobn_bwd_sums(const float* __restrict__ d
   const int c4 = c >> 2;
   const int lanes = 256 / c4 > 0 ? 256 / c4 : 1;
   const int cg = threadIdx.x % c4, rl = threadIdx.x / c4;
-  __shared__ float4 red[256];
-  float4 acc = {0, 0, 0, 0};
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
   if (rl < lanes) {
     for (int r = r0 + rl; r < r1; r += lanes) {
       const float4 g = *reinterpret_cast<const float4*>(dy + (int64_t)r * ld_dy + cg * 4);
       const float4 yy = *reinterpret_cast<const float4*>(y + (int64_t)r * ld_y + cg * 4);
-      acc.x += g.x * tgd::act_grad(yy.x, act, alpha); acc.y += g.y * tgd::act_grad(yy.y, act, alpha);
-      acc.z += g.z * tgd::act_grad(yy.z, act, alpha); acc.w += g.w * tgd::act_grad(yy.w, act, alpha);
+      acc[0] += g.x * tgd::act_grad(yy.x, act, alpha); acc[1] += g.y * tgd::act_grad(yy.y, act, alpha);
+      acc[2] += g.z * tgd::act_grad(yy.z, act, alpha); acc[3] += g.w * tgd::act_grad(yy.w, act, alpha);
     }
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  if (rl == 0) {
-    for (int k = 1; k < lanes; ++k) {
-      const float4 t = red[k * c4 + cg];
-      acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w;
-    }
-    double* o = sums + ((int64_t)(blockIdx.x % REPL) * st.nseg + seg) * c + cg * 4;
-    atomicAdd(o, (double)acc.x); atomicAdd(o + 1, (double)acc.y); atomicAdd(o + 2, (double)acc.z); atomicAdd(o + 3, (double)acc.w);
-  }
-}
-
-__device__ __forceinline__ double repl_sum(const double* __restrict__ sums, int nseg, int seg, int c, int k) {
-  double t = 0.;
-#pragma unroll
-  for (int r = 0; r < REPL; ++r) t += sums[((int64_t)r * nseg + seg) * c + k];      // fixed order
-  return t;
+  colsum_tail(acc, c4, lanes, sums, st.nseg, seg, c, 0);
 }
 
 __global__ void __launch_bounds__(256) mobn_bwd_apply(const float* __restrict__ dy, int ld_dy, const float* __restrict__ y, int ld_y,
@@ -358,15 +391,7 @@ __global__ void __launch_bounds__(256) mobn_bwd_apply(const float* __restrict__ 
   __shared__ float shift[512];
   int seg, r0, r1;
   if (!bn_chunk(st, 32, blockIdx.x, &seg, &r0, &r1)) return;
-  for (int k = threadIdx.x; k < c; k += 256) shift[k] = -(float)(repl_sum(sums, st.nseg, seg, c, k) / (double)st.rows[seg]);
-  if (blockIdx.x == 0 && db) {
-    for (int k = threadIdx.x; k < c; k += 256) {
-      double t = 0.;
-      for (int s = 0; s < st.nseg; ++s) t += repl_sum(sums, st.nseg, s, c, k);
-      db[k] = (float)t;
-    }
-  }
-  __syncthreads();
+  mobn_bwd_shift(shift, st, seg, c, sums, REPL, db);
   const int c4 = c >> 2;
   const int rows_here = r1 - r0;
   for (int i = threadIdx.x; i < rows_here * c4; i += 256) {
@@ -382,26 +407,14 @@ __global__ void __launch_bounds__(256) mobn_bwd_apply(const float* __restrict__ 
   }
 }
 
-// dx = t - mean_seg(t) given the per-segment column sums of t (single accumulator copy, written by tg_igemm_actsum_*); db = sum of sums
+// dx = t - mean_seg(t) given the per-segment column sums of t (n_repl = 1: the single accumulator copy tg_igemm_actsum_* writes;
+// REPL: the replicas of maxpool2_bwd_actsum); db = sum of sums
 __global__ void __launch_bounds__(256) mobn_center(const float* __restrict__ t, int ld_t, float* __restrict__ dx, int ld_dx, int c, SegTable st,
                                                    const double* __restrict__ sums, int n_repl, float* __restrict__ db) {
   __shared__ float shift[512];
   int seg, r0, r1;
   if (!bn_chunk(st, 32, blockIdx.x, &seg, &r0, &r1)) return;
-  auto total = [&](int s, int k) {
-    double a = 0.;
-    for (int r = 0; r < n_repl; ++r) a += sums[((int64_t)r * st.nseg + s) * c + k];      // fixed order
-    return a;
-  };
-  for (int k = threadIdx.x; k < c; k += 256) shift[k] = -(float)(total(seg, k) / (double)st.rows[seg]);
-  if (blockIdx.x == 0 && db) {
-    for (int k = threadIdx.x; k < c; k += 256) {
-      double a = 0.;
-      for (int s = 0; s < st.nseg; ++s) a += total(s, k);
-      db[k] = (float)a;
-    }
-  }
-  __syncthreads();
+  mobn_bwd_shift(shift, st, seg, c, sums, n_repl, db);
   const int c4 = c >> 2;
   const int rows_here = r1 - r0;
   for (int i = threadIdx.x; i < rows_here * c4; i += 256) {
@@ -425,7 +438,6 @@ __global__ void __launch_bounds__(256) maxpool2_bwd_actsum(const float* __restri
   const int c4 = c >> 2;
   const int lanes = 256 / c4 > 0 ? 256 / c4 : 1;
   const int cg = threadIdx.x % c4, rl = threadIdx.x / c4;
-  __shared__ float4 red[256];
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   if (rl < lanes) {
     for (int pp = r0 + rl; pp < r1; pp += lanes) {
@@ -461,16 +473,7 @@ __global__ void __launch_bounds__(256) maxpool2_bwd_actsum(const float* __restri
       for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(t + pos[q] * ld_t + cg * 4) = make_float4(o[q][0], o[q][1], o[q][2], o[q][3]);
     }
   }
-  red[threadIdx.x] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-  __syncthreads();
-  if (rl == 0) {
-    for (int k = 1; k < lanes; ++k) {
-      const float4 v = red[k * c4 + cg];
-      acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w;
-    }
-    double* o = sums + ((int64_t)(blockIdx.x % REPL) * st.nseg + seg) * c + cg * 4;
-    atomicAdd(o, (double)acc[0]); atomicAdd(o + 1, (double)acc[1]); atomicAdd(o + 2, (double)acc[2]); atomicAdd(o + 3, (double)acc[3]);
-  }
+  colsum_tail(acc, c4, lanes, sums, st.nseg, seg, c, 0);
 }
 
 // dpre = dy * act'(yact) (pad columns zeroed up to ld_out) AND its column sums (the bias gradient of a plain conv / transposed conv /
@@ -483,7 +486,6 @@ __global__ void __launch_bounds__(256) actgrad_bias(const float* __restrict__ dy
   const int g4 = ld_out >> 2;                         // column groups of the output row (covers the padding)
   const int lanes = 256 / g4 > 0 ? 256 / g4 : 1;
   const int cg = threadIdx.x % g4, rl = threadIdx.x / g4;
-  __shared__ float4 red[256];
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   const bool vec = (c & 3) == 0 && (ld_dy & 3) == 0 && (!y || (ld_y & 3) == 0);
   if (rl < lanes) {
@@ -515,26 +517,13 @@ __global__ void __launch_bounds__(256) actgrad_bias(const float* __restrict__ dy
       *reinterpret_cast<float4*>(out + (int64_t)r * ld_out + cg * 4) = make_float4(v[0], v[1], v[2], v[3]);
     }
   }
-  red[threadIdx.x] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-  __syncthreads();
-  if (rl == 0) {
-    for (int k = 1; k < lanes; ++k) {
-      const float4 t = red[k * g4 + cg];
-      acc[0] += t.x; acc[1] += t.y; acc[2] += t.z; acc[3] += t.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (cg * 4 + k < c) atomicAdd(sums + (int64_t)(blockIdx.x % REPL) * c + cg * 4 + k, (double)acc[k]);
-  }
+  colsum_tail(acc, g4, lanes, sums, 1, 0, c, 0);
 }
 
 __global__ void repl_finalize(const double* __restrict__ sums, int c, float* __restrict__ out) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= c) return;
-  double t = 0.;
-#pragma unroll
-  for (int r = 0; r < REPL; ++r) t += sums[(int64_t)r * c + k];
-  out[k] = (float)t;
+  out[k] = (float)repl_total(sums, REPL, c, k);
 }
 
 __global__ void mobn_finalize(const float* __restrict__ sums, SegTable st, int c, const float* __restrict__ b, float* __restrict__ pop, float decay,
@@ -635,7 +624,7 @@ __global__ void __launch_bounds__(256) bn_sums(const float* __restrict__ a, int 
   const int cgn = min((c - c0 + 3) / 4, BN_CW / 4);          // column groups of this block
   const int lanes = 256 / cgn;
   const int cg = threadIdx.x % cgn, rl = threadIdx.x / cgn;
-  double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+  double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};                   // S0 of four columns, then S1
   if (rl < lanes) {
     for (int r = r0 + rl; r < r1; r += lanes) {
       const float4 av = *reinterpret_cast<const float4*>(a + (int64_t)r * ld_a + c0 + cg * 4);
@@ -644,42 +633,51 @@ __global__ void __launch_bounds__(256) bn_sums(const float* __restrict__ a, int 
         const float4 bv = *reinterpret_cast<const float4*>(b + (int64_t)r * ld_b + c0 + cg * 4);
         const float bs[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { s0[k] += (double)as[k]; s1[k] += (double)as[k] * (double)bs[k]; }
+        for (int k = 0; k < 4; ++k) { acc[k] += (double)as[k]; acc[4 + k] += (double)as[k] * (double)bs[k]; }
       } else {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { s0[k] += (double)as[k]; s1[k] += (double)as[k] * (double)as[k]; }
+        for (int k = 0; k < 4; ++k) { acc[k] += (double)as[k]; acc[4 + k] += (double)as[k] * (double)as[k]; }
       }
     }
   }
-  __shared__ double red[256 * 8];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { red[threadIdx.x * 8 + k] = s0[k]; red[threadIdx.x * 8 + 4 + k] = s1[k]; }
-  __syncthreads();
-  if (rl == 0) {
-    for (int l = 1; l < lanes; ++l)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { s0[k] += red[(l * cgn + cg) * 8 + k]; s1[k] += red[(l * cgn + cg) * 8 + 4 + k]; }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int col = c0 + cg * 4 + k;
-      if (col < c) {
-        double* o = sums + (((int64_t)(blockIdx.x % REPL) * st.nseg + seg) * 2) * c + col;
-        atomicAdd(o, s0[k]);
-        atomicAdd(o + c, s1[k]);
-      }
-    }
-  }
+  colsum_tail(acc, cgn, lanes, sums, st.nseg, seg, c, c0);
 }
 
-// S0 / S1 of (segment, column) summed over the replicas (layout [REPL][nseg][2][c]); fixed order
+// S0 / S1 of (segment, column), each summed over the replicas (layout [REPL][nseg][2][c])
 __device__ __forceinline__ void bn_repl(const double* __restrict__ sums, int nseg, int seg, int c, int col, double* s0, double* s1) {
-  double a = 0., b = 0.;
-#pragma unroll
-  for (int r = 0; r < REPL; ++r) {
-    const double* o = sums + (((int64_t)r * nseg + seg) * 2) * c + col;
-    a += o[0]; b += o[c];
+  const int64_t stride = (int64_t)nseg * 2 * c, o = (int64_t)seg * 2 * c + col;
+  *s0 = repl_total(sums, REPL, stride, o);
+  *s1 = repl_total(sums, REPL, stride, o + c);
+}
+
+// mean and clamped biased variance of (segment, column) from S0 = sum x, S1 = sum x^2, in fp64 (variance = S1/n - mean^2: no cancellation problem)
+__device__ __forceinline__ void seg_moments(const double* __restrict__ sums, const SegTable& st, int seg, int c, int col, double* mu, double* var) {
+  const double n = (double)st.rows[seg];
+  double q0, q1;
+  bn_repl(sums, st.nseg, seg, c, col, &q0, &q1);
+  const double m = q0 / n;
+  const double v = q1 / n - m * m;
+  *mu = m;
+  *var = v > 0. ? v : 0.;
+}
+
+// The moving statistics of one column updated over the segments in order (= call-site order of the applications), with the Bessel-corrected
+// variance as the fused TF op.  mm == NULL: no moving statistics; mean_inv != NULL: also the per-segment mean / inv-std for the backward pass.
+__device__ __forceinline__ void bn_moving_chain(const double* __restrict__ sums, const SegTable& st, int c, int col, float decay, float* __restrict__ mm,
+                                                float* __restrict__ mv, float eps, float* __restrict__ mean_inv) {
+  float m_run = mm ? mm[col] : 0.f, v_run = mm ? mv[col] : 0.f;
+  for (int s = 0; s < st.nseg; ++s) {
+    double mu, var;
+    seg_moments(sums, st, s, c, col, &mu, &var);
+    if (mean_inv) {
+      mean_inv[((int64_t)s * 2) * c + col] = (float)mu;
+      mean_inv[((int64_t)s * 2 + 1) * c + col] = 1.f / sqrtf((float)var + eps);
+    }
+    const float vb = st.rows[s] > 1 ? (float)var * ((float)st.rows[s] / (float)(st.rows[s] - 1)) : (float)var;
+    m_run = m_run * decay + (float)mu * (1.f - decay);
+    v_run = v_run * decay + vb * (1.f - decay);
   }
-  *s0 = a; *s1 = b;
+  if (mm) { mm[col] = m_run; mv[col] = v_run; }
 }
 
 // y = x * scale + shift of four columns: the one expression both output types of bn_train_apply store (same FMA contraction)
@@ -708,12 +706,8 @@ __global__ void __launch_bounds__(256) bn_train_apply(const float* __restrict__ 
     float a = 0.f, b = 0.f;
     if (k < ncol) {
       const int col = c0 + k;
-      const double n = (double)st.rows[seg];
-      double q0, q1;
-      bn_repl(sums, st.nseg, seg, c, col, &q0, &q1);
-      const double mu = q0 / n;
-      double var = q1 / n - mu * mu;
-      var = var > 0. ? var : 0.;
+      double mu, var;
+      seg_moments(sums, st, seg, c, col, &mu, &var);
       const float inv = 1.f / sqrtf((float)var + eps);
       a = gamma[col] * inv;
       b = beta[col] - (float)mu * a;
@@ -722,24 +716,7 @@ __global__ void __launch_bounds__(256) bn_train_apply(const float* __restrict__ 
   }
   // first workgroup of this column block: per-segment mean / inv-std for the backward pass, moving statistics in segment order
   if (blockIdx.x == 0) {
-    for (int k = threadIdx.x; k < ncol; k += 256) {
-      const int col = c0 + k;
-      float m_run = mm ? mm[col] : 0.f, v_run = mv ? mv[col] : 0.f;
-      for (int s = 0; s < st.nseg; ++s) {
-        const double n = (double)st.rows[s];
-        double q0, q1;
-        bn_repl(sums, st.nseg, s, c, col, &q0, &q1);
-        const double mu = q0 / n;
-        double var = q1 / n - mu * mu;
-        var = var > 0. ? var : 0.;
-        mean_inv[((int64_t)s * 2) * c + col] = (float)mu;
-        mean_inv[((int64_t)s * 2 + 1) * c + col] = 1.f / sqrtf((float)var + eps);
-        const float vb = st.rows[s] > 1 ? (float)var * ((float)st.rows[s] / (float)(st.rows[s] - 1)) : (float)var;   // Bessel, as the fused TF op
-        m_run = m_run * decay + (float)mu * (1.f - decay);
-        v_run = v_run * decay + vb * (1.f - decay);
-      }
-      if (mm) { mm[col] = m_run; mv[col] = v_run; }
-    }
+    for (int k = threadIdx.x; k < ncol; k += 256) bn_moving_chain(sums, st, c, c0 + k, decay, mm, mv, eps, mean_inv);
   }
   __syncthreads();
   const int cgn = (ncol + 3) / 4;
@@ -758,24 +735,12 @@ __global__ void __launch_bounds__(256) bn_train_apply(const float* __restrict__ 
   }
 }
 
-// the moving-statistics chain of bn_train_apply alone (same arithmetic, same order), from the sums a forward launch left behind
+// the moving-statistics chain of bn_train_apply alone (the same bn_moving_chain), from the sums a forward launch left behind
 __global__ void __launch_bounds__(256) bn_moving_update(const double* __restrict__ sums, int c, SegTable st, float decay, float* __restrict__ mm,
                                                         float* __restrict__ mv) {
   const int col = blockIdx.x * 256 + threadIdx.x;
   if (col >= c) return;
-  float m_run = mm[col], v_run = mv[col];
-  for (int s = 0; s < st.nseg; ++s) {
-    const double n = (double)st.rows[s];
-    double q0, q1;
-    bn_repl(sums, st.nseg, s, c, col, &q0, &q1);
-    const double mu = q0 / n;
-    double var = q1 / n - mu * mu;
-    var = var > 0. ? var : 0.;
-    const float vb = st.rows[s] > 1 ? (float)var * ((float)st.rows[s] / (float)(st.rows[s] - 1)) : (float)var;
-    m_run = m_run * decay + (float)mu * (1.f - decay);
-    v_run = v_run * decay + vb * (1.f - decay);
-  }
-  mm[col] = m_run; mv[col] = v_run;
+  bn_moving_chain(sums, st, c, col, decay, mm, mv, 0.f, nullptr);
 }
 
 __global__ void __launch_bounds__(256) bn_train_bwd_apply(const float* __restrict__ dy, int ld_dy, const float* __restrict__ x, int ld_x,
@@ -841,23 +806,7 @@ __global__ void __launch_bounds__(256) bn_train_bwd_apply(const float* __restric
     }
     *reinterpret_cast<float4*>(dx + (int64_t)(r0 + rr) * ld_dx + c0 + cg * 4) = make_float4(v[0], v[1], v[2], v[3]);
   }
-  if (dsum != nullptr) {
-    __shared__ double red[256 * 4];
-    const int cg = threadIdx.x % cgn, rl = threadIdx.x / cgn, lanes = 256 / cgn;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) red[threadIdx.x * 4 + k] = cs[k];
-    __syncthreads();
-    if (rl == 0) {
-      for (int l = 1; l < lanes; ++l)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) cs[k] += red[(l * cgn + cg) * 4 + k];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int col = c0 + cg * 4 + k;
-        if (col < c) atomicAdd(dsum + (int64_t)(blockIdx.x % REPL) * c + col, cs[k]);
-      }
-    }
-  }
+  if (dsum != nullptr) colsum_tail(cs, cgn, 256 / cgn, dsum, 1, 0, c, c0);
 }
 
 int make_segs(SegTable& st, const int32_t* seg_rows, int nseg, int rows) {
@@ -869,10 +818,34 @@ int make_segs(SegTable& st, const int32_t* seg_rows, int nseg, int rows) {
   return TG_OK;
 }
 
-int num_chunks(const SegTable& st) {
+// workgroups of a launch whose workgroups walk `chunk` rows of one segment each (the host side of bn_chunk)
+int seg_chunks(const SegTable& st, int chunk) {
   int n = 0;
-  for (int i = 0; i < st.nseg; ++i) n += (st.rows[i] + RCH - 1) / RCH;
+  for (int s = 0; s < st.nseg; ++s) n += (st.rows[s] + chunk - 1) / chunk;
   return n;
+}
+
+int num_chunks(const SegTable& st) { return seg_chunks(st, RCH); }
+
+// Row-chunk size of the statistics launches: ~2 048 workgroups over all rows for a large tensor (a streaming pass needs
+// many waves in flight), never less than 32 rows.  Every workgroup ends with one fp64 atomic per column into replica
+// (workgroup % REPL) of the accumulator: <= 64 same-address adds per replica and segment, a tail of a few microseconds.
+int stats_chunk(int64_t rows) {
+  const int ch = (int)(((rows + 2047) / 2048 + 31) / 32 * 32);
+  return ch < 32 ? 32 : ch;
+}
+
+int stats_chunk(const SegTable& st) {
+  int64_t tot = 0;
+  for (int s = 0; s < st.nseg; ++s) tot += st.rows[s];
+  return stats_chunk(tot);
+}
+
+// clears a statistics accumulator unless the caller says it already is (the statistics arena of tg/runtime.py)
+int zero_unless(double* sums, size_t bytes, int zeroed, hipStream_t s, const char* what) {
+  if (zeroed) return TG_OK;
+  hipError_t e = hipMemsetAsync(sums, 0, bytes, s);
+  return e == hipSuccess ? TG_OK : tg::hip_fail(e, what);
 }
 
 int ew_grid(int64_t work) {
@@ -971,14 +944,10 @@ int tg_colstats_f32(int mode, const float* a, int ld_a, const float* b, int ld_b
   dim3 grid((c4 + 31) / 32, num_chunks(st));
   TG_REQUIRE((uintptr_t)workspace % 8 == 0, "colstats: workspace must be 8-byte aligned");
   double* wsd = reinterpret_cast<double*>(workspace);
-  switch (mode) {
-    case 0: hipLaunchKernelGGL(colstats_stage1<0>, grid, dim3(256), 0, s, a, b, ld_a, ld_b, c4, st, act, alpha, wsd, c_pad); break;
-    case 1: hipLaunchKernelGGL(colstats_stage1<1>, grid, dim3(256), 0, s, a, b, ld_a, ld_b, c4, st, act, alpha, wsd, c_pad); break;
-    case 2: hipLaunchKernelGGL(colstats_stage1<2>, grid, dim3(256), 0, s, a, b, ld_a, ld_b, c4, st, act, alpha, wsd, c_pad); break;
-    case 3: hipLaunchKernelGGL(colstats_stage1<3>, grid, dim3(256), 0, s, a, b, ld_a, ld_b, c4, st, act, alpha, wsd, c_pad); break;
-    case 4: hipLaunchKernelGGL(colstats_stage1<4>, grid, dim3(256), 0, s, a, b, ld_a, ld_b, c4, st, act, alpha, wsd, c_pad); break;
-    default: tg::set_error("colstats: bad mode %d", mode); return TG_ERR_INVALID;
-  }
+  static constexpr decltype(&colstats_stage1<0>) stage1[] = {colstats_stage1<0>, colstats_stage1<1>, colstats_stage1<2>, colstats_stage1<3>,
+                                                             colstats_stage1<4>};
+  TG_REQUIRE(mode >= 0 && mode < 5, "colstats: bad mode %d", mode);
+  hipLaunchKernelGGL(stage1[mode], grid, dim3(256), 0, s, a, b, ld_a, ld_b, c4, st, act, alpha, wsd, c_pad);
   TG_CHECK_LAUNCH("colstats_stage1");
   hipLaunchKernelGGL(colstats_stage2, dim3((c + 31) / 32, nseg), dim3(256), 0, s, wsd, st, c_pad, c, s1, s2);
   TG_CHECK_LAUNCH("colstats_stage2");
@@ -1042,21 +1011,7 @@ int tg_mobn_finalize_f32(const float* sums, const int32_t* seg_rows, int nseg, i
   return TG_OK;
 }
 
-// Row-chunk size of the statistics launches: ~2 048 workgroups over all segments for a large tensor (a streaming pass needs
-// many waves in flight), never less than 32 rows.  Every workgroup ends with one fp64 atomic per column into replica
-// (workgroup % REPL) of the accumulator: <= 64 same-address adds per replica and segment, a tail of a few microseconds.
-static int stats_chunk(const SegTable& st) {
-  int64_t tot = 0;
-  for (int s = 0; s < st.nseg; ++s) tot += st.rows[s];
-  int ch = (int)(((tot + 2047) / 2048 + 31) / 32 * 32);
-  return ch < 32 ? 32 : ch;
-}
-
-static int seg_chunks(const SegTable& st, int chunk) {
-  int n = 0;
-  for (int s = 0; s < st.nseg; ++s) n += (st.rows[s] + chunk - 1) / chunk;
-  return n;
-}
+int tg_stats_replicas(void) { return REPL; }
 
 int tg_mobn_apply_f32(float* x, int ld, int rows, int c, const int32_t* seg_rows, int nseg, const double* sums, const float* b, float* pop_mean,
                       float decay, int act, float alpha, void* stream) {
@@ -1100,10 +1055,8 @@ int tg_mobn_bwd_f32(const float* dy, int ld_dy, const float* yact, int ld_y, flo
   TG_REQUIRE(c > 0 && c <= 512 && c % 4 == 0 && ld_dy % 4 == 0 && ld_y % 4 == 0 && ld_dx % 4 == 0 && c <= ld_dy && c <= ld_y && c <= ld_dx,
              "mobn_bwd: c=%d vs ld unsupported", c);
   hipStream_t s = tg::as_stream(stream);
-  if (!sums_zeroed) {
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * REPL * nseg * c, s);
-    if (e != hipSuccess) return tg::hip_fail(e, "hipMemsetAsync(mobn_bwd sums)");
-  }
+  rc = zero_unless(sums, sizeof(double) * REPL * nseg * c, sums_zeroed, s, "hipMemsetAsync(mobn_bwd sums)");
+  if (rc != TG_OK) return rc;
   tg::ProfScope prof(tg::PC_NORM, 0, 20.0 * rows * c, s);
   const int chunk = stats_chunk(st);                             // <= 128 workgroups per segment (atomic tail, see stats_chunk)
   hipLaunchKernelGGL(mobn_bwd_sums, dim3(seg_chunks(st, chunk)), dim3(256), 0, s, dy, ld_dy, yact, ld_y, rows, c, st, act, alpha, sums, chunk);
@@ -1138,10 +1091,8 @@ int tg_maxpool2_bwd_actsum_f32(const float* dout, int ld_do, const float* mask, 
   if (rc != TG_OK) return rc;
   for (int i = 0; i < nseg; ++i) { TG_REQUIRE(st.rows[i] % (h * w) == 0, "maxpool2_bwd_actsum: segment %d is not whole images", i); st.rows[i] /= 4; }
   hipStream_t s = tg::as_stream(stream);
-  if (!sums_zeroed) {
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * REPL * nseg * c, s);
-    if (e != hipSuccess) return tg::hip_fail(e, "hipMemsetAsync(maxpool2_bwd_actsum sums)");
-  }
+  rc = zero_unless(sums, sizeof(double) * REPL * nseg * c, sums_zeroed, s, "hipMemsetAsync(maxpool2_bwd_actsum sums)");
+  if (rc != TG_OK) return rc;
   tg::ProfScope prof(tg::PC_ELEMWISE, 0, 4.0 * n * h * w * c * 2.5, s);
   const int chunk = stats_chunk(st);
   hipLaunchKernelGGL(maxpool2_bwd_actsum, dim3(seg_chunks(st, chunk)), dim3(256), 0, s, dout, ld_do, mask, ld_mask, mscale, y, ld_y, t, ld_t, h, w, c, st,
@@ -1155,13 +1106,10 @@ int tg_actgrad_bias_f32(const float* dy, int ld_dy, const float* yact, int ld_y,
   TG_REQUIRE(dy && out && sums && bias_grad && rows > 0 && c > 0, "actgrad_bias: bad args");
   TG_REQUIRE(c <= ld_dy && c <= ld_out && (!yact || c <= ld_y) && ld_out % 4 == 0 && ld_out <= 1024, "actgrad_bias: c=%d ld_out=%d unsupported", c, ld_out);
   hipStream_t s = tg::as_stream(stream);
-  if (!sums_zeroed) {
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * REPL * c, s);
-    if (e != hipSuccess) return tg::hip_fail(e, "hipMemsetAsync(actgrad_bias sums)");
-  }
+  const int rc = zero_unless(sums, sizeof(double) * REPL * c, sums_zeroed, s, "hipMemsetAsync(actgrad_bias sums)");
+  if (rc != TG_OK) return rc;
   tg::ProfScope prof(tg::PC_ELEMWISE, 0, 4.0 * rows * (ld_out + 2 * c), s);
-  int chunk = ((rows + 2047) / 2048 + 31) / 32 * 32;
-  if (chunk < 32) chunk = 32;
+  const int chunk = stats_chunk((int64_t)rows);
   hipLaunchKernelGGL(actgrad_bias, dim3((rows + chunk - 1) / chunk), dim3(256), 0, s, dy, ld_dy, yact, ld_y, out, ld_out, rows, c, act, alpha, chunk, sums);
   TG_CHECK_LAUNCH("actgrad_bias");
   hipLaunchKernelGGL(repl_finalize, dim3((c + 255) / 256), dim3(256), 0, s, sums, c, bias_grad);
@@ -1181,13 +1129,9 @@ int tg_mobn_bwd_finalize_f32(const float* sums, const int32_t* seg_rows, int nse
   return TG_OK;
 }
 
-static int bn_grid(const SegTable& st, int rows, int c, int* chunk, dim3* grid) {
-  const int ch = stats_chunk(st);
-  int n = 0;
-  for (int s = 0; s < st.nseg; ++s) n += (st.rows[s] + ch - 1) / ch;
-  *chunk = ch;
-  *grid = dim3(n, (c + BN_CW - 1) / BN_CW);
-  return TG_OK;
+static void bn_grid(const SegTable& st, int c, int* chunk, dim3* grid) {
+  *chunk = stats_chunk(st);
+  *grid = dim3(seg_chunks(st, *chunk), (c + BN_CW - 1) / BN_CW);
 }
 
 static int bn_train_impl(const float* x, int ld_x, void* y, int ld_y, int rows, int c, const int32_t* seg_rows, int nseg, const float* gamma,
@@ -1202,13 +1146,11 @@ static int bn_train_impl(const float* x, int ld_x, void* y, int ld_y, int rows, 
   TG_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), "%s: moving_mean / moving_var must both be given or both be NULL", what);
   TG_REQUIRE(!y16 || (reinterpret_cast<uintptr_t>(y) & 7) == 0, "%s: y must be 8-byte aligned", what);
   hipStream_t s = tg::as_stream(stream);
-  if (stats && !sums_zeroed) {
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * REPL * 2 * nseg * c, s);
-    if (e != hipSuccess) return tg::hip_fail(e, "hipMemsetAsync(bn sums)");
-  }
+  rc = zero_unless(sums, sizeof(double) * REPL * 2 * nseg * c, !stats || sums_zeroed, s, "hipMemsetAsync(bn sums)");
+  if (rc != TG_OK) return rc;
   tg::ProfScope prof(tg::PC_NORM, 0, ((stats ? 8.0 : 4.0) + (y16 ? 2.0 : 4.0)) * rows * c, s);
   int chunk; dim3 grid;
-  bn_grid(st, rows, c, &chunk, &grid);
+  bn_grid(st, c, &chunk, &grid);
   if (stats) {
     hipLaunchKernelGGL(bn_sums<false>, grid, dim3(256), 0, s, x, ld_x, (const float*)nullptr, 0, c, st, chunk, sums);
     TG_CHECK_LAUNCH("bn_sums");
@@ -1297,17 +1239,12 @@ static int bn_train_bwd_impl(const float* dy, int ld_dy, const float* x, int ld_
   TG_REQUIRE(c > 0 && ld_dy % 4 == 0 && ld_x % 4 == 0 && ld_dx % 4 == 0 && cp <= ld_dy && cp <= ld_x && cp <= ld_dx, "bn_train_bwd: c=%d vs ld", c);
   hipStream_t s = tg::as_stream(stream);
   const bool sums_given = sums_zeroed == 2;               // the launch that produced dy took the statistics in its epilogue (tg_igemm_bnbwdstat_*)
-  if (!sums_zeroed) {
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * REPL * 2 * nseg * c, s);
-    if (e != hipSuccess) return tg::hip_fail(e, "hipMemsetAsync(bn bwd sums)");
-  }
-  if (dsum && !dsum_zeroed) {
-    hipError_t e = hipMemsetAsync(dsum, 0, sizeof(double) * REPL * c, s);
-    if (e != hipSuccess) return tg::hip_fail(e, "hipMemsetAsync(bn bwd bias sums)");
-  }
+  rc = zero_unless(sums, sizeof(double) * REPL * 2 * nseg * c, sums_zeroed, s, "hipMemsetAsync(bn bwd sums)");
+  if (rc == TG_OK) rc = zero_unless(dsum, sizeof(double) * REPL * c, !dsum || dsum_zeroed, s, "hipMemsetAsync(bn bwd bias sums)");
+  if (rc != TG_OK) return rc;
   tg::ProfScope prof(tg::PC_NORM, 0, 20.0 * rows * c, s);
   int chunk; dim3 grid;
-  bn_grid(st, rows, c, &chunk, &grid);
+  bn_grid(st, c, &chunk, &grid);
   if (!sums_given) {
     hipLaunchKernelGGL(bn_sums<true>, grid, dim3(256), 0, s, dy, ld_dy, x, ld_x, c, st, chunk, sums);
     TG_CHECK_LAUNCH("bn_sums<bwd>");

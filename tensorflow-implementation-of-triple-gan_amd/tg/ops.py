@@ -44,6 +44,16 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+STATS_REPLICAS = 8          # replicas of an fp64 statistics accumulator = tg_stats_replicas() (csrc/norm.hip REPL; tests/test_cabi.py)
+
+
+def _sums64(cx, tag, nseg, c, pair=False, replicas=True):
+    """(tensor, zeroed) of Context.zscratch for the fp64 accumulators [replicas][nseg][2 if pair][c] of a statistics launch: one sum per
+    (segment, column), or a pair (S0, S1: batch norm); replicas=False: the single copy an igemm epilogue adds to."""
+    doubles = (STATS_REPLICAS if replicas else 1) * nseg * (2 if pair else 1) * c
+    return cx.zscratch(tag, 2 * doubles)
+
+
 def fill(t, value):
     """t[:] = value on the context's stream."""
     _call('tg_fill_f32', _p(t), float(value), t.numel(), ctx().stream)
@@ -204,7 +214,7 @@ def _fwd_colsum(cx, L):
     """convolution + per-(application, channel) sums in one launch, then ONE apply pass (mean, +b, activation, pop_mean [, 2x2 pool: returned])"""
     x, y, seg_rows, c_out = L.x, L.y, L.seg_rows, L.c_out
     b, b_grad, pop = L.mobn
-    sums, zd = cx.zscratch('cs64', 2 * len(seg_rows) * c_out)     # fp64 accumulators
+    sums, zd = _sums64(cx, 'cs64', len(seg_rows), c_out, replicas=False)
     _call('tg_igemm_colsum_f32', L.d, x.ptr, _p(L.w_oti), y.ptr, seg_array(seg_rows), len(seg_rows), _p(sums), zd, cx.stream)
     if L.pool is not None and y.h % 2 == 0 and y.w % 2 == 0 and all(r % (y.h * y.w) == 0 for r in seg_rows):
         pooled = cx.new_act(y.n, y.h // 2, y.w // 2, c_out, L.co_p, requires_grad=L.needs_w or L.needs_x)
@@ -217,7 +227,7 @@ def _fwd_colsum(cx, L):
 
 def _fwd_bnstat(cx, L):
     seg_rows = L.seg_rows
-    bsum, zd = cx.zscratch('bn64', 32 * len(seg_rows) * L.c_out)     # the batch norm's buffer: 8 replicas x nseg x 2 x c doubles
+    bsum, zd = _sums64(cx, 'bn64', len(seg_rows), L.c_out, pair=True)     # the batch norm's buffer
     _call('tg_igemm_bnstat_bf16in_bf16' if L.x16 else 'tg_igemm_bnstat_f32', L.d, L.x.ptr, _p(L.w_oti), _p(L.bias), L.y.ptr, seg_array(seg_rows),
           len(seg_rows), _p(bsum), zd, cx.stream)
     L.y.bn_sums = (bsum, tuple(seg_rows))
@@ -260,7 +270,7 @@ def _dpre_plain(cx, y, gy, act, alpha, c_out, co_p, bias_grad, head=False):
         return gy.t
     dpre = cx.scratch('dpre', y.rows * co_p)
     if bias_grad is not None and co_p <= 1024:
-        zs, zd = cx.zscratch('ab64', 16 * c_out)
+        zs, zd = _sums64(cx, 'ab64', 1, c_out)
         _call('tg_actgrad_bias_f32', gy.ptr, gy.ld, y.ptr if act else None, y.ld, _p(dpre), co_p, y.rows, c_out, ACT[act], alpha,
               _p(zs), zd, _p(bias_grad), cx.stream)
     else:
@@ -282,7 +292,7 @@ def _dpre_mobn(cx, L, gy):
               y.grad_fused[1], _p(db), cx.stream)
     elif L.narrow_mobn:
         db = L.mobn[1] if L.needs_w else cx.scratch('db', c_out)
-        sums64, zd = cx.zscratch('bs64', 16 * nseg * c_out)     # 8 replicas x nseg x c doubles
+        sums64, zd = _sums64(cx, 'bs64', nseg, c_out)
         _call('tg_mobn_bwd_f32', gy.ptr, gy.ld, y.ptr, y.ld, _p(dpre), co_p, y.rows, c_out, seg_array(seg_rows), nseg,
               ACT[L.act], L.alpha, _p(sums64), zd, _p(db), cx.stream)
     else:
@@ -306,7 +316,7 @@ def _input_grad(cx, L, dpre):
         # x is the output of a mean-only-BN layer: this launch also applies that layer's activation derivative and sums the
         # columns per application, so its backward pass needs no statistics pass of its own (tg_mobn_center_f32)
         nsg = len(sink[2])
-        gsum, zd = cx.zscratch('gs64', 2 * nsg * ci_p)
+        gsum, zd = _sums64(cx, 'gs64', nsg, ci_p, replicas=False)
         _call('tg_igemm_actsum_f32', dlist[0], _p(dpre), _p(L.w_hwio), x.ptr, ACT[sink[0]], sink[1], gx.ptr, seg_array(sink[2]), nsg,
               _p(gsum), zd, cx.stream)
         x.grad_fused = (gsum, 1)
@@ -316,7 +326,7 @@ def _input_grad(cx, L, dpre):
         # statistics (sum dy, sum dy * its input) are taken in this epilogue; batch_norm_train's backward checks that nothing else
         # contributed before it trusts them
         bn_in, segs = bsink
-        bsums, zdb = cx.zscratch('bnb64', 32 * len(segs) * ci_p)
+        bsums, zdb = _sums64(cx, 'bnb64', len(segs), ci_p, pair=True)
         _call('tg_igemm_bnbwdstat_f32', dlist[0], _p(dpre), _p(L.w_hwio), bn_in.ptr, gx.ptr, seg_array(segs), len(segs), _p(bsums), zdb, cx.stream)
         x.bn_bwd_sums = (bsums, gx)
     else:
@@ -559,7 +569,7 @@ def batch_norm_train(x, gamma, beta, mm, mv, eps, decay, gamma_grad=None, beta_g
         _call('tg_bn_train_apply_' + sfx, x.ptr, x.ld, y.ptr, y.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(beta), eps, decay, _p(mm), _p(mv),
               _p(sums), _p(mean_inv), cx.stream)
     else:
-        sums, zd = cx.zscratch('bn64', 32 * nseg * c)         # 8 replicas x 2 x nseg x c doubles
+        sums, zd = _sums64(cx, 'bn64', nseg, c, pair=True)
         _call('tg_bn_train_' + sfx, x.ptr, x.ld, y.ptr, y.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(beta), eps, decay, _p(mm), _p(mv),
               _p(sums), zd, _p(mean_inv), cx.stream)
     if cx.state_replay is not None and mm is not None:
@@ -581,13 +591,13 @@ def batch_norm_train(x, gamma, beta, mm, mv, eps, decay, gamma_grad=None, beta_g
         if y.bn_bwd_sums is not None and y.bn_bwd_sums[1] is gy and gy.contribs == 1:
             bsums, zdb = y.bn_bwd_sums[0], 2                # the launch that produced gy took the statistics in its epilogue (tg_igemm_bnbwdstat_*)
         else:
-            bsums, zdb = cx.zscratch('bnb64', 32 * nseg * c)
+            bsums, zdb = _sums64(cx, 'bnb64', nseg, c, pair=True)
         sink = x.bias_sink
         if sink is not None and x.ld == gx.ld and c % 4 == 0 and (c <= 256 and 256 % (c // 4) == 0 or c % 256 == 0):
             # x = act(conv + bias) of the layer in front (Act.bias_sink): this pass also multiplies by act'(x) and sums the columns — gx IS
             # that layer's pre-activation gradient and its bias gradient is done (no tg_actgrad_bias_f32 pass over the activation)
             act_, alpha_, bias_grad_ = sink
-            dsum, zds = cx.zscratch('bnd64', 16 * c)                # 8 replicas x c doubles
+            dsum, zds = _sums64(cx, 'bnd64', 1, c)
             _call('tg_bn_train_bwd_act_f32', gy.ptr, gy.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(mean_inv),
                   ACT[act_], alpha_, _p(bsums), zdb, _p(gamma_grad) if want else None, _p(beta_grad) if want else None, _p(dsum), zds,
                   _p(bias_grad_), cx.stream)
@@ -701,10 +711,10 @@ def _record_maxpool_bwd(cx, y, out, mask_t, mscale):
                     and all(r % (y.h * y.w) == 0 for r in sink[2])):
                 # y is the output of a mean-only-BN layer: route, multiply by its activation derivative and sum the columns in one pass
                 nsg = len(sink[2])
-                gsum, zd = cx.zscratch('ps64', 16 * nsg * y.c)
+                gsum, zd = _sums64(cx, 'ps64', nsg, y.c)
                 _call('tg_maxpool2_bwd_actsum_f32', out.grad.ptr, out.grad.ld, _p(mask_t), y.c, mscale, y.ptr, y.ld, gy.ptr, gy.ld, y.n, y.h, y.w,
                       y.c, seg_array(sink[2]), nsg, ACT[sink[0]], sink[1], _p(gsum), zd, cx.stream)
-                y.grad_fused = (gsum, 8)
+                y.grad_fused = (gsum, STATS_REPLICAS)
             else:
                 _call('tg_maxpool2_bwd_f32', out.grad.ptr, out.grad.ld, _p(mask_t), y.c, mscale, y.ptr, y.ld, gy.ptr, gy.ld, y.n, y.h, y.w,
                       y.c, cx.stream)

@@ -101,6 +101,13 @@ def test_version_and_error_string_without_gpu(has_gpu):
         assert n >= 1
 
 
+def test_stats_replica_count_matches_the_library():
+    """tg/ops.py sizes every replicated fp64 statistics accumulator with STATS_REPLICAS; the kernels index them with csrc/norm.hip's REPL
+    (8: tg_igemm_bnstat_* / _bnbwdstat_* clear all eight replicas of the batch norm's buffer, csrc/igemm.hip)."""
+    from tg import lib, ops
+    assert ops.STATS_REPLICAS == lib.call("tg_stats_replicas") == 8
+
+
 def test_desc_struct_matches_header_layout(tmp_path):
     """sizeof / offsets of the ctypes mirror against the C compiler's view of tg_igemm_desc."""
     from tg import lib

@@ -19,7 +19,7 @@ from tg import lib
 L = lib.load()
 text = re.sub(r"/\*.*?\*/", "", open(lib.HEADER_PATH).read(), flags=re.S)
 text = text[text.index('extern "C"'):]
-SKIP = re.compile(r"tg_(version|last_error_string|device_count|graph_|prof_|colstats_workspace_floats)")
+SKIP = re.compile(r"tg_(version|last_error_string|device_count|graph_|prof_|colstats_workspace_floats|stats_replicas)")   # no status code
 dev = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")           # 16 MB every pointer argument may point into
 host = (C.c_int32 * 64)()
 desc = lib.IgemmDesc()

@@ -12,7 +12,16 @@ Tolerance classes (tests/kernel_check.py):
               of tg_bn_train_apply_f32 on the same sums ("bit-identical to re-running tg_bn_train_f32", tg_kernels.h);
   pointwise   every finaliser and apply pass: |got - ref64| <= K u mag, mag the expression on absolute values (so the cancellation in
               beta - mean * scale or A dy + B x + C is covered), K the count of fp32 roundings on the way, +2 per sqrtf / division and
-              +4 per transcendental activation; the moving statistics allow 5 (mean) / 6 (variance) roundings per segment of the chain."""
+              +4 per transcendental activation; the moving statistics allow 5 (mean) / 6 (variance) roundings per segment of the chain;
+  reduction   the column sums behind the fused mean-only-BN backward passes (tg_mobn_bwd_f32, tg_maxpool2_bwd_actsum_f32,
+              tg_actgrad_bias_f32, and the db of tg_mobn_center_f32): TOL of the sum |terms| per output, negative control = the reference
+              without the last row of the last segment.
+
+The fused mean-only-BN family at the widths where its shared workgroup tail (csrc/norm.hip: colsum_tail) changes shape: c = 4 (one column
+group, 256 row lanes), 12 (85 lanes, one idle thread), 300 (3 lanes, 31 idle threads), 512 (2 lanes), and 256 column groups x one lane
+(tg_actgrad_bias_f32 at ld_out = 1024); the ragged segments add one-row segments, segments shorter than the lane count and more workgroups
+than replicas.  Every statistics workgroup there owns at most CHUNK = 32 rows, so a term of a column sum meets at most CHUNK - 1 fp32
+additions before the fp64 atomics: that is the R in the pointwise bounds of dx below."""
 import ctypes as C
 
 import numpy as np
@@ -20,12 +29,14 @@ import pytest
 
 from kernel_check import ACTS, ALPHA, act64, act_grad64, assert_bits, assert_pointwise, bits, close, dev, finish, guarded, lib, ptr, rejected, seq_sum32, st, y_for
 from oracle import tf_ops as T
+from tg.ops import STATS_REPLICAS as REPL
 
 pytestmark = pytest.mark.gpu
 
 EPS = np.float32(1e-5)
 DECAY = np.float32(0.9)
 SEGS = {'one': [250], 'ragged': [1, 7, 250, 3, 64, 1, 100, 33]}
+CHUNK = 32                                      # rows of a statistics workgroup below 65 536 rows (csrc/norm.hip: stats_chunk)
 
 
 def seg_arr(segs):
@@ -85,18 +96,18 @@ def test_bn_eval_finalize():
 
 
 def bn_sums(rng, x, segs, c):
-    """the [8][nseg][2][c] fp64 replicas of S0 = sum x, S1 = sum x^2 per segment, the total split at random over the replicas."""
+    """the [REPL][nseg][2][c] fp64 replicas of S0 = sum x, S1 = sum x^2 per segment, the total split at random over the replicas."""
     nseg = len(segs)
-    out = np.zeros((8, nseg, 2, c))
+    out = np.zeros((REPL, nseg, 2, c))
     b = 0
     for s, n in enumerate(segs):
         xs = f8(x[b:b + n])
         b += n
         for j, tot in enumerate((xs.sum(0), np.square(xs).sum(0))):
-            w = rng.random((8, c))
+            w = rng.random((REPL, c))
             w /= w.sum(0)
             out[:, s, j] = w * tot
-            out[7, s, j] = tot - out[:7, s, j].sum(0)
+            out[REPL - 1, s, j] = tot - out[:REPL - 1, s, j].sum(0)
     return out
 
 
@@ -322,3 +333,158 @@ def test_seg_actgrad_shift(case):
         ref = f8(dy[:, :c]) * g + sh
         assert_pointwise(got[:, :c], ref, np.abs(f8(dy[:, :c])) * gm + np.abs(sh), {'tanh': 5, 'sigmoid': 5, 'softplus': 7}.get(a, 2), a)
         assert (bits(got[:, c:cp]) == 0).all() and (got[:, cp:] == 9.0).all()
+
+
+# ---- the fused mean-only-BN backward family at the widths where the shared workgroup tail changes shape ----
+WIDTHS = [4, 12, 300, 512]
+
+
+def seg_bounds(segs):
+    e = np.cumsum(segs)
+    return list(zip(e - np.asarray(segs), e))
+
+
+def seg_stats(t64, segs):
+    """per segment of t64 [rows, c]: column sums, column sums of |t|, and per row the segment mean of t and of |t|."""
+    tot = np.stack([t64[a:b].sum(0) for a, b in seg_bounds(segs)])
+    sab = np.stack([np.abs(t64[a:b]).sum(0) for a, b in seg_bounds(segs)])
+    n = np.asarray(segs, np.float64)[:, None]
+    return tot, sab, (tot / n)[seg_index(segs)], (sab / n)[seg_index(segs)]
+
+
+def check_column_sums(got_seg, got_db, t64, segs, what, drop=1):
+    """reduction bound on the per-segment sums (got_seg [nseg, c], None: not read) and on db = their sum; negative control: the reference
+    without the last `drop` rows of the last segment."""
+    tot, sab, _, _ = seg_stats(t64, segs)
+    cut, _, _, _ = seg_stats(t64[:-drop], segs[:-1] + [segs[-1] - drop] if segs[-1] > drop else segs[:-1])
+    if got_seg is not None:
+        for s in range(len(segs)):
+            close(got_seg[s], tot[s], sab[s], "%s: sums of segment %d" % (what, s))
+        assert rejected(got_seg[-1], cut[-1] if segs[-1] > drop else 0.0, sab[-1]), what
+    if got_db is not None:
+        close(got_db, tot.sum(0), sab.sum(0), what + ": db")
+        assert rejected(got_db, cut.sum(0), sab.sum(0)), what
+
+
+def mobn_bwd_case(segs, c):
+    """dy, y = lrelu output (sign decides the derivative), t = dy * lrelu'(y) in float64"""
+    rng = np.random.default_rng(1000 * len(segs) + c)
+    rows = sum(segs)
+    dy = rng.standard_normal((rows, c)).astype(np.float32)
+    y = y_for(rng, (rows, c), 'lrelu')
+    return dy, y, f8(dy) * act_grad64(y, 'lrelu')[0]
+
+
+@pytest.mark.parametrize("segs", list(SEGS), ids=str)
+@pytest.mark.parametrize("c", WIDTHS)
+def test_mobn_bwd_widths(segs, c):
+    """tg_mobn_bwd_f32 (oracle.tf_ops.mobn_train_bwd behind lrelu'): the replica sums per segment and db to the reduction bound, dx = t - mean_seg(t)
+    pointwise on |t| + mean_seg |t| with K = R + 3: one rounding of t, R = CHUNK - 1 additions on a term's way into the sum, the cast of the
+    mean, the final addition."""
+    L = lib()
+    segs = SEGS[segs]
+    nseg, rows = len(segs), sum(segs)
+    dy, y, t64 = mobn_bwd_case(segs, c)
+    sums = dev(np.full((REPL, nseg, c), 5.0), np.float64)                   # not zeroed: the call clears it
+    dx, db = guarded(rows * c), guarded(c)
+    L.call('tg_mobn_bwd_f32', ptr(dev(dy)), c, ptr(dev(y)), c, dx.ptr, c, rows, c, seg_arr(segs), nseg, L.ACT['lrelu'], float(ALPHA), ptr(sums), 0,
+           db.ptr, st())
+    got_dx, got_db = finish(dx, (rows, c)), finish(db)
+    check_column_sums(sums.cpu().numpy().sum(0), got_db, t64, segs, "mobn_bwd c=%d" % c)
+    _, _, mean, mean_abs = seg_stats(t64, segs)
+    assert_pointwise(got_dx, t64 - mean, np.abs(t64) + mean_abs, CHUNK - 1 + 3, "dx")
+
+
+def split_over_replicas(rng, tot, n_repl):
+    """[n_repl][...] float64 summing to tot, split at random as bn_sums() does"""
+    if n_repl == 1:
+        return tot[None].copy()
+    w = rng.random((n_repl,) + tot.shape)
+    out = w / w.sum(0) * tot
+    out[-1] = tot - out[:-1].sum(0)
+    return out
+
+
+@pytest.mark.parametrize("segs", list(SEGS), ids=str)
+@pytest.mark.parametrize("c", WIDTHS)
+@pytest.mark.parametrize("n_repl", [1, REPL])
+def test_mobn_center_widths(segs, c, n_repl):
+    """tg_mobn_center_f32 on given fp64 sums (one copy, or REPL replicas read in order): dx = t - sums[seg] / rows_seg pointwise with K = 2 (the cast
+    of the mean, the addition), db = the sum over replicas and segments to the reduction bound."""
+    L = lib()
+    segs = SEGS[segs]
+    nseg, rows = len(segs), sum(segs)
+    rng = np.random.default_rng(2000 * nseg + c + n_repl)
+    t = rng.standard_normal((rows, c)).astype(np.float32)
+    tot, _, mean, _ = seg_stats(f8(t), segs)
+    sums = split_over_replicas(rng, tot, n_repl)
+    dx, db = guarded(rows * c), guarded(c)
+    L.call('tg_mobn_center_f32', ptr(dev(t)), c, dx.ptr, c, rows, c, seg_arr(segs), nseg, ptr(dev(sums, np.float64)), n_repl, db.ptr, st())
+    assert_pointwise(finish(dx, (rows, c)), f8(t) - mean, np.abs(f8(t)) + np.abs(mean), 2, "dx")
+    check_column_sums(None, finish(db), f8(t), segs, "mobn_center c=%d n_repl=%d" % (c, n_repl))
+
+
+POOL_IMGS = [1, 3, 9, 2]
+
+
+def pool_case(c, h, with_mask):
+    """y [n,h,h,c], pooled gradient, keep-mask (or None) and t = routed gradient * mask * 2 * lrelu'(y) in float64, [n*h*h, c]"""
+    rng = np.random.default_rng(3000 + 10 * c + h + with_mask)
+    n = sum(POOL_IMGS)
+    y = rng.standard_normal((n, h, h, c)).astype(np.float32)
+    dpool = rng.standard_normal((n, h // 2, h // 2, c)).astype(np.float32)
+    mask = (rng.random(dpool.shape) < 0.5).astype(np.float32) if with_mask else None
+    _, idx = T.maxpool2(f8(y))
+    gy = T.maxpool2_bwd(f8(dpool) * (f8(mask) * 2.0 if with_mask else 1.0), idx, y.shape)
+    return y, dpool, mask, (gy * act_grad64(y, 'lrelu')[0]).reshape(-1, c)
+
+
+@pytest.mark.parametrize("c", [12, 300])
+@pytest.mark.parametrize("h", [2, 4])
+@pytest.mark.parametrize("with_mask", [True, False], ids=['mask', 'nomask'])
+def test_maxpool_bwd_actsum_center_widths(c, h, with_mask):
+    """tg_maxpool2_bwd_actsum_f32 -> tg_mobn_center_f32(n_repl = REPL), images per application 1, 3, 9, 2: h = 2 is one pooled pixel per image
+    (chunks shorter than the lane count).  t pointwise with K = 3 (mask * scale, * gradient, * lrelu'), exact zeros off the arg-max; the replica
+    sums and db to the reduction bound — the negative control drops the last image row of t, whose pooled pixels are the kernel's last work
+    units; dx on |t| + mean_seg |t| with K = R + 5: the three roundings of a term, R = CHUNK - 1 additions, the cast of the mean, the addition."""
+    L = lib()
+    y, dpool, mask, t64 = pool_case(c, h, with_mask)
+    n, nseg = sum(POOL_IMGS), len(POOL_IMGS)
+    segs = [m * h * h for m in POOL_IMGS]
+    rows = n * h * h
+    sums = dev(np.full((REPL, nseg, c), 5.0), np.float64)
+    t = guarded(rows * c)
+    L.call('tg_maxpool2_bwd_actsum_f32', ptr(dev(dpool)), c, ptr(dev(mask)) if with_mask else None, c, 2.0 if with_mask else 1.0, ptr(dev(y)), c, t.ptr, c,
+           n, h, h, c, seg_arr(segs), nseg, L.ACT['lrelu'], float(ALPHA), ptr(sums), 0, st())
+    got_t = finish(t, (rows, c))
+    assert_pointwise(got_t, t64, np.abs(t64), 3, "t")
+    assert (got_t[t64 == 0] == 0).all()
+    dx, db = guarded(rows * c), guarded(c)
+    L.call('tg_mobn_center_f32', t.ptr, c, dx.ptr, c, rows, c, seg_arr(segs), nseg, ptr(sums), REPL, db.ptr, st())
+    got_dx, got_db = finish(dx, (rows, c)), finish(db)
+    check_column_sums(sums.cpu().numpy().sum(0), got_db, t64, segs, "maxpool2_bwd_actsum c=%d h=%d" % (c, h), drop=h)
+    _, _, mean, mean_abs = seg_stats(t64, segs)
+    assert_pointwise(got_dx, t64 - mean, np.abs(t64) + mean_abs, CHUNK - 1 + 5, "dx")
+
+
+def actgrad_bias_case():
+    rows, c = 300, 1000
+    rng = np.random.default_rng(4000)
+    dy = rng.standard_normal((rows, c)).astype(np.float32)
+    y = y_for(rng, (rows, c), 'lrelu')
+    return dy, y, f8(dy) * act_grad64(y, 'lrelu')[0]
+
+
+def test_actgrad_bias_256_column_groups():
+    """tg_actgrad_bias_f32 at (rows, c, ld_out) = (300, 1000, 1024): 256 column groups, one row lane, six of the groups all padding.  dpre
+    pointwise with K = 1, zeroed padding; the bias gradient to the reduction bound."""
+    L = lib()
+    rows, c, ld = 300, 1000, 1024
+    dy, y, t64 = actgrad_bias_case()
+    out, bg = guarded(rows * ld), guarded(c)
+    sums = dev(np.full((REPL, c), 5.0), np.float64)
+    L.call('tg_actgrad_bias_f32', ptr(dev(dy)), c, ptr(dev(y)), c, out.ptr, ld, rows, c, L.ACT['lrelu'], float(ALPHA), ptr(sums), 0, bg.ptr, st())
+    got = finish(out, (rows, ld))
+    assert_pointwise(got[:, :c], t64, np.abs(t64), 1, "dpre")
+    assert (bits(got[:, c:]) == 0).all()
+    check_column_sums(sums.cpu().numpy().sum(0)[None], finish(bg), t64, [rows], "actgrad_bias")
