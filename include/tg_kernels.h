@@ -557,9 +557,10 @@ int tg_true_fake_loss_f32(const float* unl_logits, int ld_u, int n_unl, const fl
                           float* d_unl, int ld_du, int accumulate_unl, float* d_fake, int ld_df, int accumulate_fake, float* loss, void* stream);
 /* The three heads above for k classes, 2 <= k <= 1024 (config.NUM_CLASSES; anything else is TG_ERR_INVALID): the same rows, weights,
  * outputs and padding rules with the logits' first k columns (columns >= k are never read; gradient columns k..ld_d are written 0 unless
- * the call accumulates), 1/k in the balance entropy and n_unl*k in the MSE mean; labels dense [n][k].  k == 10 runs the kernel of the
- * entry point without _k (same launch, bit-identical); any other k one workgroup of 16 waves, one row per wave, classes over the lanes
- * (bit-identical run to run). */
+ * the call accumulates), 1/k in the balance entropy and n_unl*k in the MSE mean; labels dense [n][k].  Each head is one kernel body with
+ * two layouts (csrc/loss.hip): k == 10 runs 256 threads, one row per thread; any other k one workgroup of 16 waves, one row
+ * per wave, classes over the lanes (both bit-identical run to run).  The entry points without _k above are these with k = 10: the same
+ * checks, the same launch, the same bits (their errors are reported under the _k name). */
 int tg_c_loss_k_f32(const float* c_logits, int ld, int n_real, int n_unl, int n_rep, int n_fake, int k, const float* y_real, const float* y_fake,
                     const float* d_unl_logits, int ld_dunl, const float* lambdas, float* dlogits, int ld_d, float* loss, void* stream);
 int tg_c_loss_terms_k_f32(const float* c_logits, int ld, int n_real, int n_unl, int n_rep, int n_fake, int k, const float* y_real,
@@ -623,8 +624,8 @@ int tg_minibatch_disc_bwd_f32(const float* act, int ld_a, const float* df, int l
  *                         the constant `label` everywhere (tf.ones_like / tf.zeros_like, :123-128); loss[2] = {w T, T}
  *   tg_entropy_terms_f32  H = mean_n(lse - sum_k p_k l_k) (_entropy, :43-48), Bal = -sum_k (1/K) log(mean_n p_k + 1e-12) (_balance_entropy,
  *                         :50-57); loss[3] = {w_h H + w_bal Bal, H, Bal}
- * softmax_ce / entropy_terms: 2 <= k <= 1024 classes (TG_ERR_INVALID outside); k == 10 runs the one-thread-per-row kernel, any other k
- * the one-wave-per-row kernel of tg_c_loss_k_f32. */
+ * softmax_ce / entropy_terms: 2 <= k <= 1024 classes (TG_ERR_INVALID outside); the two layouts of tg_c_loss_k_f32: one thread per row at
+ * k == 10, one wave per row at any other k. */
 int tg_softmax_ce_f32(const float* logits, int ld, const float* labels, int n, int k, float w, float* dlogits, int ld_d, int accumulate, float* loss,
                       void* stream);
 int tg_bce_logits_f32(const float* logits, int ld, const float* labels, int ld_y, float label, int n, int c, float w, float* dlogits, int ld_d,

@@ -2,7 +2,7 @@
 
 `_loss_GAN(D, C, Y, Lambda)` (train_base.py:113-154) is the loss the entry point calls by default (config.LOSS = 'WGAN_GP' selects the
 WGAN-GP heads further down instead); it is evaluated by three fused
-single-launch kernels (tg_d_loss_f32 / tg_g_loss_f32 / tg_c_loss_f32) that also write d(loss)/d(logits) into the
+single-launch kernels (tg_d_loss_f32 / tg_g_loss_f32 / tg_c_loss_k_f32) that also write d(loss)/d(logits) into the
 logits' gradient buffers.  The helper methods it is written with in the reference — `_entropy`, `_balance_entropy` (:43-57),
 `_softmax_cross_entropy_loss_w_logits`, `_sigmoid_cross_entopy_w_logits` (:75-84), `_accuracy_metric` (:107) — keep their names and
 argument order as stand-alone single-launch heads.  `_Adam_optimizer` (:91-97) returns the TF-form Adam configuration applied by
@@ -32,9 +32,22 @@ def _launch_update(name, clip_name, args, factor_dev):
         lib.call(clip_name, *args, lib.ptr(factor_dev), ctx().stream)
 
 
-def _k_head(name, name_k, k):
-    """(kernel, extra arguments) of a loss head over k classes: K = 10 keeps the ten-class launch `name`, else `name_k` takes k."""
-    return (name, ()) if k == 10 else (name_k, (k,))
+def _c_terms_head(members, n_real, n_unl, n_rep, n_fake, y_real, y_fake, d_unl, w6, loss_ptr, terms_ptr):
+    """tg_c_loss_terms_k_f32 over the concatenated `members` (rows [real | unl | unl_rep | fake], any of the last two absent) with the
+    HOST weights w6; y_fake / d_unl may be None.  Every member's `.grad` becomes its row range of the concatenated gradient.  Returns
+    the concatenated logits."""
+    cx = ctx()
+    ccat = concat_acts(members)
+    g = cx.new_act(ccat.n, 1, 1, ccat.c, ccat.ld, tag='dl')
+    lib.call('tg_c_loss_terms_k_f32', ccat.ptr, ccat.ld, n_real, n_unl, n_rep, n_fake, ccat.c, y_real.ptr,
+             y_fake.ptr if y_fake is not None else None, d_unl.ptr if d_unl is not None else None, d_unl.ld if d_unl is not None else 0,
+             (C_.c_float * 6)(*w6), g.ptr, g.ld, loss_ptr, terms_ptr, cx.stream)
+    ccat.grad = g
+    off = 0
+    for m in members:                                                  # the members' gradients are row ranges of the concatenated one
+        m.grad = g.view_rows(off, off + m.n)
+        off += m.n
+    return ccat
 
 
 class StreamingAccuracy(object):
@@ -289,8 +302,7 @@ class Train_base(object):
         """c_loss (train_base.py:118,130-152); rows of c_logits [real|unl|unl_rep|fake]."""
         cx = ctx()
         g = cx.new_act(c_logits.n, 1, 1, c_logits.c, c_logits.ld, tag='dl')
-        head, kk = _k_head('tg_c_loss_f32', 'tg_c_loss_k_f32', c_logits.c)
-        lib.call(head, c_logits.ptr, c_logits.ld, n_real, n_unl, n_rep, n_fake, *kk, y_l_c.ptr, y_g.ptr,
+        lib.call('tg_c_loss_k_f32', c_logits.ptr, c_logits.ld, n_real, n_unl, n_rep, n_fake, c_logits.c, y_l_c.ptr, y_g.ptr,
                  d_unl_logits.ptr, d_unl_logits.ld, lib.ptr(lambdas_dev), g.ptr, g.ld, lib.ptr(loss_out), cx.stream)
         c_logits.grad = g
 
@@ -330,7 +342,7 @@ class Train_base(object):
     #     D logits <- d_loss (concatenated copy in `self.last_d_cat`), D_fake_logits.grad <- gG_loss, C_bG_fake_feat.grad <- bG_loss,
     #     every classifier logit tensor <- c_loss.
     # Lambda: Python floats.  Every variant is a weighted sum of the same terms: tg_d_loss_terms_f32, tg_g_loss_f32,
-    # tg_c_loss_terms_f32, tg_true_fake_loss_f32, tg_sqdiff_rows_loss_f32, tg_feature_match_f32, tg_pull_away_f32.
+    # tg_c_loss_terms_k_f32, tg_true_fake_loss_k_f32, tg_sqdiff_rows_loss_f32, tg_feature_match_f32, tg_pull_away_f32.
 
     def _variant_terms(self, D, c_real, c_unl, c_rep, c_gfake, c_bfake, c_pert, f_bfake, f_unl, y_l_c, y_g, w6, w_bad, w_pert, pt):
         """runs the term kernels; returns the host array [d, d_real, d_fake, d_unl, gG, c_head, T_real, T_unl, T_H, T_bal, T_gfake, T_mse,
@@ -351,27 +363,15 @@ class Train_base(object):
         else:
             d_unl = None
         members = [c_real, c_unl] + ([c_rep] if c_rep is not None else []) + ([c_gfake] if c_gfake is not None else [])
-        ccat = concat_acts(members)
-        g = cx.new_act(ccat.n, 1, 1, ccat.c, ccat.ld, tag='dl')
-        n_rep = c_rep.n if c_rep is not None else 0
-        n_gf = c_gfake.n if c_gfake is not None else 0
+        ccat = _c_terms_head(members, c_real.n, c_unl.n, c_rep.n if c_rep is not None else 0, c_gfake.n if c_gfake is not None else 0, y_l_c,
+                             y_g if c_gfake is not None else None, d_unl, w6, P(5), P(6))
         k = ccat.c
-        head, kk = _k_head('tg_c_loss_terms_f32', 'tg_c_loss_terms_k_f32', k)
-        lib.call(head, ccat.ptr, ccat.ld, c_real.n, c_unl.n, n_rep, n_gf, *kk, y_l_c.ptr, y_g.ptr if c_gfake is not None else None,
-                 d_unl.ptr if d_unl is not None else None, d_unl.ld if d_unl is not None else 0, (C_.c_float * 6)(*w6), g.ptr, g.ld, P(5), P(6),
-                 cx.stream)
-        ccat.grad = g
-        off = 0
-        for m in members:                                              # the members' gradients are row ranges of the concatenated one
-            m.grad = g.view_rows(off, off + m.n)
-            off += m.n
         g_unl = c_unl.grad
         gb = cx.new_act(c_bfake.n, 1, 1, c_bfake.c, c_bfake.ld, tag='dl')
         unl_rows = ccat.view_rows(c_real.n, c_real.n + c_unl.n)
         assert c_bfake.c == k, (c_bfake.c, k)
-        head, _ = _k_head('tg_true_fake_loss_f32', 'tg_true_fake_loss_k_f32', k)
-        lib.call(head, unl_rows.ptr, ccat.ld, c_unl.n, c_bfake.ptr, c_bfake.ld, c_bfake.n, *kk, w_bad, w_bad, g_unl.ptr, g_unl.ld, 1,
-                 gb.ptr, gb.ld, 0, P(12), cx.stream)
+        lib.call('tg_true_fake_loss_k_f32', unl_rows.ptr, ccat.ld, c_unl.n, c_bfake.ptr, c_bfake.ld, c_bfake.n, k, w_bad, w_bad, g_unl.ptr,
+                 g_unl.ld, 1, gb.ptr, gb.ld, 0, P(12), cx.stream)
         c_bfake.grad = gb
         if c_pert is not None:
             gp = cx.new_act(c_pert.n, 1, 1, c_pert.c, c_pert.ld, tag='dl')
@@ -522,17 +522,8 @@ class Train_base(object):
         lib.call('tg_wgan_loss_f32', dcat.ptr, dcat.ld, d_real.n, d_fake.n, d_unl.n, lam1, lam2, g.ptr, g.ld, gf.ptr, gf.ld, P(0), cx.stream)
         dcat.grad, d_fake.grad = g, gf
         self.last_d_cat = dcat
-        ccat = concat_acts([c_real, c_unl, c_fake])                  # tg_c_loss_terms_f32 rows [real | unl | fake]; the unl terms weigh 0
-        gc = cx.new_act(ccat.n, 1, 1, ccat.c, ccat.ld, tag='dl')
-        k = ccat.c
-        head, kk = _k_head('tg_c_loss_terms_f32', 'tg_c_loss_terms_k_f32', k)
-        lib.call(head, ccat.ptr, ccat.ld, c_real.n, c_unl.n, 0, c_fake.n, *kk, Y.ptr, Y.ptr, None, 0,
-                 (C_.c_float * 6)(1.0, 0.0, 0.0, 0.0, lam2, 0.0), gc.ptr, gc.ld, P(5), P(6), cx.stream)
-        ccat.grad = gc
-        off = 0
-        for m in (c_real, c_unl, c_fake):
-            m.grad = gc.view_rows(off, off + m.n)
-            off += m.n
+        # rows [real | unl | fake]; the unl terms weigh 0
+        _c_terms_head([c_real, c_unl, c_fake], c_real.n, c_unl.n, 0, c_fake.n, Y, Y, None, (1.0, 0.0, 0.0, 0.0, lam2, 0.0), P(5), P(6))
         gp10 = self._gradient_penalty(X, G, Y, discriminator, weight=10.0)
         lv[12:13].copy_(gp10)
         v = [float(x) for x in lv.cpu().numpy()]

@@ -317,15 +317,6 @@ __global__ void __launch_bounds__(256) slab_reduce_wide(const float* __restrict_
 
 // weight norm of a transposed-conv filter V[t][a][b] = [kh*kw][Cout][Cin]: the norm runs over axes (0,1,3) = (t, b) for
 // every output channel a (Model/modle_base.py:148).  One workgroup per output channel (Cout is 3 in the reference).
-__device__ float block_sum256(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
 __global__ void __launch_bounds__(256) wn_scale_tab(const float* __restrict__ v, const float* __restrict__ g, int t_dim, int a_dim, int b_dim,
                                                     float* __restrict__ scale) {
   __shared__ float red[4];
@@ -335,7 +326,7 @@ __global__ void __launch_bounds__(256) wn_scale_tab(const float* __restrict__ v,
     const float x = v[((int64_t)(i / b_dim) * a_dim + a) * b_dim + i % b_dim];
     ss += x * x;
   }
-  ss = block_sum256(ss, red);
+  ss = tgd::block_sum<4>(ss, red);
   if (threadIdx.x == 0) scale[a] = g[a] * rsqrtf(fmaxf(ss, 1e-12f));
 }
 
@@ -349,8 +340,8 @@ __global__ void __launch_bounds__(256) wn_bwd_tab(const float* __restrict__ dw, 
     dot += dw[idx] * v[idx];
     ss += v[idx] * v[idx];
   }
-  dot = block_sum256(dot, red);
-  ss = block_sum256(ss, red);
+  dot = tgd::block_sum<4>(dot, red);
+  ss = tgd::block_sum<4>(ss, red);
   const float nrm = sqrtf(ss);
   if (threadIdx.x == 0) dg[a] = dot / nrm;
   const float c0 = g[a] / nrm, c1 = dot / ss;

@@ -49,4 +49,24 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// Sum of v over a workgroup of WAVES wavefronts, the same bits in every thread: wave_sum, one LDS slot per wave (red[WAVES]), the waves
+// added in index order.  Begins with a barrier, so red may be reused by the next call.
+template <int WAVES>
+__device__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = red[0];
+#pragma unroll
+  for (int i = 1; i < WAVES; ++i) s += red[i];
+  return s;
+}
+
 }  // namespace tgd

@@ -121,20 +121,17 @@ __global__ void __launch_bounds__(BLK) gp_rows(const float* __restrict__ g, int 
   if (threadIdx.x == 0) partials[i] = (s - 1.0) * (s - 1.0);
 }
 
-__device__ float block_sum_f(float v, float* red) {
-  v = tgd::wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
+constexpr int WV = BLK / 64;
 
-// rows [real | fake | unl] of the discriminator logits (column 0, row stride ld):
-//   wd1 = 1/2 (mean real - mean fake), wd2 = 1/2 (mean real - mean unl), wd3 = 1/2 (mean unl - mean fake)
-//   d_loss = -(wd1 + l1 wd2 + l2 wd3), g_loss = -mean fake;  loss[5] = {d_loss, g_loss, wd1, wd2, wd3}
-__global__ void __launch_bounds__(BLK) wgan_loss(const float* __restrict__ z, int ld, int n_real, int n_fake, int n_unl, float l1, float l2,
-                                                 float* __restrict__ dz, int ld_d, float* __restrict__ dfake, int ld_df, float* __restrict__ loss) {
-  __shared__ float red[4];
+// The Wasserstein distances of both loss heads below, written once.  Rows [real | fake | unl] of the discriminator logits (column 0, row
+// stride ld): writes dz = d d_loss / dz (column 0, padding 0) and returns, the same in every thread,
+//   wd1 = 1/2 (mean real - mean fake), wd2 = 1/2 (mean real - mean unl), wd3 = 1/2 (mean unl - mean fake),
+//   d_loss = -(wd1 + l1 wd2 + l2 wd3) and mean fake.
+// Every thread sums a fixed strided set of rows, tgd::block_sum adds the waves in index order: bit-identical run to run.
+struct Wd { float d_loss, m_fake, wd1, wd2, wd3; };
+
+__device__ Wd wasserstein(const float* __restrict__ z, int ld, int n_real, int n_fake, int n_unl, float l1, float l2, float* __restrict__ dz, int ld_d,
+                          float* red) {
   const int n = n_real + n_fake + n_unl;
   float s[3] = {0.f, 0.f, 0.f};
   const float w_real = (-0.5f - 0.5f * l1) / n_real, w_fake = (0.5f + 0.5f * l2) / n_fake, w_unl = (0.5f * l1 - 0.5f * l2) / n_unl;
@@ -145,59 +142,53 @@ __global__ void __launch_bounds__(BLK) wgan_loss(const float* __restrict__ z, in
     float* o = dz + (int64_t)r * ld_d;
     o[0] = which == 0 ? w_real : (which == 1 ? w_fake : w_unl);
     for (int k = 1; k < ld_d; ++k) o[k] = 0.f;
-    if (dfake && which == 1) {
-      float* f = dfake + (int64_t)(r - n_real) * ld_df;
+  }
+  const float m_real = tgd::block_sum<WV>(s[0], red) / n_real;
+  const float m_fake = tgd::block_sum<WV>(s[1], red) / n_fake;
+  const float m_unl = tgd::block_sum<WV>(s[2], red) / n_unl;
+  const float wd1 = 0.5f * (m_real - m_fake), wd2 = 0.5f * (m_real - m_unl), wd3 = 0.5f * (m_unl - m_fake);
+  return Wd{-(wd1 + l1 * wd2 + l2 * wd3), m_fake, wd1, wd2, wd3};
+}
+
+// the stand-alone loss (Train_base._loss_WGAN_GP), lambdas from the host: g_loss = -mean fake, dfake (optional) = d g_loss / d fake logits;
+// loss[5] = {d_loss, g_loss, wd1, wd2, wd3}
+__global__ void __launch_bounds__(BLK) wgan_loss(const float* __restrict__ z, int ld, int n_real, int n_fake, int n_unl, float l1, float l2,
+                                                 float* __restrict__ dz, int ld_d, float* __restrict__ dfake, int ld_df, float* __restrict__ loss) {
+  __shared__ float red[WV];
+  const Wd w = wasserstein(z, ld, n_real, n_fake, n_unl, l1, l2, dz, ld_d, red);
+  if (dfake)
+    for (int r = threadIdx.x; r < n_fake; r += BLK) {
+      float* f = dfake + (int64_t)r * ld_df;
       f[0] = -1.f / n_fake;
       for (int k = 1; k < ld_df; ++k) f[k] = 0.f;
     }
-  }
-  const float m_real = block_sum_f(s[0], red) / n_real;
-  const float m_fake = block_sum_f(s[1], red) / n_fake;
-  const float m_unl = block_sum_f(s[2], red) / n_unl;
   if (threadIdx.x == 0) {
-    const float wd1 = 0.5f * (m_real - m_fake), wd2 = 0.5f * (m_real - m_unl), wd3 = 0.5f * (m_unl - m_fake);
-    loss[0] = -(wd1 + l1 * wd2 + l2 * wd3);
-    loss[1] = -m_fake;
-    loss[2] = wd1;
-    loss[3] = wd2;
-    loss[4] = wd3;
+    loss[0] = w.d_loss;
+    loss[1] = -w.m_fake;
+    loss[2] = w.wd1;
+    loss[3] = w.wd2;
+    loss[4] = w.wd3;
   }
 }
 
 // ---- loss heads of the three-player step (Training/Train_goodGAN.py with config.LOSS = 'WGAN_GP').  Unlike wgan_loss they read lambda_1 /
 // lambda_2 from device memory (the trainer's hyper[2:4]) and the weighted penalty from the device scalar the sweeps wrote, so a recorded
-// launch plan or graph follows set_hyper().  One workgroup each; every thread sums a fixed strided set of rows, block_sum_f adds the waves
-// in a fixed order: bit-identical run to run.
+// launch plan or graph follows set_hyper().  One workgroup each, fixed summation order: bit-identical run to run.
 
 // rows [real | fake | unl]: dz = d d_loss / dz (column 0, padding 0), loss[0] = -(wd1 + l1 wd2 + l2 wd3) + gp_w[0],
 // terms[4] = {wd1, wd2, wd3, gp_w[0] / gp_weight}
 __global__ void __launch_bounds__(BLK) wgan_d_head(const float* __restrict__ z, int ld, int n_real, int n_fake, int n_unl, const float* __restrict__ lam,
                                                    const float* __restrict__ gp_w, float gp_weight, float* __restrict__ dz, int ld_d,
                                                    float* __restrict__ loss, float* __restrict__ terms) {
-  __shared__ float red[4];
-  const int n = n_real + n_fake + n_unl;
-  const float l1 = lam[0], l2 = lam[1];
-  const float w_real = (-0.5f - 0.5f * l1) / n_real, w_fake = (0.5f + 0.5f * l2) / n_fake, w_unl = (0.5f * l1 - 0.5f * l2) / n_unl;
-  float s[3] = {0.f, 0.f, 0.f};
-  for (int r = threadIdx.x; r < n; r += BLK) {
-    const float v = z[(int64_t)r * ld];
-    const int which = r < n_real ? 0 : (r < n_real + n_fake ? 1 : 2);
-    s[which] += v;
-    float* o = dz + (int64_t)r * ld_d;
-    o[0] = which == 0 ? w_real : (which == 1 ? w_fake : w_unl);
-    for (int k = 1; k < ld_d; ++k) o[k] = 0.f;
-  }
-  const float m_real = block_sum_f(s[0], red) / n_real;
-  const float m_fake = block_sum_f(s[1], red) / n_fake;
-  const float m_unl = block_sum_f(s[2], red) / n_unl;
+  __shared__ float red[WV];
+  const Wd w = wasserstein(z, ld, n_real, n_fake, n_unl, lam[0], lam[1], dz, ld_d, red);
   if (threadIdx.x == 0) {
-    const float wd1 = 0.5f * (m_real - m_fake), wd2 = 0.5f * (m_real - m_unl), wd3 = 0.5f * (m_unl - m_fake);
     const float gp = gp_w[0];
-    loss[0] = -(wd1 + l1 * wd2 + l2 * wd3) + gp;
+    loss[0] = w.d_loss + gp;
     if (terms) {
-      terms[0] = wd1;
-      terms[1] = wd2;
-      terms[2] = wd3;
+      terms[0] = w.wd1;
+      terms[1] = w.wd2;
+      terms[2] = w.wd3;
       terms[3] = gp / gp_weight;
     }
   }
@@ -205,7 +196,7 @@ __global__ void __launch_bounds__(BLK) wgan_d_head(const float* __restrict__ z, 
 
 // g_loss = -mean z over n rows (column 0): dz = -1/n, padding 0
 __global__ void __launch_bounds__(BLK) wgan_g_head(const float* __restrict__ z, int ld, int n, float* __restrict__ dz, int ld_d, float* __restrict__ loss) {
-  __shared__ float red[4];
+  __shared__ float red[WV];
   float s = 0.f;
   for (int r = threadIdx.x; r < n; r += BLK) {
     s += z[(int64_t)r * ld];
@@ -213,16 +204,18 @@ __global__ void __launch_bounds__(BLK) wgan_g_head(const float* __restrict__ z, 
     o[0] = -1.f / n;
     for (int k = 1; k < ld_d; ++k) o[k] = 0.f;
   }
-  const float m = block_sum_f(s, red) / n;
+  const float m = tgd::block_sum<WV>(s, red) / n;
   if (threadIdx.x == 0) loss[0] = -m;
 }
 
+// A third way of computing a softmax CE (a run-time loop over the k classes in one thread, expf evaluated again for the gradient): its
+// bits differ from softmax_ce of loss.hip, so it does not fold into that file's layout template and stays as it is.
 // rows [real | zero (n_zero) | fake] of k logits: c_loss = mean CE(y_real, real) + lam[1] mean CE(y_fake, fake), CE = lse sum_j y_j - y . l;
 // dl = w (softmax * sum_j y_j - y) / n on the labelled rows, 0 on the zero rows, padding columns k..ld_d 0; terms[2] = the two means
 __global__ void __launch_bounds__(BLK) wgan_c_head(const float* __restrict__ cl, int ld, int n_real, int n_zero, int n_fake, int k,
                                                    const float* __restrict__ y_real, const float* __restrict__ y_fake, const float* __restrict__ lam,
                                                    float* __restrict__ dl, int ld_d, float* __restrict__ loss, float* __restrict__ terms) {
-  __shared__ float red[4];
+  __shared__ float red[WV];
   const float l2 = n_fake > 0 ? lam[1] : 0.f;
   float ce[2] = {0.f, 0.f};
   for (int pass = 0; pass < 2; ++pass) {
@@ -248,8 +241,8 @@ __global__ void __launch_bounds__(BLK) wgan_c_head(const float* __restrict__ cl,
     }
   }
   for (int64_t i = threadIdx.x; i < (int64_t)n_zero * ld_d; i += BLK) dl[(int64_t)n_real * ld_d + i] = 0.f;
-  const float t_real = block_sum_f(ce[0], red) / n_real;
-  const float t_fake = n_fake > 0 ? block_sum_f(ce[1], red) / n_fake : 0.f;
+  const float t_real = tgd::block_sum<WV>(ce[0], red) / n_real;
+  const float t_fake = n_fake > 0 ? tgd::block_sum<WV>(ce[1], red) / n_fake : 0.f;
   if (threadIdx.x == 0) {
     loss[0] = t_real + l2 * t_fake;
     if (terms) {

@@ -1,22 +1,25 @@
-"""The classifier's loss heads at any class count K (csrc/loss.hip, the *_k_kernel heads; 2 <= K <= 1024) against the float64 restatement
-of tests/loss_heads_k_reference.py: tg_c_loss_k_f32, tg_c_loss_terms_k_f32, tg_true_fake_loss_k_f32 and the widened tg_softmax_ce_f32 /
-tg_entropy_terms_f32, called directly.
+"""The classifier's loss heads at any class count K (csrc/loss.hip: one body per head, the one-thread-per-row layout at K = 10 and the
+one-wave-per-row layout at any other 2 <= K <= 1024) against the float64 restatement of tests/loss_heads_k_reference.py:
+tg_c_loss_k_f32, tg_c_loss_terms_k_f32, tg_true_fake_loss_k_f32, tg_softmax_ce_f32 and tg_entropy_terms_f32, called directly, and the
+entry points without _k (tg_c_loss_f32, tg_c_loss_terms_f32, tg_true_fake_loss_f32), which are the same launch at K = 10.
 
 Logits carry NaN in their padding columns (ld > K: a head that reads past K fails), gradient buffers start NaN so that every owned
 element must be written; with accumulate = 0 the gradient padding up to ld_d must be 0, with accumulate = 1 it must be left as it was.
 Values within 1e-5 relative, gradients within 1e-5 of their largest entry; two launches bit-identical; the _k entry points at K = 10
-bit-identical to the ten-class entry point; K outside 2..1024 rejected."""
+bit-identical to the ten-class entry point; K outside 2..1024 rejected.  The *_row_stride tests run more rows than a workgroup has
+row owners (256 threads at K = 10, 16 waves otherwise), so that every owner takes a second row, and a single row per group."""
 import numpy as np
 import pytest
 
 from kernel_check import dev, finish, guarded, lib, ptr, st
 import loss_heads_k_reference as R
-import ten_class_heads as H
 
 pytestmark = pytest.mark.gpu
 
 KS = [2, 3, 7, 10, 33, 64, 65, 100, 1000]
 ROWS = [37, 50, 80, 100, 250]
+STRIDE_KS = [7, 10, 65]                      # both layouts; 65 needs a second class slot per lane
+STRIDE_ROWS = [1, 257, 300]                  # one row; one row past the 256 row owners of the K = 10 layout; a ragged second pass
 W6 = [1.0, 0.5, 0.3, 0.7, 0.4, 0.6]          # every term of c_loss_terms weighted so that each one shows in the gradient
 
 
@@ -49,7 +52,7 @@ def check_pad(g, g0, k, acc, what):
 
 def run_c_loss(with_terms, k, z, n_real, n_unl, n_rep, n_fake, y_real, y_fake, d_unl, w, ten_class=False):
     """with_terms: tg_c_loss_terms_k_f32 (host weights w, terms written), else tg_c_loss_k_f32 (device lambdas w[4:6]); ten_class: the
-    entry point without _k of the same head instead (tests/ten_class_heads.py).  Returns (loss, terms, grad)."""
+    entry point without _k of the same head instead.  Returns (loss, terms, grad)."""
     import ctypes as C
     L = lib()
     n, ld = z.shape
@@ -58,12 +61,14 @@ def run_c_loss(with_terms, k, z, n_real, n_unl, n_rep, n_fake, y_real, y_fake, d
     loss = guarded(1)
     terms = guarded(6) if with_terms else None
     if with_terms and ten_class:
-        H.c_loss_terms(g, loss, terms, z, n_real, n_unl, n_rep, n_fake, y_real, y_fake, d_unl, w)
+        L.call('tg_c_loss_terms_f32', ptr(dev(z)), ld, n_real, n_unl, n_rep, n_fake, ptr(dev(y_real)), ptr(dev(y_fake)) if n_fake else None,
+               ptr(dev(d_unl)), 1, (C.c_float * 6)(*w), g.ptr, ld_d, loss.ptr, terms.ptr, st())
     elif with_terms:
         L.call('tg_c_loss_terms_k_f32', ptr(dev(z)), ld, n_real, n_unl, n_rep, n_fake, k, ptr(dev(y_real)), ptr(dev(y_fake)) if n_fake else None,
                ptr(dev(d_unl)), 1, (C.c_float * 6)(*w), g.ptr, ld_d, loss.ptr, terms.ptr, st())
     elif ten_class:
-        H.c_loss(g, loss, z, n_real, n_unl, n_rep, n_fake, y_real, y_fake, d_unl, w[4:6])
+        L.call('tg_c_loss_f32', ptr(dev(z)), ld, n_real, n_unl, n_rep, n_fake, ptr(dev(y_real)), ptr(dev(y_fake)), ptr(dev(d_unl)), 1,
+               ptr(dev(np.array(w[4:6], np.float32))), g.ptr, ld_d, loss.ptr, st())
     else:
         L.call('tg_c_loss_k_f32', ptr(dev(z)), ld, n_real, n_unl, n_rep, n_fake, k, ptr(dev(y_real)), ptr(dev(y_fake)), ptr(dev(d_unl)), 1,
                ptr(dev(np.array(w[4:6], np.float32))), g.ptr, ld_d, loss.ptr, st())
@@ -71,10 +76,7 @@ def run_c_loss(with_terms, k, z, n_real, n_unl, n_rep, n_fake, y_real, y_fake, d
     return float(finish(loss)[0]), (finish(terms) if terms is not None else None), gg
 
 
-@pytest.mark.parametrize("k", KS)
-@pytest.mark.parametrize("sizes", [(50, 50, 100), (20, 80, 100), (7, 13, 5), (50, 100, 0)])
-@pytest.mark.parametrize("rep", [True, False])
-def test_c_loss_terms_k(k, sizes, rep):
+def check_c_loss_terms_k(k, sizes, rep):
     rng = np.random.default_rng(k * 1000 + sum(sizes))
     n_real, n_unl, n_fake = sizes
     n_rep = n_unl if rep else 0
@@ -98,47 +100,73 @@ def test_c_loss_terms_k(k, sizes, rep):
 
 
 @pytest.mark.parametrize("k", KS)
-@pytest.mark.parametrize("sizes", [(50, 50, 100), (7, 13, 5)])
-def test_c_loss_k_with_device_lambdas(k, sizes):
+@pytest.mark.parametrize("sizes", [(50, 50, 100), (20, 80, 100), (7, 13, 5), (50, 100, 0)])
+@pytest.mark.parametrize("rep", [True, False])
+def test_c_loss_terms_k(k, sizes, rep):
+    check_c_loss_terms_k(k, sizes, rep)
+
+
+@pytest.mark.parametrize("k", STRIDE_KS)
+@pytest.mark.parametrize("sizes", [(300, 270, 257), (1, 1, 1)])
+@pytest.mark.parametrize("rep", [True, False])
+def test_c_loss_terms_k_row_stride(k, sizes, rep):
+    check_c_loss_terms_k(k, sizes, rep)
+
+
+def check_c_loss_k(k, sizes, rep=True):
     """the _loss_GAN head: weights {1, .005, 1e-6, 1e-3} and {lambda_1, lambda_2} read from the device."""
     rng = np.random.default_rng(k + 7)
     n_real, n_unl, n_fake = sizes
-    n = n_real + 2 * n_unl + n_fake
+    n_rep = n_unl if rep else 0
+    n = n_real + n_unl + n_rep + n_fake
     z = logits(rng, n, k)
     y_real, y_fake = onehot(rng, n_real, k), onehot(rng, n_fake, k)
     d_unl = (rng.standard_normal(n_unl) * 2).astype(np.float32)
     w = [1.0, 0.005, 1e-6, 1e-3, 0.3, 0.5]
     l64 = z[:, :k].astype(np.float64)
-    o = np.cumsum([0, n_real, n_unl, n_unl, n_fake])
-    ref_loss, _, ref_g = R.c_loss(l64[o[0]:o[1]], l64[o[1]:o[2]], l64[o[2]:o[3]], l64[o[3]:o[4]], y_real, y_fake, d_unl.astype(np.float64), w)
-    loss, _, g = run_c_loss(False, k, z, n_real, n_unl, n_unl, n_fake, y_real, y_fake, d_unl, w)
+    o = np.cumsum([0, n_real, n_unl, n_rep, n_fake])
+    ref_loss, _, ref_g = R.c_loss(l64[o[0]:o[1]], l64[o[1]:o[2]], l64[o[2]:o[3]] if rep else None, l64[o[3]:o[4]], y_real, y_fake,
+                                  d_unl.astype(np.float64), w)
+    loss, _, g = run_c_loss(False, k, z, n_real, n_unl, n_rep, n_fake, y_real, y_fake, d_unl, w)
     close_value(loss, ref_loss, "loss")
     close_grad(g[:, :k], ref_g, "gradient")
     check_pad(g, None, k, 0, "c_loss_k")
     if k == 10:                                          # the _k entry point at K = 10 is the ten-class launch
         for with_terms in (False, True):
-            a = run_c_loss(with_terms, k, z, n_real, n_unl, n_unl, n_fake, y_real, y_fake, d_unl, w)
-            b = run_c_loss(with_terms, k, z, n_real, n_unl, n_unl, n_fake, y_real, y_fake, d_unl, w, ten_class=True)
+            a = run_c_loss(with_terms, k, z, n_real, n_unl, n_rep, n_fake, y_real, y_fake, d_unl, w)
+            b = run_c_loss(with_terms, k, z, n_real, n_unl, n_rep, n_fake, y_real, y_fake, d_unl, w, ten_class=True)
             assert np.float32(a[0]).view(np.int32) == np.float32(b[0]).view(np.int32) and (a[2].view(np.int32) == b[2].view(np.int32)).all()
+            assert with_terms is False or (a[1].view(np.int32) == b[1].view(np.int32)).all()
+
+
+@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("sizes", [(50, 50, 100), (7, 13, 5)])
+def test_c_loss_k_with_device_lambdas(k, sizes):
+    check_c_loss_k(k, sizes)
+
+
+@pytest.mark.parametrize("k", STRIDE_KS)
+@pytest.mark.parametrize("sizes", [(300, 270, 257), (1, 1, 1)])
+@pytest.mark.parametrize("rep", [True, False])
+def test_c_loss_k_row_stride(k, sizes, rep):
+    check_c_loss_k(k, sizes, rep)
 
 
 def run_true_fake(k, zu, zf, acc, g0u, g0f, ten_class=False):
-    """tg_true_fake_loss_k_f32, or (ten_class) tg_true_fake_loss_f32 through tests/ten_class_heads.py."""
+    """tg_true_fake_loss_k_f32, or (ten_class) tg_true_fake_loss_f32."""
     L = lib()
     gu, gf = guarded(g0u.size, fill=g0u), guarded(g0f.size, fill=g0f)
     loss = guarded(3)
     if ten_class:
-        H.true_fake_loss(zu, zf, 0.7, 1.3, gu, g0u.shape[1], acc, gf, g0f.shape[1], acc, loss)
+        L.call('tg_true_fake_loss_f32', ptr(dev(zu)), zu.shape[1], len(zu), ptr(dev(zf)), zf.shape[1], len(zf), 0.7, 1.3, gu.ptr, g0u.shape[1],
+               acc, gf.ptr, g0f.shape[1], acc, loss.ptr, st())
     else:
         L.call('tg_true_fake_loss_k_f32', ptr(dev(zu)), zu.shape[1], len(zu), ptr(dev(zf)), zf.shape[1], len(zf), k, 0.7, 1.3, gu.ptr,
                g0u.shape[1], acc, gf.ptr, g0f.shape[1], acc, loss.ptr, st())
     return finish(loss), finish(gu, g0u.shape, np.broadcast_to(np.arange(g0u.shape[1]) < k, g0u.shape) if acc else None), finish(gf, g0f.shape, None)
 
 
-@pytest.mark.parametrize("k", KS)
-@pytest.mark.parametrize("rows", [(50, 100), (80, 20), (37, 13)])
-@pytest.mark.parametrize("acc", [0, 1])
-def test_true_fake_loss_k(k, rows, acc):
+def check_true_fake_loss_k(k, rows, acc):
     rng = np.random.default_rng(k * 3 + rows[0] + acc)
     zu, zf = logits(rng, rows[0], k), logits(rng, rows[1], k)
     g0u = np.full((rows[0], k + 3), np.nan, np.float32)
@@ -161,6 +189,20 @@ def test_true_fake_loss_k(k, rows, acc):
     if k == 10:
         old = run_true_fake(k, zu, zf, acc, g0u, g0f, ten_class=True)
         assert all((a.view(np.int32) == b.view(np.int32)).all() for a, b in zip(old, (loss, gu, gf))), "K = 10 is not the ten-class launch"
+
+
+@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("rows", [(50, 100), (80, 20), (37, 13)])
+@pytest.mark.parametrize("acc", [0, 1])
+def test_true_fake_loss_k(k, rows, acc):
+    check_true_fake_loss_k(k, rows, acc)
+
+
+@pytest.mark.parametrize("k", STRIDE_KS)
+@pytest.mark.parametrize("rows", [(300, 257), (1, 1)])
+@pytest.mark.parametrize("acc", [0, 1])
+def test_true_fake_loss_k_row_stride(k, rows, acc):
+    check_true_fake_loss_k(k, rows, acc)
 
 
 def run_softmax_ce(k, z, y, acc, g0):
@@ -186,10 +228,7 @@ def grad0(rng, n, k, acc):
     return g0
 
 
-@pytest.mark.parametrize("k", KS)
-@pytest.mark.parametrize("n", ROWS)
-@pytest.mark.parametrize("acc", [0, 1])
-def test_softmax_ce_any_k(k, n, acc):
+def check_softmax_ce(k, n, acc):
     rng = np.random.default_rng(k * 7 + n + acc)
     z, y = logits(rng, n, k), onehot(rng, n, k)
     g0 = grad0(rng, n, k, acc)
@@ -206,7 +245,18 @@ def test_softmax_ce_any_k(k, n, acc):
 @pytest.mark.parametrize("k", KS)
 @pytest.mark.parametrize("n", ROWS)
 @pytest.mark.parametrize("acc", [0, 1])
-def test_entropy_terms_any_k(k, n, acc):
+def test_softmax_ce_any_k(k, n, acc):
+    check_softmax_ce(k, n, acc)
+
+
+@pytest.mark.parametrize("k", STRIDE_KS)
+@pytest.mark.parametrize("n", STRIDE_ROWS)
+@pytest.mark.parametrize("acc", [0, 1])
+def test_softmax_ce_row_stride(k, n, acc):
+    check_softmax_ce(k, n, acc)
+
+
+def check_entropy_terms(k, n, acc):
     rng = np.random.default_rng(k * 11 + n + acc)
     z = logits(rng, n, k)
     g0 = grad0(rng, n, k, acc)
@@ -221,6 +271,20 @@ def test_entropy_terms_any_k(k, n, acc):
     check_pad(g, g0, k, acc, "entropy_terms")
     again = run_entropy(k, z, acc, g0)
     assert all((a.view(np.int32) == b.view(np.int32)).all() for a, b in zip(again, (loss, g))), "not deterministic"
+
+
+@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("n", ROWS)
+@pytest.mark.parametrize("acc", [0, 1])
+def test_entropy_terms_any_k(k, n, acc):
+    check_entropy_terms(k, n, acc)
+
+
+@pytest.mark.parametrize("k", STRIDE_KS)
+@pytest.mark.parametrize("n", STRIDE_ROWS)
+@pytest.mark.parametrize("acc", [0, 1])
+def test_entropy_terms_row_stride(k, n, acc):
+    check_entropy_terms(k, n, acc)
 
 
 @pytest.mark.parametrize("k", [0, 1, 1025, 4096])
@@ -242,7 +306,7 @@ def test_class_count_outside_the_range_is_rejected(k):
 
 
 def test_ten_class_kernel_misses_hundred_class_data():
-    """negative control: the K = 10 head on K = 100 logits (what a 100-class run got before the _k heads) is far outside the bound."""
+    """negative control: the K = 10 head on K = 100 logits (what a 100-class run got before the heads took K) is far outside the bound."""
     k, rng = 100, np.random.default_rng(5)
     n_real, n_unl, n_fake = 50, 50, 100
     z = logits(rng, n_real + 2 * n_unl + n_fake, k)

@@ -1,5 +1,5 @@
 """GPU parity of SURVEY §8f N4: the loss variants of Training/train_base.py:156-574 (host composition in the package's
-Training/train_base.py over tg_c_loss_terms_f32 / tg_true_fake_loss_f32 / tg_sqdiff_rows_loss_f32 / tg_d_loss_terms_f32 and the
+Training/train_base.py over tg_c_loss_terms_k_f32 / tg_true_fake_loss_k_f32 / tg_sqdiff_rows_loss_f32 / tg_d_loss_terms_f32 and the
 feature-matching / pull-away kernels) and minibatch discrimination (Model/modle_base.py:110-128), against the float64 restatement
 oracle/loss_variants.py on identical float32 inputs: every returned value, every gradient."""
 import numpy as np

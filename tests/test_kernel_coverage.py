@@ -39,10 +39,6 @@ NOT_KERNELS = {
 THROUGH_WRAPPER = {
     "tg_d_loss_terms_f32": ("test_gpu_loss_variants.py::test_loss_variant_values_and_gradients", "Training/train_base.py",
                             "the loss-variant terms (train_base.py:156-574) against oracle/loss_variants.py, value and gradient"),
-    "tg_c_loss_terms_f32": ("test_gpu_loss_variants.py::test_loss_variant_values_and_gradients", "Training/train_base.py",
-                            "the loss-variant terms (train_base.py:156-574) against oracle/loss_variants.py, value and gradient"),
-    "tg_true_fake_loss_f32": ("test_gpu_loss_variants.py::test_loss_variant_values_and_gradients", "Training/train_base.py",
-                              "the loss-variant terms (train_base.py:156-574) against oracle/loss_variants.py, value and gradient"),
     "tg_sqdiff_rows_loss_f32": ("test_gpu_loss_variants.py::test_loss_variant_values_and_gradients", "Training/train_base.py",
                                 "the loss-variant terms (train_base.py:156-574) against oracle/loss_variants.py, value and gradient"),
     "tg_u8_affine_f32": ("test_gpu_pipeline.py::test_device_tail_is_bit_identical_to_the_host_expression", "Input_Pipeline/tfrecordDataset.py",
