@@ -1,11 +1,11 @@
 """Shared checks of the per-kernel float64 tests (tests/test_gpu_elementwise.py, _prep.py, _norm_finalize.py, _loss_heads.py, _gemm_tiles.py, _halo_tiles.py,
-_packed_tiles.py, _rng.py),
+_packed_tiles.py, _rng.py, _norm_forward.py, _colstats.py, _stats_chunk.py, _updates.py, _small_heads.py),
 and the float64 oracle of an implicit-GEMM descriptor (igemm_ref64, on the device).
 
 Every output a test reads is allocated by `guarded`: the buffer is followed by GUARD floats holding a fixed bit pattern, and the output
 itself starts as NaN.  After the launch every element the kernel owns must hold a number (no NaN left = it was written), the guard must
 hold its pattern bit for bit (nothing was written past the end), and padding the kernel must zero is exactly 0.0.  The guard is part of
-the same allocation: nothing is read or written outside a buffer.
+the same allocation: nothing is read or written outside a buffer.  `guarded16` is the same for an output of 2-byte elements (bf16).
 
 Tolerance classes (each test module states which one applies to which output):
   bit-exact  got == the fp32 value NumPy computes in the kernel's order (data movement, selection, one correctly rounded operation,
@@ -86,6 +86,57 @@ class Guarded(object):
 
 def guarded(n, offset=0, fill=None):
     return Guarded(n, offset, fill)
+
+
+GUARD16_BITS = 0x5A17            # the guard pattern of a 2-byte output
+NAN16_BITS = 0x7FC0              # bf16 quiet NaN: the "never written" fill of a 2-byte output
+
+
+class Guarded16(object):
+    """an output of `n` 2-byte elements (bf16), every element the bf16 NaN, followed by 2 * GUARD pattern halfwords (the same number of
+    guard bytes as behind a float output)."""
+
+    def __init__(self, n):
+        self.n = int(n)
+        self.base = torch.empty(self.n + 2 * GUARD, dtype=torch.int16, device='cuda')
+        self.base.fill_(GUARD16_BITS)
+        self.t = self.base[:self.n]
+        self.t.fill_(NAN16_BITS)
+
+    @property
+    def ptr(self):
+        return C.c_void_p(self.t.data_ptr())
+
+    def get(self, shape=None):
+        """the raw halfwords (uint16)"""
+        torch.cuda.synchronize()
+        a = self.t.cpu().numpy().view(np.uint16).copy()
+        return a if shape is None else a.reshape(shape)
+
+    def check_guard(self):
+        torch.cuda.synchronize()
+        del _ALIVE[:]
+        tail = self.base[self.n:].cpu().numpy()
+        assert (tail == GUARD16_BITS).all(), "write past the end of the 2-byte output: guard halfword %d changed" % int(np.argmax(tail != GUARD16_BITS))
+
+
+def guarded16(n):
+    return Guarded16(n)
+
+
+def finish16(g, shape=None, owned=None):
+    """`finish` for a Guarded16: guard intact, no owned halfword still the NaN fill; returns the raw bf16 bits (uint16)."""
+    g.check_guard()
+    a = g.get(shape)
+    m = np.ones(a.shape, bool) if owned is None else owned
+    assert not (a[m] == NAN16_BITS).any(), "%d owned 2-byte elements were never written" % int((a[m] == NAN16_BITS).sum())
+    return a
+
+
+def bf16_rne_bits(a):
+    """the bf16 halfwords of finite fp32 values rounded to nearest even (what __builtin_convertvector(float -> __bf16) stores)."""
+    x = np.ascontiguousarray(a, np.float32).view(np.uint32)
+    return ((x + np.uint32(0x7FFF) + ((x >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
 
 
 def finish(g, shape=None, owned=None):

@@ -7,7 +7,7 @@ Tolerance classes (tests/kernel_check.py):
   bit-exact   pad_add (x, or x + add: one correctly rounded addition), cond_concat and maxpool2_bwd (x * (mask * mscale) with a 0/1 mask:
               one rounding), copy_multi, copy2d, add, gmaxpool_fwd / _bwd, im2col3x3_add, gavgpool_concat (fp32 sum over the pixels in
               pixel order, then one division), splitk_reduce (bias + sum_s in slab order), act for none / relu / lrelu (one rounding),
-              tg_rng_multi_f32 against the single-draw entry points;
+              tg_rng_multi_f32 against the single-draw entry points, u8_affine (the fp32 host expression) and onehot_i32;
   pointwise   act: tanh K = 4 (the device library's tanhf is within 2 ulp, 1 ulp <= 2u relative), sigmoid and softplus K = 6 (expf 2 ulp,
               then one addition and one division / log1pf of condition <= 1); actgrad: K = 3 for none / relu / lrelu (three products),
               6 for tanh / sigmoid (1 - y*y / y*(1 - y) add two roundings, mag evaluates them on |y| so cancellation is covered), 8 for
@@ -419,3 +419,42 @@ def test_rng_multi_equals_the_single_draws():
             assert (got >= a).all() and (got <= b).all()
         if mode == 3:
             assert (got.reshape(n, int(a)).sum(axis=1) == 1).all()
+
+
+# ------------------------------------------------------------------ the input pipeline's device tail
+U8_N = 4096 * 256 + 77                    # past the 4 096-workgroup cap of ew_grid: the grid-stride loop takes a second turn
+
+
+@pytest.mark.parametrize("scale,shift", [(2.0, -1.0), (1.0, 0.0)], ids=['cifar', 'mnist'])
+def test_u8_affine(scale, shift):
+    """tg_u8_affine_f32: float(x) / 255 * scale + shift (Input_Pipeline/cifar10Dataset.py:52-60: x / 255 * 2 - 1; MNIST: x / 255) — all 256 byte
+    values, a source at an odd byte offset, n past the grid cap.  Bit-exact against the fp32 host expression: the division is correctly
+    rounded on both sides, and both scales are powers of two, so the product is exact and a contraction of `* scale + shift` into an FMA
+    could not change a bit (the library is built with -ffp-contract=off in any case)."""
+    L = lib()
+    rng = np.random.default_rng(int(scale))
+    src = rng.integers(0, 256, U8_N + 1).astype(np.uint8)
+    src[1:257] = np.arange(256)
+    src[-256:] = np.arange(256)[::-1]
+    sd = torch.from_numpy(src).cuda()
+    out = guarded(U8_N)
+    L.call('tg_u8_affine_f32', C.c_void_p(sd.data_ptr() + 1), out.ptr, U8_N, scale, shift, st())
+    ref = src[1:].astype(np.float32) / np.float32(255) * np.float32(scale) + np.float32(shift)
+    assert ref.dtype == np.float32 and len(np.unique(src[1:])) == 256
+    assert_bits(finish(out), ref, "u8_affine")
+
+
+@pytest.mark.parametrize("k,n", [(1, U8_N), (10, 104900), (100, 10500)])
+def test_onehot_i32(k, n):
+    """tg_onehot_i32_f32: out[r][j] = (labels[r] == j); labels -1 and k give an all-zero row; n * k past the grid cap of ew_grid."""
+    L = lib()
+    assert n * k > 4096 * 256
+    rng = np.random.default_rng(k)
+    lab = rng.integers(0, k, n).astype(np.int32)
+    lab[3], lab[4], lab[n - 1], lab[n - 2] = -1, k, k - 1, -1
+    ld = torch.from_numpy(lab).cuda()
+    out = guarded(n * k)
+    L.call('tg_onehot_i32_f32', C.c_void_p(ld.data_ptr()), out.ptr, n, k, st())
+    ref = (lab[:, None] == np.arange(k)[None, :]).astype(np.float32)
+    assert not ref[3].any() and not ref[4].any() and ref[n - 1, k - 1] == 1
+    assert_bits(finish(out, (n, k)), ref, "onehot_i32")

@@ -1,6 +1,7 @@
 """Per-kernel float64 tests of the stand-alone loss heads of csrc/loss.hip (the Train_base helper methods, Training/train_base.py:43-57,
 75-84: softmax cross-entropy, sigmoid cross-entropy, entropy and balance entropy; restated as in oracle.tf_ops.softmax_ce_mean, bce_mean,
-entropy, balance_entropy) and of minibatch discrimination (csrc/mbd.hip, Model/modle_base.py:110-128) called directly.
+entropy, balance_entropy), of the discriminator head with its three terms (tg_d_loss_terms_f32), of the squared row difference
+(tg_sqdiff_rows_loss_f32, train_base.py:299) and of minibatch discrimination (csrc/mbd.hip, Model/modle_base.py:110-128) called directly.
 
 The heads are single-workgroup loops: n = 1, 255, 256, 257 and 1000 rows; logits up to |z| = 80 (no inf / NaN: the stable forms
 max(z,0) - z t + log1p(exp(-|z|)) and m + log sum exp(l - m) are what the kernels compute); accumulate = 1 adds onto an existing
@@ -229,3 +230,79 @@ def test_minibatch_discrimination_kernels(case):
     close(got_db, g.sum(0), np.abs(g).sum(0), "db")
     if n > 1:
         assert rejected(got_db, g[:-1].sum(0), np.abs(g).sum(0))
+
+
+def test_d_loss_terms():
+    """tg_d_loss_terms_f32 on 700 rows in uneven thirds (the 256-thread row loop takes three turns): terms = {BCE(real, 1), .5 BCE(fake, 0),
+    .5 BCE(unl, 0)} (means over their rows) against float64 to the reduction bound, each with the negative control that drops the last row
+    of its group; loss and dlogits are the bits tg_d_loss_f32 writes on the same input; dlogits' padding up to ld_d = 4 is exactly 0."""
+    L = lib()
+    rng = np.random.default_rng(77)
+    groups = [(230, 1.0, 1.0), (250, 0.0, 0.5), (220, 0.0, 0.5)]                  # rows, target, weight
+    n, ld, ld_d = sum(g[0] for g in groups), 3, 4
+    z = np.full((n, ld), np.nan, np.float32)
+    v = np.clip(rng.standard_normal(n) * 30, -80, 80)
+    v[::17], v[::13] = 80.0, -80.0
+    ends = np.cumsum([g[0] for g in groups])
+    v[ends - 1] = [-3.0, 3.0, 3.0]                                                # the last row of each group has a large term
+    z[:, 0] = v.astype(np.float32)
+    zd = dev(z)
+    dz, loss, terms = guarded(n * ld_d), guarded(1), guarded(3)
+    L.call('tg_d_loss_terms_f32', ptr(zd), ld, groups[0][0], groups[1][0], groups[2][0], dz.ptr, ld_d, loss.ptr, terms.ptr, st())
+    dz0, loss0 = guarded(n * ld_d), guarded(1)
+    L.call('tg_d_loss_f32', ptr(zd), ld, groups[0][0], groups[1][0], groups[2][0], dz0.ptr, ld_d, loss0.ptr, st())
+    got_dz, got_terms = finish(dz, (n, ld_d)), finish(terms)
+    assert_bits(got_dz, finish(dz0, (n, ld_d)), "dlogits of d_loss_terms vs d_loss")
+    assert_bits(finish(loss), finish(loss0), "loss of d_loss_terms vs d_loss")
+    assert (bits(got_dz[:, 1:]) == 0).all(), "padding not zeroed"
+    z64, total, total_mag = f8(z[:, 0]), 0.0, 0.0
+    for i, (rows, t, w) in enumerate(groups):
+        x = z64[ends[i] - rows:ends[i]]
+        term = w / rows * (np.maximum(x, 0) - x * t + np.log1p(np.exp(-np.abs(x))))
+        mag = w / rows * (np.maximum(x, 0) + np.abs(x * t) + np.log1p(np.exp(-np.abs(x))))
+        close(got_terms[i], term.sum(), mag.sum(), "terms[%d]" % i)
+        assert rejected(got_terms[i], term[:-1].sum(), mag.sum()), "the bound on terms[%d] does not reject the mean without the last row" % i
+        total, total_mag = total + term.sum(), total_mag + mag.sum()
+    close(finish(loss), total, total_mag, "loss")
+
+
+@pytest.mark.parametrize("k", [1, 10, 100])
+@pytest.mark.parametrize("pad", [0, 3])
+@pytest.mark.parametrize("acc", [0, 1])
+def test_sqdiff_rows_loss(k, pad, acc):
+    """tg_sqdiff_rows_loss_f32: T = mean_n sum_k (a - b)^2 (train_base.py:299), loss = {w T, T}, da = 2 w (a - b) / n written or added, db = -da;
+    ld == k and ld > k; each of da and db may be NULL.  The loss is a reduction (TOL of the sum of the terms, negative control = without the
+    last row); the gradients are pointwise with K = 4 on |g| (a - b, the product with 2 w, the division 2) plus one rounding and the
+    existing value's magnitude when accumulating; the padding is zeroed only when not accumulating."""
+    L = lib()
+    n, w = 37, np.float32(0.3)
+    ld_a, ld_b, ld_da, ld_db = k + pad, k + 2 * pad, k + pad, k + 2 * pad
+    rng = np.random.default_rng(k + pad + acc)
+    a, b = np.full((n, ld_a), np.nan, np.float32), np.full((n, ld_b), np.nan, np.float32)
+    a[:, :k], b[:, :k] = rng.standard_normal((n, k)), rng.standard_normal((n, k))
+    a[-1, :k] = b[-1, :k] + 2                                                       # a large last row: the negative control drops it
+    d = f8(a[:, :k]) - f8(b[:, :k])
+    terms = (d * d).sum(1) / n
+    g = 2 * f8(w) * d / n
+    for with_da, with_db in ((True, True), (True, False), (False, True)):
+        bufs = {}
+        for name, ld, on in (('da', ld_da, with_da), ('db', ld_db, with_db)):
+            g0 = np.full((n, ld), np.nan, np.float32)
+            if acc:
+                g0[:, :k] = (rng.standard_normal((n, k)) * 1e-2).astype(np.float32)
+            bufs[name] = (guarded(n * ld, fill=g0) if on else None, g0, ld)
+        loss = guarded(2)
+        L.call('tg_sqdiff_rows_loss_f32', ptr(dev(a)), ld_a, ptr(dev(b)), ld_b, n, k, float(w), bufs['da'][0].ptr if with_da else None, ld_da, acc,
+               bufs['db'][0].ptr if with_db else None, ld_db, acc, loss.ptr, st())
+        lv = finish(loss)
+        close(lv[1], terms.sum(), terms.sum(), "T")
+        close(lv[0], f8(w) * terms.sum(), f8(w) * terms.sum(), "w T")
+        assert rejected(lv[1], terms[:-1].sum(), terms.sum()), "the bound does not reject the mean without the last row"
+        for name, sign in (('da', 1.0), ('db', -1.0)):
+            buf, g0, ld = bufs[name]
+            if buf is None:
+                continue
+            got = finish(buf, (n, ld), owned=np.broadcast_to(np.arange(ld) < k, (n, ld)) if acc else None)
+            ref = sign * g + (f8(g0[:, :k]) if acc else 0)
+            assert_pointwise(got[:, :k], ref, np.abs(g) + (np.abs(f8(g0[:, :k])) if acc else 0), 4 + acc, name)
+            check_padding(got, g0, k, acc)

@@ -21,7 +21,8 @@ The fused mean-only-BN family at the widths where its shared workgroup tail (csr
 group, 256 row lanes), 12 (85 lanes, one idle thread), 300 (3 lanes, 31 idle threads), 512 (2 lanes), and 256 column groups x one lane
 (tg_actgrad_bias_f32 at ld_out = 1024); the ragged segments add one-row segments, segments shorter than the lane count and more workgroups
 than replicas.  Every statistics workgroup there owns at most CHUNK = 32 rows, so a term of a column sum meets at most CHUNK - 1 fp32
-additions before the fp64 atomics: that is the R in the pointwise bounds of dx below."""
+additions before the fp64 atomics: that is the R in the pointwise bounds of dx below (tests/test_gpu_stats_chunk.py runs the same kernels at
+CHUNK = 64, the chunk of a tensor of more than 65 536 rows)."""
 import ctypes as C
 
 import numpy as np

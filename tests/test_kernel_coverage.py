@@ -36,16 +36,8 @@ NOT_KERNELS = {
 
 # kernels whose only GPU test calls them through the package function that owns the call, held there to a float64 restatement:
 # entry point -> (test, package file that calls the entry point by name, reason).  Each is a candidate for a direct per-kernel test.
-THROUGH_WRAPPER = {
-    "tg_d_loss_terms_f32": ("test_gpu_loss_variants.py::test_loss_variant_values_and_gradients", "Training/train_base.py",
-                            "the loss-variant terms (train_base.py:156-574) against oracle/loss_variants.py, value and gradient"),
-    "tg_sqdiff_rows_loss_f32": ("test_gpu_loss_variants.py::test_loss_variant_values_and_gradients", "Training/train_base.py",
-                                "the loss-variant terms (train_base.py:156-574) against oracle/loss_variants.py, value and gradient"),
-    "tg_u8_affine_f32": ("test_gpu_pipeline.py::test_device_tail_is_bit_identical_to_the_host_expression", "Input_Pipeline/tfrecordDataset.py",
-                         "the input pipeline's device tail, bit-identical to the host expression"),
-    "tg_onehot_i32_f32": ("test_gpu_pipeline.py::test_device_tail_is_bit_identical_to_the_host_expression", "Input_Pipeline/tfrecordDataset.py",
-                          "the input pipeline's device tail, bit-identical to the host expression"),
-}
+# Empty: every kernel entry point has a direct test.
+THROUGH_WRAPPER = {}
 PKG = os.path.join(ROOT, "tensorflow-implementation-of-triple-gan_amd")
 
 
