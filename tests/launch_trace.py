@@ -76,6 +76,8 @@ class TraceContext(Context):
 
 
 class Tracer(object):
+    launches = True            # False on a runner that computes the case without launches (tests/ops_reference.py): no trace to assert on
+
     def __init__(self, **ctx_kw):
         self.trace = []
         self.cx = TraceContext(self.trace, **ctx_kw)
@@ -196,6 +198,19 @@ def case(expect=(), absent=(), variants=None):
 BOTH_MFMA = {'': {}, '_bf16mfma': dict(mfma_dtype='bf16')}
 BOTH_SIDE = {'': {}, '_side': dict(wgrad_side=True)}
 
+# A second, ragged shape per case body (odd n, h != w, unequal segments, channel counts that are no multiple of the tile where the route
+# admits them): the bodies below take it as an optional argument, the default is the recorded shape.  tests/test_ops_reference.py runs
+# every entry through the Tracer and check_route (a shape that falls off its route fails there, without a GPU), tests/test_gpu_ops_routes.py
+# holds the numbers of both shapes to float64.  Keys are the bodies' names: every variant of a body takes the same second shape.
+RAGGED = {}
+
+
+def ragged(*shape):
+    def deco(fn):
+        RAGGED[fn.__name__] = shape
+        return fn
+    return deco
+
 
 def names(trace):
     return [e if isinstance(e, str) else e[0] for e in trace]
@@ -244,18 +259,21 @@ def fwd_bwd(tr, build, seed_ld=None):
 
 @case(expect=['tg_filter_prep_f32', 'tg_igemm_f32', 'tg_actgrad_bias_f32', 'tg_wgrad_f32', 'tg_igemm_multi_f32', 'tg_filter_grad_tail_multi_f32'],
       absent=['tg_wn_scale_f32', 'tg_actgrad_f32'], variants=BOTH_MFMA)
-def conv_plain(tr):
-    fwd_bwd(tr, lambda: conv(tr, tr.x(4, 8, 8, 32), 64, act='lrelu'))
+@ragged(3, 6, 10, 42, 138)
+def conv_plain(tr, shape=(4, 8, 8, 32, 64)):
+    fwd_bwd(tr, lambda: conv(tr, tr.x(*shape[:4]), shape[4], act='lrelu'))
 
 
 @case(expect=['tg_wn_scale_f32', 'tg_filter_prep_f32', 'tg_igemm_f32', 'tg_actgrad_bias_f32', 'tg_wgrad_f32', 'tg_filter_grad_tail_multi_f32'])
-def conv_wn_bias(tr):
-    fwd_bwd(tr, lambda: conv(tr, tr.x(4, 8, 8, 32), 64, wn=True, act='lrelu'))
+@ragged(5, 7, 9, 74, 48)
+def conv_wn_bias(tr, shape=(4, 8, 8, 32, 64)):
+    fwd_bwd(tr, lambda: conv(tr, tr.x(*shape[:4]), shape[4], wn=True, act='lrelu'))
 
 
 @case(expect=['tg_filter_prep_f32', 'tg_igemm_f32', 'tg_actgrad_bias_f32', 'tg_wgrad_f32', 'tg_igemm_multi_f32'])
-def conv_dense(tr):
-    fwd_bwd(tr, lambda: conv(tr, tr.x(4, 1, 1, 64), 32, k=1, act='relu'))
+@ragged(5, 1, 1, 74, 48)
+def conv_dense(tr, shape=(4, 1, 1, 64, 32)):
+    fwd_bwd(tr, lambda: conv(tr, tr.x(*shape[:4]), shape[4], k=1, act='relu'))
 
 
 @case(expect=['tg_igemm_f32', 'tg_colstats_f32', 'tg_wgrad_f32', 'tg_igemm_multi_f32'], absent=['tg_actgrad_f32', 'tg_actgrad_bias_f32'])
@@ -297,24 +315,28 @@ def conv_packed_concat(tr):
 
 
 @case(expect=['tg_igemm_labels_f32', 'tg_actgrad_bias_f32', 'tg_wgrad_f32'], absent=['tg_igemm_f32', 'tg_cond_concat_f32'], variants=BOTH_MFMA)
-def conv_labels(tr):
-    lab = tr.t('labels', 4 * 10)
-    fwd_bwd(tr, lambda: ops.cond_concat(conv(tr, tr.x(4, 8, 8, 32), 64, act='lrelu', concat=(lab, 10)), lab, 10))
+@ragged(3, 6, 10, 42, 96)
+def conv_labels(tr, shape=(4, 8, 8, 32, 64)):
+    lab = tr.t('labels', shape[0] * 10)
+    fwd_bwd(tr, lambda: ops.cond_concat(conv(tr, tr.x(*shape[:4]), shape[4], act='lrelu', concat=(lab, 10)), lab, 10))
 
 
 @case(expect=['tg_igemm_f32', 'tg_cond_concat_f32'], absent=['tg_igemm_labels_f32'])
-def conv_concat_not_fused(tr):
+@ragged(3, 5, 7, 74, 138)
+def conv_concat_not_fused(tr, shape=(4, 8, 8, 32, 48)):
     """c_out is no multiple of 32: the convolution cannot append the label channels, cond_concat runs its own launch"""
-    lab = tr.t('labels', 4 * 10)
-    fwd_bwd(tr, lambda: ops.cond_concat(conv(tr, tr.x(4, 8, 8, 32), 48, act='lrelu', concat=(lab, 10)), lab, 10))
+    lab = tr.t('labels', shape[0] * 10)
+    fwd_bwd(tr, lambda: ops.cond_concat(conv(tr, tr.x(*shape[:4]), shape[4], act='lrelu', concat=(lab, 10)), lab, 10))
 
 
 @case(expect=['tg_igemm_bnstat_f32', 'tg_bn_train_apply_f32', 'tg_bn_train_bwd_act_f32', 'tg_wgrad_f32', 'tg_igemm_multi_f32'],
       absent=['tg_igemm_f32', 'tg_bn_train_f32', 'tg_actgrad_f32', 'tg_actgrad_bias_f32', 'tg_bn_train_bwd_f32'], variants=BOTH_MFMA)
-def conv_bnstat_into_batch_norm(tr):
+@ragged(4, 8, 16, 42, 64, (1, 3))
+def conv_bnstat_into_batch_norm(tr, shape=(4, 8, 8, 32, 64, (2, 2))):
     """conv2d(bn_stats) -> batch_norm_train through bn_sums; backward: the batch norm folds act' and the bias gradient (bias_sink), the
     convolution takes its gradient as the pre-activation gradient (grad_is_dpre)"""
-    fwd_bwd(tr, lambda: bn(tr, conv(tr, tr.x(4, 8, 8, 32), 64, act='relu', bn_stats=True, segments=[2, 2]), segments=[2, 2]))
+    segs = list(shape[5])
+    fwd_bwd(tr, lambda: bn(tr, conv(tr, tr.x(*shape[:4]), shape[4], act='relu', bn_stats=True, segments=segs), segments=segs))
 
 
 @case(expect=['tg_igemm_f32', 'tg_bn_train_f32', 'tg_bn_train_bwd_act_f32'], absent=['tg_igemm_bnstat_f32', 'tg_bn_train_apply_f32'])
@@ -332,21 +354,23 @@ BF16_STORE = {'': dict(mfma_dtype='bf16', act_dtype='bf16')}
 
 @case(expect=['tg_bn_train_bf16', 'tg_igemm_bf16in_bf16', 'tg_wgrad_bf16in_bf16', 'tg_igemm_bnbwdstat_bf16'], absent=['tg_igemm_bf16', 'tg_wgrad_bf16'],
       variants=BF16_STORE)
-def conv_bf16_input_plain(tr):
+@ragged(3, 8, 32, 64, 128)
+def conv_bf16_input_plain(tr, shape=(4, 8, 8, 32, 64)):
     def build():
-        h = bn(tr, tr.x(4, 8, 8, 32), out_bf16=True)
+        h = bn(tr, tr.x(*shape[:4]), out_bf16=True)
         assert h.dtype == 'bf16'
-        return conv(tr, h, 64, act='relu')
+        return conv(tr, h, shape[4], act='relu')
     fwd_bwd(tr, build)
 
 
 @case(expect=['tg_igemm_bnstat_bf16', 'tg_bn_train_apply_bf16', 'tg_igemm_bnstat_bf16in_bf16', 'tg_bn_train_apply_f32', 'tg_wgrad_bf16in_bf16',
               'tg_igemm_bnbwdstat_bf16'], variants=BF16_STORE)
-def conv_bf16_input_bnstat(tr):
+@ragged(3, 8, 32, 32, 64, 128)
+def conv_bf16_input_bnstat(tr, shape=(4, 8, 8, 32, 32, 64)):
     def build():
-        h = bn(tr, conv(tr, tr.x(4, 8, 8, 32), 32, p='l1.', act='relu', bn_stats=True), p='bn1.', out_bf16=True)
+        h = bn(tr, conv(tr, tr.x(*shape[:4]), shape[4], p='l1.', act='relu', bn_stats=True), p='bn1.', out_bf16=True)
         assert h.dtype == 'bf16'
-        return bn(tr, conv(tr, h, 64, p='l2.', act='relu', bn_stats=True), p='bn2.')
+        return bn(tr, conv(tr, h, shape[5], p='l2.', act='relu', bn_stats=True), p='bn2.')
     fwd_bwd(tr, build)
 
 
@@ -354,46 +378,53 @@ def conv_bf16_input_bnstat(tr):
 
 @case(expect=['tg_wn_scale_f32', 'tg_igemm_colsum_f32', 'tg_mobn_apply_f32', 'tg_mobn_bwd_f32', 'tg_wgrad_f32', 'tg_igemm_multi_f32'],
       absent=['tg_igemm_f32', 'tg_mobn_finalize_f32', 'tg_mobn_center_f32'], variants=BOTH_MFMA)
-def mobn_fused(tr):
-    fwd_bwd(tr, lambda: conv(tr, tr.x(4, 8, 8, 32), 32, wn=True, mobn=True, act='lrelu', segments=[2, 2]))
+@ragged(4, 8, 16, 42, 64, (1, 3))
+def mobn_fused(tr, shape=(4, 8, 8, 32, 32, (2, 2))):
+    fwd_bwd(tr, lambda: conv(tr, tr.x(*shape[:4]), shape[4], wn=True, mobn=True, act='lrelu', segments=list(shape[5])))
 
 
 @case(expect=['tg_igemm_colsum_f32', 'tg_mobn_apply_pool_f32', 'tg_maxpool2_bwd_actsum_f32', 'tg_mobn_center_f32'],
       absent=['tg_mobn_apply_f32', 'tg_maxpool2_fwd_f32', 'tg_mobn_bwd_f32'])
-def mobn_fused_pool(tr):
-    mask = tr.t('keep', 4 * 4 * 4 * 32)
-    fwd_bwd(tr, lambda: conv(tr, tr.x(4, 8, 8, 32), 32, wn=True, mobn=True, act='lrelu', pool=(mask, 1.25)))
+@ragged(3, 4, 12, 42, 32)
+def mobn_fused_pool(tr, shape=(4, 8, 8, 32, 32)):
+    n, h, w, _, co = shape
+    mask = tr.t('keep', n * (h // 2) * (w // 2) * co)
+    fwd_bwd(tr, lambda: conv(tr, tr.x(*shape[:4]), co, wn=True, mobn=True, act='lrelu', pool=(mask, 1.25)))
 
 
 @case(expect=['tg_igemm_colsum_f32', 'tg_mobn_apply_f32', 'tg_maxpool2_fwd_f32', 'tg_maxpool2_bwd_actsum_f32', 'tg_mobn_center_f32'],
       absent=['tg_mobn_apply_pool_f32'])
-def mobn_pool_odd_map(tr):
-    mask = tr.t('keep', 4 * 3 * 3 * 32)
-    fwd_bwd(tr, lambda: conv(tr, tr.x(4, 7, 7, 32), 32, wn=True, mobn=True, act='lrelu', pool=(mask, 1.25)))
+def mobn_pool_odd_map(tr, shape=(4, 7, 7, 32, 32)):
+    n, h, w, _, co = shape
+    mask = tr.t('keep', n * (h // 2) * (w // 2) * co)
+    fwd_bwd(tr, lambda: conv(tr, tr.x(*shape[:4]), co, wn=True, mobn=True, act='lrelu', pool=(mask, 1.25)))
 
 
 @case(expect=['tg_igemm_colsum_f32', 'tg_mobn_apply_f32', 'tg_igemm_actsum_f32', 'tg_mobn_center_f32', 'tg_mobn_bwd_f32'], variants=BOTH_MFMA)
-def mobn_two_layers_grad_fused(tr):
+@ragged(3, 8, 16, 42, 64, 32)
+def mobn_two_layers_grad_fused(tr, shape=(4, 8, 8, 32, 32, 64)):
     """the second layer's input-gradient launch applies the first layer's act' and sums the columns (grad_fused -> tg_mobn_center_f32)"""
     def build():
-        h = conv(tr, tr.x(4, 8, 8, 32), 32, p='l1.', wn=True, mobn=True, act='lrelu')
-        return conv(tr, h, 64, p='l2.', wn=True, mobn=True, act='lrelu')
+        h = conv(tr, tr.x(*shape[:4]), shape[4], p='l1.', wn=True, mobn=True, act='lrelu')
+        return conv(tr, h, shape[5], p='l2.', wn=True, mobn=True, act='lrelu')
     fwd_bwd(tr, build)
 
 
 @case(expect=['tg_igemm_f32', 'tg_colstats_f32', 'tg_mobn_finalize_f32', 'tg_seg_scale_shift_act_f32', 'tg_mobn_bwd_f32', 'tg_igemm_multi_f32'],
       absent=['tg_igemm_colsum_f32'])
-def mobn_unfused_stride2(tr):
+@ragged(3, 6, 10, 42, 64)
+def mobn_unfused_stride2(tr, shape=(4, 8, 8, 32, 32)):
     """stride 2: no fused statistics; the input gradient is one launch over the four parity descriptors"""
-    fwd_bwd(tr, lambda: conv(tr, tr.x(4, 8, 8, 32), 32, stride=2, wn=True, mobn=True, act='lrelu'))
+    fwd_bwd(tr, lambda: conv(tr, tr.x(*shape[:4]), shape[4], stride=2, wn=True, mobn=True, act='lrelu'))
     multi = [e for e in tr.trace if e[0] == 'tg_igemm_multi_f32']
-    assert len(multi) == 1 and multi[0][2] == 4 and len(multi[0][1]) == 4
+    assert not tr.launches or (len(multi) == 1 and multi[0][2] == 4 and len(multi[0][1]) == 4)
 
 
 @case(expect=['tg_igemm_f32', 'tg_mobn_finalize_f32', 'tg_seg_scale_shift_act_f32', 'tg_mobn_bwd_finalize_f32', 'tg_seg_actgrad_shift_f32'],
       absent=['tg_igemm_colsum_f32', 'tg_mobn_bwd_f32'])
-def mobn_unfused_c48(tr):
-    fwd_bwd(tr, lambda: conv(tr, tr.x(4, 8, 8, 32), 48, wn=True, mobn=True, act='lrelu'))
+@ragged(3, 6, 10, 42, 138, (1, 2))
+def mobn_unfused_c48(tr, shape=(4, 8, 8, 32, 48, (4,))):
+    fwd_bwd(tr, lambda: conv(tr, tr.x(*shape[:4]), shape[4], wn=True, mobn=True, act='lrelu', segments=list(shape[5]) if len(shape[5]) > 1 else None))
 
 
 @case(expect=['tg_igemm_f32', 'tg_mobn_finalize_f32', 'tg_mobn_bwd_finalize_f32', 'tg_seg_actgrad_shift_f32'], absent=['tg_igemm_colsum_f32', 'tg_mobn_bwd_f32'])
@@ -427,14 +458,15 @@ def bwd_actgrad_colstats_wide(tr):
 
 
 @case(expect=['tg_actgrad_f32', 'tg_wgrad_f32'], absent=['tg_actgrad_bias_f32', 'tg_colstats_f32'])
-def bwd_actgrad_no_bias_gradient(tr):
-    fwd_bwd(tr, lambda: conv(tr, tr.x(4, 8, 8, 32), 64, act='lrelu', bias_grad=False))
+@ragged(3, 6, 10, 42, 138)
+def bwd_actgrad_no_bias_gradient(tr, shape=(4, 8, 8, 32, 64)):
+    fwd_bwd(tr, lambda: conv(tr, tr.x(*shape[:4]), shape[4], act='lrelu', bias_grad=False))
 
 
-def _bn_then(tr, consumers):
+def _bn_then(tr, consumers, shape=(4, 8, 8, 32, 64)):
     def build():
-        h = bn(tr, tr.x(4, 8, 8, 32))
-        ys = [conv(tr, h, 64, p='c%d.' % k, act='lrelu') for k in range(consumers)]
+        h = bn(tr, tr.x(*shape[:4]))
+        ys = [conv(tr, h, shape[4], p='c%d.' % k, act='lrelu') for k in range(consumers)]
         for y in ys[:-1]:
             tr.seed(y)
         return ys[-1]
@@ -442,16 +474,17 @@ def _bn_then(tr, consumers):
 
 
 @case(expect=['tg_bn_train_f32', 'tg_igemm_bnbwdstat_f32', 'tg_bn_train_bwd_f32'], absent=['tg_igemm_multi_f32'], variants=BOTH_MFMA)
-def bwd_bnbwdstat(tr):
-    fwd_bwd(tr, _bn_then(tr, 1))
-    assert [e[15] for e in tr.trace if e[0] == 'tg_bn_train_bwd_f32'] == [2]             # the epilogue's sums, marked as taken
+@ragged(3, 8, 16, 64, 138)
+def bwd_bnbwdstat(tr, shape=(4, 8, 8, 32, 64)):
+    fwd_bwd(tr, _bn_then(tr, 1, shape))
+    assert not tr.launches or [e[15] for e in tr.trace if e[0] == 'tg_bn_train_bwd_f32'] == [2]             # the epilogue's sums, marked as taken
 
 
 @case(expect=['tg_igemm_bnbwdstat_f32', 'tg_igemm_multi_f32', 'tg_bn_train_bwd_f32'])
 def bwd_bnbwdstat_invalidated(tr):
     """a second consumer adds to the batch norm's output gradient: the first launch's sums are dropped, the batch norm takes its own"""
     fwd_bwd(tr, _bn_then(tr, 2))
-    assert [e[15] for e in tr.trace if e[0] == 'tg_bn_train_bwd_f32'] == [0]
+    assert not tr.launches or [e[15] for e in tr.trace if e[0] == 'tg_bn_train_bwd_f32'] == [0]
 
 
 @case(expect=['tg_igemm_actsum_f32', 'tg_igemm_multi_f32', 'refused'], absent=['tg_mobn_center_f32'])
@@ -490,8 +523,9 @@ FG_VARIANTS = {s + w: dict(wgrad_side=bool(s)) for s in ('', '_side') for w in (
 
 
 @case(expect=['tg_wgrad_f32', 'tg_filter_grad_tail_multi_f32'], absent=['tg_slab_reduce_f32', 'tg_wn_bwd_f32'], variants=FG_VARIANTS)
-def filter_grad_deferred(tr):
-    _fg(tr, (4, 8, 8, 32, 64, 3), wn=_wn_variant(tr))
+@ragged(3, 6, 10, 64, 96, 3)
+def filter_grad_deferred(tr, shape=(4, 8, 8, 32, 64, 3)):
+    _fg(tr, shape, wn=_wn_variant(tr))
 
 
 @case(expect=['tg_wgrad_f32', 'tg_slab_reduce_f32'], absent=['tg_filter_grad_tail_multi_f32'], variants=FG_VARIANTS)
@@ -501,8 +535,9 @@ def filter_grad_wide(tr):
 
 
 @case(expect=['tg_wgrad_f32', 'tg_slab_reduce_f32'], absent=['tg_filter_grad_tail_multi_f32', 'side-begin'], variants=FG_VARIANTS)
-def filter_grad_immediate(tr):
-    _fg(tr, (4, 8, 8, 32, 64, 3), wn=_wn_variant(tr), defer=False)
+@ragged(5, 7, 9, 32, 160, 3)
+def filter_grad_immediate(tr, shape=(4, 8, 8, 32, 64, 3)):
+    _fg(tr, shape, wn=_wn_variant(tr), defer=False)
 
 
 @case(expect=['tg_wgrad_f32', 'tg_slab_reduce_f32'], absent=['tg_filter_grad_tail_multi_f32', 'side-begin'], variants=FG_VARIANTS)
@@ -533,8 +568,9 @@ def deconv(tr, x, c_out, p='', wn=False, grads=True, **kw):
 
 @case(expect=['tg_deconv_merge_prep_f32', 'tg_filter_prep_f32', 'tg_igemm_f32', 'tg_actgrad_bias_f32', 'tg_wgrad_f32', 'tg_filter_grad_tail_multi_f32'],
       absent=['tg_igemm_multi_f32', 'tg_deconv5x5s2_narrow_wgrad_f32', 'tg_deconv5x5s2_narrow_dgrad_f32'])
-def deconv_merged(tr):
-    fwd_bwd(tr, lambda: deconv(tr, tr.x(2, 4, 4, 32), 3, act='tanh'))
+@ragged(3, 3, 5, 42, 5)
+def deconv_merged(tr, shape=(2, 4, 4, 32, 3)):
+    fwd_bwd(tr, lambda: deconv(tr, tr.x(*shape[:4]), shape[4], act='tanh'))
 
 
 @case(expect=['tg_deconv_merge_prep_f32', 'tg_igemm_f32', 'tg_actgrad_bias_f32', 'tg_wgrad_f32'], absent=['tg_igemm_multi_f32'])
@@ -555,19 +591,22 @@ def deconv_narrow_backward(tr):
 
 @case(expect=['tg_filter_prep_f32', 'tg_igemm_multi_f32', 'tg_actgrad_bias_f32', 'tg_wgrad_f32', 'tg_igemm_f32', 'tg_filter_grad_tail_multi_f32'],
       absent=['tg_deconv_merge_prep_f32'], variants=BOTH_MFMA)
-def deconv_unmerged(tr):
-    fwd_bwd(tr, lambda: deconv(tr, tr.x(2, 4, 4, 64), 32, act='relu'))
+@ragged(3, 3, 5, 42, 48)
+def deconv_unmerged(tr, shape=(2, 4, 4, 64, 32)):
+    fwd_bwd(tr, lambda: deconv(tr, tr.x(*shape[:4]), shape[4], act='relu'))
 
 
 @case(expect=['tg_wn_scale_tab_f32', 'tg_filter_prep_f32', 'tg_igemm_multi_f32', 'tg_wgrad_f32', 'tg_slab_reduce_f32', 'tg_wn_bwd_tab_f32'],
       absent=['tg_filter_grad_tail_multi_f32'])
-def deconv_weight_normalised(tr):
-    fwd_bwd(tr, lambda: deconv(tr, tr.x(2, 4, 4, 64), 32, act='relu', wn=True))
+@ragged(3, 5, 3, 74, 48)
+def deconv_weight_normalised(tr, shape=(2, 4, 4, 64, 32)):
+    fwd_bwd(tr, lambda: deconv(tr, tr.x(*shape[:4]), shape[4], act='relu', wn=True))
 
 
 @case(expect=['tg_igemm_multi_f32', 'tg_bn_train_f32', 'tg_bn_train_bwd_act_f32', 'tg_wgrad_f32'], absent=['tg_actgrad_bias_f32', 'tg_actgrad_f32'])
-def deconv_into_batch_norm(tr):
-    fwd_bwd(tr, lambda: bn(tr, deconv(tr, tr.x(2, 4, 4, 64), 32, act='relu')))
+@ragged(3, 3, 5, 42, 64)
+def deconv_into_batch_norm(tr, shape=(2, 4, 4, 64, 32)):
+    fwd_bwd(tr, lambda: bn(tr, deconv(tr, tr.x(*shape[:4]), shape[4], act='relu')))
 
 
 @case(expect=['tg_actgrad_f32', 'tg_igemm_f32'], absent=['tg_actgrad_bias_f32', 'tg_wgrad_f32'])
@@ -630,11 +669,13 @@ def grad_penalty_rows(tr):
 # ================================================================== the remaining ops
 
 @case(expect=['tg_colstats_f32', 'tg_mobn_finalize_f32', 'tg_seg_scale_shift_act_f32', 'tg_mobn_bwd_finalize_f32', 'tg_seg_actgrad_shift_f32', 'tg_actgrad_f32'])
-def op_mean_only_batch_norm(tr):
+@ragged(5, 3, 7, 42)
+def op_mean_only_batch_norm(tr, shape=(4, 4, 4, 32)):
     for train in (True, False):
         tr.mark('train %s' % train)
         p = 't%d.' % train
-        fwd_bwd(tr, lambda: ops.mean_only_batch_norm(tr.x(4, 4, 4, 32), tr.t(p + 'pop', 32), tr.t(p + 'b', 32), tr.t(p + 'b_grad', 32), train=train))
+        c = shape[3]
+        fwd_bwd(tr, lambda: ops.mean_only_batch_norm(tr.x(*shape), tr.t(p + 'pop', c), tr.t(p + 'b', c), tr.t(p + 'b_grad', c), train=train))
 
 
 @case(expect=['tg_bn_eval_finalize_f32', 'tg_seg_scale_shift_act_f32'])
@@ -644,12 +685,13 @@ def op_batch_norm_eval(tr):
 
 
 @case(expect=['tg_bn_train_f32', 'tg_bn_moving_update_f32', 'tg_bn_train_bwd_f32'])
-def op_batch_norm_train(tr):
+@ragged(5, 3, 7, 42, (2, 3))
+def op_batch_norm_train(tr, shape=(4, 4, 4, 32, (2, 2))):
     """stand-alone (its own statistics launch), relu_input, in a kept forward pass whose moving-statistics update is replayed"""
     with tr.phase() as cx:
         replay = []
         with cx.sub_tape(('net',), replay=replay) as tape:
-            y = bn(tr, tr.x(4, 4, 4, 32), relu_input=True, segments=[2, 2])
+            y = bn(tr, tr.x(*shape[:4]), relu_input=True, segments=list(shape[4]))
         for fn in replay:
             fn()
         tr.seed(y)
@@ -702,13 +744,15 @@ def op_pooling_pointwise(tr):
 
 
 @case(expect=['tg_colstats_f32', 'tg_bn_finalize_f32', 'tg_seg_scale_shift_act_f32', 'tg_bn_bwd_finalize_f32', 'tg_bn_bwd_apply_f32'])
-def op_batch_norm_moments(tr):
+@ragged(5, 3, 7, 42)
+def op_batch_norm_moments(tr, shape=(4, 4, 4, 32)):
+    c = shape[3]
     for k, grads in enumerate((True, False)):
         tr.mark('grads %s' % grads)
         p = 'm%d.' % k
-        fwd_bwd(tr, lambda: ops.batch_norm_moments(tr.x(4, 4, 4, 32), tr.t(p + 'scale', 32), tr.t(p + 'beta', 32), tr.t(p + 'pm', 32), tr.t(p + 'pv', 32),
-                                                   1e-5, 0.9, True, scale_grad=tr.t(p + 'sg', 32) if grads else None,
-                                                   beta_grad=tr.t(p + 'bg', 32) if grads else None))
+        fwd_bwd(tr, lambda: ops.batch_norm_moments(tr.x(*shape), tr.t(p + 'scale', c), tr.t(p + 'beta', c), tr.t(p + 'pm', c), tr.t(p + 'pv', c),
+                                                   1e-5, 0.9, True, scale_grad=tr.t(p + 'sg', c) if grads else None,
+                                                   beta_grad=tr.t(p + 'bg', c) if grads else None))
 
 
 @case(expect=['tg_igemm_f32', 'tg_minibatch_disc_fwd_f32', 'tg_minibatch_disc_bwd_f32', 'tg_pad_add_f32', 'tg_wgrad_f32'])
@@ -739,11 +783,14 @@ def run_all():
     return out
 
 
-def run_case(name, monkeypatch):
+def run_case(name, monkeypatch, shape=None):
     c = CASES[name]
     tr = Tracer(**c.ctx_kw).install(monkeypatch)
     tr.variant = name
-    c.fn(tr)
+    if shape is None:
+        c.fn(tr)
+    else:
+        c.fn(tr, shape)
     return json.loads(json.dumps(tr.trace))                # what the fixture holds: lists, dicts, numbers, strings
 
 
