@@ -634,6 +634,35 @@ int tg_entropy_terms_f32(const float* logits, int ld, int n, int k, float w_h, f
                          void* stream);
 /* counters[0] += #correct, counters[1] += n (tf.metrics.accuracy, Training/Train_goodGAN.py:428-447). */
 int tg_accuracy_count_f32(const float* logits, int ld, const float* labels, int n, int k, float* counters, void* stream);
+/* Per-class evaluation report of a classifier (tg.metrics.ClassifierReport, Train.evaluate_report).  logits: DEVICE
+ * [n][ld] floats, labels: DEVICE [n][ld_y] floats (one-hot, or any scores); columns 0..k-1 of both are read, columns k.. never are (they
+ * may hold anything).  Per row r, with l = the logit row:
+ *   t, p        the arg-max of the label row and of the logit row, by tg_accuracy_count_f32's scan: start at 0, move to j only on
+ *               strictly greater — ties go to the lowest index, a NaN never wins (and a NaN at index 0 is never left)
+ *   confusion[t*k + p] += 1                                       (DEVICE, k*k int64; EVERY row: trace / sum is the accuracy that
+ *                                                                  tg_accuracy_count_f32 counts, for any input)
+ *   a row with a non-finite logit among its k: nonfinite[0] += 1 (DEVICE, 1 int64), and nothing below
+ *   rank = #{j : l_j > l_t} + #{j < t : l_j == l_t}               (0 exactly when p == t)
+ *   rank_hist[min(rank, nr-1)] += 1                               (DEVICE, nr int64)
+ *   m = l_p, s = sum_j exp((double)l_j - (double)m), conf = 1 / s (fp64; conf = the soft-max probability of p)
+ *   sums[0] += log(s) + ((double)m - (double)l_t)                 (NLL;   DEVICE, 2 doubles)
+ *   sums[1] += sum_j (exp(l_j - m) / s - [j == t])^2              (Brier score)
+ *   b = min(nb-1, (int)(conf * nb)):  bin_count[b] += 1, bin_correct[b] += (p == t), bin_conf[b] += conf
+ *                                                                 (DEVICE, nb int64, nb int64, nb doubles)
+ * ACCUMULATED into the caller's buffers, which the caller zeroes before the first call; any number of calls in stream order.  The
+ * integer outputs are integer atomics (exact in any order).  Nothing floating-point is atomic: launch 1 (one wavefront per row; the sums
+ * over the classes are per-lane partial sums in column order, then a fixed cross-lane tree) leaves each row's {NLL, Brier, conf, bin}
+ * in the workspace, launch 2 adds them — thread T of a workgroup the rows T, 256 + T, ... in ascending order, then a fixed tree over
+ * the 256 — and accumulates into sums / bin_conf.  Both grids are functions of n alone, so every output is bit-identical from run to
+ * run, on any stream.  2 <= k <= 1024, ld >= k, ld_y >= k, 1 <= nr <= 32, 1 <= nb <= 64, n >= 0; anything else, a NULL pointer or a
+ * workspace smaller than the query's answer is TG_ERR_INVALID before any launch.  n = 0 is a no-op (no launch; the pointers may be
+ * NULL).  The outputs are 8-byte aligned.  workspace: caller-owned scratch of at least tg_eval_report_workspace_bytes(n, k) bytes (a
+ * host query; 0 for n = 0, < 0 for a bad n or k), 16-byte aligned, needs no initialisation, nothing beyond that size is written.
+ * Every logit and label is read once: 8 n k bytes. */
+int64_t tg_eval_report_workspace_bytes(int n, int k);
+int tg_eval_report_f32(const float* logits, int ld, const float* labels, int ld_y, int n, int k, int nr, int nb, int64_t* confusion,
+                       int64_t* rank_hist, int64_t* bin_count, int64_t* bin_correct, double* bin_conf, double* sums, int64_t* nonfinite,
+                       void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- optimiser ------------------------------------------------------------------------------------ */
 /* TF-form Adam over a flat buffer (Training/train_base.py:91-97); *step_dev is incremented first, lr read from device;

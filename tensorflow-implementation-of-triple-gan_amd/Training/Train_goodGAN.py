@@ -24,9 +24,9 @@ import numpy as np
 import torch
 
 from config import Config
-from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, check_act_dtype, check_clip_norm, check_eval_ema, check_loss,  # noqa: F401
-                              check_mfma_dtype, check_num_classes, check_optimizer, check_sample_manifold_k, check_sample_metrics, check_wn_init,
-                              check_zca, cla_lr, opt, resolve)
+from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, check_act_dtype, check_clip_norm, check_eval_ema, check_eval_report,  # noqa: F401
+                              check_loss, check_mfma_dtype, check_num_classes, check_optimizer, check_sample_manifold_k, check_sample_metrics,
+                              check_wn_init, check_zca, cla_lr, opt, resolve)
 from Training.train_base import Train_base, clip_workspace_floats
 from tg import dist as tgdist
 from tg import executor, lib, ops
@@ -71,6 +71,7 @@ class Train(Train_base):
         self.wn_initialised = None       # {network: layers initialised} once data_dependent_init() has run (config.WN_INIT = 'data')
         self.zca_source = None           # config.ZCA = 'fit' resolved by train(): 'files' | 'fit' (rank 0) | 'broadcast' (other ranks)
         self._metric_latents = None      # (z, y) host arrays of sample_metrics(), drawn once per trainer from config.SEED
+        self.last_reports = {}           # config.EVAL_REPORT: the last epoch tail's report dicts {'val', 'val_ema', 'g'} (_tail_metrics)
         self._hist_runs = {}             # network -> (store layout key, tg.summary.StoreHistograms): see histograms()
         self.summary_train = self.summary_val = None
         if o.summary and log_dir and self.rank == 0:          # :37-41
@@ -503,9 +504,11 @@ class Train(Train_base):
         """the weights a forward-only classifier pass reads: the variables, or (ema) their EMA shadows — Context.reading_shadows."""
         return self.cx.reading_shadows('classifier') if ema else contextlib.nullcontext()
 
-    def evaluate(self, batches, ema=False):
+    def evaluate(self, batches, ema=False, report=None):
         """streaming accuracy of argmax C_real_logits vs argmax y over test batches with train=False (:295-351, :428-447).
         batches: iterable of (x [n,h,w,c], y onehot [n,k]) host arrays.  Returns accuracy.
+        report: a tg.metrics.ClassifierReport that every batch is also added to, from the same logits (one more
+        tg_eval_report_f32 call per batch); None: the pass issues what it always did.
         ema: evaluate the averaged classifier — every trainable variable read from its EMA shadow (ParamStore.ema: decay 0.9999 per
         C-update, no bias correction), pop_mean / batch-norm moving statistics from the store as they are: what the reference's getter
         (nn.py:98-110) would have returned had it been passed, since ema.apply covered c_vars only.  The pass leaves no
@@ -521,7 +524,23 @@ class Train(Train_base):
                 with cx.rng_scoped('val/C'):
                     logits, _ = m.classifier(xa, False)
                 metric = self._accuracy_metric(ya, logits, metric)[0]        # what _metric (:428-447) counts; its one-hot prediction output is not needed here
+                if report is not None:
+                    report.add(ya, logits, cx.stream)
         return float(metric) if metric is not None else 0.0
+
+    def _new_report(self):
+        """an empty tg.metrics.ClassifierReport for this trainer's classifier."""
+        from tg import metrics as tgm
+        return tgm.ClassifierReport(self.options.num_classes, self.cx.device)
+
+    def evaluate_report(self, batches, ema=False):
+        """evaluate's pass with the per-class report on top -> the dict of tg.metrics.report_from_counts: confusion matrix,
+        per-class recall / precision / F1, balanced accuracy, macro F1, top-5 accuracy, NLL, Brier score, ECE and the reliability table.
+        One pass: its `accuracy` (trace / sum of the confusion matrix) is what evaluate returns on the same batches, bit for bit — the
+        kernel takes both arg-maxes by tg_accuracy_count_f32's scan.  Leaves the trainer's state as evaluate leaves it."""
+        report = self._new_report()
+        self.evaluate(batches, ema=ema, report=report)
+        return report.result()
 
     def _sample_latents(self, n_batches):
         """(z [n_batches * B, Z_DIM], y one-hot of class i % NUM_CLASSES) of sample_metrics: drawn once per trainer from a RandomState
@@ -551,8 +570,21 @@ class Train(Train_base):
         written — weights, shadows, optimiser slots, step counters and the Philox state are what they were.  The pass runs under
         phases of its own ('metrics', 'metrics_g': unrecorded, buffer keys of their own), so no buffer a launch plan or graph names
         is touched.  Synchronises the device.
-        sample_manifold_metrics is this pass with the k-nearest-neighbour metrics on top."""
+        sample_manifold_metrics is this pass with the k-nearest-neighbour metrics on top, sample_metrics_report with the per-class
+        reports of both sides."""
         return self._sample_metrics_pass(batches, n_samples, ema, None)[0]
+
+    def sample_metrics_report(self, batches, n_samples, ema=False, manifold_k=None):
+        """sample_metrics (manifold_k None) or sample_manifold_metrics with the per-class report of each side on top ->
+        their keys, then `val_report` and `g_report`, two tg.metrics.report_from_counts dicts: the real side's as evaluate_report gives
+        it; the generated side's with the class asked for as target, over the n_samples rows that were scored — its per-class recall
+        says which classes the generator fails to render.  The same pass with one more tg_eval_report_f32 call per batch; what
+        sample_metrics says about the trainer's state holds unchanged.  A method of its own, as sample_manifold_metrics is: the
+        parameter lists of those two are pinned by tests."""
+        from tg import metrics as tgm
+        if manifold_k is not None:
+            manifold_k = tgm.check_k(manifold_k, 'sample_metrics_report: manifold_k')
+        return self._sample_metrics_pass(batches, n_samples, ema, manifold_k, (self._new_report(), self._new_report()))[0]
 
     def sample_manifold_metrics(self, batches, n_samples, manifold_k, ema=False, return_banks=False):
         """sample_metrics plus the k-nearest-neighbour manifold metrics -> its five keys, then `precision`, `recall`,
@@ -568,8 +600,11 @@ class Train(Train_base):
         out, banks = self._sample_metrics_pass(batches, n_samples, ema, manifold_k)
         return (out, banks) if return_banks else out
 
-    def _sample_metrics_pass(self, batches, n_samples, ema, manifold_k):
-        """the pass behind sample_metrics (manifold_k None) and sample_manifold_metrics -> (result, (real bank, fake bank) or None)."""
+    def _sample_metrics_pass(self, batches, n_samples, ema, manifold_k, reports=None):
+        """the pass behind sample_metrics (manifold_k None), sample_manifold_metrics and sample_metrics_report -> (result, (real bank,
+        fake bank) or None).  reports: None, or (real side, generated side) tg.metrics.ClassifierReport accumulators, either of which
+        may be None: each is added the rows its side's accuracy counts, and the result carries `val_report` / `g_report` for those
+        given."""
         from tg import metrics as tgm
         cx, m, c = self.cx, self.model, self.config
         n_samples = int(n_samples)
@@ -582,6 +617,7 @@ class Train(Train_base):
         z, y = self._sample_latents(n_batches)
         kept = {net: st.s.clone() for net, st in cx.stores.items()}
         real = fake = bank_real = bank_fake = None
+        rep_real, rep_fake = reports if reports is not None else (None, None)
         try:
             acc_real = None
             for xb, yb in batches:                                   # (the moments are sized by the first feature seen)
@@ -595,6 +631,8 @@ class Train(Train_base):
                     with cx.rng_scoped('val/C'):
                         logits, fm = m.classifier(xa, False)
                     acc_real = self._accuracy_metric(ya, logits, acc_real)[0]
+                    if rep_real is not None:
+                        rep_real.add(ya, logits, cx.stream)
                     if real is None:
                         real = tgm.FeatureMoments(fm.c, cx.device)
                     real.add(fm, cx.stream)
@@ -613,6 +651,8 @@ class Train(Train_base):
                     with cx.rng_scoped('val/C'):
                         logits, fm = m.classifier(xg, False)
                     acc_fake = self._accuracy_metric(yg.view_rows(0, take), logits.view_rows(0, take), acc_fake)[0]
+                    if rep_fake is not None:
+                        rep_fake.add(yg.view_rows(0, take), logits.view_rows(0, take), cx.stream)
                     if fake is None:
                         fake = tgm.FeatureMoments(fm.c, cx.device)
                     fake.add(fm.view_rows(0, take), cx.stream)
@@ -629,6 +669,10 @@ class Train(Train_base):
                 finite = real is not None and all(bool(np.isfinite(a).all()) for a in (sum_r, gram_r, sum_f, gram_f))
                 out.update(tgm.manifold_metrics(bank_real, bank_fake, manifold_k, cx.stream) if finite
                            else dict.fromkeys(tgm.MANIFOLD_KEYS, float('nan')))
+            if rep_real is not None:
+                out['val_report'] = rep_real.result()
+            if rep_fake is not None:
+                out['g_report'] = rep_fake.result()
         finally:
             for net, s_before in kept.items():
                 cx.stores[net].s.copy_(s_before)
@@ -741,33 +785,62 @@ class Train(Train_base):
     def _tail_metric_tags(self):
         """the epoch tail's extra records and val-summary scalars, in order: 'val_accuracy_ema' with config.EVAL_EMA, 'g_class_accuracy'
         and 'frechet_distance' with config.SAMPLE_METRICS, then 'precision', 'recall', 'density' and 'coverage' with
-        config.SAMPLE_MANIFOLD_K (none with all off)."""
+        config.SAMPLE_MANIFOLD_K (none with all off).  config.EVAL_REPORT appends, behind all of those, REPORT_TAGS with a 'val_' prefix
+        ('val_top5_accuracy' only with more than five classes), with EVAL_EMA the same again with an '_ema' suffix, and with
+        SAMPLE_METRICS 'g_worst_class_accuracy'."""
         from tg import metrics as tgm
         o = self.options
-        return ((('val_accuracy_ema',) if o.eval_ema else ()) + (('g_class_accuracy', 'frechet_distance') if o.sample_metrics else ())
+        tags = ((('val_accuracy_ema',) if o.eval_ema else ()) + (('g_class_accuracy', 'frechet_distance') if o.sample_metrics else ())
                 + (tgm.MANIFOLD_KEYS if o.sample_metrics and o.sample_manifold_k else ()))
+        if o.eval_report:
+            val = tuple('val_' + k for k in self._report_keys())
+            tags += val + (tuple(k + '_ema' for k in val) if o.eval_ema else ()) + (('g_worst_class_accuracy',) if o.sample_metrics else ())
+        return tags
 
-    def _tail_metrics(self, NNIO, init_op_val):
+    REPORT_TAGS = ('balanced_accuracy', 'macro_f1', 'nll', 'ece', 'top5_accuracy')
+
+    def _report_keys(self):
+        """the keys of an evaluation report that the epoch tail records: REPORT_TAGS, top-5 accuracy only where it is defined."""
+        return tuple(k for k in self.REPORT_TAGS if k != 'top5_accuracy' or self.options.num_classes > 5)
+
+    def _tail_metrics(self, NNIO, init_op_val, main_report=None):
         """{tag: value} of _tail_metric_tags() for this epoch tail, after sync_running_state: every replica computes the same numbers
         from the same averaged state, the same validation split and the same latents — no collective.  With both settings on, the
         averaged accuracy comes out of the metrics pass itself (its real side is evaluate's pass with the shadows): the split is run
-        once for both."""
+        once for both.
+        main_report (config.EVAL_REPORT): the ClassifierReport the epoch's evaluate pass filled.  The pass that reads the shadows
+        and the generated side of the metrics pass fill one more each — no forward pass is added — and self.last_reports keeps the
+        report dicts {'val', 'val_ema', 'g'} of those that ran."""
         o, out = self.options, {}
+        reports = {'val': main_report.result()} if o.eval_report else None
         if o.sample_metrics:
             init_op_val()
-            if o.sample_manifold_k:
-                sm = self.sample_manifold_metrics(NNIO.val_batches(), o.sample_metrics, o.sample_manifold_k, ema=o.eval_ema)
-            else:
-                sm = self.sample_metrics(NNIO.val_batches(), o.sample_metrics, ema=o.eval_ema)
+            # the pass of sample_metrics / sample_manifold_metrics; its real side reads the shadows only with EVAL_EMA, and only then
+            # does its report differ from the main one
+            pair = (self._new_report() if o.eval_ema else None, self._new_report()) if o.eval_report else None
+            sm = self._sample_metrics_pass(NNIO.val_batches(), o.sample_metrics, o.eval_ema, o.sample_manifold_k, pair)[0]
             if o.eval_ema:
                 out['val_accuracy_ema'] = sm['val_accuracy']
             out['g_class_accuracy'], out['frechet_distance'] = sm['g_class_accuracy'], sm['frechet_distance']
             if o.sample_manifold_k:                                                     # SAMPLE_MANIFOLD_K: the same pass, four more numbers
                 from tg import metrics as tgm
                 out.update((k, sm[k]) for k in tgm.MANIFOLD_KEYS)
+            if o.eval_report:
+                reports.update([('g', sm['g_report'])] + ([('val_ema', sm['val_report'])] if o.eval_ema else []))
         elif o.eval_ema:
             init_op_val()
-            out['val_accuracy_ema'] = self.evaluate(NNIO.val_batches(), ema=True)
+            ema_report = self._new_report() if o.eval_report else None
+            out['val_accuracy_ema'] = self.evaluate(NNIO.val_batches(), ema=True, report=ema_report)
+            if o.eval_report:
+                reports['val_ema'] = ema_report.result()
+        if o.eval_report:
+            keys = self._report_keys()
+            out.update(('val_' + k, reports['val'][k]) for k in keys)
+            if o.eval_ema:
+                out.update(('val_' + k + '_ema', reports['val_ema'][k]) for k in keys)
+            if o.sample_metrics:                               # the generated side's target is the class asked for: recall = class accuracy
+                out['g_worst_class_accuracy'] = reports['g']['worst_class_recall']
+            self.last_reports = reports
         return out
 
     # ------------------------------------------------------------------ the reference's entry point
@@ -826,10 +899,11 @@ class Train(Train_base):
             d_loss, g_loss, c_loss = self.training_statistics() if iters > 0 else self.losses()        # :280-285
             init_op_val()
             self.sync_running_state()
-            acc = self.evaluate(NNIO.val_batches())
+            main_report = self._new_report() if self.options.eval_report else None    # EVAL_REPORT: filled by the same pass
+            acc = self.evaluate(NNIO.val_batches()) if main_report is None else self.evaluate(NNIO.val_batches(), report=main_report)
             rec = dict(epoch=epoch + start_epoch, d_loss=d_loss, g_loss=g_loss, c_loss=c_loss, val_accuracy=acc,
                        images_per_sec=iters * c.BATCH_SIZE * self.world / dt)
-            extra = self._tail_metrics(NNIO, init_op_val)                              # EVAL_EMA / SAMPLE_METRICS: {} with both off
+            extra = self._tail_metrics(NNIO, init_op_val, main_report)                 # EVAL_EMA / SAMPLE_METRICS / EVAL_REPORT: {} with all off
             rec.update(extra)
             history.append(rec)
             samples = None
@@ -872,6 +946,10 @@ class Train(Train_base):
                                       **{k + '_grad_norm': v[0] for k, v in norms.items() if v is not None}), rec['epoch'],
                                  histograms=hists, images=imgs)
         self.summary_val.write(dict(dict(val_accuracy=rec['val_accuracy']), **{k: rec[k] for k in self._tail_metric_tags()}), rec['epoch'])
+        if o.eval_report:                                                              # the matrices behind the scalars, int64 [K, K]
+            for name, key in (('confusion', 'val'), ('g_confusion', 'g')):
+                if key in self.last_reports:
+                    np.save(os.path.join(self.summary_val.log_dir, '%s_%04d.npy' % (name, rec['epoch'])), self.last_reports[key]['confusion'])
         return samples
 
     def _save_sample_grid(self, samples, epoch):
@@ -1011,6 +1089,8 @@ def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
             tmp_config.SAMPLE_METRICS = FLAGS.sample_metrics
         if getattr(FLAGS, 'sample_manifold_k', None) is not None:      # --sample-manifold-k K (check_sample_manifold_k; flag objects
             tmp_config.SAMPLE_MANIFOLD_K = FLAGS.sample_manifold_k     # without the attribute are common: getattr with a default)
+        if getattr(FLAGS, 'eval_report', None) is not None:            # --eval-report (check_eval_report)
+            tmp_config.EVAL_REPORT = FLAGS.eval_report
     if epochs is not None:
         tmp_config.EPOCHS = epochs
     tmp_config.SAMPLE_DIR = os.path.join(_root_dir(), "Training", tmp_config.SAMPLE_DIR)

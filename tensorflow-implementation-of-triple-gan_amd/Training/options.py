@@ -173,6 +173,20 @@ def check_eval_ema(config):
     raise ValueError("EVAL_EMA must be None, True or False, got %r" % (v,))
 
 
+def check_eval_report(config):
+    """config.EVAL_REPORT: off (default; also when the attribute is absent — config.Config does not declare it) or on: the epoch tail's
+    evaluation passes also accumulate the classifier's per-class report (tg.metrics.ClassifierReport) and record
+    `val_balanced_accuracy`, `val_macro_f1`, `val_nll`, `val_ece` and, with more than five classes, `val_top5_accuracy` — with EVAL_EMA
+    the same for the averaged weights, with SAMPLE_METRICS `g_worst_class_accuracy`.  -> bool.  Needs no device; ValueError for
+    anything but None, a bool or 0 / 1."""
+    v = getattr(config, 'EVAL_REPORT', None)
+    if v is None:
+        return False
+    if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and v in (0, 1)):
+        return bool(v)
+    raise ValueError("EVAL_REPORT must be None, True or False, got %r" % (v,))
+
+
 def check_sample_metrics(config):
     """config.SAMPLE_METRICS: None (default; also when the attribute is absent — config.Config does not declare it) or a positive int N:
     the epoch tail scores N generated samples with the run's own classifier and records `g_class_accuracy` and `frechet_distance`
@@ -208,21 +222,24 @@ _Fields = collections.namedtuple('Options', 'mfma_dtype act_dtype num_classes lo
 
 class Options(_Fields):
     """the record resolve() returns.  Its tuple fields are the settings config.Config declares a default for (and NO_GRAD_BUCKETS);
-    `wn_init`, `eval_ema`, `sample_metrics` and `sample_manifold_k` (check_wn_init, check_eval_ema, check_sample_metrics,
-    check_sample_manifold_k: settings Config deliberately does not declare) are carried as attributes beside them, so the field
-    list — what _asdict() and unpacking give — stays what it was.  Two records are equal when the fields and these attributes are."""
-    EXTRAS = ('wn_init', 'eval_ema', 'sample_metrics', 'sample_manifold_k')
+    `wn_init`, `eval_ema`, `sample_metrics`, `sample_manifold_k` and `eval_report` (check_wn_init, check_eval_ema,
+    check_sample_metrics, check_sample_manifold_k, check_eval_report: settings Config deliberately does not declare) are carried as
+    attributes beside them, so the field list — what _asdict() and unpacking give — stays what it was.  Two records are equal when the
+    fields and these attributes are."""
+    EXTRAS = ('wn_init', 'eval_ema', 'sample_metrics', 'sample_manifold_k', 'eval_report')
 
-    def __new__(cls, wn_init=None, eval_ema=False, sample_metrics=None, sample_manifold_k=None, **fields):
+    def __new__(cls, wn_init=None, eval_ema=False, sample_metrics=None, sample_manifold_k=None, eval_report=False, **fields):
         self = super(Options, cls).__new__(cls, **fields)
         self.wn_init, self.eval_ema, self.sample_metrics, self.sample_manifold_k = wn_init, eval_ema, sample_metrics, sample_manifold_k
+        self.eval_report = eval_report
         return self
 
     def _extras(self):
         return tuple(getattr(self, k) for k in self.EXTRAS)
 
     def __eq__(self, other):
-        return tuple.__eq__(self, other) and tuple(getattr(other, k, d) for k, d in zip(self.EXTRAS, (None, False, None, None))) == self._extras()
+        return (tuple.__eq__(self, other)
+                and tuple(getattr(other, k, d) for k, d in zip(self.EXTRAS, (None, False, None, None, False))) == self._extras())
 
     def __ne__(self, other):
         return not self == other
@@ -236,7 +253,7 @@ def resolve(config):
     excepted: those stay live, read per iteration).  The string form of ZCA is checked here; against a Dataset, where one is known."""
     check_zca(config)
     return Options(wn_init=check_wn_init(config), eval_ema=check_eval_ema(config), sample_metrics=check_sample_metrics(config),
-                   sample_manifold_k=check_sample_manifold_k(config),
+                   sample_manifold_k=check_sample_manifold_k(config), eval_report=check_eval_report(config),
                    mfma_dtype=check_mfma_dtype(config), act_dtype=check_act_dtype(config), num_classes=check_num_classes(config),
                    loss=check_loss(config), optimizers=check_optimizer(config), clip_norms=check_clip_norm(config),
                    momentum=float(opt(config, 'MOMENTUM')), seed=opt(config, 'SEED'),

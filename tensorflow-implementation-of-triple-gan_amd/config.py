@@ -95,8 +95,14 @@ class Config(object):
     #   SAMPLE_MANIFOLD_K = k (--sample-manifold-k k), an int in 1..16, with SAMPLE_METRICS: the same pass also records the
     #     k-nearest-neighbour `precision`, `recall`, `density` and `coverage` of the samples against the validation split (k = 3 in
     #     Kynkäänniemi et al. 2019; tg_knn_self_f32 / tg_manifold_query_f32).  The radii depend on k and on both counts.
+    #   EVAL_REPORT = True (--eval-report): the evaluation passes of the epoch tail also accumulate the classifier's per-class report
+    #     (tg_eval_report_f32: confusion matrix, rank histogram, calibration bins, NLL; no forward pass is added) and record
+    #     `val_balanced_accuracy`, `val_macro_f1`, `val_nll`, `val_ece`, with NUM_CLASSES > 5 `val_top5_accuracy`; with EVAL_EMA the
+    #     same with an `_ema` suffix; with SAMPLE_METRICS `g_worst_class_accuracy`, the lowest per-class share of generated samples
+    #     classified as asked.  With summaries on, rank 0 writes confusion_<epoch>.npy (and g_confusion_<epoch>.npy) beside the
+    #     validation events (Train.evaluate_report).
     # Absent, None or False: the epoch tail is what it was.  Read by Training/options.check_eval_ema / check_sample_metrics /
-    # check_sample_manifold_k.
+    # check_sample_manifold_k / check_eval_report.
 
     def __init__(self):
         """Set values of computed attributes (config.py:70-73)."""

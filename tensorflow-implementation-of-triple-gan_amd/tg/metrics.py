@@ -1,10 +1,12 @@
 """Generated-sample metrics on classifier features (Train.sample_metrics): the host side of tg_feature_moments_f32
 (include/tg_kernels.h, csrc/moments.hip) and the Fréchet distance between two Gaussians in NumPy float64; the host side of
-tg_knn_self_f32 / tg_manifold_query_f32 (csrc/knn.hip) and the k-nearest-neighbour precision, recall, density and coverage.
+tg_knn_self_f32 / tg_manifold_query_f32 (csrc/knn.hip) and the k-nearest-neighbour precision, recall, density and coverage.  And the
+classifier's own evaluation report (Train.evaluate_report): the host side of tg_eval_report_f32 (csrc/evalreport.hip) —
+ClassifierReport — and the algebra on its counts, report_from_counts.
 
 The device adds up a feature matrix's column sums and Gram matrix in fp64, batch after batch; the host turns them into a mean and a
 covariance once, at the end, and takes the distance — c x c eigenproblems, no scipy.  Importable without a device: torch and the HIP
-library are touched only by FeatureMoments, FeatureBank and manifold_metrics."""
+library are touched only by FeatureMoments, FeatureBank, manifold_metrics and ClassifierReport."""
 import numpy as np
 
 from . import lib
@@ -208,3 +210,128 @@ def manifold_metrics(real_bank, fake_bank, k, stream=None):
     count_fr, _, _ = manifold_query(fake, real, r2_real, stream)
     count_rf, nn_rf, _ = manifold_query(real, fake, r2_fake, stream)
     return manifold_from_counts(k, fake_bank.n, count_fr.cpu().numpy(), count_rf.cpu().numpy(), nn_rf.cpu().numpy(), r2_real.cpu().numpy())
+
+
+# ---- the per-class evaluation report of the classifier (Train.evaluate_report) ------------------------------------------
+MAX_CLASSES = 1024          # tg_eval_report_f32 accepts 2 <= k <= 1024 (Training/options.NUM_CLASSES_RANGE),
+MAX_RANKS = 32              # 1 <= nr <= 32 rank-histogram entries
+MAX_BINS = 64               # and 1 <= nb <= 64 calibration bins
+REPORT_SCALARS = ('n', 'n_nonfinite', 'accuracy', 'top5_accuracy', 'nll', 'brier', 'ece', 'balanced_accuracy', 'macro_f1',
+                  'worst_class_recall', 'worst_class', 'predicted_class_entropy')
+REPORT_ARRAYS = ('support', 'predicted', 'recall', 'precision', 'f1')
+
+
+class ClassifierReport(object):
+    """streaming counts of [n, k] logit batches against their labels on `device`: add() is one tg_eval_report_f32 call into the device
+    accumulators — the int64 confusion matrix [k, k], rank histogram [ranks], calibration bin counts and hits [bins], the non-finite
+    row count, and the fp64 confidence sums [bins] and {NLL, Brier} sums — counts() one device->host copy of all of them.  ranks is
+    clipped to min(ranks, num_classes).  The workspace grows to the largest batch seen and belongs to this object."""
+
+    def __init__(self, num_classes, device, ranks=16, bins=15):
+        import torch
+        k = int(num_classes)
+        if not 2 <= k <= MAX_CLASSES:
+            raise ValueError("ClassifierReport: num_classes must be in 2..%d, got %r" % (MAX_CLASSES, num_classes))
+        if not 1 <= int(ranks) <= MAX_RANKS or not 1 <= int(bins) <= MAX_BINS:
+            raise ValueError("ClassifierReport: ranks must be in 1..%d and bins in 1..%d, got %r and %r" % (MAX_RANKS, MAX_BINS, ranks, bins))
+        self.k, self.device, self.ranks, self.bins, self.n = k, device, min(int(ranks), k), int(bins), 0
+        # one buffer of 8-byte words, so that counts() is one copy: int64 [confusion | rank_hist | bin_count | bin_correct | nonfinite],
+        # then the same storage read as fp64 [bin_conf | sums]
+        sizes = (k * k, self.ranks, self.bins, self.bins, 1, self.bins, 2)
+        self._off = tuple(int(v) for v in np.concatenate([[0], np.cumsum(sizes)]))
+        self.acc = torch.zeros(self._off[-1], dtype=torch.int64, device=device)
+        self.workspace = None
+
+    def reset(self):
+        self.n = 0
+        self.acc.zero_()
+        return self
+
+    def _part(self, i):
+        return self.acc[self._off[i]:self._off[i + 1]]
+
+    def add(self, labels, logits, stream=None):
+        """labels, logits: Acts whose logical shape is [n, k] (h = w = 1), channel strides >= k; the arg-max of both is taken in the
+        kernel, as tg_accuracy_count_f32 takes it."""
+        import torch
+        for what, a in (('labels', labels), ('logits', logits)):
+            if a.h != 1 or a.w != 1 or a.c != self.k or a.dtype != 'f32':
+                raise lib.TgError("ClassifierReport.add: fp32 [n, %d] %s are needed, got [%d, %d, %d, %d] %s" % (self.k, what, a.n, a.h, a.w, a.c, a.dtype))
+        if labels.n != logits.n:
+            raise lib.TgError("ClassifierReport.add: %d label rows for %d logit rows" % (labels.n, logits.n))
+        need = lib.call('tg_eval_report_workspace_bytes', logits.n, self.k)
+        if self.workspace is None or self.workspace.numel() * 8 < need:
+            self.workspace = torch.empty(max((need + 7) // 8, 2), dtype=torch.float64, device=self.device)
+        if stream is None:
+            stream = lib.cur_stream()
+        P = lambda i: lib.ptr(self._part(i))
+        lib.call('tg_eval_report_f32', logits.ptr, logits.ld, labels.ptr, labels.ld, logits.n, self.k, self.ranks, self.bins, P(0), P(1), P(2), P(3),
+                 P(5), P(6), P(4), lib.ptr(self.workspace), self.workspace.numel() * 8, stream)
+        self.n += logits.n
+        return self
+
+    def counts(self):
+        """{confusion [k, k], rank_hist, bin_count, bin_correct, nonfinite: int64; bin_conf, sums: float64} as host arrays — the
+        arguments of report_from_counts (synchronises)."""
+        host = self.acc.cpu().numpy()
+        part = lambda i: host[self._off[i]:self._off[i + 1]].copy()
+        return dict(confusion=part(0).reshape(self.k, self.k), rank_hist=part(1), bin_count=part(2), bin_correct=part(3),
+                    bin_conf=part(5).view(np.float64), sums=part(6).view(np.float64), nonfinite=part(4))
+
+    def result(self):
+        """report_from_counts of what has been added."""
+        return report_from_counts(**self.counts())
+
+
+def report_from_counts(confusion, rank_hist, bin_count, bin_correct, bin_conf, sums, nonfinite):
+    """The classifier's evaluation report from what tg_eval_report_f32 accumulates, in NumPy float64 on the host.
+    confusion [K, K] counts rows by (target, prediction), every row of the pass; the other counts cover the rows whose logits are all
+    finite.  -> dict:
+      n, n_nonfinite            rows counted, and those among them with a non-finite logit
+      accuracy                  trace / sum of confusion (0 for an empty pass, as Train.evaluate)
+      top5_accuracy             sum(rank_hist[:5]) / n_finite; NaN when K <= 5 or the histogram has no more than 5 entries
+      nll, brier                means over the finite rows of -log softmax_t and of sum_j (softmax_j - [j == t])^2
+      ece                       sum_b (n_b / n_finite) |acc_b - conf_b| over the equal-width confidence bins (Guo et al. 2017)
+      support, predicted        [K] rows per target class, rows per predicted class
+      recall, precision, f1     [K]; NaN where the denominator is 0 (recall of an absent class, precision of a never-predicted one)
+      balanced_accuracy         mean recall over the classes with support > 0
+      macro_f1                  mean F1 over the same classes (a present class that is never predicted has F1 0)
+      worst_class_recall, worst_class   the lowest recall among the present classes and the lowest class index attaining it (-1: none)
+      predicted_class_entropy   the entropy of predicted / n over log K: 1 for a uniform prediction histogram, 0 for a collapsed one
+      reliability               [bins, 3]: count, mean confidence, accuracy per bin (NaN in the last two for an empty bin)
+      confusion                 the matrix itself, int64
+    Means over an empty set are NaN."""
+    conf_m = np.asarray(confusion, np.int64)
+    K = conf_m.shape[0]
+    if conf_m.ndim != 2 or conf_m.shape[1] != K or K < 2:
+        raise ValueError("report_from_counts: confusion must be a square [K, K] matrix with K >= 2, got shape %r" % (conf_m.shape,))
+    rank_hist, bin_count, bin_correct = (np.asarray(a, np.int64).reshape(-1) for a in (rank_hist, bin_count, bin_correct))
+    bin_conf, sums = np.asarray(bin_conf, np.float64).reshape(-1), np.asarray(sums, np.float64).reshape(-1)
+    if not (bin_count.shape == bin_correct.shape == bin_conf.shape) or sums.shape != (2,):
+        raise ValueError("report_from_counts: bin_count, bin_correct and bin_conf must have one length and sums two entries")
+    n, n_bad = int(conf_m.sum()), int(np.asarray(nonfinite).reshape(-1)[0])
+    n_fin = int(rank_hist.sum())
+    nan = float('nan')
+    with np.errstate(divide='ignore', invalid='ignore'):
+        diag = np.diag(conf_m).astype(np.float64)
+        support, predicted = conf_m.sum(axis=1), conf_m.sum(axis=0)
+        recall = np.where(support > 0, diag / support, np.nan)
+        precision = np.where(predicted > 0, diag / predicted, np.nan)
+        f1 = np.where(support + predicted > 0, 2.0 * diag / (support + predicted), np.nan)
+        present = support > 0
+        cnt = bin_count.astype(np.float64)
+        mean_conf = np.where(bin_count > 0, bin_conf / cnt, np.nan)
+        acc_b = np.where(bin_count > 0, bin_correct / cnt, np.nan)
+        ece = float(np.sum(np.where(bin_count > 0, cnt / n_fin * np.abs(acc_b - mean_conf), 0.0))) if n_fin > 0 else nan
+        q = predicted[predicted > 0] / float(max(n, 1))
+    worst = int(np.argmin(np.where(present, recall, np.inf))) if present.any() else -1
+    out = dict(n=n, n_nonfinite=n_bad, accuracy=float(np.trace(conf_m)) / max(float(n), 1.0),
+               top5_accuracy=float(rank_hist[:5].sum()) / n_fin if K > 5 and rank_hist.shape[0] > 5 and n_fin > 0 else nan,
+               nll=float(sums[0]) / n_fin if n_fin > 0 else nan, brier=float(sums[1]) / n_fin if n_fin > 0 else nan, ece=ece,
+               balanced_accuracy=float(recall[present].mean()) if present.any() else nan,
+               macro_f1=float(f1[present].mean()) if present.any() else nan,
+               worst_class_recall=float(recall[worst]) if worst >= 0 else nan, worst_class=worst,
+               predicted_class_entropy=float(-(q * np.log(q)).sum() / np.log(K)) if n > 0 else nan)
+    out.update(support=support, predicted=predicted, recall=recall, precision=precision, f1=f1,
+               reliability=np.stack([cnt, mean_conf, acc_b], axis=1), confusion=conf_m)
+    return out
