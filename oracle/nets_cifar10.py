@@ -298,6 +298,46 @@ def discriminator_bwd(P, c, dlogits, rnd, want_weight_grads=True, want_input_gra
     return G, dimage
 
 
+# --------------------------------------------------------------------- kinks
+# Every non-smooth decision of the three backward passes above is read from the cache: the sign of a ReLU / leaky-ReLU output
+# ('<layer>/y' of C and D, 'r<i>' of G: *_bwd_from_out only test y > 0) and the arg-max of a pooling window ('<layer>/pool_idx',
+# 'gpool/idx').  A parity test that wants to compare gradients BEHIND identical decisions takes them from the implementation under test
+# and puts them into the cache between forward and backward (tests/kink_reference.py).
+
+def _kink_kind(key):
+    if key.endswith('idx'):
+        return 'idx'
+    if key.endswith('/y') or (key[0] == 'r' and key[1:].isdigit()):
+        return 'sign'
+    return None
+
+
+def kinks_of(cache):
+    """the cache's own kinks: key -> boolean 'positive' mask (activations) or index array (pools)."""
+    out = {}
+    for k, v in cache.items():
+        kind = _kink_kind(k)
+        if kind == 'sign':
+            out[k] = v > 0
+        elif kind == 'idx':
+            out[k] = v.copy()
+    return out
+
+
+def apply_kinks(cache, kinks):
+    """a copy of `cache` whose backward pass takes the decisions in `kinks` (every kink site of the cache must be given).  The sign
+    carriers become +1 / -1 arrays: nothing but `> 0` is ever asked of them.  kinks_of(cache) reproduces the cache's gradients bit for bit."""
+    out = dict(cache)
+    for k, v in cache.items():
+        kind = _kink_kind(k)
+        if kind is None:
+            continue
+        kk = np.asarray(kinks[k])
+        assert kk.shape == v.shape, (k, kk.shape, v.shape)
+        out[k] = np.where(kk, 1, -1).astype(v.dtype) if kind == 'sign' else kk.astype(v.dtype)
+    return out
+
+
 # ----------------------------------------------------------------------- ZCA
 
 def zca_apply(x, mean, mat):

@@ -296,6 +296,36 @@ def seq_bwd(P, layers, caches, d, y, rnd, want_params=True, dfeat=None):
     return G, d
 
 
+def kink_sites(layers):
+    """indices of the layers whose backward takes a non-smooth decision from its cache: relu / lrelu ('sign') and maxpool ('idx')."""
+    out = {}
+    for i, l in enumerate(layers):
+        if l[0] == 'act' and l[1] in ('relu', 'lrelu'):
+            out[i] = 'sign'
+        elif l[0] == 'maxpool':
+            out[i] = 'idx'
+    return out
+
+
+def kinks_of(layers, caches):
+    """layer index -> boolean 'positive' mask of a relu / lrelu output, or index array of a 2x2 max-pool (see oracle/nets_cifar10.py)."""
+    return {i: (caches[i] > 0) if kind == 'sign' else caches[i][0].copy() for i, kind in kink_sites(layers).items()}
+
+
+def apply_kinks(layers, caches, kinks):
+    """a copy of `caches` whose seq_bwd takes the decisions in `kinks`; kinks_of(layers, caches) reproduces the gradients bit for bit."""
+    out = list(caches)
+    for i, kind in kink_sites(layers).items():
+        kk = np.asarray(kinks[i])
+        if kind == 'sign':
+            assert kk.shape == caches[i].shape, (i, kk.shape, caches[i].shape)
+            out[i] = np.where(kk, 1, -1).astype(caches[i].dtype)
+        else:
+            assert kk.shape == caches[i][0].shape, (i, kk.shape, caches[i][0].shape)
+            out[i] = (kk.astype(caches[i][0].dtype), caches[i][1])
+    return out
+
+
 def commit_bn(P, bn_updates):
     for name, (mm, mv) in bn_updates.items():
         P[name + '/moving_mean'], P[name + '/moving_variance'] = mm, mv

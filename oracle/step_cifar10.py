@@ -44,47 +44,62 @@ def _commit_pop(P, pop_updates):
         P[p + 'meanOnlyBatchNormalization/pop_mean'] = v
 
 
-def d_phase(st, batch, rnd, hyper, zca):
-    """sess.run([d_solver, d_loss]) — Train_goodGAN.py:267."""
+def _kinked(kinks, key, cache):
+    """kinks (tests only): None, or a callable (application key, cache) -> the kink dict nets_cifar10.apply_kinks puts into that
+    application's cache between its forward and its backward pass — the decisions (ReLU signs, pool arg-max) of the implementation under
+    test, so that a parity test compares gradients behind identical kinks.  None: the cache as it is."""
+    return cache if kinks is None else N.apply_kinks(cache, kinks(key, cache))
+
+
+def _onehot(logits, labels, key):
+    """labels (tests only): None, or {key: one-hot} to use INSTEAD of the arg-max of the classifier's logits (see step_goodgan.d_phase)."""
+    return T.argmax_onehot(logits) if labels is None else np.asarray(labels[key], logits.dtype)
+
+
+def d_phase(st, batch, rnd, hyper, zca, kinks=None, labels=None):
+    """sess.run([d_solver, d_loss]) — Train_goodGAN.py:267.  kinks / labels: see _kinked / _onehot (keys 'D_real', 'D_fake', 'D_unl';
+    'unl', 'unl_d')."""
     P = st['P']
     Gimg, _ = N.generator_fwd(P, batch['z_g'], batch['y_g'], moving=P)
     pops = {}
     c_unl, _, _ = N.classifier_fwd(P, N.zca_apply(batch['x_u_c'], *zca), True, rnd['C_unl'], pops)
     c_unl_d, _, _ = N.classifier_fwd(P, N.zca_apply(batch['x_u_d'], *zca), True, rnd['C_unl_d'], pops)
     _commit_pop(P, pops)
+    st['last_logits'] = {'unl': c_unl, 'unl_d': c_unl_d}
     X_P = np.concatenate([batch['x_l_d'], batch['x_u_d']], axis=0)
-    Y_P = np.concatenate([batch['y_l_d'], T.argmax_onehot(c_unl_d)], axis=0)
+    Y_P = np.concatenate([batch['y_l_d'], _onehot(c_unl_d, labels, 'unl_d')], axis=0)
     grads = {}
     total = 0.0
     for key, img, y, target, wgt in (
             ('D_real', X_P, Y_P, 1.0, 1.0),
             ('D_fake', Gimg, batch['y_g'], 0.0, 0.5),
-            ('D_unl', batch['x_u_c'], T.argmax_onehot(c_unl), 0.0, 0.5)):
+            ('D_unl', batch['x_u_c'], _onehot(c_unl, labels, 'unl'), 0.0, 0.5)):
         logits, c = N.discriminator_fwd(P, img, y, rnd[key])
         l, dl = T.bce_mean(logits, np.full_like(logits, target))
         total += wgt * l
-        g, _ = N.discriminator_bwd(P, c, (wgt * dl).astype(logits.dtype), rnd[key])
+        g, _ = N.discriminator_bwd(P, _kinked(kinks, key, c), (wgt * dl).astype(logits.dtype), rnd[key])
         for k, v in g.items():
             grads[k] = grads.get(k, 0) + v
     _adam(st, 'D', grads, hyper['lr'], hyper['beta1'])
     return float(total)
 
 
-def g_phase(st, batch, rnd, hyper):
-    """sess.run([g_solver, g_loss]) — Train_goodGAN.py:270."""
+def g_phase(st, batch, rnd, hyper, kinks=None):
+    """sess.run([g_solver, g_loss]) — Train_goodGAN.py:270.  kinks: see _kinked (keys 'D_fake', 'G')."""
     P = st['P']
     Gimg, gc = N.generator_fwd(P, batch['z_g'], batch['y_g'], moving=P)
     logits, c = N.discriminator_fwd(P, Gimg, batch['y_g'], rnd['D_fake'])
     l, dl = T.bce_mean(logits, np.ones_like(logits))
-    _, dimg = N.discriminator_bwd(P, c, (0.5 * dl).astype(logits.dtype), rnd['D_fake'],
+    _, dimg = N.discriminator_bwd(P, _kinked(kinks, 'D_fake', c), (0.5 * dl).astype(logits.dtype), rnd['D_fake'],
                                   want_weight_grads=False, want_input_grad=True)
-    grads = N.generator_bwd(P, gc, dimg)
+    grads = N.generator_bwd(P, _kinked(kinks, 'G', gc), dimg)
     _adam(st, 'G', grads, hyper['lr'], hyper['beta1'])
     return float(0.5 * l)
 
 
-def c_phase(st, batch, rnd, hyper, zca):
-    """sess.run([c_solver, c_loss]) — Train_goodGAN.py:275 (c_solver includes the EMA apply)."""
+def c_phase(st, batch, rnd, hyper, zca, kinks=None, labels=None):
+    """sess.run([c_solver, c_loss]) — Train_goodGAN.py:275 (c_solver includes the EMA apply).  kinks / labels: see _kinked / _onehot
+    (keys 'C_real', 'C_unl', 'C_unl_rep', 'C_fake'; 'unl')."""
     P = st['P']
     Gimg, _ = N.generator_fwd(P, batch['z_g'], batch['y_g'], moving=P)
     pops = {}
@@ -94,7 +109,8 @@ def c_phase(st, batch, rnd, hyper, zca):
     c_rep, _, cc_rep = N.classifier_fwd(P, x_u_c_z, True, rnd['C_unl_rep'], pops)
     c_fake, _, cc_fake = N.classifier_fwd(P, N.zca_apply(Gimg, *zca), True, rnd['C_fake'], pops)
     _commit_pop(P, pops)
-    d_unl, _ = N.discriminator_fwd(P, batch['x_u_c'], T.argmax_onehot(c_unl), rnd['D_unl'])
+    st['last_logits'] = {'unl': c_unl}
+    d_unl, _ = N.discriminator_fwd(P, batch['x_u_c'], _onehot(c_unl, labels, 'unl'), rnd['D_unl'])
 
     lam1, lam2 = hyper['lambda_1'], hyper['lambda_2']
     l_real, g_real = T.softmax_ce_mean(c_real, batch['y_l_c'])
@@ -109,7 +125,7 @@ def c_phase(st, batch, rnd, hyper, zca):
     grads = {}
     for cache, dl, key in ((cc_real, g_real, 'C_real'), (cc_unl, d_unl_logits, 'C_unl'),
                            (cc_rep, f(lam2) * g_mse_rep, 'C_unl_rep'), (cc_fake, f(lam1) * g_fake, 'C_fake')):
-        g = N.classifier_bwd(P, cache, dl.astype(c_real.dtype), rnd[key])
+        g = N.classifier_bwd(P, _kinked(kinks, key, cache), dl.astype(c_real.dtype), rnd[key])
         for k, v in g.items():
             grads[k] = grads.get(k, 0) + v
     _adam(st, 'C', grads, hyper['cla_lr'], 0.5)

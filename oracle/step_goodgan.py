@@ -24,8 +24,14 @@ def _gen(P, data, b, bn_updates=None):
     return N.seq_fwd(P, N.generator_layers(data), b['z_g'], b['y_g'], {}, True, bn_updates)
 
 
-def d_phase(st, data, b, rnd, hyper, labels=None):
-    """labels (tests only): {'unl': one-hot [U_C,10], 'unl_d': one-hot [U_D,10]} to use INSTEAD of the arg-max of the classifier's logits —
+def _kinked(kinks, key, layers, caches):
+    """kinks (tests only): None, or a callable (application key, layers, caches) -> the kink dict nets_goodgan.apply_kinks puts into that
+    application's caches between its forward and its backward pass (see oracle/step_cifar10.py)."""
+    return caches if kinks is None else N.apply_kinks(layers, caches, kinks(key, layers, caches))
+
+
+def d_phase(st, data, b, rnd, hyper, labels=None, kinks=None):
+    """kinks: see _kinked (keys 'D_real', 'D_fake', 'D_unl').  labels (tests only): {'unl': one-hot [U_C,10], 'unl_d': one-hot [U_D,10]} to use INSTEAD of the arg-max of the classifier's logits —
     lets a parity test give the oracle's discriminator the labels the implementation under test fed its own, when a near-tie arg-max
     (random-init logits, bf16 operand noise) came out differently on the two sides."""
     P = st['P']
@@ -46,14 +52,15 @@ def d_phase(st, data, b, rnd, hyper, labels=None):
         logits, caches, _ = N.seq_fwd(P, DL, img, y, rnd[key], True)
         l, dl = T.bce_mean(logits, np.full_like(logits, target))
         total += wgt * l
-        g, _ = N.seq_bwd(P, DL, caches, (wgt * dl).astype(logits.dtype), y, rnd[key])
+        g, _ = N.seq_bwd(P, DL, _kinked(kinks, key, DL, caches), (wgt * dl).astype(logits.dtype), y, rnd[key])
         for k, v in g.items():
             grads[k] = grads.get(k, 0) + v
     _adam(st, 'D', grads, hyper['lr'], hyper['beta1'])
     return float(total)
 
 
-def g_phase(st, data, b, rnd, hyper):
+def g_phase(st, data, b, rnd, hyper, kinks=None):
+    """kinks: see _kinked (keys 'D_fake', 'G')."""
     P = st['P']
     GL, DL = N.generator_layers(data), N.discriminator_layers(data)
     bnu = {}
@@ -62,13 +69,14 @@ def g_phase(st, data, b, rnd, hyper):
     img = Gimg.reshape((-1,) + N.image_shape(data))
     logits, dc, _ = N.seq_fwd(P, DL, img, b['y_g'], rnd['D_fake'], True)
     l, dl = T.bce_mean(logits, np.ones_like(logits))
-    _, dimg = N.seq_bwd(P, DL, dc, (0.5 * dl).astype(logits.dtype), b['y_g'], rnd['D_fake'], want_params=False)
-    grads, _ = N.seq_bwd(P, GL, gc, dimg.reshape(Gimg.shape), b['y_g'], {})
+    _, dimg = N.seq_bwd(P, DL, _kinked(kinks, 'D_fake', DL, dc), (0.5 * dl).astype(logits.dtype), b['y_g'], rnd['D_fake'], want_params=False)
+    grads, _ = N.seq_bwd(P, GL, _kinked(kinks, 'G', GL, gc), dimg.reshape(Gimg.shape), b['y_g'], {})
     _adam(st, 'G', grads, hyper['lr'], hyper['beta1'])
     return float(0.5 * l)
 
 
-def c_phase(st, data, b, rnd, hyper):
+def c_phase(st, data, b, rnd, hyper, kinks=None, labels=None):
+    """kinks: see _kinked (keys 'C_real', 'C_unl', 'C_fake').  labels: {'unl': one-hot [U_C,10]} instead of the arg-max of C_unl's logits."""
     P = st['P']
     CL, DL = N.classifier_layers(data), N.discriminator_layers(data)
     bnu = {}
@@ -78,7 +86,8 @@ def c_phase(st, data, b, rnd, hyper):
     c_unl, cc_unl, _ = N.seq_fwd(P, CL, b['x_u_c'], None, rnd['C_unl'], True, bnu)
     c_fake, cc_fake, _ = N.seq_fwd(P, CL, gimg, None, rnd['C_fake'], True, bnu)
     N.commit_bn(P, bnu)
-    oh = T.argmax_onehot(c_unl)
+    oh = T.argmax_onehot(c_unl) if labels is None else np.asarray(labels['unl'], c_unl.dtype)
+    st['last_logits'] = {'unl': c_unl}
     d_unl, _, _ = N.seq_fwd(P, DL, b['x_u_c'], oh, rnd['D_unl'], True)
     lam1 = hyper['lambda_1']
     l_real, g_real = T.softmax_ce_mean(c_real, b['y_l_c'])
@@ -91,7 +100,7 @@ def c_phase(st, data, b, rnd, hyper):
     grads = {}
     for caches, dl, key in ((cc_real, g_real, 'C_real'), (cc_unl, f(0.005) * g_unl + f(1e-6) * g_ent + f(1e-3) * g_bal, 'C_unl'),
                             (cc_fake, f(lam1) * g_fake, 'C_fake')):
-        g, _ = N.seq_bwd(P, CL, caches, dl.astype(c_real.dtype), None, rnd[key])
+        g, _ = N.seq_bwd(P, CL, _kinked(kinks, key, CL, caches), dl.astype(c_real.dtype), None, rnd[key])
         for k, v in g.items():
             grads[k] = grads.get(k, 0) + v
     _adam(st, 'C', grads, hyper['cla_lr'], 0.5)

@@ -332,7 +332,14 @@ def _input_grad(cx, L, dpre):
     else:
         x.bn_bwd_sums = None                              # a second contribution to that gradient: the sums of the first alone are not the statistics
         dds = lib.desc_array(dlist)
-        _call('tg_igemm_multi_f32', dds, len(dds), _p(dpre), _p(L.w_hwio), None, gx.ptr, cx.stream)
+        if fresh:
+            _call('tg_igemm_multi_f32', dds, len(dds), _p(dpre), _p(L.w_hwio), None, gx.ptr, cx.stream)
+        else:
+            # x already carries a gradient — a loss seeded it (the pooled feature: feat.grad) or another consumer's backward ran first:
+            # this layer's contribution is ADDED to it (the launch itself only stores), never written over it
+            part = cx.scratch('gxp', gx.rows * gx.ld)
+            _call('tg_igemm_multi_f32', dds, len(dds), _p(dpre), _p(L.w_hwio), None, _p(part), cx.stream)
+            _call('tg_add_f32', gx.ptr, gx.ptr, _p(part), gx.rows * gx.ld, cx.stream)
 
 
 def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=None, mobn=None, segments=None,

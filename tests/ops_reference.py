@@ -567,7 +567,7 @@ class RefOps(object):
                     else:
                         kernel_grad.set(dw)
                 if needs_x:
-                    cx.add_grad(x, conv_dx(dq, wq, x.v.shape, stride, padding))
+                    cx.add_grad(x, conv_dx(dq, wq, x.v.shape, stride, padding), accumulate=True)
             cx.record(bwd)
         return y if pool is None else self.maxpool2_dropout(y, pool[0], pool[1])
 
@@ -929,13 +929,16 @@ class RefContext(object):
         if self.tape is not None:
             self.tape.append(fn)
 
-    def add_grad(self, a, g):
-        """a backward closure (or a loss head) writes g as the gradient of `a`.  tg/ops.py's tape serves chains: every backward launch
-        OVERWRITES its destination and every alias replaces the gradient; nothing accumulates but minibatch_discrimination's skip path.  Where a case body gives an activation a
-        second writer (a seeded output that is also consumed, two consumers of one tensor) the writer that runs last therefore defines
-        the gradient, and that is what this reference restates; the fused paths that cannot tolerate a second writer refuse it
-        (bwd_single_consumer_refusal).  The networks batch the applications of a layer into segments instead of consuming a tensor twice."""
-        a.grad = g
+    def add_grad(self, a, g, accumulate=False):
+        """a backward closure (or a loss head) writes g as the gradient of `a`.  tg/ops.py's tape serves chains: a backward launch
+        OVERWRITES its destination and every alias replaces the gradient, with two exceptions that ADD to a gradient that is already
+        there — minibatch_discrimination's skip path, and (accumulate) the generic input-gradient launch of conv2d / the dense layers
+        (ops._input_grad: the product goes to a scratch buffer and tg_add_f32 adds it, one more float32 rounding), so that a gradient a
+        loss seeded on a layer's input (the classifier's pooled feature) or that another consumer wrote first is not lost.  Where a case
+        body gives an activation a second writer of any other kind the writer that runs last defines the gradient, and that is what
+        this reference restates; the fused paths that cannot tolerate a second writer refuse it (bwd_single_consumer_refusal).  The
+        networks batch the applications of a layer into segments instead of consuming a tensor twice."""
+        a.grad = add(a.grad, g) if (accumulate and a.grad is not None) else g
 
     def mask_of(self, a):
         """the stored forward output of the implementation under test for activation `a` (None: the reference's own)"""

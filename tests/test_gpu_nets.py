@@ -20,7 +20,8 @@ def check_classifier_grad(name, got, ref):
     cut in K segments — values equal to 1e-6 — flipped lrelu'(y) for ONE element of conv2_2's output: that layer's b / g gradient moved in one
     channel (5.4e-2 of the largest element: a bias gradient is a sum over only 1 280 pixels here), its V gradient in that channel's 2 304
     entries, and every layer below by 5e-3 ... 9e-3.  So: GRAD_TOL, or — the flip budget — 6e-2 of the largest element and 2e-2 in L2 (the one moved element
-    of that 256-entry bias gradient is 1.25e-2 of its norm; tests/test_gpu_step.py budgets 5e-2 / 1e-2 at larger batches)."""
+    of that 256-entry bias gradient is 1.25e-2 of its norm; tests/test_gpu_step.py budgets 5e-2 / 1e-2 at larger batches).
+    tests/test_gpu_kink_parity.py runs the same networks with the HIP path's kinks given to the oracle and needs no such budget."""
     d = np.asarray(got, np.float64) - ref
     mx = np.abs(ref).max() + 1e-30
     if np.abs(d).max() <= GRAD_TOL * mx:
