@@ -12,11 +12,9 @@ created in the constructor with the initialisers the reference passes — includ
 `segments=` (extension): the classifier uses full batch norm, whose statistics are per application, so a batched
 call runs the applications one after the other and concatenates the logits.
 """
-import numpy as np
-
 from Model import model_base
 from tg import grad_penalty, ops
-from tg.runtime import Act, ParamStore, ctx
+from tg.runtime import ctx
 
 D_MNIST_DENSE = (1000, 500, 250, 250, 250)                    # d_h0_wndense0 .. d_h4_wndense0 (:93-124), then the head d_h5_wndense0
 D_SVHN_CONVS = [  # name, filters, stride, dropout after, label copies concatenated in front (:126-165)
@@ -28,16 +26,9 @@ GP_MNIST = (grad_penalty.mnist_sweeps, [grad_penalty.weight_normed('d_h%d_wndens
 GP_SVHN = (grad_penalty.conv_sweeps, [grad_penalty.weight_normed(*row) for row in D_SVHN_CONVS], grad_penalty.weight_normed('d_h3_wndense', 1))
 
 
-def _trunc_normal(rng, shape):
-    x = rng.standard_normal(shape)
-    bad = np.abs(x) > 2
-    while bad.any():
-        x[bad] = rng.standard_normal(int(bad.sum()))
-        bad = np.abs(x) > 2
-    return x
-
-
 class Good_GAN(model_base.NN_Base):
+    CONSISTENCY = False        # no second classifier pass on x_u_c, no lambda_2 term (Good_GAN_cifar10 has both)
+
     def __init__(self, config):
         super(Good_GAN, self).__init__(config.BATCH_NORM_DECAY, config.BATCH_NORM_EPSILON)
         self.config = config
@@ -45,7 +36,7 @@ class Good_GAN(model_base.NN_Base):
             raise ValueError("The specified dataset is not yet implemented!")
         self.mnist = config.DATA_NAME == 'mnist'
         self._gp = GP_MNIST if self.mnist else GP_SVHN
-        self._create_variables(getattr(config, 'SEED', 0))
+        self._create_variables(getattr(config, 'SEED', 0), self.param_specs())
 
     # ------------------------------------------------------------------ variables
     def param_specs(self):
@@ -113,37 +104,12 @@ class Good_GAN(model_base.NN_Base):
         bn(c, C + 'c_h3_bn0', k)
         return {'good_generator': g, 'discriminator': d, 'classifier': c}
 
-    def _create_variables(self, seed):
-        cx = ctx()
-        rng = np.random.default_rng(seed)
-        for net, specs in self.param_specs().items():
-            if net in cx.stores:
-                continue
-            st = ParamStore(net, [(n, s, t) for n, s, t, _ in specs], cx.device)
-            for name, shape, _, init in specs:
-                if init == 'n02':
-                    st.set(name, 0.02 + rng.standard_normal(shape))
-                elif init == 'tn02':
-                    st.set(name, 0.02 + _trunc_normal(rng, shape))
-                elif init == 'n05':
-                    st.set(name, 0.05 * rng.standard_normal(shape))
-                elif init == 'xavier':                                   # tf.contrib.layers.xavier_initializer(): uniform, fan_avg
-                    lim = np.sqrt(6.0 / (shape[0] + shape[1]))
-                    st.set(name, rng.uniform(-lim, lim, shape))
-                else:
-                    st.set(name, np.full(shape, init, np.float32))
-            cx.stores[net] = st
-        cx.stores['classifier'].enable_ema()
-
     # ------------------------------------------------------------------ helpers
     def as_image(self, a):
         """common per-image layout for batch concatenation: MNIST images travel flattened ([N,784], as the generator emits them)."""
         if self.mnist and (a.h, a.w) != (1, 1):
             return ops.view(a, 1, 1, a.h * a.w * a.c)
         return a
-
-    def zca(self):
-        return None
 
     # ------------------------------------------------------------------ networks
     def good_generator(self, z, y, reuse=False, init=False):
@@ -170,13 +136,6 @@ class Good_GAN(model_base.NN_Base):
     def good_sampler(self, z, y, reuse=True):
         """:356-426 — the generator graph with reuse."""
         return self.good_generator(z, y, reuse=True)
-
-    def _d_out(self, logits, want_prob):
-        """(tf.nn.sigmoid(logits), logits) (:124,206); no loss differentiates through the sigmoid."""
-        if not want_prob:
-            return None, logits
-        with ctx().no_record():
-            return ops.activation(logits, 'sigmoid'), logits
 
     def discriminator(self, image, y, reuse=False, want_prob=True, init=False):
         """:89-206.  Returns (sigmoid(logits), logits [N,1]); want_prob=False (extension, the trainer's solver runs): (None, logits).
@@ -288,7 +247,7 @@ class Good_GAN(model_base.NN_Base):
         the batch norms in between use batch statistics without moving theirs: only */g and */b change.
         Returns {network: [scopes of the layers initialised]}; the labels the discriminator saw stay in self.wn_init_labels."""
         from tg.batching import concat_acts
-        cx, k = ctx(), self.config.NUM_CLASSES
+        cx = ctx()
         layers = self.WN_INIT_LAYERS
         with cx.assigning_init() as done:
             with cx.rng_scoped('init/G'):
@@ -302,36 +261,12 @@ class Good_GAN(model_base.NN_Base):
             logits, _ = self.classifier(self.as_image(x_u_d), False)
         if ids is not None:
             cx.rng.stream_ids = ids
-        oh = Act(ops.argmax_onehot(logits, k), x_u_d.n, 1, 1, k, k)
+        oh = self._onehot_act(logits)
         self.wn_init_labels = oh
         with cx.assigning_init() as done_d:
             with cx.rng_scoped('init/D'):
                 self.discriminator(concat_acts([self.as_image(x_l_d), self.as_image(x_u_d)]), concat_acts([y_l_d, oh]), want_prob=False, init=True)
-        done = list(done) + list(done_d)
-        return {net: [s for s in done if s.startswith(net + '/')] for net in ('good_generator', 'classifier', 'discriminator')}
-
-    def forward_pass(self, z_g, y_g, x_l_c, y_l_c, x_l_d, y_l_d, x_u_d, x_u_c, train):
-        """:428-472 (evaluation / tests; the trainer runs per-solver sub-graphs)."""
-        from tg.batching import concat_acts
-        cx = ctx()
-        k = self.config.NUM_CLASSES
-        G = self.good_generator(z_g, y_g)
-        parts = [self.as_image(a) for a in (x_l_c, x_u_c, x_u_d, G)]
-        segs = [p.n for p in parts]
-        with cx.rng_scoped(cx.phase + '/C'):
-            logits, _ = self.classifier(concat_acts(parts), train, segments=segs)
-        offs = [int(v) for v in np.cumsum([0] + segs)]
-        C_real, C_unl, C_unl_d, C_fake = [logits.view_rows(offs[i], offs[i + 1]) for i in range(4)]
-        oh_d = Act(ops.argmax_onehot(C_unl_d, k), C_unl_d.n, 1, 1, k, k)
-        oh_u = Act(ops.argmax_onehot(C_unl, k), C_unl.n, 1, 1, k, k)
-        ximg = concat_acts([self.as_image(a) for a in (x_l_d, x_u_d, G, x_u_c)])
-        yall = concat_acts([y_l_d, oh_d, y_g, oh_u])
-        with cx.rng_scoped(cx.phase + '/D'):
-            dp, dl = self.discriminator(ximg, yall)
-        n_p = x_l_d.n + x_u_d.n
-        cut = lambda a: [a.view_rows(0, n_p), a.view_rows(n_p, n_p + G.n), a.view_rows(n_p + G.n, a.n)]
-        (p_real, p_fake, p_unl), (l_real, l_fake, l_unl) = cut(dp), cut(dl)
-        return [G, [p_real, l_real, p_fake, l_fake, p_unl, l_unl], [C_real, C_unl, C_unl_d, C_fake]]
+        return self._by_network(list(done) + list(done_d))
 
 
 def _twice(y):

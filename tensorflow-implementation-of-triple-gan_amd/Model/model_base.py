@@ -9,15 +9,21 @@ inside `with tf.variable_scope(name)` with `name=name`).
 
 Extensions (keyword-only, default = reference behaviour): `activation` fuses the nonlinearity the
 model applies next into the MFMA kernel's epilogue; `narrow` stores only the logical channels.
-Initialisers are applied when the Model creates its variables (see Good_GAN_cifar10.param_specs),
-so `kernel_initializer` is accepted and ignored here.
+Initialisers are applied when the Model creates its variables (NN_Base._create_variables over the model's
+param_specs), so `kernel_initializer` is accepted and ignored here.
+
+NN_Base also carries what the models of this package share above the layers: variable creation, the whole-graph
+forward_pass (steered by the model's CONSISTENCY, as_image and zca()), the discriminator's no-gradient sigmoid output and the
+arg-max one-hot labels.
 
 `init=True` of the _WN_* layers is the reference's live tf.assign branch (modle_base.py:68-71,103-106,150-153): g and b are assigned
 from the moments of the unit-gain pre-activation (eps 1e-10, init_scale honoured) and the layer's value is computed through them
 (NN_Base._wn_init).  The fused layouts (narrow, then_concat) serve init=False; the init runs through the plain one.
 """
+import numpy as np
+
 from tg import ops
-from tg.runtime import ctx
+from tg.runtime import Act, ParamStore, ctx
 
 
 def _act_of(fn):
@@ -36,13 +42,120 @@ def _cat_of(then_concat):
     return (then_concat.t, then_concat.c)
 
 
+def _trunc_normal(rng, shape):
+    """tf.truncated_normal: standard normal draws (float64), those beyond two standard deviations drawn again."""
+    x = rng.standard_normal(shape)
+    bad = np.abs(x) > 2
+    while bad.any():
+        x[bad] = rng.standard_normal(int(bad.sum()))
+        bad = np.abs(x) > 2
+    return x
+
+
+def _fan_in(shape):
+    return shape[-2] * int(np.prod(shape[:-2])) if len(shape) > 2 else shape[0]
+
+
+def _xavier_uniform(rng, shape):
+    """tf.contrib.layers.xavier_initializer(): uniform, fan_avg."""
+    lim = np.sqrt(6.0 / (shape[0] + shape[1]))
+    return rng.uniform(-lim, lim, shape)
+
+
+# initialiser name of a param_specs() row -> float64 draw(rng, shape); a row may also carry a float, the constant the variable starts at
+INITIALISERS = {
+    # tf.random_normal_initializer(0.02) / tf.truncated_normal_initializer(0.02): the MEAN is 0.02, stddev 1.0 (modle_base.py:28,159,248)
+    'n02': lambda rng, shape: 0.02 + rng.standard_normal(shape),
+    'tn02': lambda rng, shape: 0.02 + _trunc_normal(rng, shape),
+    'n05': lambda rng, shape: 0.05 * rng.standard_normal(shape),                                        # nn.py:478
+    'xavier': _xavier_uniform,
+    # variance_scaling_initializer(): factor 2, FAN_IN, truncated normal, std sqrt(1.3*2/fan_in) (Good_GAN_cifar10.py:8-9)
+    'he': lambda rng, shape: _trunc_normal(rng, shape) * np.sqrt(1.3 * 2.0 / _fan_in(shape)),
+}
+
+
 class NN_Base(object):
+    CONSISTENCY = False        # True: forward_pass applies C to x_u_c a second time and returns C_unl_logits_rep (Good_GAN_cifar10.py:232-235)
+    GRAD_BUCKETS = {}          # {network: first variable of every data-parallel gradient bucket after the first} (Good_GAN_cifar10)
+
     def __init__(self, batch_norm_decay=0.9, batch_norm_epsilon=1e-5):
         self._batch_norm_decay = batch_norm_decay
         self._batch_norm_epsilon = batch_norm_epsilon
 
-    def forward_pass(self, x):
-        raise NotImplementedError('forward_pass() is implemented in Model sub classes')
+    def _create_variables(self, seed, specs):
+        """the three networks' variables — specs: the model's param_specs(), {network: [(name, shape, trainable, init)]} in TF creation
+        order — each in a ParamStore of the active Context, initialised from ONE np.random.default_rng(seed) network after network and
+        row after row (INITIALISERS, in float64, rounded to float32 once).  A store that exists already is left alone (reuse=True) and
+        draws nothing.  The classifier gets its EMA shadows (Train_goodGAN.py:101-103)."""
+        cx = ctx()
+        rng = np.random.default_rng(seed)
+        for net in ('good_generator', 'discriminator', 'classifier'):
+            if net in cx.stores:
+                continue
+            st = ParamStore(net, [(n, s, t) for n, s, t, _ in specs[net]], cx.device)
+            for name, shape, _, init in specs[net]:
+                st.set(name, INITIALISERS[init](rng, shape) if isinstance(init, str) else np.full(shape, init, np.float32))
+            cx.stores[net] = st
+        cx.stores['classifier'].enable_ema()
+
+    def as_image(self, a):
+        """the per-image layout in which batches of this model's images are concatenated."""
+        return a
+
+    def zca(self):
+        """the whitening in front of the classifier (Model/zca.py), or None: the classifier sees the images as they are."""
+        return None
+
+    def _d_out(self, logits, want_prob=True):
+        """the discriminator's return value (tf.nn.sigmoid(logits), logits) (Good_GAN.py:124,206, Good_GAN_cifar10.py:99).  The sigmoid is an
+        output only: no loss of the reference differentiates through it (they all take the logits), so it is not recorded — and with
+        want_prob=False (the trainer's solver runs, which fetch only the losses) not launched: None in its place."""
+        if not want_prob:
+            return None, logits
+        with ctx().no_record():
+            return ops.activation(logits, 'sigmoid'), logits
+
+    @staticmethod
+    def _by_network(scopes):
+        """data_dependent_init's return value: {network: [those of `scopes` that lie in it]}."""
+        return {net: [s for s in scopes if s.startswith(net + '/')] for net in ('good_generator', 'classifier', 'discriminator')}
+
+    def _onehot_act(self, logits):
+        """one_hot(argmax(logits)) as a label Act [n, NUM_CLASSES]."""
+        k = self.config.NUM_CLASSES
+        return Act(ops.argmax_onehot(logits, k), logits.n, 1, 1, k, k)
+
+    def forward_pass(self, z_g, y_g, x_l_c, y_l_c, x_l_d, y_l_d, x_u_d, x_u_c, train):
+        """Good_GAN.py:428-472 / Good_GAN_cifar10.py:204-278.  Executes every application eagerly (the trainer runs per-solver sub-graphs
+        instead, Training/Train_goodGAN.py).  Returns [G, [D_real, D_real_logits, D_fake, D_fake_logits, D_unl, D_unl_logits],
+        [C_real_logits, C_unl_logits, C_unl_d_logits, C_fake_logits]] as Act handles, with CONSISTENCY C_unl_logits_rep behind them.  The
+        three discriminator applications run as one batched call (no batch statistics in D: identical arithmetic), the classifier ones as
+        one call with per-application statistics and running-statistics updates in the reference's call-site order (real, unl, unl_rep
+        with CONSISTENCY, unl_d, fake: Good_GAN_cifar10.py:228-240), each part whitened on its own where the model has a zca()."""
+        from tg.batching import concat_acts
+        cx = ctx()
+        G = self.good_generator(z_g, y_g)
+        w = self.zca()
+        parts = [self.as_image(a) for a in [x_l_c, x_u_c] + ([x_u_c] if self.CONSISTENCY else []) + [x_u_d, G]]
+        segs = [p.n for p in parts]
+        if w is not None:
+            parts = [w.apply(p) for p in parts]
+        with cx.rng_scoped(cx.phase + '/C'):
+            logits, _ = self.classifier(concat_acts(parts), train, segments=segs)
+        offs = [int(v) for v in np.cumsum([0] + segs)]
+        C = [logits.view_rows(offs[i], offs[i + 1]) for i in range(len(segs))]
+        C_rep = [C.pop(2)] if self.CONSISTENCY else []
+        C_real, C_unl, C_unl_d, C_fake = C
+        oh_d = self._onehot_act(C_unl_d)
+        oh_u = self._onehot_act(C_unl)
+        ximg = concat_acts([self.as_image(a) for a in (x_l_d, x_u_d, G, x_u_c)])
+        yall = concat_acts([y_l_d, oh_d, y_g, oh_u])
+        with cx.rng_scoped(cx.phase + '/D'):
+            dp, dl = self.discriminator(ximg, yall)
+        n_p = x_l_d.n + x_u_d.n
+        cut = lambda a: [a.view_rows(0, n_p), a.view_rows(n_p, n_p + G.n), a.view_rows(n_p + G.n, a.n)]
+        (p_real, p_fake, p_unl), (l_real, l_fake, l_unl) = cut(dp), cut(dl)
+        return [G, [p_real, l_real, p_fake, l_fake, p_unl, l_unl], C + C_rep]
 
     # ---- activations: callable on a tensor (one elementwise launch, modle_base.py:170-188) AND usable as `activation=` /
     # `nonlinearity=` of a layer, which fuses them into the producing kernel's epilogue (what the models of this package do)

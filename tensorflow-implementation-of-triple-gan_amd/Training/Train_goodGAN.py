@@ -24,14 +24,25 @@ import numpy as np
 import torch
 
 from config import Config
-from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, check_act_dtype, check_clip_norm, check_eval_ema, check_eval_report,  # noqa: F401
-                              check_loss, check_mfma_dtype, check_num_classes, check_optimizer, check_sample_manifold_k, check_sample_metrics,
-                              check_wn_init, check_zca, cla_lr, opt, resolve)
+from Model.zca import resolve_zca, synthetic_zca as _synthetic_zca         # (tools/ reach the synthetic rotation under this name)
+from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, Options, check_act_dtype, check_clip_norm, check_eval_ema,  # noqa: F401
+                              check_eval_report, check_loss, check_mfma_dtype, check_num_classes, check_optimizer, check_sample_manifold_k,
+                              check_sample_metrics, check_wn_init, check_zca, cla_lr, opt, resolve)
 from Training.train_base import Train_base, clip_workspace_floats
 from tg import dist as tgdist
 from tg import executor, lib, ops
 from tg.batching import concat_acts
 from tg.runtime import Act, Context, PhiloxRNG, ctx, set_context
+
+
+class _Scores(object):
+    """what Train._score_batch adds a scored batch to: the streaming accuracy, a tg.metrics.ClassifierReport (handed in, or None) and —
+    features — the tg.metrics.FeatureMoments of the classifier's pooled feature plus, bank, a tg.metrics.FeatureBank of its rows; those
+    two are sized by the first feature seen and stay None on a side that saw no batch."""
+
+    def __init__(self, report=None, features=False, bank=False):
+        self.report, self.features, self.want_bank = report, features, bank
+        self.accuracy = self.moments = self.bank = None
 
 
 class Train(Train_base):
@@ -69,7 +80,7 @@ class Train(Train_base):
         self.iteration = 0
         self._label_override = {}        # see label_override()
         self.wn_initialised = None       # {network: layers initialised} once data_dependent_init() has run (config.WN_INIT = 'data')
-        self.zca_source = None           # config.ZCA = 'fit' resolved by train(): 'files' | 'fit' (rank 0) | 'broadcast' (other ranks)
+        self.zca_source = None           # config.ZCA = 'fit' resolved by train() (Model/zca.resolve_zca): 'files' | 'fit' (rank 0) | 'broadcast' (other ranks)
         self._metric_latents = None      # (z, y) host arrays of sample_metrics(), drawn once per trainer from config.SEED
         self.last_reports = {}           # config.EVAL_REPORT: the last epoch tail's report dicts {'val', 'val_ema', 'g'} (_tail_metrics)
         self._hist_runs = {}             # network -> (store layout key, tg.summary.StoreHistograms): see histograms()
@@ -254,7 +265,7 @@ class Train(Train_base):
     def _c_forward_backward(self, split=False):
         """split: stop the backward pass at the classifier's last gradient-bucket boundary (the rest runs in _backward_rest)."""
         c, cx, m = self.config, self.cx, self.model
-        rep = bool(getattr(m, 'CONSISTENCY', False))       # Good_GAN_cifar10 only: second stochastic pass on x_u_c
+        rep = m.CONSISTENCY                                # Good_GAN_cifar10 only: second stochastic pass on x_u_c
         with cx.phase_scope('C', train_nets=('classifier',)):
             G = m.good_generator(self.z_g_ph, self.y_g_ph)
             parts = [self.x_l_c_ph, self.x_u_c_ph] + ([self.x_u_c_ph] if rep else []) + [G]
@@ -312,7 +323,7 @@ class Train(Train_base):
         """the flat gradient buffer of `net` cut at the model's GRAD_BUCKETS, in the order the backward pass completes them (last
         variables first); one slice — the whole buffer — without replicas."""
         st = self.cx.stores[net]
-        names = getattr(self.model, 'GRAD_BUCKETS', {}).get(net, ())
+        names = self.model.GRAD_BUCKETS.get(net, ())
         if not tgdist.active() or self.options.no_grad_buckets or not names:
             return [st.g]
         offs = [0] + sorted(st.offset(n) for n in names) + [st.n_p]
@@ -392,6 +403,11 @@ class Train(Train_base):
                 cx.rng.uniform(cx, 'z', self.z_g_ph.t.numel(), -1.0, 1.0, out=self.z_g_ph.t)
                 cx.rng.onehot(cx, 'y', self.y_g_ph.n, self.config.NUM_CLASSES, out=self.y_g_ph.t)
 
+    def _require_eager(self, what, it_is):
+        """lib.TgError when `what` is called while a hipGraph is captured or a launch plan recorded: its launches belong outside both."""
+        if self.cx.capturing or lib._recorder is not None:
+            raise lib.TgError("%s: called inside a hipGraph capture / launch-plan recording; it is an %s" % (what, it_is))
+
     def data_dependent_init(self):
         """config.WN_INIT = 'data' (DESIGN §9.9): the model's data-dependent initialisation pass, run eagerly on the batch the placeholders
         hold (feed() + sample_latent()) — every weight-normalised layer's g and b are assigned from that batch, nothing else changes.  Then
@@ -402,8 +418,7 @@ class Train(Train_base):
         cx = self.cx
         if self.model is None:
             raise lib.TgError("data_dependent_init: no model yet (_build_train_graph first)")
-        if cx.capturing or lib._recorder is not None:
-            raise lib.TgError("data_dependent_init: called inside a hipGraph capture / launch-plan recording; it is an eager pass before the step")
+        self._require_eager("data_dependent_init", "eager pass before the step")
         if self.iteration > 0:
             raise lib.TgError("data_dependent_init: %d training iteration(s) have run; the initialisation belongs before the first (the optimiser "
                               "slots, the EMA shadows and any recorded launch already follow the present g and b)" % self.iteration)
@@ -513,20 +528,50 @@ class Train(Train_base):
         C-update, no bias correction), pop_mean / batch-norm moving statistics from the store as they are: what the reference's getter
         (nn.py:98-110) would have returned had it been passed, since ema.apply covered c_vars only.  The pass leaves no
         trace: it writes no store, draws from the Philox state without advancing it, and runs outside every prepared-filter cache."""
-        cx, m = self.cx, self.model
-        metric = None
+        cx, scores = self.cx, _Scores(report)
         for x, y in batches:
             with cx.phase_scope('val', record=False), self._classifier_weights(ema):
-                xa = cx.from_numpy(x, key='val:x')
-                ya = cx.from_numpy(y, key='val:y')
-                if m.zca() is not None:
-                    xa = m.zca().apply(m.as_image(xa))
-                with cx.rng_scoped('val/C'):
-                    logits, _ = m.classifier(xa, False)
-                metric = self._accuracy_metric(ya, logits, metric)[0]        # what _metric (:428-447) counts; its one-hot prediction output is not needed here
-                if report is not None:
-                    report.add(ya, logits, cx.stream)
-        return float(metric) if metric is not None else 0.0
+                self._score_batch(cx.from_numpy(x, key='val:x'), cx.from_numpy(y, key='val:y'), scores)
+        return float(scores.accuracy) if scores.accuracy is not None else 0.0
+
+    def _score_batch(self, x, y, scores, take=None):
+        """Score one device batch with the classifier, inside the caller's phase (and its _classifier_weights): whiten the images x where
+        the model whitens, classifier(x, False), then add the batch — its first `take` rows; None: all of it — to `scores` (_Scores):
+        the streaming accuracy of the arg-max against the labels y (what _metric, :428-447, counts; its one-hot prediction output is
+        not needed here), the report, the feature moments and the feature bank, in that order.
+        The input noise is drawn under evaluate's Philox stream id whatever the caller's phase: ids are handed out in order of first
+        use, and a pass that registered one of its own would shift those of a solver run that first runs later (the full step after
+        pre-training)."""
+        from tg import metrics as tgm
+        cx, m = self.cx, self.model
+        if m.zca() is not None:
+            x = m.zca().apply(m.as_image(x))
+        with cx.rng_scoped('val/C'):
+            logits, fm = m.classifier(x, False)
+        if take is not None:
+            y, logits, fm = y.view_rows(0, take), logits.view_rows(0, take), fm.view_rows(0, take)
+        scores.accuracy = self._accuracy_metric(y, logits, scores.accuracy)[0]
+        if scores.report is not None:
+            scores.report.add(y, logits, cx.stream)
+        if scores.features:
+            if scores.moments is None:
+                scores.moments = tgm.FeatureMoments(fm.c, cx.device)
+            scores.moments.add(fm, cx.stream)
+            if scores.want_bank:
+                if scores.bank is None:
+                    scores.bank = tgm.FeatureBank(fm.c, cx.device)
+                scores.bank.add(fm, cx.stream)
+
+    @contextlib.contextmanager
+    def _running_state_kept(self):
+        """every store's `s` (pop_mean, batch-norm moving statistics) as it is on entry, put back on the way out: around a pass whose
+        sampler — batch norms in training mode (reference :176-202) — moves them."""
+        kept = {net: st.s.clone() for net, st in self.cx.stores.items()}
+        try:
+            yield
+        finally:
+            for net, s_before in kept.items():
+                self.cx.stores[net].s.copy_(s_before)
 
     def _new_report(self):
         """an empty tg.metrics.ClassifierReport for this trainer's classifier."""
@@ -610,73 +655,37 @@ class Train(Train_base):
         n_samples = int(n_samples)
         if n_samples < 1:
             raise ValueError("sample_metrics: n_samples must be a positive integer, got %r" % (n_samples,))
-        if cx.capturing or lib._recorder is not None:
-            raise lib.TgError("sample_metrics: called inside a hipGraph capture / launch-plan recording; it is an eager pass beside the step")
+        self._require_eager("sample_metrics", "eager pass beside the step")
         B = int(c.BATCH_SIZE_G)
         n_batches = -(-n_samples // B)
         z, y = self._sample_latents(n_batches)
-        kept = {net: st.s.clone() for net, st in cx.stores.items()}
-        real = fake = bank_real = bank_fake = None
         rep_real, rep_fake = reports if reports is not None else (None, None)
-        try:
-            acc_real = None
-            for xb, yb in batches:                                   # (the moments are sized by the first feature seen)
+        real, fake = _Scores(rep_real, True, manifold_k is not None), _Scores(rep_fake, True, manifold_k is not None)
+        with self._running_state_kept():
+            for xb, yb in batches:
                 with cx.phase_scope('metrics', record=False), self._classifier_weights(ema):
-                    xa = cx.from_numpy(xb, key='metrics:x')
-                    ya = cx.from_numpy(yb, key='metrics:y')
-                    if m.zca() is not None:
-                        xa = m.zca().apply(m.as_image(xa))
-                    # the input noise is drawn under evaluate's Philox stream id: ids are handed out in order of first use, and a pass that
-                    # registered one of its own would shift those of a solver run that first runs later (the full step after pre-training)
-                    with cx.rng_scoped('val/C'):
-                        logits, fm = m.classifier(xa, False)
-                    acc_real = self._accuracy_metric(ya, logits, acc_real)[0]
-                    if rep_real is not None:
-                        rep_real.add(ya, logits, cx.stream)
-                    if real is None:
-                        real = tgm.FeatureMoments(fm.c, cx.device)
-                    real.add(fm, cx.stream)
-                    if manifold_k is not None:
-                        bank_real = bank_real or tgm.FeatureBank(fm.c, cx.device)
-                        bank_real.add(fm, cx.stream)
-            acc_fake = None
+                    self._score_batch(cx.from_numpy(xb, key='metrics:x'), cx.from_numpy(yb, key='metrics:y'), real)
             for k in range(n_batches):
-                take = min(B, n_samples - k * B)
                 with cx.phase_scope('metrics_g', record=False), self._classifier_weights(ema):
                     za = cx.from_numpy(z[k * B:(k + 1) * B], key='metrics:z')
                     yg = cx.from_numpy(y[k * B:(k + 1) * B], key='metrics:y_g')
-                    xg = m.as_image(m.good_sampler(za, yg))
-                    if m.zca() is not None:
-                        xg = m.zca().apply(xg)
-                    with cx.rng_scoped('val/C'):
-                        logits, fm = m.classifier(xg, False)
-                    acc_fake = self._accuracy_metric(yg.view_rows(0, take), logits.view_rows(0, take), acc_fake)[0]
-                    if rep_fake is not None:
-                        rep_fake.add(yg.view_rows(0, take), logits.view_rows(0, take), cx.stream)
-                    if fake is None:
-                        fake = tgm.FeatureMoments(fm.c, cx.device)
-                    fake.add(fm.view_rows(0, take), cx.stream)
-                    if manifold_k is not None:
-                        bank_fake = bank_fake or tgm.FeatureBank(fm.c, cx.device)
-                        bank_fake.add(fm.view_rows(0, take), cx.stream)
-            (n_real, sum_r, gram_r), (n_fake, sum_f, gram_f) = real.sums() if real is not None else (0, None, None), fake.sums()
-            mu_r, cov_r = tgm.mean_cov(n_real, sum_r, gram_r) if real is not None else (None, None)
+                    self._score_batch(m.as_image(m.good_sampler(za, yg)), yg, fake, take=min(B, n_samples - k * B))
+            seen = real.moments is not None                         # (a real side without batches: no moments, no bank)
+            (n_real, sum_r, gram_r), (n_fake, sum_f, gram_f) = real.moments.sums() if seen else (0, None, None), fake.moments.sums()
+            mu_r, cov_r = tgm.mean_cov(n_real, sum_r, gram_r) if seen else (None, None)
             mu_f, cov_f = tgm.mean_cov(n_fake, sum_f, gram_f)
             fd = tgm.frechet_distance(mu_r, cov_r, mu_f, cov_f) if n_real >= 2 and n_fake >= 2 else float('nan')
-            out = dict(val_accuracy=float(acc_real) if acc_real is not None else 0.0, g_class_accuracy=float(acc_fake),
+            out = dict(val_accuracy=float(real.accuracy) if real.accuracy is not None else 0.0, g_class_accuracy=float(fake.accuracy),
                        frechet_distance=fd, n_real=int(n_real), n_fake=int(n_fake))
             if manifold_k is not None:
-                finite = real is not None and all(bool(np.isfinite(a).all()) for a in (sum_r, gram_r, sum_f, gram_f))
-                out.update(tgm.manifold_metrics(bank_real, bank_fake, manifold_k, cx.stream) if finite
+                finite = seen and all(bool(np.isfinite(a).all()) for a in (sum_r, gram_r, sum_f, gram_f))
+                out.update(tgm.manifold_metrics(real.bank, fake.bank, manifold_k, cx.stream) if finite
                            else dict.fromkeys(tgm.MANIFOLD_KEYS, float('nan')))
             if rep_real is not None:
                 out['val_report'] = rep_real.result()
             if rep_fake is not None:
                 out['g_report'] = rep_fake.result()
-        finally:
-            for net, s_before in kept.items():
-                cx.stores[net].s.copy_(s_before)
-        return out, (None if manifold_k is None else (bank_real, bank_fake))
+        return out, (None if manifold_k is None else (real.bank, fake.bank))
 
     def sync_running_state(self):
         """Replicas keep their own running statistics (pop_mean, batch-norm moving mean / variance) and EMA shadows while
@@ -694,45 +703,6 @@ class Train(Train_base):
             out = self.model.good_sampler(cx.from_numpy(sample_z, key='smp:z'), cx.from_numpy(sample_y, key='smp:y'))
             return out.numpy().reshape([-1] + list(self.config.IMAGE_DIM))
 
-    def _resolve_zca(self, dataset_train):
-        """config.ZCA = 'fit' -> (mean, mat) float32 arrays, before the model first whitens.  Rank 0 loads
-        DATA_DIR/<data>_zca_{mean,mat}.npy when both exist (the reference's path, no refit), else fits them from the training split
-        (Model/Good_GAN_cifar10.cifar10_ZCA.fit) and writes them; with data parallelism the other ranks receive rank 0's constants
-        (tg.dist.broadcast_), so every replica holds the same bits and there is exactly one writer."""
-        c = self.config
-        if not isinstance(opt(c, 'ZCA'), str):
-            return
-        check_zca(c, dataset_train)
-        from Model.Good_GAN_cifar10 import cifar10_ZCA, write_zca_files, zca_paths
-        d = int(np.prod(c.IMAGE_DIM))
-        mean = mat = None
-        if self.rank == 0:
-            m_path, mat_path = zca_paths(c)
-            if os.path.exists(m_path) and os.path.exists(mat_path):
-                mean, mat = np.load(m_path), np.load(mat_path)
-                self.zca_source = 'files'
-            else:
-                ddir = os.path.dirname(m_path) or '.'
-                if not os.access(ddir, os.W_OK):
-                    raise lib.TgError("ZCA = 'fit': %s is not writable (the fitted constants go to %s)" % (ddir, m_path))
-                mean, mat = cifar10_ZCA.fit(dataset_train)
-                write_zca_files(c, mean, mat)
-                self.zca_source = 'fit'
-            mean = np.asarray(mean, np.float32).reshape(-1)
-            mat = np.asarray(mat, np.float32)
-            if mean.shape != (d,) or mat.shape != (d, d):
-                raise lib.TgError("ZCA constants of shapes %s / %s do not match images of %d values" % (mean.shape, mat.shape, d))
-        if tgdist.active():
-            flat = torch.empty(d + d * d, dtype=torch.float32, device=self.cx.device)
-            if self.rank == 0:
-                flat.copy_(torch.from_numpy(np.concatenate([mean, mat.reshape(-1)])))
-            tgdist.broadcast_(flat)
-            if self.rank != 0:
-                host = flat.cpu().numpy()
-                mean, mat = host[:d].copy(), host[d:].reshape(d, d).copy()
-                self.zca_source = 'broadcast'
-        c.ZCA = (mean, mat)
-
     HISTOGRAM_BUFFERS = {'value': 'p', 'grad': 'g', 'ema': 'ema'}
 
     def histograms(self, which='value', nets=NETS):
@@ -747,8 +717,7 @@ class Train(Train_base):
         from tg import summary as tgsum
         if which not in self.HISTOGRAM_BUFFERS:
             raise ValueError("histograms: which must be one of %s, got %r" % (', '.join(repr(k) for k in self.HISTOGRAM_BUFFERS), which))
-        if self.cx.capturing or lib._recorder is not None:
-            raise lib.TgError("histograms: called inside a hipGraph capture / launch-plan recording; it is an eager launch beside the step")
+        self._require_eager("histograms", "eager launch beside the step")
         out = {}
         for net in nets:
             st = self.cx.stores[net]
@@ -782,20 +751,29 @@ class Train(Train_base):
         """the train summary's extra scalars: '<d|g|c>_grad_norm' for every clipped network (none without a clip)."""
         return tuple(k + '_grad_norm' for k, net in zip('dgc', NETS) if net in self._clip_views)
 
-    def _tail_metric_tags(self):
-        """the epoch tail's extra records and val-summary scalars, in order: 'val_accuracy_ema' with config.EVAL_EMA, 'g_class_accuracy'
-        and 'frechet_distance' with config.SAMPLE_METRICS, then 'precision', 'recall', 'density' and 'coverage' with
-        config.SAMPLE_MANIFOLD_K (none with all off).  config.EVAL_REPORT appends, behind all of those, REPORT_TAGS with a 'val_' prefix
-        ('val_top5_accuracy' only with more than five classes), with EVAL_EMA the same again with an '_ema' suffix, and with
-        SAMPLE_METRICS 'g_worst_class_accuracy'."""
+    def _tail_rows(self):
+        """the epoch tail's extra records and val-summary scalars, in order, as (tag, result, key): the value of `tag` is `key` of the
+        result dict named `result` that _tail_metrics gathers — 'sm', the sample-metrics pass (with config.EVAL_EMA alone: evaluate's
+        pass over the shadows), or one of the report dicts 'val', 'val_ema', 'g' of self.last_reports.
+        'val_accuracy_ema' with config.EVAL_EMA, 'g_class_accuracy' and 'frechet_distance' with config.SAMPLE_METRICS, then 'precision',
+        'recall', 'density' and 'coverage' with config.SAMPLE_MANIFOLD_K (none with all off).  config.EVAL_REPORT appends, behind all of
+        those, REPORT_TAGS with a 'val_' prefix ('val_top5_accuracy' only with more than five classes), with EVAL_EMA the same again
+        with an '_ema' suffix, and with SAMPLE_METRICS 'g_worst_class_accuracy' (the generated side's target is the class asked for:
+        recall = class accuracy)."""
         from tg import metrics as tgm
         o = self.options
-        tags = ((('val_accuracy_ema',) if o.eval_ema else ()) + (('g_class_accuracy', 'frechet_distance') if o.sample_metrics else ())
-                + (tgm.MANIFOLD_KEYS if o.sample_metrics and o.sample_manifold_k else ()))
+        rows = [('val_accuracy_ema', 'sm', 'val_accuracy')] if o.eval_ema else []
+        if o.sample_metrics:
+            rows += [(k, 'sm', k) for k in ('g_class_accuracy', 'frechet_distance') + (tgm.MANIFOLD_KEYS if o.sample_manifold_k else ())]
         if o.eval_report:
-            val = tuple('val_' + k for k in self._report_keys())
-            tags += val + (tuple(k + '_ema' for k in val) if o.eval_ema else ()) + (('g_worst_class_accuracy',) if o.sample_metrics else ())
-        return tags
+            keys = self._report_keys()
+            rows += [('val_' + k, 'val', k) for k in keys] + ([('val_' + k + '_ema', 'val_ema', k) for k in keys] if o.eval_ema else [])
+            rows += [('g_worst_class_accuracy', 'g', 'worst_class_recall')] if o.sample_metrics else []
+        return rows
+
+    def _tail_metric_tags(self):
+        """the tags of _tail_rows(), in order: what _tail_metrics returns a value for."""
+        return tuple(tag for tag, _, _ in self._tail_rows())
 
     REPORT_TAGS = ('balanced_accuracy', 'macro_f1', 'nll', 'ece', 'top5_accuracy')
 
@@ -811,37 +789,25 @@ class Train(Train_base):
         main_report (config.EVAL_REPORT): the ClassifierReport the epoch's evaluate pass filled.  The pass that reads the shadows
         and the generated side of the metrics pass fill one more each — no forward pass is added — and self.last_reports keeps the
         report dicts {'val', 'val_ema', 'g'} of those that ran."""
-        o, out = self.options, {}
-        reports = {'val': main_report.result()} if o.eval_report else None
+        o = self.options
+        res = {'val': main_report.result()} if o.eval_report else {}
         if o.sample_metrics:
             init_op_val()
             # the pass of sample_metrics / sample_manifold_metrics; its real side reads the shadows only with EVAL_EMA, and only then
             # does its report differ from the main one
             pair = (self._new_report() if o.eval_ema else None, self._new_report()) if o.eval_report else None
-            sm = self._sample_metrics_pass(NNIO.val_batches(), o.sample_metrics, o.eval_ema, o.sample_manifold_k, pair)[0]
-            if o.eval_ema:
-                out['val_accuracy_ema'] = sm['val_accuracy']
-            out['g_class_accuracy'], out['frechet_distance'] = sm['g_class_accuracy'], sm['frechet_distance']
-            if o.sample_manifold_k:                                                     # SAMPLE_MANIFOLD_K: the same pass, four more numbers
-                from tg import metrics as tgm
-                out.update((k, sm[k]) for k in tgm.MANIFOLD_KEYS)
+            sm = res['sm'] = self._sample_metrics_pass(NNIO.val_batches(), o.sample_metrics, o.eval_ema, o.sample_manifold_k, pair)[0]
             if o.eval_report:
-                reports.update([('g', sm['g_report'])] + ([('val_ema', sm['val_report'])] if o.eval_ema else []))
+                res.update([('g', sm['g_report'])] + ([('val_ema', sm['val_report'])] if o.eval_ema else []))
         elif o.eval_ema:
             init_op_val()
             ema_report = self._new_report() if o.eval_report else None
-            out['val_accuracy_ema'] = self.evaluate(NNIO.val_batches(), ema=True, report=ema_report)
+            res['sm'] = dict(val_accuracy=self.evaluate(NNIO.val_batches(), ema=True, report=ema_report))
             if o.eval_report:
-                reports['val_ema'] = ema_report.result()
+                res['val_ema'] = ema_report.result()
         if o.eval_report:
-            keys = self._report_keys()
-            out.update(('val_' + k, reports['val'][k]) for k in keys)
-            if o.eval_ema:
-                out.update(('val_' + k + '_ema', reports['val_ema'][k]) for k in keys)
-            if o.sample_metrics:                               # the generated side's target is the class asked for: recall = class accuracy
-                out['g_worst_class_accuracy'] = reports['g']['worst_class_recall']
-            self.last_reports = reports
-        return out
+            self.last_reports = {k: res[k] for k in ('val', 'val_ema', 'g') if k in res}
+        return {tag: res[name][key] for tag, name, key in self._tail_rows()}
 
     # ------------------------------------------------------------------ the reference's entry point
     def train(self, Dataset, Model, sample_y):
@@ -851,7 +817,9 @@ class Train(Train_base):
         c = self.config
         dataset_train = Dataset(c.DATA_DIR, c, c.NUM_LABEL, 'train', True)
         dataset_val = Dataset(c.DATA_DIR, c, c.NUM_LABEL, 'test', False)
-        self._resolve_zca(dataset_train)
+        if isinstance(opt(c, 'ZCA'), str):                                             # 'fit': the constants, before the model first whitens
+            check_zca(c, dataset_train)
+            c.ZCA, self.zca_source = resolve_zca(c, dataset_train, self.rank, self.cx.device)
         init_op_train, init_op_val, NNIO = dataset_train.inputpipline_train_val(dataset_val)
         self._build_train_graph(Model)
         sample_z = np.random.uniform(low=-1.0, high=1.0, size=(c.SAMPLE_SIZE, c.Z_DIM)).astype(np.float32)   # :130
@@ -880,7 +848,7 @@ class Train(Train_base):
         iters = int(c.TRAIN_SIZE / c.BATCH_SIZE)
         for epoch in range(1, c.EPOCHS + 1):
             lambda_1 = c.FAKE_G_LAMBDA if (start_epoch + epoch) > 200 else 0.          # :165
-            lambda_2 = (0.5 if epoch > 67 else 0.) if getattr(self.model, 'CONSISTENCY', False) else 0.  # :171
+            lambda_2 = (0.5 if epoch > 67 else 0.) if self.model.CONSISTENCY else 0.                       # :171
             if start_epoch + epoch >= 300:                                             # :175-177
                 lr, c_lr = lr * 0.995, c_lr * 0.99
             self.set_hyper(lr, c_lr, lambda_1, lambda_2)
@@ -936,11 +904,8 @@ class Train(Train_base):
             # The sampler's batch norms run in training mode (reference :176-202) and move their running statistics.  A run
             # without the flag samples only for the sample grid: when there is none, the statistics are put back, so the
             # summary leaves every store as it found it.
-            kept = None if grid else {net: st.s.clone() for net, st in self.cx.stores.items()}
-            samples = self.sample(sample_z, sample_y)
-            if kept is not None:
-                for net, s_before in kept.items():
-                    self.cx.stores[net].s.copy_(s_before)
+            with contextlib.nullcontext() if grid else self._running_state_kept():
+                samples = self.sample(sample_z, sample_y)
             imgs = {'generated': samples}
         self.summary_train.write(dict(dict(g_loss=rec['g_loss'], d_loss=rec['d_loss'], c_loss=rec['c_loss']),
                                       **{k + '_grad_norm': v[0] for k, v in norms.items() if v is not None}), rec['epoch'],
@@ -1063,16 +1028,6 @@ class Stress64Config(ExperimentConfig):
     SAMPLE_DIR, WEIGHT_DIR, LOG_DIR = "stress64_good_GAN", "Training/Weight_stress64", "Training/Log_stress64"
 
 
-def _synthetic_zca(tmp_config):
-    """the ZCA-whitened (CIFAR) experiments without whitening constants — config.ZCA is None and DATA_DIR holds no <data>_zca_mat.npy —
-    whiten with a fixed random rotation and a zero mean."""
-    from Model.Good_GAN_cifar10 import ZCA_DATA
-    if tmp_config.DATA_NAME in ZCA_DATA and tmp_config.ZCA is None and not os.path.exists(os.path.join(tmp_config.DATA_DIR, tmp_config.DATA_NAME + "_zca_mat.npy")):
-        d = int(np.prod(tmp_config.IMAGE_DIM))
-        q, _ = np.linalg.qr(np.random.default_rng(4321).standard_normal((d, d)))
-        tmp_config.ZCA = (np.zeros(d, np.float32), q.astype(np.float32))
-
-
 def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
     from Input_Pipeline.syntheticDataset import syntheticDataset
     tmp_config = TempConfig()
@@ -1081,16 +1036,12 @@ def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
     _synthetic_zca(tmp_config)                                         # a default like the class body's: FLAGS below override it
     if FLAGS:
         _customize_config(tmp_config, FLAGS)
-        if getattr(FLAGS, 'wn_init', None) is not None:                # --wn-init data: Config does not declare WN_INIT, so the hasattr rule
-            tmp_config.WN_INIT = FLAGS.wn_init                         # of _customize_config would drop it (Training/options.check_wn_init)
-        if getattr(FLAGS, 'eval_ema', None) is not None:               # --eval-ema, --sample-metrics N: likewise undeclared
-            tmp_config.EVAL_EMA = FLAGS.eval_ema                       # (Training/options.check_eval_ema, check_sample_metrics)
-        if getattr(FLAGS, 'sample_metrics', None) is not None:
-            tmp_config.SAMPLE_METRICS = FLAGS.sample_metrics
-        if getattr(FLAGS, 'sample_manifold_k', None) is not None:      # --sample-manifold-k K (check_sample_manifold_k; flag objects
-            tmp_config.SAMPLE_MANIFOLD_K = FLAGS.sample_manifold_k     # without the attribute are common: getattr with a default)
-        if getattr(FLAGS, 'eval_report', None) is not None:            # --eval-report (check_eval_report)
-            tmp_config.EVAL_REPORT = FLAGS.eval_report
+        # --wn-init data, --eval-ema, --sample-metrics N, --sample-manifold-k K, --eval-report: Config does not declare these settings, so
+        # the hasattr rule of _customize_config would drop them (Training/options.check_wn_init ... check_eval_report).  Flag objects
+        # without the attribute are common: getattr with a default
+        for name in Options.EXTRAS:
+            if getattr(FLAGS, name, None) is not None:
+                setattr(tmp_config, name.upper(), getattr(FLAGS, name))
     if epochs is not None:
         tmp_config.EPOCHS = epochs
     tmp_config.SAMPLE_DIR = os.path.join(_root_dir(), "Training", tmp_config.SAMPLE_DIR)

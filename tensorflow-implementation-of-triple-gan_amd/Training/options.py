@@ -135,7 +135,7 @@ def check_zca(config, Dataset=None):
         return zc
     if zc != 'fit':
         raise ValueError("ZCA must be None, (mean, mat) arrays or 'fit', got %r" % (zc,))
-    from Model.Good_GAN_cifar10 import ZCA_DATA
+    from Model.zca import ZCA_DATA
     if opt(config, 'DATA_NAME') not in ZCA_DATA:
         raise lib.TgError("ZCA = 'fit' applies to the ZCA-whitened classifiers of %s; DATA_NAME %r has no ZCA whitening"
                           % (' / '.join(ZCA_DATA), opt(config, 'DATA_NAME')))

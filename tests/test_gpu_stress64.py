@@ -144,3 +144,36 @@ def test_stress64_at_its_stated_batch_sizes_properties():
             assert float(pad.abs().max()) == 0.0, tag
     ref = np.concatenate([outs['a'], outs['b']])
     assert np.abs(outs['ab'] - ref).max() <= 2e-5 * np.abs(ref).max(), np.abs(outs['ab'] - ref).max()
+
+
+def test_stress64_epoch_tail_paths_run_without_whitening():
+    """The model-side paths of an epoch tail on the model whose zca() is None, at ragged small batches (B_G 8, L_C = U_C 4, L_D 3, U_D 5;
+    the 64x64 maps keep every layer's shape legal), eager: data_dependent_init initialises the classifier's thirteen weight-normalised
+    layers — the ten of its own C_CONVS, two NiN, the head — and nothing of G or D; an iteration runs; training_statistics
+    (Model.forward_pass on the unwhitened images) returns three finite losses and moves every pop_mean of the classifier."""
+    from gpu_common import fresh_trainer
+    import bench_config as stress64
+    from Model.Good_GAN_stress64 import Good_GAN_stress64
+    cfg = stress64.make_config()
+    cfg.BATCH_SIZE_G = cfg.BATCH_SIZE = 8
+    cfg.BATCH_SIZE_L_C = cfg.BATCH_SIZE_U_C = 4
+    cfg.BATCH_SIZE_L_D, cfg.BATCH_SIZE_U_D = 3, 5
+    cfg.USE_HIP_GRAPH = False
+    tr = fresh_trainer(cfg, Model=Good_GAN_stress64)
+    assert tr.model.zca() is None
+    tr.set_hyper(lambda_1=0.3, lambda_2=0.5)
+    rng = np.random.default_rng(3)
+    img = lambda n: rng.uniform(-1, 1, (n, 64, 64, 3)).astype(np.float32)
+    oh = lambda n: np.eye(10, dtype=np.float32)[rng.integers(0, 10, n)]
+    tr.feed(dict(x_l_c=img(4), y_l_c=oh(4), x_l_d=img(3), y_l_d=oh(3), x_u_d=img(5), x_u_c=img(4)))
+    tr.sample_latent()
+    assert tr.data_dependent_init() == {'good_generator': 0, 'classifier': 13, 'discriminator': 0}
+    tr.train_iteration(use_graph=False)
+    st = tr.cx.stores['classifier']
+    pops = [nm for nm in st.names(False) if nm.endswith('/pop_mean')]
+    assert len(pops) == 13
+    before = {nm: st.get(nm).copy() for nm in pops}
+    losses = tr.training_statistics()
+    assert len(losses) == 3 and all(np.isfinite(losses)), losses
+    for nm in pops:
+        assert (st.get(nm) != before[nm]).any(), nm

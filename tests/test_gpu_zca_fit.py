@@ -124,7 +124,7 @@ def _train(cfg):
 
 def test_fit_end_to_end_from_tfrecords(tmp_path, monkeypatch):
     import torch
-    from Model.Good_GAN_cifar10 import ZCA_EPS, cifar10_ZCA, zca_paths
+    from Model.zca import ZCA_EPS, cifar10_ZCA, zca_paths
     from tg.runtime import Act
     root = str(tmp_path)
     train = _write_files(root)
@@ -189,7 +189,7 @@ def _free_port():
 def test_two_replicas_hold_identical_constants_with_one_writer(tmp_path):
     """two gloo ranks on one GPU (tests/test_gpu_dp.py): rank 0 fits and writes, rank 1 receives the constants by broadcast."""
     import torch
-    from Model.Good_GAN_cifar10 import zca_paths
+    from Model.zca import zca_paths
     data = str(tmp_path / 'data')
     os.makedirs(data)
     _write_files(data)

@@ -14,7 +14,7 @@ def _images(rng, n, d):
 
 
 def test_host_derivation_matches_the_float64_restatement():
-    from Model.Good_GAN_cifar10 import ZCA_EPS, zca_constants
+    from Model.zca import ZCA_EPS, zca_constants
     assert ZCA_EPS == 1e-5
     x = _images(np.random.default_rng(0), 500, 48)
     mean, mat = zca_constants(*R.int_moments(x))
@@ -28,7 +28,7 @@ def test_host_derivation_matches_the_float64_restatement():
 def test_whitening_property(n, d):
     """mat is symmetric and mat · cov · mat has the eigenvalues s / (s + eps); (20, 48) is the rank-deficient case n < d, where the
     clipping at 0 keeps the constants finite."""
-    from Model.Good_GAN_cifar10 import zca_constants
+    from Model.zca import zca_constants
     x = _images(np.random.default_rng(n), n, d)
     mean, mat = zca_constants(*R.int_moments(x))
     assert np.isfinite(mean).all() and np.isfinite(mat).all()
@@ -43,7 +43,7 @@ def test_whitening_property(n, d):
 
 
 def test_derivation_rejects_counts_outside_the_exact_range():
-    from Model.Good_GAN_cifar10 import ZCA_N_MAX, zca_constants
+    from Model.zca import ZCA_N_MAX, zca_constants
     assert ZCA_N_MAX ** 2 << 14 <= 2 ** 63 - 1 < (ZCA_N_MAX + 1) ** 2 << 14
     for n in (0, ZCA_N_MAX + 1):
         with pytest.raises(ValueError, match="exact"):
@@ -69,7 +69,7 @@ def _write_cifar10_files(root, n_lab, n_unl, n_test, seed=0):
 def test_the_fit_reads_every_training_record_once_and_never_the_test_split(tmp_path, monkeypatch):
     from tg import io as tgio
     from Input_Pipeline.cifar10Dataset import cifar10Dataset
-    from Model.Good_GAN_cifar10 import zca_training_chunks, zca_training_files
+    from Model.zca import zca_training_chunks, zca_training_files
     train, test_path = _write_cifar10_files(str(tmp_path), 40, 90, 30)
     opened = []
     real = tgio.RecordFile
@@ -96,7 +96,7 @@ def test_the_fit_reads_every_training_record_once_and_never_the_test_split(tmp_p
 
 def test_zca_files_are_written_atomically_or_the_error_names_the_path(tmp_path):
     from tg import lib
-    from Model.Good_GAN_cifar10 import write_zca_files, zca_paths
+    from Model.zca import write_zca_files, zca_paths
 
     class C(object):
         DATA_NAME, DATA_DIR = 'cifar100', str(tmp_path)

@@ -39,7 +39,7 @@ def main():
     ap.add_argument('--data-dir', help='DATA_DIR: holds Tfrecord/<data>_train_*.tfrecords; receives the .npy files')
     ap.add_argument('--num-label', type=int, default=None, help='labelled records (default 4000 for CIFAR-10, 10000 for CIFAR-100)')
     ap.add_argument('--synthetic', type=int, metavar='N', help='write N random records to a temporary DATA_DIR and fit those')
-    ap.add_argument('--eps', type=float, default=None, help='regularisation (default Model.Good_GAN_cifar10.ZCA_EPS)')
+    ap.add_argument('--eps', type=float, default=None, help='regularisation (default Model.zca.ZCA_EPS)')
     a = ap.parse_args()
     if (a.data_dir is None) == (a.synthetic is None):
         ap.error('give exactly one of --data-dir and --synthetic')
@@ -47,7 +47,7 @@ def main():
     import torch
     from tg import lib
     from tg.runtime import Context, set_context
-    from Model.Good_GAN_cifar10 import ZCA_EPS, cifar10_ZCA, write_zca_files, zca_paths
+    from Model.zca import ZCA_EPS, cifar10_ZCA, write_zca_files, zca_paths
     if a.data == 'cifar100':
         from Input_Pipeline.cifar100Dataset import cifar100Dataset as Dataset
     else:
