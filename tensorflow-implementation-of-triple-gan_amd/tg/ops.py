@@ -2,6 +2,7 @@
 Model/model_base.py compose.  Every function launches tg_* kernels through the C ABI on the
 context's stream and, when a tape is active, records a closure producing the input / variable
 gradients.  Gradient of an activation `a` lives in `a.grad` (an Act of identical layout)."""
+import collections
 import contextlib
 import ctypes as C
 import types
@@ -67,13 +68,62 @@ def require_f32(x, op):
                               "may feed conv2d only)" % (op, a.n, a.h, a.w, a.c, a.dtype))
 
 
-def _single_consumer(y, gy):
-    """The fused backward paths hand a layer its gradient ALREADY multiplied by act'(y) (Act.grad_is_dpre: a batch norm behind it did; Act.grad_fused:
-    the consumer's input-gradient launch did).  That is only the layer's pre-activation gradient if that consumer was the ONLY writer of the
-    buffer: a second consumer's raw contribution in the same buffer cannot be told apart afterwards — refuse instead of training on it."""
-    if (y.grad_is_dpre or y.grad_fused is not None) and gy.contribs > 1:
+# Hand-offs of the fused backward paths (Act.offer / Act.taken, protocol in runtime.Act), one record type per kind: the producer offers it
+# with the result fields empty, the consumer that takes it fills them in (`_replace`) and leaves it in Act.taken.
+#   ActSums     a mean-only-BN layer's output: the taker stores dy*act'(y) in .grad and the column sums per application in `sums` (fp64, `replicas` copies)
+#   BiasSums    conv / deconv + bias + relu-like activation: the taker (a batch norm's backward) stores the PRE-activation gradient, writes bias_grad
+#   BnBwdStats  a training-mode batch norm of input x: the taker leaves sum dy, sum dy*x in `sums`; `grad` is the gradient handle it wrote
+# and the forward notes BnSums (Act.bn_sums), Labels (Act.labels), Pending (Act.pending) an op leaves for the op that follows directly.
+ActSums, BiasSums = collections.namedtuple('ActSums', 'act alpha seg_rows sums replicas'), collections.namedtuple('BiasSums', 'act alpha bias_grad')
+BnBwdStats, BnSums = collections.namedtuple('BnBwdStats', 'x seg_rows sums grad'), collections.namedtuple('BnSums', 'sums seg_rows')
+Labels, Pending = collections.namedtuple('Labels', 'address ncls'), collections.namedtuple('Pending', 'x mask scale')
+
+
+def _offer(y, record):
+    assert y.offer is None, "a producer makes at most one offer (Act.offer)"
+    y.offer = record
+
+
+def _trusted(y, gy):
+    """y.taken if y's producer may trust it, given y's gradient handle gy, else None: what a taker left is valid only while the taker is the ONE
+    writer of the gradient.  A batch norm then takes its own statistics; a gradient ALREADY multiplied by act'(y) (ActSums, BiasSums) cannot
+    be told apart from a second consumer's raw contribution in the same buffer: refuse instead of training on it."""
+    t = y.taken
+    if t is None:
+        return None
+    if isinstance(t, BnBwdStats):
+        return t if (t.grad is gy and gy.contribs == 1) else None
+    if gy.contribs > 1:
         raise lib.TgError("fused backward: the gradient of a %dx%dx%dx%d activation was written by %d consumers, but one of them already folded "
                           "the activation derivative into it" % (y.n, y.h, y.w, y.c, gy.contribs))
+    return t
+
+
+def _write_grad(cx, x, store=None, alias=None):
+    """THE way a backward closure contributes to x.grad.  store(dst): issue the closure's launch(es), which OVERWRITE dst, an Act of the
+    layout of x's gradient.  The first writer (x.grad is None) stores into the buffer of Context.grad_of; a later writer stores into a
+    scratch Act and tg_add_f32 adds that to the gradient (one more fp32 rounding), so no contribution is lost, whichever order the tape runs
+    the consumers in.  alias (instead of store): the contribution IS already in memory, as a fresh Act view of a consumer's gradient buffer
+    with x's logical shape: the first writer adopts it without a launch (every reader of a gradient goes through (pointer, channel stride));
+    a later one adds it, through a tg_actgrad_f32 copy into scratch where the channel strides differ.
+    -> (gradient handle, whether this was the first writer); handle.contribs counts the writers."""
+    first = x.grad is None
+    if first and alias is not None:
+        x.grad = alias
+    gx = cx.grad_of(x)
+    if first:
+        if alias is None:
+            store(gx)
+        return gx, first
+    part = alias
+    if alias is None or alias.ld != gx.ld:
+        part = Act(cx.scratch('gxp', gx.rows * gx.ld), gx.n, gx.h, gx.w, gx.c, gx.ld)
+        if alias is None:
+            store(part)
+        else:
+            _call('tg_actgrad_f32', alias.ptr, alias.ld, None, 0, None, 0, 1.0, part.ptr, part.ld, x.rows, x.c, 0, 0.0, cx.stream)
+    _call('tg_add_f32', gx.ptr, gx.ptr, part.ptr, gx.rows * gx.ld, cx.stream)
+    return gx, first
 
 
 def _segs(x, segments):
@@ -230,7 +280,7 @@ def _fwd_bnstat(cx, L):
     bsum, zd = _sums64(cx, 'bn64', len(seg_rows), L.c_out, pair=True)     # the batch norm's buffer
     _call('tg_igemm_bnstat_bf16in_bf16' if L.x16 else 'tg_igemm_bnstat_f32', L.d, L.x.ptr, _p(L.w_oti), _p(L.bias), L.y.ptr, seg_array(seg_rows),
           len(seg_rows), _p(bsum), zd, cx.stream)
-    L.y.bn_sums = (bsum, tuple(seg_rows))
+    L.y.bn_sums = BnSums(bsum, tuple(seg_rows))
 
 
 def _fwd_packed(cx, L):
@@ -261,12 +311,14 @@ def _mobn_unfused(cx, src, dst, c, seg_rows, b, pop, decay, train, act=None, alp
 
 def _dpre_plain(cx, y, gy, act, alpha, c_out, co_p, bias_grad, head=False):
     """pre-activation gradient [rows][co_p] of y = act(pre + bias) from gy = y.grad, and the bias gradient (None: not wanted).  gy itself where a
-    batch norm behind the layer already made it that (Act.grad_is_dpre) or — head: conv2d only — the loss head wrote a padded dlogits."""
+    batch norm behind the layer already made it that (it took the layer's BiasSums offer) or — head: conv2d only — the loss head wrote a padded
+    dlogits."""
+    taken = _trusted(y, gy)
     if head and act is None and gy.ld == co_p:
         if bias_grad is not None:
             colstats(0, gy.t, co_p, None, 0, y.rows, c_out, [y.rows], s1=bias_grad)
         return gy.t
-    if y.grad_is_dpre and gy.ld == co_p:
+    if isinstance(taken, BiasSums) and gy.ld == co_p:
         return gy.t
     dpre = cx.scratch('dpre', y.rows * co_p)
     if bias_grad is not None and co_p <= 1024:
@@ -284,12 +336,13 @@ def _dpre_plain(cx, y, gy, act, alpha, c_out, co_p, bias_grad, head=False):
 def _dpre_mobn(cx, L, gy):
     y, seg_rows, c_out, co_p = L.y, L.seg_rows, L.c_out, L.co_p
     nseg = len(seg_rows)
+    taken = _trusted(y, gy)
     dpre = cx.scratch('dpre', y.rows * co_p)
-    if y.grad_fused is not None:
-        # the consumer's input-gradient launch already stored t = dy*act'(y) in y.grad and summed its columns per application
+    if taken is not None:
+        # the consumer's backward launch already stored t = dy*act'(y) in y.grad and summed its columns per application (ActSums)
         db = L.mobn[1] if L.needs_w else cx.scratch('db', c_out)
-        _call('tg_mobn_center_f32', gy.ptr, gy.ld, _p(dpre), co_p, y.rows, c_out, seg_array(seg_rows), nseg, _p(y.grad_fused[0]),
-              y.grad_fused[1], _p(db), cx.stream)
+        _call('tg_mobn_center_f32', gy.ptr, gy.ld, _p(dpre), co_p, y.rows, c_out, seg_array(seg_rows), nseg, _p(taken.sums),
+              taken.replicas, _p(db), cx.stream)
     elif L.narrow_mobn:
         db = L.mobn[1] if L.needs_w else cx.scratch('db', c_out)
         sums64, zd = _sums64(cx, 'bs64', nseg, c_out)
@@ -307,39 +360,33 @@ def _dpre_mobn(cx, L, gy):
 
 def _input_grad(cx, L, dpre):
     x, ci_p = L.x, L.ci_p
-    fresh = x.grad is None
-    gx = cx.grad_of(x)
-    dlist = geom.conv_dgrad(x.n, x.h, x.w, ci_p, L.co_p, L.k, L.stride, L.padding, ld_out=gx.ld, n_store=ci_p)
-    takes_over = fresh and len(dlist) == 1 and x.c == ci_p == gx.ld == x.ld
-    sink, bsink = x.grad_sink, x.bn_bwd_sink
-    if sink is not None and takes_over and sum(sink[2]) == x.rows and geom.colsum_supported(dlist[0], sink[2]):
-        # x is the output of a mean-only-BN layer: this launch also applies that layer's activation derivative and sums the
-        # columns per application, so its backward pass needs no statistics pass of its own (tg_mobn_center_f32)
-        nsg = len(sink[2])
-        gsum, zd = _sums64(cx, 'gs64', nsg, ci_p, replicas=False)
-        _call('tg_igemm_actsum_f32', dlist[0], _p(dpre), _p(L.w_hwio), x.ptr, ACT[sink[0]], sink[1], gx.ptr, seg_array(sink[2]), nsg,
-              _p(gsum), zd, cx.stream)
-        x.grad_fused = (gsum, 1)
-    elif (bsink is not None and takes_over and bsink[0].ld == gx.ld and len(bsink[1]) <= 8 and sum(bsink[1]) == x.rows
-          and geom.colsum_supported(dlist[0], bsink[1])):
-        # x is a training-mode batch norm's output and this launch is the first to write its gradient: the batch norm's backward
-        # statistics (sum dy, sum dy * its input) are taken in this epilogue; batch_norm_train's backward checks that nothing else
-        # contributed before it trusts them
-        bn_in, segs = bsink
-        bsums, zdb = _sums64(cx, 'bnb64', len(segs), ci_p, pair=True)
-        _call('tg_igemm_bnbwdstat_f32', dlist[0], _p(dpre), _p(L.w_hwio), bn_in.ptr, gx.ptr, seg_array(segs), len(segs), _p(bsums), zdb, cx.stream)
-        x.bn_bwd_sums = (bsums, gx)
-    else:
-        x.bn_bwd_sums = None                              # a second contribution to that gradient: the sums of the first alone are not the statistics
-        dds = lib.desc_array(dlist)
-        if fresh:
-            _call('tg_igemm_multi_f32', dds, len(dds), _p(dpre), _p(L.w_hwio), None, gx.ptr, cx.stream)
+    first = x.grad is None
+
+    def store(gx):
+        dlist = geom.conv_dgrad(x.n, x.h, x.w, ci_p, L.co_p, L.k, L.stride, L.padding, ld_out=gx.ld, n_store=ci_p)
+        takes_over = first and len(dlist) == 1 and x.c == ci_p == gx.ld == x.ld
+        o = x.offer
+        if isinstance(o, ActSums) and takes_over and sum(o.seg_rows) == x.rows and geom.colsum_supported(dlist[0], o.seg_rows):
+            # x is the output of a mean-only-BN layer: this launch also applies that layer's activation derivative and sums the
+            # columns per application, so its backward pass needs no statistics pass of its own (tg_mobn_center_f32)
+            nsg = len(o.seg_rows)
+            gsum, zd = _sums64(cx, 'gs64', nsg, ci_p, replicas=False)
+            _call('tg_igemm_actsum_f32', dlist[0], _p(dpre), _p(L.w_hwio), x.ptr, ACT[o.act], o.alpha, gx.ptr, seg_array(o.seg_rows), nsg,
+                  _p(gsum), zd, cx.stream)
+            x.taken = o._replace(sums=gsum, replicas=1)
+        elif (isinstance(o, BnBwdStats) and takes_over and o.x.ld == gx.ld and len(o.seg_rows) <= 8 and sum(o.seg_rows) == x.rows
+              and geom.colsum_supported(dlist[0], o.seg_rows)):
+            # x is a training-mode batch norm's output and this launch is the first to write its gradient: the batch norm's backward
+            # statistics (sum dy, sum dy * its input) are taken in this epilogue
+            segs = o.seg_rows
+            bsums, zdb = _sums64(cx, 'bnb64', len(segs), ci_p, pair=True)
+            _call('tg_igemm_bnbwdstat_f32', dlist[0], _p(dpre), _p(L.w_hwio), o.x.ptr, gx.ptr, seg_array(segs), len(segs), _p(bsums), zdb, cx.stream)
+            x.taken = o._replace(sums=bsums, grad=gx)
         else:
-            # x already carries a gradient — a loss seeded it (the pooled feature: feat.grad) or another consumer's backward ran first:
-            # this layer's contribution is ADDED to it (the launch itself only stores), never written over it
-            part = cx.scratch('gxp', gx.rows * gx.ld)
-            _call('tg_igemm_multi_f32', dds, len(dds), _p(dpre), _p(L.w_hwio), None, _p(part), cx.stream)
-            _call('tg_add_f32', gx.ptr, gx.ptr, _p(part), gx.rows * gx.ld, cx.stream)
+            dds = lib.desc_array(dlist)
+            _call('tg_igemm_multi_f32', dds, len(dds), _p(dpre), _p(L.w_hwio), None, gx.ptr, cx.stream)
+
+    _write_grad(cx, x, store)
 
 
 def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=None, mobn=None, segments=None,
@@ -381,20 +428,19 @@ def conv2d(x, kernel, bias, c_out, k, stride, padding, act=None, alpha=0.2, wn=N
     fwd = _conv_route(cx, L, bn_stats, n_store_ld)
     pooled = fwd(cx, L)
     if L.fuse_cat:
-        y.labels = (concat[0].data_ptr(), concat[1])
+        y.labels = Labels(concat[0].data_ptr(), concat[1])
     if mobn is not None and fwd is not _fwd_colsum:
         _mobn_unfused(cx, y, y, c_out, L.seg_rows, mobn[0], mobn[2], 0.9, train, act, alpha)
     if not (needs_w or needs_x):
         return _pool_after(cx, y, pooled, pool)
     if L.narrow_mobn and train and act is not None and ld_out == co_p:
-        y.grad_sink = (act, alpha, tuple(L.seg_rows))      # see Act.grad_sink
+        _offer(y, ActSums(act, alpha, tuple(L.seg_rows), None, 0))
     if mobn is None and act in ('relu', 'lrelu') and needs_w and bias_grad is not None and c_out == co_p == ld_out:
-        y.bias_sink = (act, alpha, bias_grad)            # a batch norm behind this layer may fold act' and the bias gradient into its backward
+        _offer(y, BiasSums(act, alpha, bias_grad))       # a batch norm behind this layer may fold act' and the bias gradient into its backward
 
     def bwd():
         gy = y.grad
         assert gy is not None, "conv2d backward: no gradient reached the output"
-        _single_consumer(y, gy)
         if mobn is not None:
             dpre = _dpre_mobn(cx, L, gy)
         else:
@@ -459,7 +505,7 @@ def deconv2d(x, kernel, bias, c_out, act=None, kernel_grad=None, bias_grad=None,
     y = cx.new_act(x.n, 2 * x.h, 2 * x.w, c_out, ld_out, requires_grad=needs_w or needs_x)
     y.strided_grad_ok = True
     if act in ('relu', 'lrelu') and needs_w and bias_grad is not None and c_out == co_p == ld_out:
-        y.bias_sink = (act, 0.2, bias_grad)              # see conv2d
+        _offer(y, BiasSums(act, 0.2, bias_grad))         # see conv2d
     if merged:
         _call('tg_igemm_f32', d, x.ptr, _p(w_m), _p(bias), y.ptr, cx.stream)
     else:
@@ -471,7 +517,6 @@ def deconv2d(x, kernel, bias, c_out, act=None, kernel_grad=None, bias_grad=None,
     def bwd():
         gy = y.grad
         assert gy is not None
-        _single_consumer(y, gy)
         dpre = _dpre_plain(cx, y, gy, act, 0.2, c_out, co_p, bias_grad if needs_w else None)
         # the 3-channel image layer: both gradients as K-packed products (csrc/narrow.hip) — the generic tiles would pad 3 channels to 32
         if needs_w:
@@ -485,14 +530,16 @@ def deconv2d(x, kernel, bias, c_out, act=None, kernel_grad=None, bias_grad=None,
                 filter_grad(geom.deconv_wgrad(x.n, x.h, x.w, co_p, ci_p), dpre, x.t, 25, c_out, c_in, dw, defer=wn is None)
             if wn is not None:
                 _call('tg_wn_bwd_tab_f32', _p(dw), _p(kernel), _p(wn[0]), 25, c_out, c_in, _p(kernel_grad), _p(wn[1]), cx.stream)
-        if needs_x:
-            gx = cx.grad_of(x)
+
+        def store(gx):
             if narrow and gx.ld >= ci_p:
                 _call('tg_deconv5x5s2_narrow_dgrad_f32', _p(dpre), co_p, _p(kernel), _p(scale_a), x.n, x.h, x.w, c_out, c_in, ci_p, gx.ptr, gx.ld, cx.stream)
             else:
                 assert w_tr is not None, "deconv2d backward: the transposed filter was not prepared (gradient buffer narrower than the input's channel stride)"
                 _call('tg_igemm_f32', geom.deconv_dgrad(x.n, x.h, x.w, ci_p, co_p, ld_out=gx.ld, n_store=ci_p), _p(dpre), _p(w_tr), None,
                       gx.ptr, cx.stream)
+        if needs_x:
+            _write_grad(cx, x, store)
 
     cx.record(bwd)
     return y
@@ -517,17 +564,20 @@ def mean_only_batch_norm(x, pop_mean, b, b_grad=None, train=True, decay=0.9, seg
     def bwd():
         gy = y.grad
         assert gy is not None
-        gx = cx.grad_of(x)
-        if train:
-            s1, _ = colstats(0, gy.t, gy.ld, None, 0, x.rows, c, seg_rows)
-            sh = cx.scratch('bshift', nseg * c)
-            db = b_grad if want_b else cx.scratch('db', c)
-            _call('tg_mobn_bwd_finalize_f32', _p(s1), seg_array(seg_rows), nseg, x.rows, c, _p(sh), _p(db), cx.stream)
-            _call('tg_seg_actgrad_shift_f32', gy.ptr, gy.ld, gy.ptr, gy.ld, gx.ptr, gx.ld, x.rows, c, seg_array(seg_rows), nseg, _p(sh), 0, 0.0, cx.stream)
-        else:
-            _call('tg_actgrad_f32', gy.ptr, gy.ld, None, 0, None, 0, 1.0, gx.ptr, gx.ld, x.rows, c, 0, 0.0, cx.stream)
-            if want_b:
-                colstats(0, gy.t, gy.ld, None, 0, x.rows, c, [x.rows], s1=b_grad)
+
+        def store(gx):
+            if train:
+                s1, _ = colstats(0, gy.t, gy.ld, None, 0, x.rows, c, seg_rows)
+                sh = cx.scratch('bshift', nseg * c)
+                db = b_grad if want_b else cx.scratch('db', c)
+                _call('tg_mobn_bwd_finalize_f32', _p(s1), seg_array(seg_rows), nseg, x.rows, c, _p(sh), _p(db), cx.stream)
+                _call('tg_seg_actgrad_shift_f32', gy.ptr, gy.ld, gy.ptr, gy.ld, gx.ptr, gx.ld, x.rows, c, seg_array(seg_rows), nseg, _p(sh), 0, 0.0,
+                      cx.stream)
+            else:
+                _call('tg_actgrad_f32', gy.ptr, gy.ld, None, 0, None, 0, 1.0, gx.ptr, gx.ld, x.rows, c, 0, 0.0, cx.stream)
+                if want_b:
+                    colstats(0, gy.t, gy.ld, None, 0, x.rows, c, [x.rows], s1=b_grad)
+        _write_grad(cx, x, store)
 
     cx.record(bwd)
     return y
@@ -571,8 +621,8 @@ def batch_norm_train(x, gamma, beta, mm, mv, eps, decay, gamma_grad=None, beta_g
     sfx = 'bf16' if y16 else 'f32'
     if y16:
         cx.bf16_act_layers.add(cx.scope_name())
-    if x.bn_sums is not None and x.bn_sums[1] == tuple(seg_rows):
-        sums = x.bn_sums[0]                                   # the producing convolution took the statistics in its epilogue (conv2d(bn_stats=True))
+    if x.bn_sums is not None and x.bn_sums.seg_rows == tuple(seg_rows):
+        sums = x.bn_sums.sums                                # the producing convolution took the statistics in its epilogue (conv2d(bn_stats=True))
         _call('tg_bn_train_apply_' + sfx, x.ptr, x.ld, y.ptr, y.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(beta), eps, decay, _p(mm), _p(mv),
               _p(sums), _p(mean_inv), cx.stream)
     else:
@@ -588,30 +638,32 @@ def batch_norm_train(x, gamma, beta, mm, mv, eps, decay, gamma_grad=None, beta_g
     if not needs:
         return y
     if x.ld == y.ld and nseg <= 8:
-        y.bn_bwd_sink = (x, tuple(seg_rows))              # see Act.bn_bwd_sink
+        _offer(y, BnBwdStats(x, tuple(seg_rows), None, None))
 
     def bwd():
         gy = y.grad
         assert gy is not None
         want = trains and gamma_grad is not None
-        gx = cx.grad_of(x)
-        if y.bn_bwd_sums is not None and y.bn_bwd_sums[1] is gy and gy.contribs == 1:
-            bsums, zdb = y.bn_bwd_sums[0], 2                # the launch that produced gy took the statistics in its epilogue (tg_igemm_bnbwdstat_*)
-        else:
-            bsums, zdb = _sums64(cx, 'bnb64', nseg, c, pair=True)
-        sink = x.bias_sink
-        if sink is not None and x.ld == gx.ld and c % 4 == 0 and (c <= 256 and 256 % (c // 4) == 0 or c % 256 == 0):
-            # x = act(conv + bias) of the layer in front (Act.bias_sink): this pass also multiplies by act'(x) and sums the columns — gx IS
-            # that layer's pre-activation gradient and its bias gradient is done (no tg_actgrad_bias_f32 pass over the activation)
-            act_, alpha_, bias_grad_ = sink
-            dsum, zds = _sums64(cx, 'bnd64', 1, c)
-            _call('tg_bn_train_bwd_act_f32', gy.ptr, gy.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(mean_inv),
-                  ACT[act_], alpha_, _p(bsums), zdb, _p(gamma_grad) if want else None, _p(beta_grad) if want else None, _p(dsum), zds,
-                  _p(bias_grad_), cx.stream)
-            x.grad_is_dpre = True
-            return
-        _call('tg_bn_train_bwd_f32', gy.ptr, gy.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(mean_inv),
-              1 if relu_input else 0, _p(bsums), zdb, _p(gamma_grad) if want else None, _p(beta_grad) if want else None, cx.stream)
+        taken = _trusted(y, gy)
+
+        def store(gx):
+            if taken is not None:
+                bsums, zdb = taken.sums, 2                  # the launch that produced gy took the statistics in its epilogue (tg_igemm_bnbwdstat_*)
+            else:
+                bsums, zdb = _sums64(cx, 'bnb64', nseg, c, pair=True)
+            o = x.offer
+            if isinstance(o, BiasSums) and x.ld == gx.ld and c % 4 == 0 and (c <= 256 and 256 % (c // 4) == 0 or c % 256 == 0):
+                # x = act(conv + bias) of the layer in front: this pass also multiplies by act'(x) and sums the columns — what it stores IS
+                # that layer's pre-activation gradient and its bias gradient is done (no tg_actgrad_bias_f32 pass over the activation)
+                dsum, zds = _sums64(cx, 'bnd64', 1, c)
+                _call('tg_bn_train_bwd_act_f32', gy.ptr, gy.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(mean_inv),
+                      ACT[o.act], o.alpha, _p(bsums), zdb, _p(gamma_grad) if want else None, _p(beta_grad) if want else None, _p(dsum), zds,
+                      _p(o.bias_grad), cx.stream)
+                x.taken = o
+                return
+            _call('tg_bn_train_bwd_f32', gy.ptr, gy.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.rows, c, seg_array(seg_rows), nseg, _p(gamma), _p(mean_inv),
+                  1 if relu_input else 0, _p(bsums), zdb, _p(gamma_grad) if want else None, _p(beta_grad) if want else None, cx.stream)
+        _write_grad(cx, x, store)
 
     cx.record(bwd)
     return y
@@ -627,15 +679,13 @@ def scale_mask(x, mask_t, mscale, defer=False):
     cx = ctx()
     if defer:
         y = Act(None, x.n, x.h, x.w, x.c, x.ld, requires_grad=x.requires_grad)
-        y.pending = (x, mask_t, mscale)
+        y.pending = Pending(x, mask_t, mscale)
         return y
     y = cx.new_act(x.n, x.h, x.w, x.c, x.ld, requires_grad=x.requires_grad)
     _call('tg_actgrad_f32', x.ptr, x.ld, None, 0, _p(mask_t), x.c, mscale, y.ptr, y.ld, x.rows, x.c, 0, 0.0, cx.stream)
     if cx.tape is not None and x.requires_grad:
-        def bwd():
-            gx = cx.grad_of(x)
-            _call('tg_actgrad_f32', y.grad.ptr, y.grad.ld, None, 0, _p(mask_t), x.c, mscale, gx.ptr, gx.ld, x.rows, x.c, 0, 0.0, cx.stream)
-        cx.record(bwd)
+        cx.record(lambda: _write_grad(cx, x, lambda gx: _call('tg_actgrad_f32', y.grad.ptr, y.grad.ld, None, 0, _p(mask_t), x.c, mscale, gx.ptr,
+                                                              gx.ld, x.rows, x.c, 0, 0.0, cx.stream)))
     return y
 
 
@@ -644,15 +694,12 @@ def cond_concat(x, y_onehot_t, ncls):
     require_f32(x, 'cond_concat')
     cx = ctx()
     ld = pad32(x.c + ncls)
-    if x.labels is not None and x.labels == (y_onehot_t.data_ptr(), ncls) and x.ld == ld and x.pending is None:
+    if x.labels == Labels(y_onehot_t.data_ptr(), ncls) and x.ld == ld and x.pending is None:
         # the producing convolution already wrote this concatenation into its own (wide) buffer: the same storage, seen with the label channels
         out = Act(x.t, x.n, x.h, x.w, x.c + ncls, ld, requires_grad=x.requires_grad)
         if cx.tape is not None and x.requires_grad:
-            def bwd_alias():                     # the convolution's backward reads its gradient through (pointer, channel stride): no copy
-                g = out.grad
-                x.grad = Act(g.t, x.n, x.h, x.w, x.c, g.ld)
-                x.grad.contribs = 1
-            cx.record(bwd_alias)
+            # the convolution's backward reads its gradient through (pointer, channel stride): no copy
+            cx.record(lambda: _write_grad(cx, x, alias=Act(out.grad.t, x.n, x.h, x.w, x.c, out.grad.ld)))
         return out
     mask_t, mscale = None, 1.0
     if x.pending is not None:                    # a deferred dropout in front (scale_mask(defer=True)): one launch for both
@@ -662,17 +709,11 @@ def cond_concat(x, y_onehot_t, ncls):
     if cx.tape is not None and x.requires_grad:
         def bwd():   # gradient of the first x.c channels; the label channels are constants
             g = out.grad
-            if mask_t is not None:
-                gx = cx.grad_of(x)
-                _call('tg_actgrad_f32', g.ptr, g.ld, None, 0, _p(mask_t), x.c, mscale, gx.ptr, gx.ld, x.rows, x.c, 0, 0.0, cx.stream)
-            elif x.grad is None and x.strided_grad_ok:
-                # no copy: x's gradient IS the leading channels of the concatenated gradient (every consumer of an activation
-                # gradient reads it through (pointer, channel stride))
-                x.grad = Act(g.t, x.n, x.h, x.w, x.c, g.ld)
-                x.grad.contribs = 1
-            else:
-                gx = cx.grad_of(x)
-                _call('tg_actgrad_f32', g.ptr, g.ld, None, 0, None, 0, 1.0, gx.ptr, gx.ld, x.rows, x.c, 0, 0.0, cx.stream)
+            if mask_t is None and x.strided_grad_ok:
+                # no copy: x's gradient IS the leading channels of the concatenated gradient
+                return _write_grad(cx, x, alias=Act(g.t, x.n, x.h, x.w, x.c, g.ld))
+            _write_grad(cx, x, lambda gx: _call('tg_actgrad_f32', g.ptr, g.ld, None, 0, _p(mask_t), x.c if mask_t is not None else 0, mscale, gx.ptr,
+                                                gx.ld, x.rows, x.c, 0, 0.0, cx.stream))
         cx.record(bwd)
     return out
 
@@ -711,20 +752,21 @@ def _record_maxpool_bwd(cx, y, out, mask_t, mscale):
     """backward closure of max-pool 2x2 + dropout from y to out (shared by maxpool2_dropout and the fused apply + pool launch of conv2d)."""
     if cx.tape is not None and y.requires_grad:
         def bwd():
-            fresh = y.grad is None
-            gy = cx.grad_of(y)
-            sink = y.grad_sink
-            if (sink is not None and fresh and y.c % 4 == 0 and y.c <= 512 and sum(sink[2]) == y.rows
-                    and all(r % (y.h * y.w) == 0 for r in sink[2])):
-                # y is the output of a mean-only-BN layer: route, multiply by its activation derivative and sum the columns in one pass
-                nsg = len(sink[2])
-                gsum, zd = _sums64(cx, 'ps64', nsg, y.c)
-                _call('tg_maxpool2_bwd_actsum_f32', out.grad.ptr, out.grad.ld, _p(mask_t), y.c, mscale, y.ptr, y.ld, gy.ptr, gy.ld, y.n, y.h, y.w,
-                      y.c, seg_array(sink[2]), nsg, ACT[sink[0]], sink[1], _p(gsum), zd, cx.stream)
-                y.grad_fused = (gsum, STATS_REPLICAS)
-            else:
-                _call('tg_maxpool2_bwd_f32', out.grad.ptr, out.grad.ld, _p(mask_t), y.c, mscale, y.ptr, y.ld, gy.ptr, gy.ld, y.n, y.h, y.w,
-                      y.c, cx.stream)
+            first, o = y.grad is None, y.offer
+
+            def store(gy):
+                if (isinstance(o, ActSums) and first and y.c % 4 == 0 and y.c <= 512 and sum(o.seg_rows) == y.rows
+                        and all(r % (y.h * y.w) == 0 for r in o.seg_rows)):
+                    # y is the output of a mean-only-BN layer: route, multiply by its activation derivative and sum the columns in one pass
+                    nsg = len(o.seg_rows)
+                    gsum, zd = _sums64(cx, 'ps64', nsg, y.c)
+                    _call('tg_maxpool2_bwd_actsum_f32', out.grad.ptr, out.grad.ld, _p(mask_t), y.c, mscale, y.ptr, y.ld, gy.ptr, gy.ld, y.n, y.h, y.w,
+                          y.c, seg_array(o.seg_rows), nsg, ACT[o.act], o.alpha, _p(gsum), zd, cx.stream)
+                    y.taken = o._replace(sums=gsum, replicas=STATS_REPLICAS)
+                else:
+                    _call('tg_maxpool2_bwd_f32', out.grad.ptr, out.grad.ld, _p(mask_t), y.c, mscale, y.ptr, y.ld, gy.ptr, gy.ld, y.n, y.h, y.w,
+                          y.c, cx.stream)
+            _write_grad(cx, y, store)
         cx.record(bwd)
 
 
@@ -734,10 +776,8 @@ def global_maxpool(x):
     out = cx.new_act(x.n, 1, 1, x.c, pad32(x.c), requires_grad=x.requires_grad)
     _call('tg_gmaxpool_fwd_f32', x.ptr, x.ld, out.ptr, out.ld, x.n, x.h * x.w, x.c, cx.stream)
     if cx.tape is not None and x.requires_grad:
-        def bwd():
-            gx = cx.grad_of(x)
-            _call('tg_gmaxpool_bwd_f32', out.grad.ptr, out.grad.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.n, x.h * x.w, x.c, cx.stream)
-        cx.record(bwd)
+        cx.record(lambda: _write_grad(cx, x, lambda gx: _call('tg_gmaxpool_bwd_f32', out.grad.ptr, out.grad.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.n,
+                                                              x.h * x.w, x.c, cx.stream)))
     return out
 
 
@@ -748,10 +788,8 @@ def global_avgpool_concat(x, y_onehot_t, ncls):
     out = cx.new_act(x.n, 1, 1, x.c + ncls, pad32(x.c + ncls), requires_grad=x.requires_grad)
     _call('tg_gavgpool_concat_f32', x.ptr, x.ld, x.c, _p(y_onehot_t), ncls, out.ptr, out.ld, x.n, x.h * x.w, cx.stream)
     if cx.tape is not None and x.requires_grad:
-        def bwd():
-            gx = cx.grad_of(x)
-            _call('tg_gavgpool_bwd_f32', out.grad.ptr, out.grad.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.n, x.h * x.w, x.c, 0, 0.0, cx.stream)
-        cx.record(bwd)
+        cx.record(lambda: _write_grad(cx, x, lambda gx: _call('tg_gavgpool_bwd_f32', out.grad.ptr, out.grad.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.n,
+                                                              x.h * x.w, x.c, 0, 0.0, cx.stream)))
     return out
 
 
@@ -782,9 +820,8 @@ def minibatch_discrimination(x, w, b, num_kernels, dim, w_grad=None, b_grad=None
         def bwd():
             g = out.grad
             holder['g'] = g
-            ga = cx.grad_of(a)
-            _call('tg_minibatch_disc_bwd_f32', a.ptr, a.ld, C.c_void_p(g.t.data_ptr() + 4 * c0), g.ld, ga.ptr, ga.ld, _p(b_grad), x.n, num_kernels,
-                  dim, cx.stream)
+            _write_grad(cx, a, lambda ga: _call('tg_minibatch_disc_bwd_f32', a.ptr, a.ld, C.c_void_p(g.t.data_ptr() + 4 * c0), g.ld, ga.ptr, ga.ld,
+                                                _p(b_grad), x.n, num_kernels, dim, cx.stream))
         cx.record(bwd)
     return out
 
@@ -825,10 +862,7 @@ def reshape(x, n, h, w, c):
     assert x.ld == x.c and n * h * w * c == x.rows * x.c
     y = Act(x.t, n, h, w, c, c, x.requires_grad)
     if cx.tape is not None and x.requires_grad:
-        def bwd():
-            g = y.grad
-            x.grad = Act(g.t, x.n, x.h, x.w, x.c, x.c)
-        cx.record(bwd)
+        cx.record(lambda: _write_grad(cx, x, alias=Act(y.grad.t, x.n, x.h, x.w, x.c, x.c)))
     return y
 
 
@@ -839,9 +873,7 @@ def add_noise(x, noise_t):
     y = cx.new_act(x.n, x.h, x.w, x.c, x.ld, requires_grad=x.requires_grad)
     _call('tg_pad_add_f32', x.ptr, x.ld, x.c, _p(noise_t), x.c, y.ptr, y.ld, x.rows, cx.stream)
     if cx.tape is not None and x.requires_grad:
-        def bwd():
-            x.grad = y.grad
-        cx.record(bwd)
+        cx.record(lambda: _write_grad(cx, x, alias=Act(y.grad.t, x.n, x.h, x.w, x.c, y.grad.ld)))
     return y
 
 
@@ -863,7 +895,7 @@ def concat_batch(acts):
                 return
             off = 0
             for a in acts:
-                a.grad = out.grad.view_rows(off, off + a.n)
+                _write_grad(cx, a, alias=out.grad.view_rows(off, off + a.n))
                 off += a.n
         cx.record(bwd)
     return out
@@ -880,10 +912,8 @@ def activation(x, act, alpha=0.2):
     y.strided_grad_ok = True
     _call('tg_act_f32', x.ptr, x.ld, y.ptr, y.ld, x.rows, x.c, ACT[act], alpha, cx.stream)
     if cx.tape is not None and x.requires_grad:
-        def bwd():
-            gx = cx.grad_of(x)
-            _call('tg_actgrad_f32', y.grad.ptr, y.grad.ld, y.ptr, y.ld, None, 0, 1.0, gx.ptr, gx.ld, x.rows, x.c, ACT[act], alpha, cx.stream)
-        cx.record(bwd)
+        cx.record(lambda: _write_grad(cx, x, lambda gx: _call('tg_actgrad_f32', y.grad.ptr, y.grad.ld, y.ptr, y.ld, None, 0, 1.0, gx.ptr, gx.ld, x.rows,
+                                                              x.c, ACT[act], alpha, cx.stream)))
     return y
 
 
@@ -911,14 +941,16 @@ def batch_norm_moments(x, scale, beta, pop_mean, pop_var, eps, decay, train, sca
     def bwd():
         gy = y.grad
         assert gy is not None
-        gx = cx.grad_of(x)
-        d1, d2 = colstats(3, gy.t, gy.ld, x.t, x.ld, x.rows, c, [x.rows])
-        abc = cx.scratch('bnabc', 3 * c)
-        want = trains and scale_grad is not None
-        dg = scale_grad if want else cx.scratch('bndg', c)
-        db = beta_grad if want else cx.scratch('bndb', c)
-        _call('tg_bn_bwd_finalize_f32', _p(d1), _p(d2), x.rows, c, _p(scale), _p(mean_inv), _p(abc), _p(dg), _p(db), cx.stream)
-        _call('tg_bn_bwd_apply_f32', gy.ptr, gy.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.rows, c, _p(abc), 0, cx.stream)
+
+        def store(gx):
+            d1, d2 = colstats(3, gy.t, gy.ld, x.t, x.ld, x.rows, c, [x.rows])
+            abc = cx.scratch('bnabc', 3 * c)
+            want = trains and scale_grad is not None
+            dg = scale_grad if want else cx.scratch('bndg', c)
+            db = beta_grad if want else cx.scratch('bndb', c)
+            _call('tg_bn_bwd_finalize_f32', _p(d1), _p(d2), x.rows, c, _p(scale), _p(mean_inv), _p(abc), _p(dg), _p(db), cx.stream)
+            _call('tg_bn_bwd_apply_f32', gy.ptr, gy.ld, x.ptr, x.ld, gx.ptr, gx.ld, x.rows, c, _p(abc), 0, cx.stream)
+        _write_grad(cx, x, store)
 
     cx.record(bwd)
     return y

@@ -28,8 +28,8 @@ class Act(object):
     dtype: storage type of the elements — 'f32', or 'bf16' (config.ACT_DTYPE: a batch norm's output whose only reader is a bf16-operand
     convolution; t is then a torch.bfloat16 view of the workspace, ld and the offsets count bf16 elements).  Only the ops that name a
     bf16 reader accept such a handle (ops.require_f32)."""
-    __slots__ = ('t', 'n', 'h', 'w', 'c', 'ld', 'dtype', 'grad', 'requires_grad', 'strided_grad_ok', 'grad_sink', 'grad_fused', 'pending', 'bias_sink',
-                 'grad_is_dpre', 'bn_sums', 'bn_bwd_sink', 'bn_bwd_sums', 'contribs', 'labels')
+    __slots__ = ('t', 'n', 'h', 'w', 'c', 'ld', 'dtype', 'grad', 'requires_grad', 'strided_grad_ok', 'offer', 'taken', 'bn_sums', 'labels', 'pending',
+                 'contribs')
 
     def __init__(self, t, n, h, w, c, ld, requires_grad=False, dtype='f32'):
         if dtype not in ('f32', 'bf16'):
@@ -40,18 +40,18 @@ class Act(object):
         self.grad = None
         self.requires_grad = requires_grad
         self.strided_grad_ok = False      # set by producers whose backward reads .grad through (pointer, channel stride) only
-        self.grad_sink = None             # (act, alpha, seg_rows): the producer is a mean-only-BN layer — a consumer whose input-gradient
-        self.grad_fused = None            # launch can apply act'(y) and sum the columns stores t = dx*act'(y) in .grad and the sums here
-        self.bias_sink = None             # (act, alpha, bias gradient): the producer is conv / deconv + bias + relu-like activation — a batch norm
-        self.grad_is_dpre = False         # consuming it folds act'(y) and the bias-gradient sums into its backward pass and sets this flag
-        self.bn_sums = None               # (fp64 sums buffer, seg_rows): the producing convolution took the batch-norm statistics of this tensor
-        self.bn_bwd_sink = None           # (batch norm's input Act, seg_rows): this tensor is a training-mode batch norm's output — the launch that
-        self.bn_bwd_sums = None           # produces its gradient can take the backward statistics (sum dy, sum dy*x) and leaves the buffer here
-        self.labels = None                # (label tensor address, n labels): the producing convolution wrote the cond_concat behind it into this buffer
-        self.contribs = 0                 # on a GRADIENT handle: how many backward closures have written into it (Context.grad_of) — the fused
-                                          # backward paths above are only valid for exactly one
-        self.pending = None               # (source Act, keep-mask, scale): a dropout the NEXT op applies in its own launch (ops.scale_mask(defer=True));
-                                          # such a handle has no storage of its own (t is None) until that op has run
+        self.contribs = 0                 # on a GRADIENT handle: how many backward closures have written into it (Context.grad_of)
+        # Fused backward hand-offs (the records and the rule are in tg/ops.py).  A PRODUCER leaves at most one `offer` on its output: work of
+        # its own backward pass that a launch writing that output's gradient can do on the way (a mean-only-BN layer: act' and the column
+        # sums; conv / deconv + bias + relu-like activation: act' and the bias gradient; a training-mode batch norm: its backward
+        # statistics).  A CONSUMER whose backward launch is eligible takes the offer and leaves what it did in `taken`.  The producer's
+        # backward TRUSTS `taken` only while that consumer is the gradient's one writer (ops._trusts).
+        self.offer = None
+        self.taken = None
+        self.bn_sums = None               # (this and the next two: notes for the op that follows directly) the producing convolution took the batch-norm statistics
+        self.labels = None                # the producing convolution wrote the cond_concat behind it into this buffer
+        self.pending = None               # a dropout the NEXT op applies in its own launch (ops.scale_mask(defer=True)); such a handle has no
+                                          # storage of its own (t is None) until that op has run
 
     @property
     def rows(self):

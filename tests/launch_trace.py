@@ -77,6 +77,7 @@ class TraceContext(Context):
 
 class Tracer(object):
     launches = True            # False on a runner that computes the case without launches (tests/ops_reference.py): no trace to assert on
+    names_buffers = True       # False on a runner whose trace holds every pointer as an opaque '<ptr>' (tests/test_gpu_ops_routes.py)
 
     def __init__(self, **ctx_kw):
         self.trace = []
@@ -333,8 +334,8 @@ def conv_concat_not_fused(tr, shape=(4, 8, 8, 32, 48)):
       absent=['tg_igemm_f32', 'tg_bn_train_f32', 'tg_actgrad_f32', 'tg_actgrad_bias_f32', 'tg_bn_train_bwd_f32'], variants=BOTH_MFMA)
 @ragged(4, 8, 16, 42, 64, (1, 3))
 def conv_bnstat_into_batch_norm(tr, shape=(4, 8, 8, 32, 64, (2, 2))):
-    """conv2d(bn_stats) -> batch_norm_train through bn_sums; backward: the batch norm folds act' and the bias gradient (bias_sink), the
-    convolution takes its gradient as the pre-activation gradient (grad_is_dpre)"""
+    """conv2d(bn_stats) -> batch_norm_train through bn_sums; backward: the batch norm folds act' and the bias gradient (the convolution's
+    BiasSums offer), the convolution takes its gradient as the pre-activation gradient (what the batch norm left in Act.taken)"""
     segs = list(shape[5])
     fwd_bwd(tr, lambda: bn(tr, conv(tr, tr.x(*shape[:4]), shape[4], act='relu', bn_stats=True, segments=segs), segments=segs))
 
@@ -403,7 +404,7 @@ def mobn_pool_odd_map(tr, shape=(4, 7, 7, 32, 32)):
 @case(expect=['tg_igemm_colsum_f32', 'tg_mobn_apply_f32', 'tg_igemm_actsum_f32', 'tg_mobn_center_f32', 'tg_mobn_bwd_f32'], variants=BOTH_MFMA)
 @ragged(3, 8, 16, 42, 64, 32)
 def mobn_two_layers_grad_fused(tr, shape=(4, 8, 8, 32, 32, 64)):
-    """the second layer's input-gradient launch applies the first layer's act' and sums the columns (grad_fused -> tg_mobn_center_f32)"""
+    """the second layer's input-gradient launch applies the first layer's act' and sums the columns (ActSums in Act.taken -> tg_mobn_center_f32)"""
     def build():
         h = conv(tr, tr.x(*shape[:4]), shape[4], p='l1.', wn=True, mobn=True, act='lrelu')
         return conv(tr, h, shape[5], p='l2.', wn=True, mobn=True, act='lrelu')
@@ -770,6 +771,84 @@ def op_colstats(tr):
         a, b = tr.t('a', 64 * 32), tr.t('b', 64 * 32)
         ops.colstats(1, a, 32, None, 0, 64, 32, [32, 32])
         ops.colstats(3, a, 32, b, 32, 64, 32, [64], act='lrelu', s1=tr.t('s1', 36), s2=tr.t('s2', 36))
+
+
+# ================================================================== a second writer of one gradient (ops._write_grad)
+
+def second_writer(tr, name, build, launch=None, via=None, shape=(2, 4, 4, 32)):
+    """One solver run `name`: h = x (or via(x)) feeds the op under test, build(h) -> its output[s], and an activation recorded AFTER it, whose
+    backward therefore runs first and is the first writer of h's gradient.  The op's own backward launch (`launch`) must then name a
+    scratch buffer, not the gradient buffer, and tg_add_f32 add that scratch to the gradient; launch None: an alias of the same channel
+    stride, added from where it lies in the consumer's gradient buffer."""
+    tr.mark(name)
+    start = len(tr.trace)
+    with tr.phase(name) as cx:
+        x = tr.x(*shape)
+        h = x if via is None else via(x)
+        outs = build(h)
+        tr.seed(ops.activation(h, 'lrelu'))
+        for o in outs if isinstance(outs, (list, tuple)) else [outs]:
+            tr.seed(o)
+        cx.backward()
+    if tr.launches and tr.names_buffers:
+        seg = [e for e in tr.trace[start:] if not isinstance(e, str)]
+        gbuf = [e[8] for e in seg if e[0] == 'tg_actgrad_f32' and re.match(r'%s/g\d+\+0$' % name, e[8])][0]      # the first writer's destination
+        add = [e for e in seg if e[0] == 'tg_add_f32'][-1]
+        assert add[1] == add[2] == gbuf and add[3] != gbuf, add
+        if launch is None:
+            assert re.match(r'%s/g\d+\+0$' % name, add[3]), add
+        else:
+            own = [e for e in seg if e[0] == launch and add[3] in e[1:]]      # the one launch that names the scratch buffer
+            assert add[3].startswith(name + '/gxp') and len(own) == 1 and gbuf not in own[0][1:], (own, add)
+
+
+@case(expect=['tg_act_f32', 'tg_actgrad_f32', 'tg_add_f32'])
+def second_writer_pointwise(tr, shape=(2, 4, 4, 32)):
+    second_writer(tr, 'activation', lambda x: ops.activation(x, 'tanh'), 'tg_actgrad_f32', shape=shape)
+    second_writer(tr, 'scale_mask', lambda x: ops.scale_mask(x, tr.t('keep', x.rows * x.c), 1.25), 'tg_actgrad_f32', shape=shape)
+
+
+@case(expect=['tg_act_f32', 'tg_actgrad_f32', 'tg_add_f32'])
+def second_writer_pointwise_c48(tr):
+    """48 channels in a channel stride of 64: the scratch buffer and the sum carry the zero padding"""
+    second_writer_pointwise(tr, (2, 4, 4, 48))
+
+
+@case(expect=['tg_maxpool2_bwd_f32', 'tg_gmaxpool_bwd_f32', 'tg_gavgpool_bwd_f32', 'tg_add_f32'], absent=['tg_maxpool2_bwd_actsum_f32'])
+def second_writer_pooling(tr):
+    second_writer(tr, 'maxpool2', lambda x: ops.maxpool2_dropout(x, tr.t('keep', 2 * 2 * 2 * 32), 1.25), 'tg_maxpool2_bwd_f32')
+    second_writer(tr, 'gmaxpool', ops.global_maxpool, 'tg_gmaxpool_bwd_f32')
+    second_writer(tr, 'gavgpool', lambda x: ops.global_avgpool_concat(x, tr.t('labels', 2 * 10), 10), 'tg_gavgpool_bwd_f32')
+
+
+@case(expect=['tg_seg_actgrad_shift_f32', 'tg_bn_train_bwd_f32', 'tg_bn_bwd_apply_f32', 'tg_add_f32'], absent=['tg_bn_train_bwd_act_f32'])
+def second_writer_norms(tr):
+    second_writer(tr, 'mobn', lambda x: ops.mean_only_batch_norm(x, tr.t('pop', 32), tr.t('b', 32), tr.t('b_grad', 32)), 'tg_seg_actgrad_shift_f32')
+    second_writer(tr, 'bn', lambda x: bn(tr, x), 'tg_bn_train_bwd_f32')
+    second_writer(tr, 'moments', lambda x: ops.batch_norm_moments(x, tr.t('m.scale', 32), tr.t('m.beta', 32), tr.t('m.pm', 32), tr.t('m.pv', 32), 1e-5, 0.9,
+                                                                  True, scale_grad=tr.t('m.sg', 32), beta_grad=tr.t('m.bg', 32)), 'tg_bn_bwd_apply_f32')
+
+
+@case(expect=['tg_igemm_multi_f32', 'tg_igemm_f32', 'tg_deconv5x5s2_narrow_dgrad_f32', 'tg_add_f32'])
+def second_writer_deconv(tr):
+    """the generic input gradient (tg_igemm_f32 on the transposed filter) and the K-packed one of the 3-channel image layer, whose smallest map is 4x16"""
+    second_writer(tr, 'generic', lambda x: deconv(tr, x, 32, p='g.', act='relu'), 'tg_igemm_f32')
+    second_writer(tr, 'narrow', lambda x: deconv(tr, x, 3, p='n.', act='tanh', narrow_out=True), 'tg_deconv5x5s2_narrow_dgrad_f32', shape=(2, 4, 16, 32))
+
+
+@case(expect=['tg_igemm_labels_f32', 'tg_cond_concat_f32', 'tg_actgrad_f32', 'tg_add_f32'])
+def second_writer_aliases(tr):
+    """the closures whose contribution is a view of the consumer's gradient buffer: added from where it lies, or, where the channel strides
+    differ (cond_concat behind an op that reads its gradient through a stride), copied into scratch first; and cond_concat's copying paths"""
+    lab = tr.t('labels', 2 * 10)
+    second_writer(tr, 'reshape', lambda x: ops.reshape(x, 2, 1, 1, 4 * 4 * 32))
+    second_writer(tr, 'add_noise', lambda x: ops.add_noise(x, tr.t('noise', x.rows * x.c)))
+    second_writer(tr, 'concat_batch', lambda x: ops.concat_batch([x, tr.x(3, 4, 4, 32)]))
+    second_writer(tr, 'concat_alias', lambda h: ops.cond_concat(h, lab, 10), via=lambda x: conv(tr, x, 32, p='a.', act='lrelu', concat=(lab, 10)))
+    second_writer(tr, 'concat_strided', lambda h: ops.cond_concat(h, lab, 10), 'tg_actgrad_f32', via=lambda x: ops.activation(x, 'relu'))
+    second_writer(tr, 'concat_copy', lambda x: ops.cond_concat(x, lab, 10), 'tg_actgrad_f32')
+    second_writer(tr, 'concat_dropout', lambda x: ops.cond_concat(ops.scale_mask(x, tr.t('keep', x.rows * x.c), 1.25, defer=True), lab, 10),
+                  'tg_actgrad_f32')
 
 
 # ================================================================== recording

@@ -31,6 +31,7 @@ import torch.nn.functional as F
 
 import kernel_check as KC
 from oracle import tf_ops as T
+from tg.ops import Labels, Pending
 
 U, TOL = KC.U, KC.TOL
 F64 = torch.float64
@@ -544,7 +545,7 @@ class RefOps(object):
         ld = pad32(c_out + concat[1]) if fuse_cat else n_store_ld[1] if n_store_ld is not None else None
         y = self._out(act_fn(pre, act, alpha), needs_w or needs_x, ld)
         if fuse_cat:
-            y.labels = (concat[0], concat[1])
+            y.labels = Labels(concat[0], concat[1])
         if needs_w or needs_x:
             def bwd():
                 assert y.grad is not None, "conv2d backward: no gradient reached the output"
@@ -567,7 +568,7 @@ class RefOps(object):
                     else:
                         kernel_grad.set(dw)
                 if needs_x:
-                    cx.add_grad(x, conv_dx(dq, wq, x.v.shape, stride, padding), accumulate=True)
+                    cx.add_grad(x, conv_dx(dq, wq, x.v.shape, stride, padding))
             cx.record(bwd)
         return y if pool is None else self.maxpool2_dropout(y, pool[0], pool[1])
 
@@ -714,7 +715,7 @@ class RefOps(object):
         cx = self.cx
         if defer:
             y = RAct(x.v, x.requires_grad, x.ld)
-            y.pending = (x, mask_t, mscale)
+            y.pending = Pending(x, mask_t, mscale)
             return y
         m = mask_t.val.reshape(x.v.shape)
         y = self._out(dropout(x.v, m, mscale), x.requires_grad, x.ld)
@@ -929,16 +930,13 @@ class RefContext(object):
         if self.tape is not None:
             self.tape.append(fn)
 
-    def add_grad(self, a, g, accumulate=False):
-        """a backward closure (or a loss head) writes g as the gradient of `a`.  tg/ops.py's tape serves chains: a backward launch
-        OVERWRITES its destination and every alias replaces the gradient, with two exceptions that ADD to a gradient that is already
-        there — minibatch_discrimination's skip path, and (accumulate) the generic input-gradient launch of conv2d / the dense layers
-        (ops._input_grad: the product goes to a scratch buffer and tg_add_f32 adds it, one more float32 rounding), so that a gradient a
-        loss seeded on a layer's input (the classifier's pooled feature) or that another consumer wrote first is not lost.  Where a case
-        body gives an activation a second writer of any other kind the writer that runs last defines the gradient, and that is what
-        this reference restates; the fused paths that cannot tolerate a second writer refuse it (bwd_single_consumer_refusal).  The
-        networks batch the applications of a layer into segments instead of consuming a tensor twice."""
-        a.grad = add(a.grad, g) if (accumulate and a.grad is not None) else g
+    def add_grad(self, a, g):
+        """a backward closure writes g as its contribution to the gradient of `a` (ops._write_grad).  The first writer's launch stores, and an
+        alias adopts the consumer's buffer: g as it is.  Every later writer ADDS: its launch stores into a scratch buffer (an alias is
+        already in memory) and tg_add_f32 adds that to the gradient, one more float32 rounding.  minibatch_discrimination's skip path adds
+        in place (tg_pad_add_f32) and states that itself.  The fused paths that cannot tolerate a second writer refuse it
+        (bwd_single_consumer_refusal)."""
+        a.grad = g if a.grad is None else add(a.grad, g)
 
     def mask_of(self, a):
         """the stored forward output of the implementation under test for activation `a` (None: the reference's own)"""
@@ -1013,7 +1011,7 @@ class RefRunner(object):
     def seed(self, y, ld=None):
         g = V(self._tensor(fill_seed(self.fill_seed, len(self.seeds), y.v.shape)))
         self.seeds.append(y)
-        self.cx.add_grad(y, g)
+        y.grad = g                                         # the loss head's write: an assignment, as Tracer.seed
         return y.grad
 
     def mark(self, text):

@@ -86,7 +86,7 @@ class GpuContext(Context):
 
 def snap(a):
     """a device copy of an activation (taken on the launch stream, where its producer ran)"""
-    own = a.c + (a.labels[1] if a.labels is not None else 0)      # a convolution that appends the label channels owns them too
+    own = a.c + (a.labels.ncls if a.labels is not None else 0)     # a convolution that appends the label channels owns them too
     return dict(t=a.t.detach().float().clone(), rows=a.rows, ld=a.ld, shape=(a.n, a.h, a.w, a.c), own=own)
 
 
@@ -99,6 +99,8 @@ def padding(s):
 
 
 class GpuRunner(LT.Tracer):
+    names_buffers = False      # pointers are opaque in this trace
+
     def __init__(self, name, ident, **ctx_kw):
         self.trace, self.labels, self.label_guards, self._real_call = [], {}, {}, None
         self.variant, self.key = name, R.fill_key(name, ident)

@@ -368,11 +368,12 @@ def test_salimans_layers_and_data_dependent_init(plain):
 
 def test_fused_backward_paths_refuse_a_second_consumer(plain):
     """advisor (round 3): the batch-norm backward fusions assume ONE consumer per tensor.  (a) conv -> relu -> x, consumed by a batch norm AND by
-    a second convolution: the batch norm's backward folds relu'(x) and the bias gradient into x's gradient buffer (Act.grad_is_dpre), the other
-    consumer writes a raw gradient into the same buffer — the producing convolution must refuse to train on that buffer (Act.contribs, counted
-    in Context.grad_of) instead of treating it as its pre-activation gradient.  (b) a batch norm's OUTPUT consumed by two convolutions: the
-    backward statistics the first consumer's input-gradient launch took (Act.bn_bwd_sums) are not the statistics of the final gradient — the
-    batch norm must fall back to its own statistics pass, and then gives the oracle's gradient for the gradient buffer as it stands."""
+    a second convolution: the batch norm's backward folds relu'(x) and the bias gradient into x's gradient (it takes the convolution's
+    ops.BiasSums offer and leaves it in Act.taken), the other consumer contributes a raw gradient to the same buffer — the producing convolution
+    must refuse to train on that buffer (Act.contribs, counted in Context.grad_of; ops._trusted) instead of treating it as its pre-activation
+    gradient.  (b) a batch norm's OUTPUT consumed by two convolutions: the backward statistics the first consumer's input-gradient launch
+    took (ops.BnBwdStats in Act.taken) are not the statistics of the final gradient — the batch norm must not trust them and fall back to its
+    own statistics pass, and then gives the oracle's gradient for the gradient buffer as it stands."""
     from tg import lib, ops
     cx = plain.cx
     rng = np.random.default_rng(21)
@@ -405,7 +406,8 @@ def test_fused_backward_paths_refuse_a_second_consumer(plain):
         with cx.variable_scope('discriminator'):
             x, y = graph('y')
             cx.backward()
-            assert y.grad.contribs == 2 and y.bn_bwd_sums is None          # the second consumer withdrew the first one's statistics
+            # the first consumer took the statistics hand-off, the second one's contribution made it void: the batch norm did not use it
+            assert y.grad.contribs == 2 and isinstance(y.taken, ops.BnBwdStats) and ops._trusted(y, y.grad) is None
             gy = y.grad.numpy().astype(np.float64)
             xr = x.numpy().astype(np.float64)
             _, cache = T.batch_norm_train(xr, np.ones(c), np.zeros(c), 1e-3)
