@@ -29,14 +29,8 @@
 #include <type_traits>
 #include "tg_common.h"
 #include "tg_device.h"
+#include "tg_mfma.h"
 #include "tg_conv3x3_bf16.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 #ifdef TG_STAMP
 // Diagnostic build (csrc/Makefile target libtg_stamp.so, never shipped): cycle stamps of workgroup phases, wave 0 of a few workgroups,
@@ -65,8 +59,9 @@ __device__ unsigned long long tg_conv_stamps[8 * 64];
 
 namespace {
 
+using namespace tgm;
+
 constexpr int BN = 128, KC = 64;               // output channels per tile, channels per chunk
-constexpr uint32_t OOB = 0x80000000u;          // byte offset beyond any (< 2 GiB) tensor: buffer loads return 0, stores are dropped
 
 struct ConvParams {
   const float* in;
@@ -95,26 +90,6 @@ int compute_units() {
   return n;
 }
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t pack2(uint32_t a, uint32_t b) {   // 2 fp32 -> 2 bf16 (RNE): one v_cvt_pk_bf16_f32
-  const f32x2 f = {__builtin_bit_cast(float, a), __builtin_bit_cast(float, b)};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2));
-}
-
-__device__ __forceinline__ u32x2 pack4(u32x4 v) {             // 4 fp32 -> 4 bf16 (RNE), 8 bytes, channel order kept
-  u32x2 r;
-  r.x = pack2(v.x, v.y);
-  r.y = pack2(v.z, v.w);
-  return r;
-}
-
 // v + (v of the lane the DPP control names); lanes the row mask excludes add 0
 template <int CTRL, int ROW_MASK = 0xF>
 __device__ __forceinline__ float dpp_add(float v) {
@@ -140,10 +115,6 @@ __global__ void __launch_bounds__(256) filter_pack_kernel(ConvParams p, int nchu
   o.x = a.x; o.y = a.y; o.z = b.x; o.w = b.y;
   *reinterpret_cast<u32x4*>(static_cast<unsigned char*>(const_cast<void*>(p.wpk)) + (size_t)img * (BN * 128) + lds_off(r, q)) = o;
 }
-
-// s_waitcnt vmcnt(N) lgkmcnt(0) + s_barrier: the N youngest vector-memory operations of this wave stay in flight across the barrier
-template <int N>
-__device__ __forceinline__ void barrier_keep() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory"); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Persistent, tile-pipelined, role-specialised kernel.  Stamped on its one-tile-per-workgroup predecessor (conv1_2, bf16 operands): of
@@ -218,7 +189,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pipe_kernel(ConvParams p) {
         const int hy = hp / HW_, hx = hp - hy * HW_;
         const int iy = row0 + hy - 1, ix = hx - 1;
         const bool ok = hp < HP && (unsigned)iy < (unsigned)p.h && (unsigned)ix < (unsigned)W;
-        a_voff[i] = ok ? (uint32_t)(((img * p.h + iy) * W + ix) * p.ld_in + 4 * qu) * (IN16 ? 2u : 4u) : OOB;
+        a_voff[i] = ok ? (uint32_t)(((img * p.h + iy) * W + ix) * p.ld_in + 4 * qu) * (IN16 ? 2u : 4u) : OOB_OFF;
       }
     };
     int nt_b = 0, bbuf_w = 0;                                   // filter column tile the fetches read; filter buffer the next fetch fills
@@ -547,7 +518,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_pipe_kernel(ConvParams p) {
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           const int n = n0 + ni * 32 + col;
-          ch_off[ni] = n < p.n_store ? px0 * row_bytes + (uint32_t)n * 4u : OOB;
+          ch_off[ni] = n < p.n_store ? px0 * row_bytes + (uint32_t)n * 4u : OOB_OFF;
           cs[ni] = 0.f;
         }
         // pixel of fragment row (r & 3) + 8*(r >> 2) + 4*half, less the 4*half that px0 carries; W = 16: rows 16.. are rotated (see pc

@@ -5,6 +5,7 @@
 
 namespace tgd {
 
+// The activation with the library exponential (expf): every kernel but the generic conv GEMM.
 __device__ __forceinline__ float act(float v, int a, float alpha) {
   switch (a) {
     case TG_ACT_LRELU: return v > 0.f ? v : alpha * v;       // relu(x) - alpha*relu(-x), Good_GAN_cifar10.py:26-27
@@ -12,6 +13,19 @@ __device__ __forceinline__ float act(float v, int a, float alpha) {
     case TG_ACT_TANH: return tanhf(v);
     case TG_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
     case TG_ACT_SOFTPLUS: return v > 20.f ? v : log1pf(expf(v));
+    default: return v;
+  }
+}
+
+// The same activation with the hardware exponential (__expf) in sigmoid and softplus: the epilogues of the generic conv GEMM
+// (igemm_kernel.h).  The two differ in the last bits of those two activations and stay apart: stored outputs are pinned bit for bit.
+__device__ __forceinline__ float act_fast(float v, int a, float alpha) {
+  switch (a) {
+    case TG_ACT_LRELU: return v > 0.f ? v : alpha * v;
+    case TG_ACT_RELU: return v > 0.f ? v : 0.f;
+    case TG_ACT_TANH: return tanhf(v);
+    case TG_ACT_SIGMOID: return 1.f / (1.f + __expf(-v));
+    case TG_ACT_SOFTPLUS: return v > 20.f ? v : log1pf(__expf(v));
     default: return v;
   }
 }

@@ -22,20 +22,14 @@
 #include <type_traits>
 #include "tg_common.h"
 #include "tg_device.h"
+#include "tg_mfma.h"
 #include "tg_conv3x3_bf16.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
+using namespace tgm;
+
 constexpr int CC = 32, NT = 128;                 // input channels / output channels per workgroup
-constexpr uint32_t OOB = 0x80000000u;            // byte offset beyond any (< 2 GiB) tensor: buffer loads return 0
 
 struct WParams {
   const float* x;
@@ -46,20 +40,6 @@ struct WParams {
   int tap_of[9];                                 // descriptor tap index of window position (ky, kx) = (dy + 1, dx + 1), g = 3 ky + kx
   uint32_t x_bytes, dy_bytes;
 };
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-__device__ __forceinline__ u32x2 pack4(u32x4 v) {              // 4 fp32 -> 4 bf16 (RNE), channel order kept
-  return __builtin_bit_cast(u32x2, __builtin_convertvector(__builtin_bit_cast(f32x4, v), bf16x4));
-}
-
-__device__ __forceinline__ int dy_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-
-template <int N>
-__device__ __forceinline__ void barrier_keep() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory"); }
 
 // IN16: the activation x is STORED as bf16 (tg_wgrad_bf16in_bf16) — 8-byte loads of four channels, the same X_IT loads per tile as the
 // fp32 form, written to the halo image as they arrive (no conversion); dy stays fp32
@@ -103,13 +83,13 @@ __global__ void __launch_bounds__(512, 2) wgrad3x3_kernel(WParams p) {
     const int dq = lt & 31, dpx = lt >> 5, xq = lt & 7, xhp = lt >> 3;
     const uint32_t d_voff = (uint32_t)(dpx * p.ld_out + n0 + 4 * dq) * 4u;
     const uint32_t d_step = (uint32_t)(8 * p.ld_out * 4);
-    auto x_voff = [&](int t, int i) -> uint32_t {                  // halo pixel xhp + 32 i of tile t: global byte offset, OOB outside the image
+    auto x_voff = [&](int t, int i) -> uint32_t {                  // halo pixel xhp + 32 i of tile t: global byte offset, OOB_OFF outside the image
       const int img = t / tiles_per_img, row0 = (t - img * tiles_per_img) * R;
       const int hp = xhp + 32 * i;
       const int hy = hp / HW_, hx = hp - hy * HW_;
       const int iy = row0 + hy - 1, ix = hx - 1;
       const bool ok = hp < HP && (unsigned)iy < (unsigned)p.h && (unsigned)ix < (unsigned)W;
-      return ok ? (uint32_t)(((img * p.h + iy) * W + ix) * p.ld_in + c0 + 4 * xq) * (IN16 ? 2u : 4u) : OOB;
+      return ok ? (uint32_t)(((img * p.h + iy) * W + ix) * p.ld_in + c0 + 4 * xq) * (IN16 ? 2u : 4u) : OOB_OFF;
     };
     typedef typename std::conditional<IN16, u32x2, u32x4>::type XReg;
     struct Set { XReg x[X_IT]; u32x4 d[D_IT]; };
@@ -137,7 +117,7 @@ __global__ void __launch_bounds__(512, 2) wgrad3x3_kernel(WParams p) {
 #pragma unroll
       for (int i = 0; i < D_IT; ++i) {
         const int px = dpx + 8 * i;
-        if constexpr (BF16) *reinterpret_cast<u32x2*>(ds + dy_off(px, dq >> 1) + 8 * (dq & 1)) = pack4(r.d[i]);
+        if constexpr (BF16) *reinterpret_cast<u32x2*>(ds + swz256(px, dq >> 1) + 8 * (dq & 1)) = pack4(r.d[i]);
         else *reinterpret_cast<u32x4*>(ds + px * DROW + dq * 16) = r.d[i];
       }
     };
@@ -185,8 +165,8 @@ __global__ void __launch_bounds__(512, 2) wgrad3x3_kernel(WParams p) {
           const int cs = 32 * wave + cq;
           const unsigned char* xa = xs + (8 * half + q) * XROW + cq * 2;
           // gradient rows 16ks + 8h + q (+4): row & 3 = q and (row >> 2) & 3 = 2h (+1) for every ks, so the swizzled chunk is a per-lane constant
-          const unsigned char* dlo = ds + dy_off(8 * half + q, cs >> 3) + 8 * ((cs >> 2) & 1);
-          const unsigned char* dhi = ds + dy_off(8 * half + q + 4, cs >> 3) + 8 * ((cs >> 2) & 1);
+          const unsigned char* dlo = ds + swz256(8 * half + q, cs >> 3) + 8 * ((cs >> 2) & 1);
+          const unsigned char* dhi = ds + swz256(8 * half + q + 4, cs >> 3) + 8 * ((cs >> 2) & 1);
 #pragma unroll
           for (int ks = 0; ks < BMW / 16; ++ks) {
             const int p0 = 16 * ks, ty = p0 / W, tx0 = p0 - ty * W;
