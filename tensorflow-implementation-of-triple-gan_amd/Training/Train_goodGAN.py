@@ -15,7 +15,6 @@ RNG step) live in device memory.  Applications of one network inside a solver ru
 application).  Data-parallel replicas (one process per GPU) sum-all-reduce the trained network's flat gradient
 buffer over RCCL after each backward (tg/dist.py); the reference has no multi-device path.
 """
-import contextlib
 import math
 import os
 import time
@@ -25,27 +24,30 @@ import torch
 
 from config import Config
 from Model.zca import resolve_zca, synthetic_zca as _synthetic_zca         # (tools/ reach the synthetic rotation under this name)
+from Training.epoch_tail import EpochTail
+from Training.evaluation import Evaluation
 from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, Options, check_act_dtype, check_clip_norm, check_eval_ema,  # noqa: F401
                               check_eval_report, check_loss, check_mfma_dtype, check_num_classes, check_optimizer, check_sample_manifold_k,
                               check_sample_metrics, check_wn_init, check_zca, cla_lr, opt, resolve)
+from Training.schedule import epoch_schedule
 from Training.train_base import Train_base, clip_workspace_floats
 from tg import dist as tgdist
 from tg import executor, lib, ops
 from tg.batching import concat_acts
 from tg.runtime import Act, Context, PhiloxRNG, ctx, set_context
 
-
-class _Scores(object):
-    """what Train._score_batch adds a scored batch to: the streaming accuracy, a tg.metrics.ClassifierReport (handed in, or None) and —
-    features — the tg.metrics.FeatureMoments of the classifier's pooled feature plus, bank, a tg.metrics.FeatureBank of its rows; those
-    two are sized by the first feature seen and stay None on a side that saw no batch."""
-
-    def __init__(self, report=None, features=False, bank=False):
-        self.report, self.features, self.want_bank = report, features, bank
-        self.accuracy = self.moments = self.bank = None
+# The placeholders of the training graph (:400-413), in the order of Model.forward_pass's arguments: (feed key, the config attribute
+# that holds its batch size, what it holds).  What it holds decides a row's dimensions: see _build_train_graph.
+PLACEHOLDERS = (('z_g', 'BATCH_SIZE_G', 'latent'), ('y_g', 'BATCH_SIZE_G', 'labels'),
+                ('x_l_c', 'BATCH_SIZE_L_C', 'image'), ('y_l_c', 'BATCH_SIZE_L_C', 'labels'),
+                ('x_l_d', 'BATCH_SIZE_L_D', 'image'), ('y_l_d', 'BATCH_SIZE_L_D', 'labels'),
+                ('x_u_d', 'BATCH_SIZE_U_D', 'image'), ('x_u_c', 'BATCH_SIZE_U_C', 'image'))
 
 
-class Train(Train_base):
+class Train(Evaluation, EpochTail, Train_base):
+    """The trainer: the device state of a run, the three solver runs and the reference's epoch loop.  Its forward-only scoring passes
+    are Training/evaluation.py, what follows an epoch's iterations Training/epoch_tail.py, the epoch schedule Training/schedule.py."""
+
     def __init__(self, config, log_dir, save_dir, **kwargs):
         super(Train, self).__init__()
         self.config = config
@@ -100,20 +102,18 @@ class Train(Train_base):
     def _build_train_graph(self, Model):
         """:400-426: the placeholders become persistent device buffers of the static batch sizes."""
         c, cx = self.config, self.cx
-        dims = c.IMAGE_DIM
+        shapes = dict(latent=[c.Z_DIM], labels=[c.NUM_CLASSES], image=c.IMAGE_DIM)
 
         def ph(key, n, shape):
             t = cx.ws('ph:' + key, n * int(np.prod(shape)))
             return Act(t, n, *(shape if len(shape) == 3 else (1, 1, shape[0])), ld=shape[-1])
 
-        self.z_g_ph = ph('z_g', c.BATCH_SIZE_G, [c.Z_DIM])
-        self.y_g_ph = ph('y_g', c.BATCH_SIZE_G, [c.NUM_CLASSES])
-        self.x_l_c_ph = ph('x_l_c', c.BATCH_SIZE_L_C, dims)
-        self.y_l_c_ph = ph('y_l_c', c.BATCH_SIZE_L_C, [c.NUM_CLASSES])
-        self.x_l_d_ph = ph('x_l_d', c.BATCH_SIZE_L_D, dims)
-        self.y_l_d_ph = ph('y_l_d', c.BATCH_SIZE_L_D, [c.NUM_CLASSES])
-        self.x_u_d_ph = ph('x_u_d', c.BATCH_SIZE_U_D, dims)
-        self.x_u_c_ph = ph('x_u_c', c.BATCH_SIZE_U_C, dims)
+        # the eight Acts in PLACEHOLDERS' order; each is self.<key>_ph as well.  feed and training_statistics read the list, the step
+        # reads the attributes: the two name the same Acts and neither is rebound after the build
+        self.placeholders = []
+        for key, size, holds in PLACEHOLDERS:
+            self.placeholders.append(ph(key, getattr(c, size), shapes[holds]))
+            setattr(self, key + '_ph', self.placeholders[-1])
         self.model = Model(c)
         st = cx.stores
         # three optimisers, Adam unless config.OPTIMIZER says otherwise (:85-87): G and D share lr_ph / config.BETA1, C uses cla_lr_ph / 0.5
@@ -137,8 +137,7 @@ class Train(Train_base):
                 tgdist.broadcast_(s.p)
                 tgdist.broadcast_(s.s)
             st['classifier'].ema.copy_(st['classifier'].p)
-        PH = [self.z_g_ph, self.y_g_ph, self.x_l_c_ph, self.y_l_c_ph, self.x_l_d_ph, self.y_l_d_ph, self.x_u_d_ph,
-              self.x_u_c_ph, True, self.hyper[2:4]]
+        PH = self.placeholders + [True, self.hyper[2:4]]
         return PH, self.model
 
     def _make_optimizer(self, kind, lr_dev, beta1):
@@ -368,8 +367,7 @@ class Train(Train_base):
         """host feed_dict (:249-263) -> placeholders.  batch keys: z_g,y_g,x_l_c,y_l_c,x_l_d,y_l_d,x_u_d,x_u_c
         (numpy arrays or device Acts)."""
         dev = []
-        for key, ph in (('z_g', self.z_g_ph), ('y_g', self.y_g_ph), ('x_l_c', self.x_l_c_ph), ('y_l_c', self.y_l_c_ph),
-                        ('x_l_d', self.x_l_d_ph), ('y_l_d', self.y_l_d_ph), ('x_u_d', self.x_u_d_ph), ('x_u_c', self.x_u_c_ph)):
+        for (key, _, _), ph in zip(PLACEHOLDERS, self.placeholders):
             if key not in batch:
                 continue
             v = batch[key]
@@ -489,8 +487,7 @@ class Train(Train_base):
         last iteration's.  Returns (d_loss, g_loss, c_loss) as floats (a device->host sync)."""
         cx = self.cx
         with cx.phase_scope('stats', record=False):
-            PH = [self.z_g_ph, self.y_g_ph, self.x_l_c_ph, self.y_l_c_ph, self.x_l_d_ph, self.y_l_d_ph, self.x_u_d_ph, self.x_u_c_ph]
-            G, D, C = self.model.forward_pass(*PH, True)                                                       # :422
+            G, D, C = self.model.forward_pass(*self.placeholders, True)                                        # :422
             d, g, c = self._goodGAN_loss(G, D, C, None, [self.y_g_ph, self.y_l_c_ph], self.hyper[2:4], self.model.discriminator)
             out = (float(d), float(g), float(c))
         cx.rng.advance(cx)                       # the next iteration draws fresh numbers again
@@ -515,178 +512,6 @@ class Train(Train_base):
             return self._loss_WGAN_GP_step(m.as_image(G), D, C, X, Y, Lambda, discriminator or m.discriminator)
         return self._loss_GAN(D, C, Y, Lambda)
 
-    def _classifier_weights(self, ema):
-        """the weights a forward-only classifier pass reads: the variables, or (ema) their EMA shadows — Context.reading_shadows."""
-        return self.cx.reading_shadows('classifier') if ema else contextlib.nullcontext()
-
-    def evaluate(self, batches, ema=False, report=None):
-        """streaming accuracy of argmax C_real_logits vs argmax y over test batches with train=False (:295-351, :428-447).
-        batches: iterable of (x [n,h,w,c], y onehot [n,k]) host arrays.  Returns accuracy.
-        report: a tg.metrics.ClassifierReport that every batch is also added to, from the same logits (one more
-        tg_eval_report_f32 call per batch); None: the pass issues what it always did.
-        ema: evaluate the averaged classifier — every trainable variable read from its EMA shadow (ParamStore.ema: decay 0.9999 per
-        C-update, no bias correction), pop_mean / batch-norm moving statistics from the store as they are: what the reference's getter
-        (nn.py:98-110) would have returned had it been passed, since ema.apply covered c_vars only.  The pass leaves no
-        trace: it writes no store, draws from the Philox state without advancing it, and runs outside every prepared-filter cache."""
-        cx, scores = self.cx, _Scores(report)
-        for x, y in batches:
-            with cx.phase_scope('val', record=False), self._classifier_weights(ema):
-                self._score_batch(cx.from_numpy(x, key='val:x'), cx.from_numpy(y, key='val:y'), scores)
-        return float(scores.accuracy) if scores.accuracy is not None else 0.0
-
-    def _score_batch(self, x, y, scores, take=None):
-        """Score one device batch with the classifier, inside the caller's phase (and its _classifier_weights): whiten the images x where
-        the model whitens, classifier(x, False), then add the batch — its first `take` rows; None: all of it — to `scores` (_Scores):
-        the streaming accuracy of the arg-max against the labels y (what _metric, :428-447, counts; its one-hot prediction output is
-        not needed here), the report, the feature moments and the feature bank, in that order.
-        The input noise is drawn under evaluate's Philox stream id whatever the caller's phase: ids are handed out in order of first
-        use, and a pass that registered one of its own would shift those of a solver run that first runs later (the full step after
-        pre-training)."""
-        from tg import metrics as tgm
-        cx, m = self.cx, self.model
-        if m.zca() is not None:
-            x = m.zca().apply(m.as_image(x))
-        with cx.rng_scoped('val/C'):
-            logits, fm = m.classifier(x, False)
-        if take is not None:
-            y, logits, fm = y.view_rows(0, take), logits.view_rows(0, take), fm.view_rows(0, take)
-        scores.accuracy = self._accuracy_metric(y, logits, scores.accuracy)[0]
-        if scores.report is not None:
-            scores.report.add(y, logits, cx.stream)
-        if scores.features:
-            if scores.moments is None:
-                scores.moments = tgm.FeatureMoments(fm.c, cx.device)
-            scores.moments.add(fm, cx.stream)
-            if scores.want_bank:
-                if scores.bank is None:
-                    scores.bank = tgm.FeatureBank(fm.c, cx.device)
-                scores.bank.add(fm, cx.stream)
-
-    @contextlib.contextmanager
-    def _running_state_kept(self):
-        """every store's `s` (pop_mean, batch-norm moving statistics) as it is on entry, put back on the way out: around a pass whose
-        sampler — batch norms in training mode (reference :176-202) — moves them."""
-        kept = {net: st.s.clone() for net, st in self.cx.stores.items()}
-        try:
-            yield
-        finally:
-            for net, s_before in kept.items():
-                self.cx.stores[net].s.copy_(s_before)
-
-    def _new_report(self):
-        """an empty tg.metrics.ClassifierReport for this trainer's classifier."""
-        from tg import metrics as tgm
-        return tgm.ClassifierReport(self.options.num_classes, self.cx.device)
-
-    def evaluate_report(self, batches, ema=False):
-        """evaluate's pass with the per-class report on top -> the dict of tg.metrics.report_from_counts: confusion matrix,
-        per-class recall / precision / F1, balanced accuracy, macro F1, top-5 accuracy, NLL, Brier score, ECE and the reliability table.
-        One pass: its `accuracy` (trace / sum of the confusion matrix) is what evaluate returns on the same batches, bit for bit — the
-        kernel takes both arg-maxes by tg_accuracy_count_f32's scan.  Leaves the trainer's state as evaluate leaves it."""
-        report = self._new_report()
-        self.evaluate(batches, ema=ema, report=report)
-        return report.result()
-
-    def _sample_latents(self, n_batches):
-        """(z [n_batches * B, Z_DIM], y one-hot of class i % NUM_CLASSES) of sample_metrics: drawn once per trainer from a RandomState
-        of its own seeded by config.SEED (NumPy's global state and the device Philox state are not touched), the same every epoch.  A
-        longer request extends the draw; its head stays what it was."""
-        c = self.config
-        rows = n_batches * c.BATCH_SIZE_G
-        if self._metric_latents is None or self._metric_latents[0].shape[0] < rows:
-            rs = np.random.RandomState((int(self.options.seed) * 1000003 + 0x5A17) % (1 << 32))
-            z = rs.uniform(low=-1.0, high=1.0, size=(rows, c.Z_DIM)).astype(np.float32)
-            y = np.eye(c.NUM_CLASSES, dtype=np.float32)[np.arange(rows) % c.NUM_CLASSES]
-            self._metric_latents = (z, y)
-        z, y = self._metric_latents
-        return z[:rows], y[:rows]
-
-    def sample_metrics(self, batches, n_samples, ema=False):
-        """Score the generator with the run's own classifier -> dict(val_accuracy, g_class_accuracy, frechet_distance,
-        n_real, n_fake).
-        Real side: ONE pass over `batches` exactly as evaluate makes it (raw weights, or the shadows with `ema`), which yields
-        val_accuracy and the moments of the pooled feature `fm` (the classifier's second return value).
-        Generated side: ceil(n_samples / BATCH_SIZE_G) batches of BATCH_SIZE_G fixed latents (_sample_latents; the generator's batch
-        norms use batch statistics, so the batch size is part of the definition) through good_sampler, as_image, the model's ZCA and
-        classifier(x, False); the first n_samples are scored.  g_class_accuracy: the share whose arg-max is the class asked for
-        (tg_accuracy_count_f32).  frechet_distance: tg.metrics.frechet_distance between the two Gaussians fitted to the features
-        (tg_feature_moments_f32 in fp64 on the device, the c x c algebra on the host); NaN with fewer than two rows on either side.
-        The sampler's batch norms move their running statistics: every store's `s` is put back afterwards, and nothing else is
-        written — weights, shadows, optimiser slots, step counters and the Philox state are what they were.  The pass runs under
-        phases of its own ('metrics', 'metrics_g': unrecorded, buffer keys of their own), so no buffer a launch plan or graph names
-        is touched.  Synchronises the device.
-        sample_manifold_metrics is this pass with the k-nearest-neighbour metrics on top, sample_metrics_report with the per-class
-        reports of both sides."""
-        return self._sample_metrics_pass(batches, n_samples, ema, None)[0]
-
-    def sample_metrics_report(self, batches, n_samples, ema=False, manifold_k=None):
-        """sample_metrics (manifold_k None) or sample_manifold_metrics with the per-class report of each side on top ->
-        their keys, then `val_report` and `g_report`, two tg.metrics.report_from_counts dicts: the real side's as evaluate_report gives
-        it; the generated side's with the class asked for as target, over the n_samples rows that were scored — its per-class recall
-        says which classes the generator fails to render.  The same pass with one more tg_eval_report_f32 call per batch; what
-        sample_metrics says about the trainer's state holds unchanged.  A method of its own, as sample_manifold_metrics is: the
-        parameter lists of those two are pinned by tests."""
-        from tg import metrics as tgm
-        if manifold_k is not None:
-            manifold_k = tgm.check_k(manifold_k, 'sample_metrics_report: manifold_k')
-        return self._sample_metrics_pass(batches, n_samples, ema, manifold_k, (self._new_report(), self._new_report()))[0]
-
-    def sample_manifold_metrics(self, batches, n_samples, manifold_k, ema=False, return_banks=False):
-        """sample_metrics plus the k-nearest-neighbour manifold metrics -> its five keys, then `precision`, `recall`,
-        `density` and `coverage`.  manifold_k: the k of the radii, 1..16 (tg.metrics.check_k).
-        The same two passes also keep their feature rows — every real one, the first n_samples generated ones — in a
-        tg.metrics.FeatureBank each, and tg.metrics.manifold_metrics (tg_knn_self_f32 and tg_manifold_query_f32, twice each) turns the
-        banks into the four numbers.  They are NaN, and the kernels are not called, when a side's moment sums are not finite (a
-        diverged run) or a side has fewer than k + 1 rows.  The banks are buffers of their own and the kernels write nothing else:
-        what sample_metrics says about the trainer's state holds unchanged.
-        return_banks: return (result, (real bank, fake bank)) — the rows that were scored — instead of the result alone."""
-        from tg import metrics as tgm
-        manifold_k = tgm.check_k(manifold_k, 'sample_manifold_metrics: manifold_k')
-        out, banks = self._sample_metrics_pass(batches, n_samples, ema, manifold_k)
-        return (out, banks) if return_banks else out
-
-    def _sample_metrics_pass(self, batches, n_samples, ema, manifold_k, reports=None):
-        """the pass behind sample_metrics (manifold_k None), sample_manifold_metrics and sample_metrics_report -> (result, (real bank,
-        fake bank) or None).  reports: None, or (real side, generated side) tg.metrics.ClassifierReport accumulators, either of which
-        may be None: each is added the rows its side's accuracy counts, and the result carries `val_report` / `g_report` for those
-        given."""
-        from tg import metrics as tgm
-        cx, m, c = self.cx, self.model, self.config
-        n_samples = int(n_samples)
-        if n_samples < 1:
-            raise ValueError("sample_metrics: n_samples must be a positive integer, got %r" % (n_samples,))
-        self._require_eager("sample_metrics", "eager pass beside the step")
-        B = int(c.BATCH_SIZE_G)
-        n_batches = -(-n_samples // B)
-        z, y = self._sample_latents(n_batches)
-        rep_real, rep_fake = reports if reports is not None else (None, None)
-        real, fake = _Scores(rep_real, True, manifold_k is not None), _Scores(rep_fake, True, manifold_k is not None)
-        with self._running_state_kept():
-            for xb, yb in batches:
-                with cx.phase_scope('metrics', record=False), self._classifier_weights(ema):
-                    self._score_batch(cx.from_numpy(xb, key='metrics:x'), cx.from_numpy(yb, key='metrics:y'), real)
-            for k in range(n_batches):
-                with cx.phase_scope('metrics_g', record=False), self._classifier_weights(ema):
-                    za = cx.from_numpy(z[k * B:(k + 1) * B], key='metrics:z')
-                    yg = cx.from_numpy(y[k * B:(k + 1) * B], key='metrics:y_g')
-                    self._score_batch(m.as_image(m.good_sampler(za, yg)), yg, fake, take=min(B, n_samples - k * B))
-            seen = real.moments is not None                         # (a real side without batches: no moments, no bank)
-            (n_real, sum_r, gram_r), (n_fake, sum_f, gram_f) = real.moments.sums() if seen else (0, None, None), fake.moments.sums()
-            mu_r, cov_r = tgm.mean_cov(n_real, sum_r, gram_r) if seen else (None, None)
-            mu_f, cov_f = tgm.mean_cov(n_fake, sum_f, gram_f)
-            fd = tgm.frechet_distance(mu_r, cov_r, mu_f, cov_f) if n_real >= 2 and n_fake >= 2 else float('nan')
-            out = dict(val_accuracy=float(real.accuracy) if real.accuracy is not None else 0.0, g_class_accuracy=float(fake.accuracy),
-                       frechet_distance=fd, n_real=int(n_real), n_fake=int(n_fake))
-            if manifold_k is not None:
-                finite = seen and all(bool(np.isfinite(a).all()) for a in (sum_r, gram_r, sum_f, gram_f))
-                out.update(tgm.manifold_metrics(real.bank, fake.bank, manifold_k, cx.stream) if finite
-                           else dict.fromkeys(tgm.MANIFOLD_KEYS, float('nan')))
-            if rep_real is not None:
-                out['val_report'] = rep_real.result()
-            if rep_fake is not None:
-                out['g_report'] = rep_fake.result()
-        return out, (None if manifold_k is None else (real.bank, fake.bank))
-
     def sync_running_state(self):
         """Replicas keep their own running statistics (pop_mean, batch-norm moving mean / variance) and EMA shadows while
         training; they are averaged over the replicas before evaluation and before a checkpoint is written."""
@@ -695,119 +520,6 @@ class Train(Train_base):
                 tgdist.allreduce_mean_(st.s)
                 if st.ema is not None:
                     tgdist.allreduce_mean_(st.ema)
-
-    def sample(self, sample_z, sample_y):
-        """model.good_sampler on fixed latents (:68,353-364) -> host array [N,H,W,C] in [-1,1]."""
-        cx = self.cx
-        with cx.phase_scope('sample', record=False):
-            out = self.model.good_sampler(cx.from_numpy(sample_z, key='smp:z'), cx.from_numpy(sample_y, key='smp:y'))
-            return out.numpy().reshape([-1] + list(self.config.IMAGE_DIM))
-
-    HISTOGRAM_BUFFERS = {'value': 'p', 'grad': 'g', 'ema': 'ema'}
-
-    def histograms(self, which='value', nets=NETS):
-        """tf.summary.histogram of every trainable variable of the networks `nets`: {TF variable name (as Saver spells it): {min, max, num,
-        sum, sum_squares, limits, counts, nan, inf}} — TensorFlow's 1 551 bucket limits (shared array) and the count of every bucket,
-        uncompressed; nan / inf count the non-finite elements, which are in no bucket and no statistic.
-        which: 'value' (store.p), 'grad' (store.g: the gradient as the last iteration's optimiser READ it — summed over the replicas when
-        there are several, before the 1/world scale and before any clip factor; a network whose solver did not run keeps its last one) or
-        'ema' (the classifier's shadows; networks without one are skipped).
-        One tg_tf_histogram_f32 call and ONE device->host copy per network.  Launched eagerly on the launch stream, outside the replayed
-        step, and it only reads the stores: usable at any time, also while a launch plan or a hipGraph is held."""
-        from tg import summary as tgsum
-        if which not in self.HISTOGRAM_BUFFERS:
-            raise ValueError("histograms: which must be one of %s, got %r" % (', '.join(repr(k) for k in self.HISTOGRAM_BUFFERS), which))
-        self._require_eager("histograms", "eager launch beside the step")
-        out = {}
-        for net in nets:
-            st = self.cx.stores[net]
-            buf = getattr(st, self.HISTOGRAM_BUFFERS[which])
-            if buf is None:
-                continue
-            names = st.names(True)
-            key = (len(st.specs), st.n_p)
-            run = self._hist_runs.get(net)
-            if run is None or run[0] != key:
-                run = self._hist_runs[net] = (key, tgsum.StoreHistograms([st.index[nm][1:3] for nm in names], self.cx.device))
-            counts, stats = run[1].run(buf, self.cx.stream)
-            out.update(tgsum.as_dicts(names, counts, stats))
-        return out
-
-    def _register_summaries(self, want_hist, want_img):
-        """the reference's image / histogram keys (Summary.py:37-40) on the train summary, beside the scalars it already holds: the
-        samples as 'generated', every trainable variable of D, G and C under its name and its gradient under 'gradients/<name>'."""
-        c, sm = self.config, self.summary_train
-        kinds = dict(scalar=dict.fromkeys(sm._tags)) if sm._tags else {}
-        if want_img:
-            kinds['image'] = {'generated': None}
-        if want_hist:
-            tags = [nm for net in NETS for nm in self.cx.stores[net].names(True)]
-            kinds['histogram'] = dict.fromkeys(tags + ['gradients/' + nm for nm in tags])
-        sm.add_summary(kinds)
-        if want_img:                                     # (add_summary registers images with the reference's default max_outputs of 2)
-            sm._image_outputs = sm._image_summary(kinds['image'], min(self.options.summary_image_max_outputs, int(c.SAMPLE_SIZE)))
-
-    def _norm_tags(self):
-        """the train summary's extra scalars: '<d|g|c>_grad_norm' for every clipped network (none without a clip)."""
-        return tuple(k + '_grad_norm' for k, net in zip('dgc', NETS) if net in self._clip_views)
-
-    def _tail_rows(self):
-        """the epoch tail's extra records and val-summary scalars, in order, as (tag, result, key): the value of `tag` is `key` of the
-        result dict named `result` that _tail_metrics gathers — 'sm', the sample-metrics pass (with config.EVAL_EMA alone: evaluate's
-        pass over the shadows), or one of the report dicts 'val', 'val_ema', 'g' of self.last_reports.
-        'val_accuracy_ema' with config.EVAL_EMA, 'g_class_accuracy' and 'frechet_distance' with config.SAMPLE_METRICS, then 'precision',
-        'recall', 'density' and 'coverage' with config.SAMPLE_MANIFOLD_K (none with all off).  config.EVAL_REPORT appends, behind all of
-        those, REPORT_TAGS with a 'val_' prefix ('val_top5_accuracy' only with more than five classes), with EVAL_EMA the same again
-        with an '_ema' suffix, and with SAMPLE_METRICS 'g_worst_class_accuracy' (the generated side's target is the class asked for:
-        recall = class accuracy)."""
-        from tg import metrics as tgm
-        o = self.options
-        rows = [('val_accuracy_ema', 'sm', 'val_accuracy')] if o.eval_ema else []
-        if o.sample_metrics:
-            rows += [(k, 'sm', k) for k in ('g_class_accuracy', 'frechet_distance') + (tgm.MANIFOLD_KEYS if o.sample_manifold_k else ())]
-        if o.eval_report:
-            keys = self._report_keys()
-            rows += [('val_' + k, 'val', k) for k in keys] + ([('val_' + k + '_ema', 'val_ema', k) for k in keys] if o.eval_ema else [])
-            rows += [('g_worst_class_accuracy', 'g', 'worst_class_recall')] if o.sample_metrics else []
-        return rows
-
-    def _tail_metric_tags(self):
-        """the tags of _tail_rows(), in order: what _tail_metrics returns a value for."""
-        return tuple(tag for tag, _, _ in self._tail_rows())
-
-    REPORT_TAGS = ('balanced_accuracy', 'macro_f1', 'nll', 'ece', 'top5_accuracy')
-
-    def _report_keys(self):
-        """the keys of an evaluation report that the epoch tail records: REPORT_TAGS, top-5 accuracy only where it is defined."""
-        return tuple(k for k in self.REPORT_TAGS if k != 'top5_accuracy' or self.options.num_classes > 5)
-
-    def _tail_metrics(self, NNIO, init_op_val, main_report=None):
-        """{tag: value} of _tail_metric_tags() for this epoch tail, after sync_running_state: every replica computes the same numbers
-        from the same averaged state, the same validation split and the same latents — no collective.  With both settings on, the
-        averaged accuracy comes out of the metrics pass itself (its real side is evaluate's pass with the shadows): the split is run
-        once for both.
-        main_report (config.EVAL_REPORT): the ClassifierReport the epoch's evaluate pass filled.  The pass that reads the shadows
-        and the generated side of the metrics pass fill one more each — no forward pass is added — and self.last_reports keeps the
-        report dicts {'val', 'val_ema', 'g'} of those that ran."""
-        o = self.options
-        res = {'val': main_report.result()} if o.eval_report else {}
-        if o.sample_metrics:
-            init_op_val()
-            # the pass of sample_metrics / sample_manifold_metrics; its real side reads the shadows only with EVAL_EMA, and only then
-            # does its report differ from the main one
-            pair = (self._new_report() if o.eval_ema else None, self._new_report()) if o.eval_report else None
-            sm = res['sm'] = self._sample_metrics_pass(NNIO.val_batches(), o.sample_metrics, o.eval_ema, o.sample_manifold_k, pair)[0]
-            if o.eval_report:
-                res.update([('g', sm['g_report'])] + ([('val_ema', sm['val_report'])] if o.eval_ema else []))
-        elif o.eval_ema:
-            init_op_val()
-            ema_report = self._new_report() if o.eval_report else None
-            res['sm'] = dict(val_accuracy=self.evaluate(NNIO.val_batches(), ema=True, report=ema_report))
-            if o.eval_report:
-                res['val_ema'] = ema_report.result()
-        if o.eval_report:
-            self.last_reports = {k: res[k] for k in ('val', 'val_ema', 'g') if k in res}
-        return {tag: res[name][key] for tag, name, key in self._tail_rows()}
 
     # ------------------------------------------------------------------ the reference's entry point
     def train(self, Dataset, Model, sample_y):
@@ -823,21 +535,10 @@ class Train(Train_base):
         init_op_train, init_op_val, NNIO = dataset_train.inputpipline_train_val(dataset_val)
         self._build_train_graph(Model)
         sample_z = np.random.uniform(low=-1.0, high=1.0, size=(c.SAMPLE_SIZE, c.Z_DIM)).astype(np.float32)   # :130
-        lr, c_lr = c.LEARNING_RATE, cla_lr(c)
-        start_epoch = 0
-        saver = None
-        wn_pending = self.options.wn_init == 'data'                                    # a restored run never re-initialises (below)
-        if self.save_dir:
-            from Training.Saver import Saver
-            saver = Saver(self.save_dir)
-            if c.RESTORE:                                                              # :140-147
-                start_epoch = saver.restore(self, dir_names=c.RUN, epoch=c.RESTORE_EPOCH)
-                wn_pending = False
-                if start_epoch >= 300:
-                    lr = lr * 0.995 ** (start_epoch - 300)
-                    c_lr = c_lr * 0.99 ** (start_epoch - 300)
-            elif self.rank == 0:
-                saver.set_save_path(comments=self.comments)                            # :150
+        saver, start_epoch = self._open_run()
+        wn_pending = self.options.wn_init == 'data'
+        if saver is not None and c.RESTORE:                                            # a restored run never re-initialises
+            wn_pending = False
         if self.summary_train is not None and self.options.summary_scalar:             # :105-118
             self.summary_train.add_summary({'scalar': dict.fromkeys(('g_loss', 'd_loss', 'c_loss', 'train_accuracy') + self._norm_tags())})
             self.summary_val.add_summary({'scalar': dict.fromkeys(('val_accuracy',) + self._tail_metric_tags())})
@@ -846,14 +547,9 @@ class Train(Train_base):
             sample_y = np.eye(c.NUM_CLASSES, dtype=np.float32)[np.arange(c.SAMPLE_SIZE) % c.NUM_CLASSES]      # the entry points' cyclic ones
         history = []
         iters = int(c.TRAIN_SIZE / c.BATCH_SIZE)
-        for epoch in range(1, c.EPOCHS + 1):
-            lambda_1 = c.FAKE_G_LAMBDA if (start_epoch + epoch) > 200 else 0.          # :165
-            lambda_2 = (0.5 if epoch > 67 else 0.) if self.model.CONSISTENCY else 0.                       # :171
-            if start_epoch + epoch >= 300:                                             # :175-177
-                lr, c_lr = lr * 0.995, c_lr * 0.99
-            self.set_hyper(lr, c_lr, lambda_1, lambda_2)
+        for epoch, now in zip(range(1, c.EPOCHS + 1), epoch_schedule(c, self.model.CONSISTENCY, start_epoch)):
+            self.set_hyper(now.lr, now.cla_lr, now.lambda_1, now.lambda_2)
             init_op_train()
-            pre = bool(c.PRE_TRAIN and (start_epoch + epoch <= 30))                    # :182
             t0 = time.time()
             for i in range(iters):
                 self.feed(NNIO.next())
@@ -861,67 +557,28 @@ class Train(Train_base):
                 if wn_pending:                                                         # WN_INIT = 'data': on the first batch, which is
                     self.data_dependent_init()                                         # then iteration 1 as well
                     wn_pending = False
-                self.train_iteration(pre_train=pre)
+                self.train_iteration(pre_train=now.pre_train)
             torch.cuda.synchronize()
             dt = time.time() - t0
-            d_loss, g_loss, c_loss = self.training_statistics() if iters > 0 else self.losses()        # :280-285
-            init_op_val()
-            self.sync_running_state()
-            main_report = self._new_report() if self.options.eval_report else None    # EVAL_REPORT: filled by the same pass
-            acc = self.evaluate(NNIO.val_batches()) if main_report is None else self.evaluate(NNIO.val_batches(), report=main_report)
-            rec = dict(epoch=epoch + start_epoch, d_loss=d_loss, g_loss=g_loss, c_loss=c_loss, val_accuracy=acc,
-                       images_per_sec=iters * c.BATCH_SIZE * self.world / dt)
-            extra = self._tail_metrics(NNIO, init_op_val, main_report)                 # EVAL_EMA / SAMPLE_METRICS / EVAL_REPORT: {} with all off
-            rec.update(extra)
-            history.append(rec)
-            samples = None
-            if self.summary_train is not None:                                         # :293,346
-                samples = self._write_epoch_summaries(rec, sample_z, sample_y, grid, first=epoch == 1)
-            if saver is not None and self.rank == 0 and epoch % c.SAVE_PER_EPOCH == 0:  # :366-369
-                saver.save(self, 'model_' + str(epoch + start_epoch).zfill(4) + '.ckpt')
-            if self.rank == 0:
-                print("epoch {epoch}: g_loss {g_loss:.3f} d_loss {d_loss:.3f} c_loss {c_loss:.3f} val_acc {val_accuracy:.4f} "
-                      "{images_per_sec:.0f} img/s".format(**rec) + "".join(" %s %.4f" % (k, rec[k]) for k in extra), flush=True)
-                if grid:
-                    self._save_sample_grid(samples if samples is not None else self.sample(sample_z, sample_y), rec['epoch'])
+            history.append(self._epoch_tail(NNIO, init_op_val, epoch, start_epoch, iters, dt, sample_z, sample_y, grid, saver))
         if saver is not None and self.rank == 0 and c.EPOCHS > 0:                      # :378-379 (after all epochs)
             saver.save(self, 'model_' + str(c.EPOCHS + start_epoch).zfill(4) + '.ckpt')
         return history
 
-    def _write_epoch_summaries(self, rec, sample_z, sample_y, grid, first):
-        """The summaries of one epoch tail (:293,346): the losses and the validation accuracy of `rec`, the last iteration's gradient norms
-        of the clipped networks and, with config.SUMMARY_HISTOGRAM / SUMMARY_IMAGE, the histograms and the epoch's samples — which are
-        returned (None without images) for the sample grid to reuse when one follows (`grid`).  first: this train() call's first tail."""
-        o = self.options
-        norms = self.grad_norms() if self._norm_tags() else {}
-        hists = imgs = samples = None
-        if first and (o.summary_histogram or o.summary_image):                         # at the first tail: by now every variable exists
-            self._register_summaries(o.summary_histogram, o.summary_image)
-        if o.summary_histogram:                                                        # values, and store.g as the last optimiser step read it
-            hists = self.histograms('value')
-            hists.update(('gradients/' + nm, h) for nm, h in self.histograms('grad').items())
-        if o.summary_image:
-            # The sampler's batch norms run in training mode (reference :176-202) and move their running statistics.  A run
-            # without the flag samples only for the sample grid: when there is none, the statistics are put back, so the
-            # summary leaves every store as it found it.
-            with contextlib.nullcontext() if grid else self._running_state_kept():
-                samples = self.sample(sample_z, sample_y)
-            imgs = {'generated': samples}
-        self.summary_train.write(dict(dict(g_loss=rec['g_loss'], d_loss=rec['d_loss'], c_loss=rec['c_loss']),
-                                      **{k + '_grad_norm': v[0] for k, v in norms.items() if v is not None}), rec['epoch'],
-                                 histograms=hists, images=imgs)
-        self.summary_val.write(dict(dict(val_accuracy=rec['val_accuracy']), **{k: rec[k] for k in self._tail_metric_tags()}), rec['epoch'])
-        if o.eval_report:                                                              # the matrices behind the scalars, int64 [K, K]
-            for name, key in (('confusion', 'val'), ('g_confusion', 'g')):
-                if key in self.last_reports:
-                    np.save(os.path.join(self.summary_val.log_dir, '%s_%04d.npy' % (name, rec['epoch'])), self.last_reports[key]['confusion'])
-        return samples
-
-    def _save_sample_grid(self, samples, epoch):
-        """:359-363: the epoch's samples as one image, SAMPLE_DIR/train_<epoch>.png."""
-        from utils import save_images, image_manifold_size
-        os.makedirs(self.config.SAMPLE_DIR, exist_ok=True)
-        save_images(samples, image_manifold_size(samples.shape[0]), os.path.join(self.config.SAMPLE_DIR, 'train_{:02d}.png'.format(epoch)))
+    def _open_run(self):
+        """the run directory of this train() call (:139-150) -> (saver, start_epoch): with config.RESTORE the state of the run
+        config.RUN / config.RESTORE_EPOCH is read back and start_epoch is the number of epochs behind it; else rank 0 names a new run
+        directory and start_epoch is 0.  (None, 0) without a save_dir."""
+        c = self.config
+        if not self.save_dir:
+            return None, 0
+        from Training.Saver import Saver
+        saver, start_epoch = Saver(self.save_dir), 0
+        if c.RESTORE:                                                                  # :140-147
+            start_epoch = saver.restore(self, dir_names=c.RUN, epoch=c.RESTORE_EPOCH)
+        elif self.rank == 0:
+            saver.set_save_path(comments=self.comments)                                # :150
+        return saver, start_epoch
 
 
 def rampup(epoch):

@@ -40,9 +40,10 @@ def test_a_bad_mfma_dtype_raises_before_any_device_is_touched(monkeypatch):
 
 
 def test_the_trainer_restates_no_config_default():
-    """no getattr(x, 'UPPER_CASE', default) in Training/Train_goodGAN.py — but for the two optional class attributes of a MODEL, which are
-    no config settings and have no Config default to fall back to."""
-    src = open(os.path.join(ROOT, 'tensorflow-implementation-of-triple-gan_amd', 'Training', 'Train_goodGAN.py')).read()
+    """no getattr(x, 'UPPER_CASE', default) in Training/Train_goodGAN.py or the three modules that hold the trainer's other parts — but
+    for the two optional class attributes of a MODEL, which are no config settings and have no Config default to fall back to."""
+    training = os.path.join(ROOT, 'tensorflow-implementation-of-triple-gan_amd', 'Training')
+    src = ''.join(open(os.path.join(training, name)).read() for name in ('Train_goodGAN.py', 'evaluation.py', 'epoch_tail.py', 'schedule.py'))
     found = re.findall(r"""getattr\(\s*([^\n]*?)\s*,\s*['"]([A-Z][A-Z0-9_]*)['"]\s*,""", src)
     assert set(found) <= {('m', 'CONSISTENCY'), ('self.model', 'CONSISTENCY'), ('self.model', 'GRAD_BUCKETS')}, found
     assert not re.search(r"""^def check_|^    def check_""", src, flags=re.M)          # the validators live in Training/options.py
