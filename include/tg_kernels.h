@@ -770,6 +770,32 @@ int tg_knn_self_f32(const float* x, int ld, int n, int c, int k, float* out_d2, 
 int64_t tg_manifold_query_workspace_bytes(int m, int n);
 int tg_manifold_query_f32(const float* q, int ld_q, int m, const float* r, int ld_r, int n, int c, const float* r2, int32_t* count,
                           float* nn_d2, int32_t* nn_idx, void* workspace, int64_t workspace_bytes, void* stream);
+/* exact k-nearest rows between two sets of uint8 images (the nearest training images of generated samples, tg.metrics.nearest_pixels,
+ * Train.nearest_training).  q: DEVICE [m][d], r: DEVICE [n][d], contiguous uint8.  The distance is part of the
+ * interface:  d2(a, b) = sum_ch (a[ch] - b[ch])^2  as an exact integer (int32: 255^2 d < 2^31 for d <= 16 384).
+ *   tg_nearest_u8_i32  for every query row i, best_d2[i*k + t] and best_idx[i*k + t], t = 0..k-1 (DEVICE, m*k int32 each), hold the k
+ *                      smallest pairs (d2(q_i, r_j), base + j) in lexicographic order: the smaller d2 first, on a tie the lower index.
+ *                      merge != 0: the k pairs already in best_* take part in the selection, so a reference set can be fed in chunks
+ *                      (base = the chunk's first row); the answer depends neither on the chunking nor on the order of the chunks.
+ *                      merge == 0 and n < k: the unused slots hold (INT32_MAX, -1).
+ *                      1 <= d <= 16 384, 1 <= k <= 16, m >= 1, n >= 1, base >= 0, base + n <= INT32_MAX; anything else, a NULL pointer
+ *                      or a workspace smaller than the queried size is TG_ERR_INVALID before any launch.
+ * The products run on v_mfma_i32_32x32x32_i8 over x' = x ^ 0x80 read as int8 (d2 = |q'|^2 + |r'|^2 - 2 q'.r', every term exact in
+ * int32), the norms come out of the same pass, and the m x n distances are never written: a workgroup owns a query tile and a range of
+ * reference tiles — the rows are cut into tg_nearest_u8_ranges(m, n) ranges by a function of (m, n) alone — and leaves the k best of
+ * the range in the workspace; a finishing launch merges them by (d2, index).  No atomics, the grid a function of the shapes alone:
+ * bit-identical from run to run, on any stream.
+ * workspace: caller-owned scratch of at least tg_nearest_u8_workspace_bytes(m, n, d, k) bytes (host query, as tg_nearest_u8_ranges;
+ * both < 0 for a bad argument), 16-byte aligned, needs no initialisation, nothing beyond that size is written.  2 m n d integer
+ * operations on the int8 MFMA. */
+int64_t tg_nearest_u8_workspace_bytes(int m, int n, int d, int k);
+int tg_nearest_u8_ranges(int m, int n);
+int tg_nearest_u8_i32(const uint8_t* q, int m, const uint8_t* r, int n, int d, int k, int32_t base, int merge, int32_t* best_d2,
+                      int32_t* best_idx, void* workspace, int64_t workspace_bytes, void* stream);
+/* the inverse of tg_u8_affine_f32: generated images back into the bytes of the input pipeline.  inv = 255.0f / scale (host, fp32);
+ * t = (src - shift) * inv (two rounded operations, no fma); dst = floorf(t + 0.5f) clamped to 0..255, NaN -> 0.  quantize(affine(u)) = u
+ * for every byte under (scale, shift) = (2, -1) and (1, 0).  n = 0 is a no-op; scale must be finite and not 0. */
+int tg_f32_quantize_u8(const float* src, uint8_t* dst, int64_t n, float scale, float shift, void* stream);
 
 /* ---- RNG(Philox4x32-10; state = device {seed, step}) -------------------------------------------- */
 /* Element e of a draw is word e % 4 of the block with counter (lo32(e / 4), hi32(e / 4), stream_id, lo32(step)) and key (lo32(seed),

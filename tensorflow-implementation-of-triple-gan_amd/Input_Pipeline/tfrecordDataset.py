@@ -167,6 +167,45 @@ class _Prefetcher(object):
             pass
 
 
+TRAINING_CHUNK = 16384          # records per piece of training_chunks (50 MB of CIFAR bytes)
+
+
+def training_files(dataset):
+    """The record files of the training split of a tfrecordDataset (subset 'train'; MNIST's UNIT_RANGE scaling included), each once and
+    in file order: input_from_tfrecord_filename() returns the labelled file twice ([labelled for D, labelled for C, unlabelled]).  The
+    test split is not opened.  lib.TgError for any other Dataset or subset."""
+    from tg import lib
+    if not isinstance(dataset, tfrecordDataset):
+        raise lib.TgError("the training records are those of a tfrecordDataset (such as cifar10Dataset); %s has none" % type(dataset).__name__)
+    if dataset.subset != 'train':
+        raise lib.TgError("the training records are read from the training split only, got subset %r" % (dataset.subset,))
+    return each_once(dataset.input_from_tfrecord_filename())
+
+
+def each_once(files):
+    """the record files of a list, each once, in the order of first appearance."""
+    out = []
+    for rec in files:
+        if all(rec is not r for r in out):
+            out.append(rec)
+    return out
+
+
+def record_chunks(files, rows):
+    """(RecordFile, record indices) pieces of at most `rows` records over the files given: file order, then record order."""
+    for rec in files:
+        for s in range(0, len(rec), rows):
+            yield rec, np.arange(s, min(s + rows, len(rec)), dtype=np.int64)
+
+
+def training_chunks(dataset, rows=TRAINING_CHUNK):
+    """(RecordFile, record indices) pieces of at most `rows` records that cover every training record exactly once: file order, then
+    record order.  That order defines the training index — the position of a record in the concatenation of the pieces — which
+    Train.nearest_training's `nn_idx` refers to."""
+    for piece in record_chunks(training_files(dataset), rows):
+        yield piece
+
+
 class _NNIO(object):
     """what Training/Train_goodGAN.py consumes: next() = the feed of one iteration, val_batches() = the test split."""
 

@@ -65,25 +65,22 @@ def zca_constants(n, colsum, gram, eps=ZCA_EPS, timings=None):
 def zca_training_files(dataset):
     """The record files of the training split of a TFRecord dataset, each once: input_from_tfrecord_filename() returns the labelled file
     twice ([labelled for D, labelled for C, unlabelled]).  The test split is not opened."""
-    from Input_Pipeline.tfrecordDataset import tfrecordDataset
+    from Input_Pipeline.tfrecordDataset import each_once, tfrecordDataset
     from tg import lib
     if not isinstance(dataset, tfrecordDataset) or dataset.UNIT_RANGE:
         raise lib.TgError("ZCA = 'fit' needs a training split of uint8 TFRecords in [-1, 1] scaling (a tfrecordDataset such as "
                           "cifar10Dataset); %s has none" % type(dataset).__name__)
     if dataset.subset != 'train':
         raise lib.TgError("ZCA = 'fit' reads the training split only, got subset %r" % (dataset.subset,))
-    out = []
-    for rec in dataset.input_from_tfrecord_filename():
-        if all(rec is not r for r in out):
-            out.append(rec)
-    return out
+    return each_once(dataset.input_from_tfrecord_filename())
 
 
 def zca_training_chunks(dataset, rows=ZCA_CHUNK):
-    """(RecordFile, record indices) pieces of at most `rows` records that cover every training record exactly once."""
-    for rec in zca_training_files(dataset):
-        for s in range(0, len(rec), rows):
-            yield rec, np.arange(s, min(s + rows, len(rec)), dtype=np.int64)
+    """(RecordFile, record indices) pieces of at most `rows` records that cover every training record exactly once: the pieces and the
+    order of Input_Pipeline.tfrecordDataset.training_chunks (record_chunks), behind this module's own checks and errors."""
+    from Input_Pipeline.tfrecordDataset import record_chunks
+    for piece in record_chunks(zca_training_files(dataset), rows):
+        yield piece
 
 
 def write_zca_files(config, mean, mat):

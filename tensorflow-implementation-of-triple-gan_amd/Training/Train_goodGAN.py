@@ -28,7 +28,7 @@ from Training.epoch_tail import EpochTail
 from Training.evaluation import Evaluation
 from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, Options, check_act_dtype, check_clip_norm, check_eval_ema,  # noqa: F401
                               check_eval_report, check_loss, check_mfma_dtype, check_num_classes, check_optimizer, check_sample_manifold_k,
-                              check_sample_metrics, check_wn_init, check_zca, cla_lr, opt, resolve)
+                              check_sample_metrics, check_sample_nearest, check_wn_init, check_zca, cla_lr, opt, resolve)
 from Training.schedule import epoch_schedule
 from Training.train_base import Train_base, clip_workspace_floats
 from tg import dist as tgdist
@@ -84,7 +84,11 @@ class Train(Evaluation, EpochTail, Train_base):
         self.wn_initialised = None       # {network: layers initialised} once data_dependent_init() has run (config.WN_INIT = 'data')
         self.zca_source = None           # config.ZCA = 'fit' resolved by train() (Model/zca.resolve_zca): 'files' | 'fit' (rank 0) | 'broadcast' (other ranks)
         self._metric_latents = None      # (z, y) host arrays of sample_metrics(), drawn once per trainer from config.SEED
+        self._nearest = {}               # {'pixel': nearest_training()'s resident training bytes, labels and kept controls}
+        self._dataset_train = None       # the training Dataset of train(): what the epoch tail's nearest_training() searches
         self.last_reports = {}           # config.EVAL_REPORT: the last epoch tail's report dicts {'val', 'val_ema', 'g'} (_tail_metrics)
+        self.last_nearest = None         # config.SAMPLE_NEAREST: (result, (query bank, training bank)) of the last tail's nearest_training
+        self.nearest_decoded = 0         # training records nearest_training has decoded so far (Evaluation._training_pixels: once)
         self._hist_runs = {}             # network -> (store layout key, tg.summary.StoreHistograms): see histograms()
         self.summary_train = self.summary_val = None
         if o.summary and log_dir and self.rank == 0:          # :37-41
@@ -532,6 +536,8 @@ class Train(Evaluation, EpochTail, Train_base):
         if isinstance(opt(c, 'ZCA'), str):                                             # 'fit': the constants, before the model first whitens
             check_zca(c, dataset_train)
             c.ZCA, self.zca_source = resolve_zca(c, dataset_train, self.rank, self.cx.device)
+        check_sample_nearest(c, dataset_train)                                         # SAMPLE_NEAREST: a TFRecord training split
+        self._dataset_train = dataset_train
         init_op_train, init_op_val, NNIO = dataset_train.inputpipline_train_val(dataset_val)
         self._build_train_graph(Model)
         sample_z = np.random.uniform(low=-1.0, high=1.0, size=(c.SAMPLE_SIZE, c.Z_DIM)).astype(np.float32)   # :130
@@ -693,9 +699,9 @@ def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
     _synthetic_zca(tmp_config)                                         # a default like the class body's: FLAGS below override it
     if FLAGS:
         _customize_config(tmp_config, FLAGS)
-        # --wn-init data, --eval-ema, --sample-metrics N, --sample-manifold-k K, --eval-report: Config does not declare these settings, so
-        # the hasattr rule of _customize_config would drop them (Training/options.check_wn_init ... check_eval_report).  Flag objects
-        # without the attribute are common: getattr with a default
+        # --wn-init data, --eval-ema, --sample-metrics N, --sample-manifold-k K, --eval-report, --sample-nearest K: Config does not
+        # declare these settings, so the hasattr rule of _customize_config would drop them (Training/options.check_wn_init ...
+        # check_sample_nearest).  Flag objects without the attribute are common: getattr with a default
         for name in Options.EXTRAS:
             if getattr(FLAGS, name, None) is not None:
                 setattr(tmp_config, name.upper(), getattr(FLAGS, name))
@@ -705,6 +711,7 @@ def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
     if tmp_config.NUM_LABEL < 1000:
         tmp_config.PRE_TRAIN = True                                    # :537-538,614-615
     check_zca(tmp_config, Dataset or syntheticDataset)                 # --zca fit: before any device work
+    check_sample_nearest(tmp_config, Dataset or syntheticDataset)      # --sample-nearest K: it needs a training split to search
     tmp_config.display()
     training = Train(tmp_config, tmp_config.LOG_DIR, tmp_config.WEIGHT_DIR, comments=comments + tmp_config.config_str())
     sample_y = np.eye(tmp_config.NUM_CLASSES, dtype=np.float32)[np.arange(tmp_config.SAMPLE_SIZE) % tmp_config.NUM_CLASSES]

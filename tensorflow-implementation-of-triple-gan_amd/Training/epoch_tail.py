@@ -4,9 +4,10 @@ sample grid.  Train (Training/Train_goodGAN.py) inherits it.
 
 _epoch_tail is the whole tail in the reference's order; the other methods are its parts, usable on their own (histograms by tools and
 tests at any time).  The tail calls the trainer's training_statistics, sync_running_state, grad_norms and the scoring passes of
-Training/evaluation.py, and reads config, options, cx.stores, _clip_views, rank, world and the two Summary writers.  It OWNS two
-attributes, both set by Train.__init__: `last_reports` (the report dicts of the last tail) and `_hist_runs` (the histogram launches per
-network).  Apart from what training_statistics moves — as the reference's run does — it leaves the training state alone."""
+Training/evaluation.py, and reads config, options, cx.stores, _clip_views, rank, world and the two Summary writers.  It OWNS three
+attributes, set by Train.__init__: `last_reports` (the report dicts of the last tail), `last_nearest` (config.SAMPLE_NEAREST: the last
+tail's nearest_training result and its two banks) and `_hist_runs` (the histogram launches per network).  Apart from what
+training_statistics moves — as the reference's run does — it leaves the training state alone."""
 import contextlib
 import os
 
@@ -15,6 +16,27 @@ import numpy as np
 from Training.options import NETS
 from tg import metrics as tgm
 from tg import summary as tgsum
+
+
+NEAREST_GRID_ROWS = 16
+
+
+def write_nearest_grid(path, nn_idx, fake, train, image_dim, rows=NEAREST_GRID_ROWS):
+    """Train.nearest_training's pixel result as one PNG (the epoch tail's SAMPLE_DIR/nearest_<epoch>.png, tools/nearest_training.py):
+    one row for each of the first min(rows, N) samples — the sample, as the bytes that were compared, then its k nearest training
+    images, nearest first (a black cell where the training split has fewer than k images).  nn_idx: int32 [N, k]; fake, train: the
+    tg.metrics.PixelBank pair the distances were taken between."""
+    import torch
+    from utils import merge, write_png
+    h, w, ch = (int(v) for v in image_dim)
+    rows = min(int(rows), fake.n)
+    idx = np.asarray(nn_idx)[:rows]
+    cells = np.zeros((rows, 1 + idx.shape[1], h, w, ch), np.uint8)
+    cells[:, 0] = fake.rows(0, rows).cpu().numpy().reshape(rows, h, w, ch)
+    pick = torch.from_numpy(np.maximum(idx, 0).reshape(-1).astype(np.int64)).to(train.device)
+    near = train.rows()[pick].cpu().numpy().reshape(rows, idx.shape[1], h, w, ch)
+    cells[:, 1:] = np.where((idx >= 0)[:, :, None, None, None], near, 0)
+    write_png(path, merge(cells.reshape((-1, h, w, ch)) / 255.0, (rows, 1 + idx.shape[1])))
 
 
 class EpochTail(object):
@@ -42,6 +64,8 @@ class EpochTail(object):
                   "{images_per_sec:.0f} img/s".format(**rec) + "".join(" %s %.4f" % (k, rec[k]) for k in extra), flush=True)
             if grid:
                 self._save_sample_grid(samples if samples is not None else self.sample(sample_z, sample_y), rec['epoch'])
+            if self.options.sample_nearest and c.SAMPLE_DIR:
+                self._save_nearest_grid(rec['epoch'])
         return rec
 
     HISTOGRAM_BUFFERS = {'value': 'p', 'grad': 'g', 'ema': 'ema'}
@@ -99,7 +123,8 @@ class EpochTail(object):
         'recall', 'density' and 'coverage' with config.SAMPLE_MANIFOLD_K (none with all off).  config.EVAL_REPORT appends, behind all of
         those, REPORT_TAGS with a 'val_' prefix ('val_top5_accuracy' only with more than five classes), with EVAL_EMA the same again
         with an '_ema' suffix, and with SAMPLE_METRICS 'g_worst_class_accuracy' (the generated side's target is the class asked for:
-        recall = class accuracy)."""
+        recall = class accuracy).  config.SAMPLE_NEAREST appends, last of all, 'g_nn_rmse', 'g_nn_rmse_min', 'g_nn_class_agreement' and
+        'val_nn_rmse' (Train.nearest_training)."""
         o = self.options
         rows = [('val_accuracy_ema', 'sm', 'val_accuracy')] if o.eval_ema else []
         if o.sample_metrics:
@@ -108,6 +133,8 @@ class EpochTail(object):
             keys = self._report_keys()
             rows += [('val_' + k, 'val', k) for k in keys] + ([('val_' + k + '_ema', 'val_ema', k) for k in keys] if o.eval_ema else [])
             rows += [('g_worst_class_accuracy', 'g', 'worst_class_recall')] if o.sample_metrics else []
+        if o.sample_nearest:                            # config.SAMPLE_NEAREST: behind every other row (result 'nn': nearest_training)
+            rows += [(k, 'nn', k) for k in self.NEAREST_KEYS]
         return rows
 
     def _tail_metric_tags(self):
@@ -146,6 +173,13 @@ class EpochTail(object):
                 res['val_ema'] = ema_report.result()
         if o.eval_report:
             self.last_reports = {k: res[k] for k in ('val', 'val_ema', 'g') if k in res}
+        if o.sample_nearest:
+            # the nearest training images of the samples that pass scored (same latents, same batch-norm rule), against the training
+            # split train() opened; last_nearest keeps the result and the two banks for the grid
+            init_op_val()
+            self.last_nearest = self.nearest_training(self._dataset_train, NNIO.val_batches(), o.sample_metrics, o.sample_nearest,
+                                                      return_banks=True)
+            res['nn'] = self.last_nearest[0]
         return {tag: res[name][key] for tag, name, key in self._tail_rows()}
 
     def _write_epoch_summaries(self, rec, sample_z, sample_y, grid, first):
@@ -176,6 +210,13 @@ class EpochTail(object):
                 if key in self.last_reports:
                     np.save(os.path.join(self.summary_val.log_dir, '%s_%04d.npy' % (name, rec['epoch'])), self.last_reports[key]['confusion'])
         return samples
+
+    def _save_nearest_grid(self, epoch):
+        """config.SAMPLE_NEAREST: SAMPLE_DIR/nearest_<epoch>.png from the last tail's nearest_training (write_nearest_grid)."""
+        out, (fake, train) = self.last_nearest
+        os.makedirs(self.config.SAMPLE_DIR, exist_ok=True)
+        write_nearest_grid(os.path.join(self.config.SAMPLE_DIR, 'nearest_{:04d}.png'.format(epoch)), out['nn_idx'], fake, train,
+                           self.config.IMAGE_DIM)
 
     def _save_sample_grid(self, samples, epoch):
         """:359-363: the epoch's samples as one image, SAMPLE_DIR/train_<epoch>.png."""

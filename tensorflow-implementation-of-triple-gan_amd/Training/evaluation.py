@@ -9,7 +9,8 @@ The contract, once for all of them.  These passes READ from the trainer
     _accuracy_metric   the streaming accuracy of Train_base
     _require_eager     refuses a pass inside a hipGraph capture / launch-plan recording
 
-and OWN one attribute, `_metric_latents` (the fixed latents of sample_metrics, set to None by Train.__init__).  They write no store:
+and OWN `_metric_latents` (the fixed latents of sample_metrics) and `_nearest` / `nearest_decoded` (nearest_training's resident
+training bytes and cached control, and the records decoded for them), all set by Train.__init__.  They write no store:
 no weight, shadow, optimiser slot or step counter, and the Philox state is not advanced.  The one exception is every store's `s`
 (pop_mean, batch-norm moving statistics), which a sampler pass moves and _running_state_kept puts back."""
 import contextlib
@@ -196,6 +197,120 @@ class Evaluation(object):
             if rep_fake is not None:
                 out['g_report'] = rep_fake.result()
         return out, (None if manifold_k is None else (real.bank, fake.bank))
+
+    NEAREST_KEYS = ('g_nn_rmse', 'g_nn_rmse_min', 'g_nn_class_agreement', 'val_nn_rmse')
+
+    def _training_pixels(self, dataset_train):
+        """(tg.metrics.PixelBank of the training split's bytes, its labels int32 [n]) in the order of
+        Input_Pipeline.tfrecordDataset.training_chunks — the training index.  Decoded once per trainer and kept on the device (n x d
+        bytes: 150 MB for CIFAR); `nearest_decoded` counts the records decoded so far."""
+        from Input_Pipeline.tfrecordDataset import training_chunks
+        kept = self._nearest.get('pixel')
+        if kept is not None and kept['dataset'] is dataset_train:
+            return kept['bank'], kept['labels']
+        bank = tgm.PixelBank(int(np.prod(self.config.IMAGE_DIM)), self.cx.device)
+        labels = bank.add_records(training_chunks(dataset_train))
+        self.nearest_decoded += bank.n
+        if bank.n == 0:
+            raise tgm.lib.TgError("nearest_training: the training split is empty")
+        self._nearest['pixel'] = dict(dataset=dataset_train, bank=bank, labels=labels, val={})
+        return bank, labels
+
+    def _pixel_scaling(self, dataset_train):
+        """(scale, shift) of the input pipeline's tail x = u / 255 * scale + shift for this dataset."""
+        return (1.0, 0.0) if dataset_train.UNIT_RANGE else (2.0, -1.0)
+
+    def _generated(self, n_samples, each):
+        """run the first n_samples samples of _sample_latents through the sampler, batch by batch as sample_metrics does, and hand
+        each(images Act, labels Act, rows to take) every batch inside the 'metrics_g' phase."""
+        cx, m, B = self.cx, self.model, int(self.config.BATCH_SIZE_G)
+        n_batches = -(-n_samples // B)
+        z, y = self._sample_latents(n_batches)
+        for k in range(n_batches):
+            with cx.phase_scope('metrics_g', record=False):
+                za = cx.from_numpy(z[k * B:(k + 1) * B], key='metrics:z')
+                yg = cx.from_numpy(y[k * B:(k + 1) * B], key='metrics:y_g')
+                each(m.as_image(m.good_sampler(za, yg)), yg, min(B, n_samples - k * B))
+
+    def nearest_training(self, dataset_train, val_batches, n_samples, k, space='pixel', return_banks=False):
+        """The nearest training images of generated samples: are the samples copies of training images?
+        The generated side is the first n_samples samples of _sample_latents — those sample_metrics scores, taken under the same
+        batch-norm rule.  dataset_train: the training tfrecordDataset; its records in the order of training_chunks define the training
+        index.  -> dict:
+          space 'pixel'    the samples, quantised back to the input pipeline's bytes (tg_f32_quantize_u8), against the training split's
+                           bytes with tg_nearest_u8_i32: exact integer squared distances, ties to the lower index.
+            nn_idx, nn_d2, nn_label   int32 [n_samples, k]: training index, squared distance and label of the k nearest, nearest first
+            g_nn_rmse                 mean_i sqrt(d2_i,1 / d) / 255: the root-mean-square pixel difference to the nearest, full range = 1
+            g_nn_rmse_min             the smallest of them: the most suspicious sample
+            g_nn_class_agreement      the share of samples whose nearest training image carries the class asked for
+            val_nn_rmse               the control: g_nn_rmse's statistic for the first n_samples images of val_batches (quantised back
+                                      to bytes) — how near a real held-out image lies.  Computed once per trainer and n_samples:
+                                      the validation split is taken as fixed, so a later call with the same n_samples returns the
+                                      kept control and does not read the val_batches it is handed.
+            val_nn_d2                 int32 [<= n_samples]: the control's squared distances, image by image
+          Every scalar is reduced in float64 on the host from the exact integers.  No threshold: g_nn_rmse is read against val_nn_rmse.
+          space 'feature'  the training split through the classifier in evaluation mode (_score_batch) into a FeatureBank, the samples'
+                           pooled features queried with tg_manifold_query_f32: nn_idx int32 and nn_d2 float32 [n_samples, 1]; k must
+                           be 1 (ValueError otherwise).
+        The training bytes are decoded once per trainer and stay on the device.  Running statistics are put back afterwards and
+        nothing else is written: what sample_metrics says about the trainer's state holds unchanged.  Synchronises the device.
+        return_banks: return (result, (query bank, training bank)) — the rows that were compared."""
+        k = tgm.check_k(k, 'nearest_training: k')
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError("nearest_training: n_samples must be a positive integer, got %r" % (n_samples,))
+        if space not in ('pixel', 'feature'):
+            raise ValueError("nearest_training: space must be 'pixel' or 'feature', got %r" % (space,))
+        if space == 'feature' and k != 1:
+            raise ValueError("nearest_training: space 'feature' returns the single nearest row (tg_manifold_query_f32): k must be 1, got %d" % k)
+        self._require_eager("nearest_training", "eager pass beside the step")
+        cx, c = self.cx, self.config
+        with self._running_state_kept():
+            if space == 'feature':
+                out, banks = self._nearest_features(dataset_train, n_samples)
+                return (out, banks) if return_banks else out
+            train, labels = self._training_pixels(dataset_train)
+            scale, shift = self._pixel_scaling(dataset_train)
+            d = train.d
+            fake = tgm.PixelBank(d, cx.device)
+            self._generated(n_samples, lambda img, yg, take: fake.add_act(img.view_rows(0, take), scale, shift, cx.stream))
+            d2, idx = (t.cpu().numpy() for t in tgm.nearest_pixels(fake, train, k, cx.stream))
+            rmse = tgm.nearest_rmse(d2, d)
+            asked = np.arange(n_samples) % int(c.NUM_CLASSES)
+            nn_label = np.where(idx >= 0, labels[np.maximum(idx, 0)], -1).astype(np.int32)
+            kept = self._nearest['pixel']['val']
+            if n_samples not in kept:
+                real, left = tgm.PixelBank(d, cx.device), n_samples
+                for xb, _ in val_batches:
+                    if left <= 0:                                  # (the rest is drained: the pipeline's prefetch thread ends with it)
+                        continue
+                    xa = self.model.as_image(cx.from_numpy(np.asarray(xb, np.float32)[:left]))
+                    real.add_act(xa, scale, shift, cx.stream)
+                    left -= xa.n
+                v_d2 = tgm.nearest_pixels(real, train, 1, cx.stream)[0].cpu().numpy()[:, 0] if real.n else np.zeros(0, np.int32)
+                kept[n_samples] = (float(tgm.nearest_rmse(v_d2, d).mean()) if real.n else float('nan'), v_d2)
+            out = dict(nn_idx=idx, nn_d2=d2, nn_label=nn_label, g_nn_rmse=float(rmse.mean()), g_nn_rmse_min=float(rmse.min()),
+                       g_nn_class_agreement=float(np.mean(nn_label[:, 0] == asked)), val_nn_rmse=kept[n_samples][0],
+                       val_nn_d2=kept[n_samples][1])
+        return (out, (fake, train)) if return_banks else out
+
+    def _nearest_features(self, dataset_train, n_samples):
+        """nearest_training's space 'feature' -> ({nn_idx, nn_d2}, (generated FeatureBank, training FeatureBank))."""
+        from Input_Pipeline.tfrecordDataset import training_chunks
+        cx, c = self.cx, self.config
+        train, fake = _Scores(None, True, True), _Scores(None, True, True)
+        B = int(c.BATCH_SIZE)
+        for rec, idx in training_chunks(dataset_train, B):
+            img, lab = np.empty((len(idx),) + tuple(rec.shape), np.uint8), np.empty(len(idx), np.int32)
+            rec.gather(idx, img.reshape(-1), lab, n_threads=1)
+            xb, yb = dataset_train._to_host(img, lab)
+            with cx.phase_scope('metrics', record=False), self._classifier_weights(False):
+                self._score_batch(cx.from_numpy(xb, key='metrics:x'), cx.from_numpy(yb, key='metrics:y'), train)
+        if train.bank is None:
+            raise tgm.lib.TgError("nearest_training: the training split is empty")
+        self._generated(n_samples, lambda img, yg, take: self._score_batch(img, yg, fake, take=take))
+        _, nn_d2, nn_idx = tgm.manifold_query(fake.bank.rows(), train.bank.rows(), None, cx.stream)
+        return dict(nn_idx=nn_idx.cpu().numpy().reshape(-1, 1), nn_d2=nn_d2.cpu().numpy().reshape(-1, 1)), (fake.bank, train.bank)
 
     def sample(self, sample_z, sample_y):
         """model.good_sampler on fixed latents (:68,353-364) -> host array [N,H,W,C] in [-1,1]."""

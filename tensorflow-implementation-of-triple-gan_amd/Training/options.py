@@ -216,22 +216,48 @@ def check_sample_manifold_k(config):
     return v
 
 
+def check_sample_nearest(config, Dataset=None):
+    """config.SAMPLE_NEAREST: None (default; also when the attribute is absent — config.Config does not declare it) or an int k in
+    1..16: the epoch tail also finds the k nearest training images, in pixel space, of the generated samples the sample-metrics pass
+    scores, records `g_nn_rmse`, `g_nn_rmse_min`, `g_nn_class_agreement` and `val_nn_rmse` and writes SAMPLE_DIR/nearest_<epoch>.png
+    (Train.nearest_training).  -> None or int.  Needs no device; ValueError for what tg.metrics.check_k refuses (a value
+    outside 1..16, a bool, a float, any other type) and when set without SAMPLE_METRICS (which gives it its sample count); lib.TgError
+    when a Dataset (class or instance) is given that is not a TFRecord source, e.g. the default syntheticDataset: there is no training
+    split to search."""
+    from tg.metrics import check_k
+    v = getattr(config, 'SAMPLE_NEAREST', None)
+    if v is None:
+        return None
+    v = check_k(v, 'SAMPLE_NEAREST')
+    if check_sample_metrics(config) is None:
+        raise ValueError("SAMPLE_NEAREST = %r needs SAMPLE_METRICS = N: the nearest training images are those of the N samples that "
+                         "pass scores" % (v,))
+    if Dataset is not None:
+        from Input_Pipeline.tfrecordDataset import tfrecordDataset
+        cls = Dataset if isinstance(Dataset, type) else type(Dataset)
+        if not issubclass(cls, tfrecordDataset):
+            raise lib.TgError("SAMPLE_NEAREST needs a training split of uint8 TFRecords (a tfrecordDataset such as cifar10Dataset); %s has "
+                              "none" % cls.__name__)
+    return v
+
+
 _Fields = collections.namedtuple('Options', 'mfma_dtype act_dtype num_classes loss optimizers clip_norms momentum seed no_grad_buckets '
                                             'summary summary_scalar summary_histogram summary_image summary_image_max_outputs')
 
 
 class Options(_Fields):
     """the record resolve() returns.  Its tuple fields are the settings config.Config declares a default for (and NO_GRAD_BUCKETS);
-    `wn_init`, `eval_ema`, `sample_metrics`, `sample_manifold_k` and `eval_report` (check_wn_init, check_eval_ema,
-    check_sample_metrics, check_sample_manifold_k, check_eval_report: settings Config deliberately does not declare) are carried as
-    attributes beside them, so the field list — what _asdict() and unpacking give — stays what it was.  Two records are equal when the
-    fields and these attributes are."""
-    EXTRAS = ('wn_init', 'eval_ema', 'sample_metrics', 'sample_manifold_k', 'eval_report')
+    `wn_init`, `eval_ema`, `sample_metrics`, `sample_manifold_k`, `eval_report` and `sample_nearest` (check_wn_init, check_eval_ema,
+    check_sample_metrics, check_sample_manifold_k, check_eval_report, check_sample_nearest: settings Config deliberately does not
+    declare) are carried as attributes beside them, so the field list — what _asdict() and unpacking give — stays what it was.  Two
+    records are equal when the fields and these attributes are."""
+    EXTRAS = ('wn_init', 'eval_ema', 'sample_metrics', 'sample_manifold_k', 'eval_report', 'sample_nearest')
 
-    def __new__(cls, wn_init=None, eval_ema=False, sample_metrics=None, sample_manifold_k=None, eval_report=False, **fields):
+    def __new__(cls, wn_init=None, eval_ema=False, sample_metrics=None, sample_manifold_k=None, eval_report=False, sample_nearest=None,
+                **fields):
         self = super(Options, cls).__new__(cls, **fields)
         self.wn_init, self.eval_ema, self.sample_metrics, self.sample_manifold_k = wn_init, eval_ema, sample_metrics, sample_manifold_k
-        self.eval_report = eval_report
+        self.eval_report, self.sample_nearest = eval_report, sample_nearest
         return self
 
     def _extras(self):
@@ -239,7 +265,7 @@ class Options(_Fields):
 
     def __eq__(self, other):
         return (tuple.__eq__(self, other)
-                and tuple(getattr(other, k, d) for k, d in zip(self.EXTRAS, (None, False, None, None, False))) == self._extras())
+                and tuple(getattr(other, k, d) for k, d in zip(self.EXTRAS, (None, False, None, None, False, None))) == self._extras())
 
     def __ne__(self, other):
         return not self == other
@@ -254,6 +280,7 @@ def resolve(config):
     check_zca(config)
     return Options(wn_init=check_wn_init(config), eval_ema=check_eval_ema(config), sample_metrics=check_sample_metrics(config),
                    sample_manifold_k=check_sample_manifold_k(config), eval_report=check_eval_report(config),
+                   sample_nearest=check_sample_nearest(config),
                    mfma_dtype=check_mfma_dtype(config), act_dtype=check_act_dtype(config), num_classes=check_num_classes(config),
                    loss=check_loss(config), optimizers=check_optimizer(config), clip_norms=check_clip_norm(config),
                    momentum=float(opt(config, 'MOMENTUM')), seed=opt(config, 'SEED'),

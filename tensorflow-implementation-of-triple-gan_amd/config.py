@@ -85,7 +85,8 @@ class Config(object):
     # training batch, g <- init_scale / sqrt(var + eps), b <- -mean * g (Salimans & Kingma 2016; Train.data_dependent_init,
     # DESIGN §9.9); absent or None: g = 1, b = 0 as created.  Read by Training/options.check_wn_init.
 
-    # EVAL_EMA, SAMPLE_METRICS — NOT declared here either, for the same reason; an instance or subclass may set
+    # EVAL_EMA, SAMPLE_METRICS, SAMPLE_MANIFOLD_K, EVAL_REPORT, SAMPLE_NEAREST — NOT declared here either, for the same reason; an
+    # instance or subclass may set
     #   EVAL_EMA = True (--eval-ema): the epoch tail also evaluates the classifier's averaged weights (the EMA shadows, decay 0.9999
     #     without bias correction: they lag the weights by roughly 1e4 iterations) and records `val_accuracy_ema`;
     #   SAMPLE_METRICS = N (--sample-metrics N), a positive int: the epoch tail scores N generated samples with the run's own
@@ -101,8 +102,13 @@ class Config(object):
     #     same with an `_ema` suffix; with SAMPLE_METRICS `g_worst_class_accuracy`, the lowest per-class share of generated samples
     #     classified as asked.  With summaries on, rank 0 writes confusion_<epoch>.npy (and g_confusion_<epoch>.npy) beside the
     #     validation events (Train.evaluate_report).
+    #   SAMPLE_NEAREST = k (--sample-nearest k), an int in 1..16, with SAMPLE_METRICS = N and a TFRecord Dataset: the epoch tail also
+    #     finds the k nearest training images, in pixel space, of those N samples (tg_nearest_u8_i32: exact integer distances against
+    #     the whole training split, resident on the device as uint8) and records `g_nn_rmse`, `g_nn_rmse_min`,
+    #     `g_nn_class_agreement` and the held-out control `val_nn_rmse`; rank 0 writes SAMPLE_DIR/nearest_<epoch>.png
+    #     (Train.nearest_training).
     # Absent, None or False: the epoch tail is what it was.  Read by Training/options.check_eval_ema / check_sample_metrics /
-    # check_sample_manifold_k / check_eval_report.
+    # check_sample_manifold_k / check_eval_report / check_sample_nearest.
 
     def __init__(self):
         """Set values of computed attributes (config.py:70-73)."""

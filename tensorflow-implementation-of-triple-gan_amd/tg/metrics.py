@@ -2,11 +2,13 @@
 (include/tg_kernels.h, csrc/moments.hip) and the Fréchet distance between two Gaussians in NumPy float64; the host side of
 tg_knn_self_f32 / tg_manifold_query_f32 (csrc/knn.hip) and the k-nearest-neighbour precision, recall, density and coverage.  And the
 classifier's own evaluation report (Train.evaluate_report): the host side of tg_eval_report_f32 (csrc/evalreport.hip) —
-ClassifierReport — and the algebra on its counts, report_from_counts.
+ClassifierReport — and the algebra on its counts, report_from_counts.  And the nearest training images of generated samples in pixel
+space (Train.nearest_training): PixelBank and nearest_pixels, the host side of tg_nearest_u8_i32 / tg_f32_quantize_u8
+(csrc/nearest.hip).
 
 The device adds up a feature matrix's column sums and Gram matrix in fp64, batch after batch; the host turns them into a mean and a
 covariance once, at the end, and takes the distance — c x c eigenproblems, no scipy.  Importable without a device: torch and the HIP
-library are touched only by FeatureMoments, FeatureBank, manifold_metrics and ClassifierReport."""
+library are touched only by FeatureMoments, FeatureBank, manifold_metrics, ClassifierReport, PixelBank and nearest_pixels."""
 import numpy as np
 
 from . import lib
@@ -210,6 +212,142 @@ def manifold_metrics(real_bank, fake_bank, k, stream=None):
     count_fr, _, _ = manifold_query(fake, real, r2_real, stream)
     count_rf, nn_rf, _ = manifold_query(real, fake, r2_fake, stream)
     return manifold_from_counts(k, fake_bank.n, count_fr.cpu().numpy(), count_rf.cpu().numpy(), nn_rf.cpu().numpy(), r2_real.cpu().numpy())
+
+
+# ---- the nearest training images of generated samples, in pixel space (Train.nearest_training) ----------------------------
+MAX_PIXELS = 16384          # tg_nearest_u8_i32 accepts 1 <= d <= 16 384 (255^2 d stays below 2^31)
+PIXEL_STAGE = 16384         # rows per pinned staging copy of PixelBank.add_u8
+
+
+class PixelBank(object):
+    """growing [n, d] uint8 image rows, dense on `device`, for tg_nearest_u8_i32: add_u8() copies host bytes through pinned staging,
+    add_act() quantises an fp32 image batch back to the input pipeline's bytes (tg_f32_quantize_u8).  The buffer grows by
+    re-allocation (doubling), which a hipGraph capture or a launch-plan recording must not see: both refuse to run inside one."""
+
+    def __init__(self, d, device):
+        if not 1 <= int(d) <= MAX_PIXELS:
+            raise ValueError("PixelBank: d must be in 1..%d, got %r" % (MAX_PIXELS, d))
+        self.d, self.device, self.n = int(d), device, 0
+        self.buf = None
+
+    def reset(self):
+        self.n = 0
+        return self
+
+    def _reserve(self, rows):
+        import torch
+        if lib._recorder is not None or torch.cuda.is_current_stream_capturing():
+            raise lib.TgError("PixelBank: called inside a hipGraph capture / launch-plan recording; the bank re-allocates as it grows")
+        have = 0 if self.buf is None else self.buf.numel() // self.d
+        if rows <= have:
+            return
+        grown = torch.empty(max(rows, 2 * have, 64) * self.d, dtype=torch.uint8, device=self.device)
+        if self.n:
+            grown[:self.n * self.d].copy_(self.buf[:self.n * self.d])
+        self.buf = grown
+
+    def add_u8(self, rows):
+        """rows: a host uint8 array of n * d values (any shape whose rows flatten to d) -> copied behind the rows already there."""
+        import torch
+        a = np.ascontiguousarray(rows, np.uint8).reshape(-1, self.d)
+        self._reserve(self.n + a.shape[0])
+        for s in range(0, a.shape[0], PIXEL_STAGE):
+            part = a[s:s + PIXEL_STAGE]
+            stage = torch.from_numpy(part).pin_memory()
+            self.buf[(self.n + s) * self.d:(self.n + s + part.shape[0]) * self.d].copy_(stage.reshape(-1), non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()         # the staging buffers are released with this call
+        self.n += a.shape[0]
+        return self
+
+    def add_records(self, chunks, n_threads=4):
+        """chunks: (tg.io.RecordFile, record indices) pieces, e.g. Input_Pipeline.tfrecordDataset.training_chunks — every piece is
+        decoded straight into one pinned staging buffer and copied behind the rows already there -> the records' labels, int32 [n]."""
+        import torch
+        labels, stage = [], None
+        for rec, idx in chunks:
+            m = len(idx)
+            if int(np.prod(rec.shape)) != self.d:
+                raise lib.TgError("PixelBank.add_records: %s holds images of shape %r, the bank rows of %d values" % (rec.path, rec.shape, self.d))
+            if stage is None or stage.numel() < m * self.d:
+                stage = torch.empty(m * self.d, dtype=torch.uint8).pin_memory()
+            lab = np.empty(m, np.int32)
+            rec.gather(idx, stage.numpy(), lab, n_threads=n_threads)
+            self._reserve(self.n + m)
+            self.buf[self.n * self.d:(self.n + m) * self.d].copy_(stage[:m * self.d], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()      # the staging buffer is refilled by the next piece
+            self.n += m
+            labels.append(lab)
+        return np.concatenate(labels) if labels else np.zeros(0, np.int32)
+
+    def add_act(self, act, scale, shift, stream=None):
+        """act: an fp32 image Act of h * w * c == d values per row, in the scaling x = u / 255 * scale + shift; padding channels
+        (ld > c) are dropped by one tg_copy2d_f32 launch first."""
+        import torch
+        if act.dtype != 'f32' or act.h * act.w * act.c != self.d:
+            raise lib.TgError("PixelBank.add_act: fp32 images of %d values are needed, got [%d, %d, %d, %d] %s"
+                              % (self.d, act.n, act.h, act.w, act.c, act.dtype))
+        if act.n == 0:
+            return self
+        self._reserve(self.n + act.n)
+        stream = lib.cur_stream() if stream is None else stream
+        src = act.ptr
+        if act.ld != act.c:
+            dense = torch.empty(act.n * self.d, dtype=torch.float32, device=self.device)
+            lib.call('tg_copy2d_f32', act.ptr, act.ld, lib.ptr(dense), act.c, act.n * act.h * act.w, act.c, stream)
+            src = lib.ptr(dense)
+        lib.call('tg_f32_quantize_u8', src, lib.ptr(self.buf[self.n * self.d:]), act.n * self.d, float(scale), float(shift), stream)
+        self.n += act.n
+        return self
+
+    def rows(self, lo=0, hi=None):
+        """the [hi - lo, d] device tensor of rows lo..hi (a view of the buffer; hi None: all that has been added)."""
+        import torch
+        hi = self.n if hi is None else hi
+        if self.buf is None:
+            return torch.empty((0, self.d), dtype=torch.uint8, device=self.device)
+        return self.buf[lo * self.d:hi * self.d].view(hi - lo, self.d)
+
+    def numpy(self):
+        """the rows as a host [n, d] uint8 array (synchronises)."""
+        return self.rows().cpu().numpy().copy()
+
+
+def nearest_pixels(query_bank, ref, k, stream=None):
+    """the k nearest rows of a reference set for every row of `query_bank` (PixelBank) -> (d2 int32 [m, k], idx int32 [m, k]) device
+    tensors of tg_nearest_u8_i32: exact integer squared distances, the smaller first, on a tie the lower index; (INT32_MAX, -1) where
+    the set has fewer than k rows.  ref: a PixelBank (one call), or an iterable of (base, [n, d] uint8 device tensor) chunks — one call
+    per chunk, merging from the second on; the answer depends neither on the chunking nor on the order of the chunks."""
+    import torch
+    k = check_k(k, 'nearest_pixels: k')
+    m, d = query_bank.n, query_bank.d
+    if m < 1:
+        raise ValueError("nearest_pixels: the query bank is empty")
+    chunks = [(0, ref.rows())] if isinstance(ref, PixelBank) else ref
+    q = query_bank.rows()
+    best_d2 = torch.empty((m, k), dtype=torch.int32, device=q.device)
+    best_idx = torch.empty((m, k), dtype=torch.int32, device=q.device)
+    stream = lib.cur_stream() if stream is None else stream
+    work, calls = None, 0
+    for base, rows in chunks:
+        n = int(rows.shape[0])
+        if n == 0:
+            continue
+        if rows.dtype != torch.uint8 or rows.shape[1] != d or not rows.is_contiguous():
+            raise ValueError("nearest_pixels: a chunk must be a contiguous [n, %d] uint8 tensor, got %s %s" % (d, tuple(rows.shape), rows.dtype))
+        need = lib.call('tg_nearest_u8_workspace_bytes', m, n, d, k)
+        if work is None or work.numel() * 8 < need:
+            work = torch.empty(max((need + 7) // 8, 2), dtype=torch.int64, device=q.device)
+        lib.call('tg_nearest_u8_i32', lib.ptr(q), m, lib.ptr(rows), n, d, k, int(base), int(calls > 0), lib.ptr(best_d2), lib.ptr(best_idx),
+                 lib.ptr(work), work.numel() * 8, stream)
+        calls += 1
+    if calls == 0:
+        raise ValueError("nearest_pixels: the reference set is empty")
+    return best_d2, best_idx
+
+
+def nearest_rmse(nn_d2, d):
+    """[m] float64: sqrt(d2 of the nearest row / d) / 255 — the root-mean-square pixel difference in units of the full range."""
+    return np.sqrt(np.asarray(nn_d2, np.int64).reshape(len(nn_d2), -1)[:, 0].astype(np.float64) / float(d)) / 255.0
 
 
 # ---- the per-class evaluation report of the classifier (Train.evaluate_report, DESIGN §9.12) ------------------------------------------
