@@ -1,5 +1,6 @@
 """Shared checks of the per-kernel float64 tests (tests/test_gpu_elementwise.py, _prep.py, _norm_finalize.py, _loss_heads.py, _gemm_tiles.py, _halo_tiles.py,
-_packed_tiles.py, _rng.py, _norm_forward.py, _colstats.py, _stats_chunk.py, _updates.py, _small_heads.py), of the route-level float64 test
+_packed_tiles.py, _rng.py, _norm_forward.py, _colstats.py, _stats_chunk.py, _updates.py, _small_heads.py, _wgan_kernels.py and its reference
+tests/wgan_kernels_reference.py with the CPU check tests/test_wgan_kernels_reference.py), of the route-level float64 test
 of tg/ops.py (tests/test_gpu_ops_routes.py and its reference tests/ops_reference.py, which propagates the tolerance classes below through
 whole ops: guarded allocations, U, TOL, ALPHA, worst / rejected, bf16_rne_bits), and the float64 oracle of an implicit-GEMM descriptor
 (igemm_ref64, on the device).

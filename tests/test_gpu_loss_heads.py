@@ -1,6 +1,7 @@
 """Per-kernel float64 tests of the stand-alone loss heads of csrc/loss.hip (the Train_base helper methods, Training/train_base.py:43-57,
 75-84: softmax cross-entropy, sigmoid cross-entropy, entropy and balance entropy; restated as in oracle.tf_ops.softmax_ce_mean, bce_mean,
-entropy, balance_entropy), of the discriminator head with its three terms (tg_d_loss_terms_f32), of the squared row difference
+entropy, balance_entropy), of the discriminator head with its three terms (tg_d_loss_terms_f32), of the generator head (tg_g_loss_f32;
+reference, inputs and bounds in tests/wgan_kernels_reference.py), of the squared row difference
 (tg_sqdiff_rows_loss_f32, train_base.py:299) and of minibatch discrimination (csrc/mbd.hip, Model/modle_base.py:110-128) called directly.
 
 The heads are single-workgroup loops: n = 1, 255, 256, 257 and 1000 rows; logits up to |z| = 80 (no inf / NaN: the stable forms
@@ -19,6 +20,7 @@ Tolerance classes (tests/kernel_check.py):
 import numpy as np
 import pytest
 
+import wgan_kernels_reference as WR
 from kernel_check import FLT_MIN, TOL, U, assert_bits, assert_pointwise, bits, close, dev, finish, guarded, lib, ptr, rejected, seq_sum32, st
 
 pytestmark = pytest.mark.gpu
@@ -264,6 +266,32 @@ def test_d_loss_terms():
         assert rejected(got_terms[i], term[:-1].sum(), mag.sum()), "the bound on terms[%d] does not reject the mean without the last row" % i
         total, total_mag = total + term.sum(), total_mag + mag.sum()
     close(finish(loss), total, total_mag, "loss")
+
+
+@pytest.mark.parametrize("case", WR.G_LOSS_CASES, ids=lambda s: "x".join(map(str, s)))
+def test_g_loss(case):
+    """tg_g_loss_f32 (0.5 BCE(D_fake, 1), train_base.py:123-128) on 1, 100 and 700 rows (three turns of the 256-thread row loop), logits as
+    in test_d_loss_terms with NaN padding, fresh guarded dz and loss, two launches with the same bits: the value in the reduction class
+    with the negative control that drops the last row, dz[:, 0] pointwise (tests/wgan_kernels_reference.py counts its K), dz's padding up
+    to ld_d exactly 0."""
+    L = lib()
+    n, ld, ld_d = case
+    z = WR.g_loss_case(case)
+    zd = dev(z)
+    outs = []
+    for _ in range(2):
+        dz, loss = guarded(n * ld_d), guarded(1)
+        L.call('tg_g_loss_f32', ptr(zd), ld, n, dz.ptr, ld_d, loss.ptr, st())
+        outs.append((finish(dz, (n, ld_d)), finish(loss)))
+    (got_dz, got_loss), (dz2, loss2) = outs
+    assert_bits(dz2, got_dz, "dz of a second launch")
+    assert_bits(loss2, got_loss, "loss of a second launch")
+    val, sabs, ref_dz, mag = WR.g_loss(z)
+    close(got_loss[0], val, sabs, "g_loss")
+    if n > 1:
+        assert rejected(got_loss[0], WR.g_loss(z, drop=True)[0], sabs), "the bound does not reject the mean without the last row"
+    assert_pointwise(got_dz[:, 0], ref_dz, mag, WR.K_G_LOSS_DZ, "dz")
+    assert (bits(got_dz[:, 1:]) == 0).all(), "padding not zeroed"
 
 
 @pytest.mark.parametrize("k", [1, 10, 100])

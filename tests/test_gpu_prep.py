@@ -5,7 +5,8 @@ tg_filter_grad_tail_multi_f32: the deferred filter-gradient tails of Context.flu
 
 Tolerance classes (tests/kernel_check.py):
   bit-exact   filter_prep / filter_prep_multi (a copy times at most two per-channel scales: fp32 products restated in NumPy's float32),
-              the slab reduction of filter_grad_tail_multi (sum over the splits in slab order), and the twin paths the code says give
+              the slab reduction of filter_grad_tail_multi (sum over the splits in slab order), both paths of tg_slab_reduce_f32 (the
+              in-order restatements of tests/wgan_kernels_reference.py; also held in the reduction class), and the twin paths the code says give
               identical bits: wn_scale against the wn_scale_multi pass of filter_prep_multi, filter_prep against filter_prep_multi;
   reduction   wn_scale, wn_scale_tab: |got - ref| <= (TOL / 2 + 4u) |ref| (a sum of squares of one sign: its relative error TOL halves
               under the square root; rsqrtf and the product by g add 4u); wn_bwd, the WN tail of filter_grad_tail_multi, wn_bwd_tab:
@@ -21,7 +22,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from kernel_check import TOL, U, assert_bits, dev, finish, guarded, lib, ptr, seq_sum32, st, worst
+import wgan_kernels_reference as WR
+from kernel_check import TOL, U, assert_bits, close, dev, finish, guarded, lib, ptr, rejected, seq_sum32, st, worst
 from oracle import tf_ops as T
 
 pytestmark = pytest.mark.gpu
@@ -224,6 +226,43 @@ def test_filter_prep_multi_equals_the_single_launches():
             assert np.isnan(dt.get()).all()
         ds.check_guard()
         dt.check_guard()
+
+
+@pytest.fixture(scope="module")
+def slabs():
+    """the slabs of tests/wgan_kernels_reference.py's cases on the host and the device, built when first asked for and left unchanged."""
+    made = {}
+
+    def get(case):
+        if case not in made:
+            slab = WR.slab_case(case)
+            made[case] = (slab, dev(slab))
+        return made[case]
+    return get
+
+
+@pytest.mark.parametrize("case", WR.SLAB_CASES, ids=lambda s: "x".join(map(str, s)))
+def test_slab_reduce(case, slabs):
+    """tg_slab_reduce_f32, the kernel that finishes every split filter gradient: dst[t][c][n] = sum_s slab[s][t][c][n] with the slab padding
+    (c >= c_dim, n >= n_dim) NaN and dst guarded.  Bit-exact against the in-order fp32 restatement of the path the case takes — one thread per
+    output walking the slabs in order, or (n_split >= 32 and at most 65536 outputs) 8 lane groups with a contiguous range of slabs each,
+    their partial sums added in index order — on both sides of the path switch (31 / 32 / 33 slabs, 65536 / 65792 outputs), with an empty
+    trailing range (33 slabs) and past the 4096 x 256 outputs of one grid turn; and in the reduction class against float64 with the negative
+    control that drops the last slab."""
+    L = lib()
+    n_split, t, c_pad, n_pad, c, n = case
+    slab, sd = slabs(case)
+    outs = []
+    for _ in range(2):
+        dst = guarded(t * c * n)
+        L.call('tg_slab_reduce_f32', ptr(sd), n_split, t, c_pad, n_pad, c, n, dst.ptr, st())
+        outs.append(finish(dst, (t, c, n)))
+    got = outs[0]
+    assert_bits(outs[1], got, "a second launch")
+    assert_bits(got, WR.slab32(case, slab), "slab_reduce (%s path) vs its in-order fp32 restatement" % WR.slab_path(case))
+    ref, sabs = WR.slab64(slab, c, n)
+    close(got, ref, sabs, "slab sum")
+    assert rejected(got, WR.slab64(slab, c, n, drop_last=True)[0], sabs), "the bound does not reject the sum without the last slab"
 
 
 TAIL_JOBS = [  # n_split, t, c_in, c_pad, c_out, n_pad, weight-normalised
