@@ -792,6 +792,30 @@ int64_t tg_nearest_u8_workspace_bytes(int m, int n, int d, int k);
 int tg_nearest_u8_ranges(int m, int n);
 int tg_nearest_u8_i32(const uint8_t* q, int m, const uint8_t* r, int n, int d, int k, int32_t base, int merge, int32_t* best_d2,
                       int32_t* best_idx, void* workspace, int64_t workspace_bytes, void* stream);
+/* Sums of the cubic polynomial kernel over pairs of fp32 feature rows: the three sums of the unbiased kernel distance (MMD^2 with the
+ * kernel of the "Kernel Inception Distance", Binkowski et al. 2018) of generated samples, whole-set and per class
+ * (tg.metrics.kernel_distance).  a: DEVICE [.][ld_a], b: DEVICE [.][ld_b] fp32 rows of width c; columns c..ld-1 are never
+ * read (they may hold anything).  seg_a, seg_b: HOST arrays of nseg + 1 non-negative, non-decreasing row offsets, read before the call
+ * returns.  For every segment s, A_s = rows [seg_a[s], seg_a[s+1]) of a and B_s = rows [seg_b[s], seg_b[s+1]) of b:
+ *   out[s] = sum over i in A_s, j in B_s of k(a_i, b_j),   k(x, y) = t * t * t,   t = <x, y> / c + 1      (DEVICE, nseg doubles, overwritten)
+ * exclude_diag = 1 leaves out the pairs with i - seg_a[s] == j - seg_b[s] — by INDEX, as tg_knn_self_f32 leaves out a row itself: the self
+ * case, a == b with seg_a == seg_b.  An empty segment (no rows on either side) gives 0.  The arithmetic is part of the interface: every
+ * fp32 feature is widened to fp64, so every product is exact; <x, y> is accumulated in fp64 on v_mfma_f64_16x16x4_f64, channels
+ * ascending; the division by (double)c, the + 1, the two multiplies (t * t) * t and every addition are fp64, separately rounded (no
+ * contraction).  The rows(a) x rows(b) matrix is never written: a 256-thread workgroup owns a 64 x 64 tile of pairs of one segment (each
+ * wave 2 x 2 accumulators of 16 x 16), channel chunks of both row tiles staged in LDS as fp32; rows past a segment's end and channels past
+ * c are excluded by index, never loaded.  One fp64 partial per tile goes to the workspace and a finishing launch (one workgroup per
+ * segment) adds a segment's partials in a fixed order — no floating-point atomics, and the launch sequence (one copy of the host-built
+ * (segment, tile-row, tile-column) map into the workspace, one workgroup per tile, one per segment) depends on the segment tables alone:
+ * out is bit-identical from run to run, on any stream.  An eager launch: not for a stream that is being captured.
+ * 1 <= c <= 512, ld >= c, 1 <= nseg <= 1024, at most 2^24 tiles per call; anything else, a NULL pointer, a negative or decreasing
+ * offset, exclude_diag outside {0, 1} or a workspace smaller than the query's answer is TG_ERR_INVALID before any launch.  Behaviour on
+ * non-finite features is unspecified apart from staying in bounds.
+ * workspace: caller-owned scratch of at least tg_poly3_sums_workspace_bytes(seg_a, seg_b, nseg) bytes (a host query; < 0 for a bad
+ * argument), 16-byte aligned, needs no initialisation, nothing beyond that size is written.  2 c FLOP per pair on the fp64 MFMA. */
+int64_t tg_poly3_sums_workspace_bytes(const int32_t* seg_a, const int32_t* seg_b, int nseg);
+int tg_poly3_sums_f32(const float* a, int ld_a, const float* b, int ld_b, int c, const int32_t* seg_a, const int32_t* seg_b, int nseg,
+                      int exclude_diag, double* out, void* workspace, int64_t workspace_bytes, void* stream);
 /* the inverse of tg_u8_affine_f32: generated images back into the bytes of the input pipeline.  inv = 255.0f / scale (host, fp32);
  * t = (src - shift) * inv (two rounded operations, no fma); dst = floorf(t + 0.5f) clamped to 0..255, NaN -> 0.  quantize(affine(u)) = u
  * for every byte under (scale, shift) = (2, -1) and (1, 0).  n = 0 is a no-op; scale must be finite and not 0. */

@@ -87,6 +87,7 @@ class Train(Evaluation, EpochTail, Train_base):
         self._nearest = {}               # {'pixel': nearest_training()'s resident training bytes, labels and kept controls}
         self._dataset_train = None       # the training Dataset of train(): what the epoch tail's nearest_training() searches
         self.last_reports = {}           # config.EVAL_REPORT: the last epoch tail's report dicts {'val', 'val_ema', 'g'} (_tail_metrics)
+        self.last_kid_per_class = None   # config.SAMPLE_KID = 'per_class': the last tail's kernel_distance_per_class, float64 [NUM_CLASSES]
         self.last_nearest = None         # config.SAMPLE_NEAREST: (result, (query bank, training bank)) of the last tail's nearest_training
         self.nearest_decoded = 0         # training records nearest_training has decoded so far (Evaluation._training_pixels: once)
         self._hist_runs = {}             # network -> (store layout key, tg.summary.StoreHistograms): see histograms()
@@ -699,9 +700,9 @@ def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
     _synthetic_zca(tmp_config)                                         # a default like the class body's: FLAGS below override it
     if FLAGS:
         _customize_config(tmp_config, FLAGS)
-        # --wn-init data, --eval-ema, --sample-metrics N, --sample-manifold-k K, --eval-report, --sample-nearest K: Config does not
-        # declare these settings, so the hasattr rule of _customize_config would drop them (Training/options.check_wn_init ...
-        # check_sample_nearest).  Flag objects without the attribute are common: getattr with a default
+        # --wn-init data, --eval-ema, --sample-metrics N, --sample-manifold-k K, --eval-report, --sample-kid [per_class],
+        # --sample-nearest K: Config does not declare these settings, so the hasattr rule of _customize_config would drop them
+        # (Training/options.check_wn_init ... check_sample_nearest).  Flag objects without the attribute are common: getattr with a default
         for name in Options.EXTRAS:
             if getattr(FLAGS, name, None) is not None:
                 setattr(tmp_config, name.upper(), getattr(FLAGS, name))

@@ -4,9 +4,10 @@ sample grid.  Train (Training/Train_goodGAN.py) inherits it.
 
 _epoch_tail is the whole tail in the reference's order; the other methods are its parts, usable on their own (histograms by tools and
 tests at any time).  The tail calls the trainer's training_statistics, sync_running_state, grad_norms and the scoring passes of
-Training/evaluation.py, and reads config, options, cx.stores, _clip_views, rank, world and the two Summary writers.  It OWNS three
-attributes, set by Train.__init__: `last_reports` (the report dicts of the last tail), `last_nearest` (config.SAMPLE_NEAREST: the last
-tail's nearest_training result and its two banks) and `_hist_runs` (the histogram launches per network).  Apart from what
+Training/evaluation.py, and reads config, options, cx.stores, _clip_views, rank, world and the two Summary writers.  It OWNS four
+attributes, set by Train.__init__: `last_reports` (the report dicts of the last tail), `last_kid_per_class` (config.SAMPLE_KID =
+'per_class': the last tail's per-class kernel distances), `last_nearest` (config.SAMPLE_NEAREST: the last tail's nearest_training
+result and its two banks) and `_hist_runs` (the histogram launches per network).  Apart from what
 training_statistics moves — as the reference's run does — it leaves the training state alone."""
 import contextlib
 import os
@@ -123,8 +124,9 @@ class EpochTail(object):
         'recall', 'density' and 'coverage' with config.SAMPLE_MANIFOLD_K (none with all off).  config.EVAL_REPORT appends, behind all of
         those, REPORT_TAGS with a 'val_' prefix ('val_top5_accuracy' only with more than five classes), with EVAL_EMA the same again
         with an '_ema' suffix, and with SAMPLE_METRICS 'g_worst_class_accuracy' (the generated side's target is the class asked for:
-        recall = class accuracy).  config.SAMPLE_NEAREST appends, last of all, 'g_nn_rmse', 'g_nn_rmse_min', 'g_nn_class_agreement' and
-        'val_nn_rmse' (Train.nearest_training)."""
+        recall = class accuracy).  config.SAMPLE_KID appends 'kernel_distance' and, as 'per_class', 'kernel_distance_worst'
+        (Train.sample_kernel_distance).  config.SAMPLE_NEAREST appends, last of all, 'g_nn_rmse', 'g_nn_rmse_min',
+        'g_nn_class_agreement' and 'val_nn_rmse' (Train.nearest_training)."""
         o = self.options
         rows = [('val_accuracy_ema', 'sm', 'val_accuracy')] if o.eval_ema else []
         if o.sample_metrics:
@@ -133,6 +135,8 @@ class EpochTail(object):
             keys = self._report_keys()
             rows += [('val_' + k, 'val', k) for k in keys] + ([('val_' + k + '_ema', 'val_ema', k) for k in keys] if o.eval_ema else [])
             rows += [('g_worst_class_accuracy', 'g', 'worst_class_recall')] if o.sample_metrics else []
+        if o.sample_kid:                                # config.SAMPLE_KID: behind the report rows, out of the same 'sm' pass
+            rows += [(k, 'sm', k) for k in ('kernel_distance',) + (('kernel_distance_worst',) if o.sample_kid == 'per_class' else ())]
         if o.sample_nearest:                            # config.SAMPLE_NEAREST: behind every other row (result 'nn': nearest_training)
             rows += [(k, 'nn', k) for k in self.NEAREST_KEYS]
         return rows
@@ -162,7 +166,11 @@ class EpochTail(object):
             # the pass of sample_metrics / sample_manifold_metrics; its real side reads the shadows only with EVAL_EMA, and only then
             # does its report differ from the main one
             pair = (self._new_report() if o.eval_ema else None, self._new_report()) if o.eval_report else None
-            sm = res['sm'] = self._sample_metrics_pass(NNIO.val_batches(), o.sample_metrics, o.eval_ema, o.sample_manifold_k, pair)[0]
+            # (the keyword is passed only with config.SAMPLE_KID: with it off the call is what it was)
+            kid = dict(kernel_distance=o.sample_kid) if o.sample_kid else {}
+            sm = res['sm'] = self._sample_metrics_pass(NNIO.val_batches(), o.sample_metrics, o.eval_ema, o.sample_manifold_k, pair, **kid)[0]
+            if o.sample_kid == 'per_class':
+                self.last_kid_per_class = sm['kernel_distance_per_class']
             if o.eval_report:
                 res.update([('g', sm['g_report'])] + ([('val_ema', sm['val_report'])] if o.eval_ema else []))
         elif o.eval_ema:
@@ -209,6 +217,8 @@ class EpochTail(object):
             for name, key in (('confusion', 'val'), ('g_confusion', 'g')):
                 if key in self.last_reports:
                     np.save(os.path.join(self.summary_val.log_dir, '%s_%04d.npy' % (name, rec['epoch'])), self.last_reports[key]['confusion'])
+        if o.sample_kid == 'per_class':                                                # the per-class distances behind the worst one, float64 [K]
+            np.save(os.path.join(self.summary_val.log_dir, 'kid_per_class_%04d.npy' % rec['epoch']), self.last_kid_per_class)
         return samples
 
     def _save_nearest_grid(self, epoch):

@@ -1,5 +1,5 @@
-"""Evaluation — the trainer's forward-only scoring passes: evaluate, the per-class report, the generated-sample and manifold metrics, and
-the sampler.  Train (Training/Train_goodGAN.py) inherits it; the methods are used as `Train.<method>`.
+"""Evaluation — the trainer's forward-only scoring passes: evaluate, the per-class report, the generated-sample, manifold and kernel-distance
+metrics, and the sampler.  Train (Training/Train_goodGAN.py) inherits it; the methods are used as `Train.<method>`.
 
 The contract, once for all of them.  These passes READ from the trainer
 
@@ -133,6 +133,25 @@ class Evaluation(object):
         reports of both sides."""
         return self._sample_metrics_pass(batches, n_samples, ema, None)[0]
 
+    def sample_kernel_distance(self, batches, n_samples, ema=False, per_class=False, return_banks=False):
+        """sample_metrics plus the unbiased kernel distance of the generated samples -> its five keys, then
+        `kernel_distance`: the cubic-kernel MMD^2 (the "Kernel Inception Distance" of Binkowski et al. 2018) between the pooled
+        features of the real and the generated rows, unbiased at any sample count (and so possibly negative).  per_class adds
+        `kernel_distance_per_class` (float64 [NUM_CLASSES]: the same estimator between the rows of each class — the real side's by
+        its label, the generated side's by the class asked for — NaN where a class has fewer than two rows on either side),
+        `kernel_distance_worst` (its largest non-NaN entry) and `kernel_distance_worst_class` (the lowest index attaining it, -1
+        if there is none): which class's samples are distributed least like that class.
+        The same two passes keep their feature rows in a tg.metrics.FeatureBank each, as sample_manifold_metrics does, and
+        tg.metrics.kernel_distance (tg_poly3_sums_f32: three launches, with per_class three more over the class segments) turns
+        them into the numbers; the labels are the host arg-max of the one-hot rows the pass already holds.  They are NaN, and the
+        kernel is not called, when a side's moment sums are not finite (a diverged run).  The banks are buffers of their own and
+        the kernel writes nothing else: what sample_metrics says about the trainer's state holds unchanged.  A method of its own:
+        the parameter lists and result keys of sample_metrics, sample_manifold_metrics and sample_metrics_report are pinned by tests.
+        The extractor is the run's own classifier, which moves: compare generators under one classifier, not epochs.
+        return_banks: return (result, (real bank, fake bank)) — the rows that were scored — instead of the result alone."""
+        out, banks = self._sample_metrics_pass(batches, n_samples, ema, None, kernel_distance='per_class' if per_class else True)
+        return (out, banks) if return_banks else out
+
     def sample_metrics_report(self, batches, n_samples, ema=False, manifold_k=None):
         """sample_metrics (manifold_k None) or sample_manifold_metrics with the per-class report of each side on top ->
         their keys, then `val_report` and `g_report`, two tg.metrics.report_from_counts dicts: the real side's as evaluate_report gives
@@ -157,11 +176,12 @@ class Evaluation(object):
         out, banks = self._sample_metrics_pass(batches, n_samples, ema, manifold_k)
         return (out, banks) if return_banks else out
 
-    def _sample_metrics_pass(self, batches, n_samples, ema, manifold_k, reports=None):
-        """the pass behind sample_metrics (manifold_k None), sample_manifold_metrics and sample_metrics_report -> (result, (real bank,
-        fake bank) or None).  reports: None, or (real side, generated side) tg.metrics.ClassifierReport accumulators, either of which
-        may be None: each is added the rows its side's accuracy counts, and the result carries `val_report` / `g_report` for those
-        given."""
+    def _sample_metrics_pass(self, batches, n_samples, ema, manifold_k, reports=None, *, kernel_distance=None):
+        """the pass behind sample_metrics (manifold_k None), sample_manifold_metrics, sample_metrics_report and
+        sample_kernel_distance -> (result, (real bank, fake bank) or None).  reports: None, or (real side, generated side)
+        tg.metrics.ClassifierReport accumulators, either of which may be None: each is added the rows its side's accuracy counts, and
+        the result carries `val_report` / `g_report` for those given.  kernel_distance: None / False (off), True or 'per_class' — the
+        result also carries tg.metrics.kernel_distance of the two banks, with 'per_class' over the classes of the rows' labels."""
         cx, m, c = self.cx, self.model, self.config
         n_samples = int(n_samples)
         if n_samples < 1:
@@ -171,16 +191,22 @@ class Evaluation(object):
         n_batches = -(-n_samples // B)
         z, y = self._sample_latents(n_batches)
         rep_real, rep_fake = reports if reports is not None else (None, None)
-        real, fake = _Scores(rep_real, True, manifold_k is not None), _Scores(rep_fake, True, manifold_k is not None)
+        want_bank = manifold_k is not None or bool(kernel_distance)       # the manifold metrics or the kernel distance ask for the rows
+        real, fake = _Scores(rep_real, True, want_bank), _Scores(rep_fake, True, want_bank)
+        lab_real, lab_fake = [], []                                       # per_class: the host arg-max of the one-hot rows, batch by batch
         with self._running_state_kept():
             for xb, yb in batches:
                 with cx.phase_scope('metrics', record=False), self._classifier_weights(ema):
                     self._score_batch(cx.from_numpy(xb, key='metrics:x'), cx.from_numpy(yb, key='metrics:y'), real)
+                if kernel_distance == 'per_class':
+                    lab_real.append(np.argmax(np.asarray(yb), axis=1))
             for k in range(n_batches):
                 with cx.phase_scope('metrics_g', record=False), self._classifier_weights(ema):
                     za = cx.from_numpy(z[k * B:(k + 1) * B], key='metrics:z')
                     yg = cx.from_numpy(y[k * B:(k + 1) * B], key='metrics:y_g')
                     self._score_batch(m.as_image(m.good_sampler(za, yg)), yg, fake, take=min(B, n_samples - k * B))
+                if kernel_distance == 'per_class':
+                    lab_fake.append(np.argmax(y[k * B:k * B + min(B, n_samples - k * B)], axis=1))
             seen = real.moments is not None                         # (a real side without batches: no moments, no bank)
             (n_real, sum_r, gram_r), (n_fake, sum_f, gram_f) = real.moments.sums() if seen else (0, None, None), fake.moments.sums()
             mu_r, cov_r = tgm.mean_cov(n_real, sum_r, gram_r) if seen else (None, None)
@@ -188,15 +214,31 @@ class Evaluation(object):
             fd = tgm.frechet_distance(mu_r, cov_r, mu_f, cov_f) if n_real >= 2 and n_fake >= 2 else float('nan')
             out = dict(val_accuracy=float(real.accuracy) if real.accuracy is not None else 0.0, g_class_accuracy=float(fake.accuracy),
                        frechet_distance=fd, n_real=int(n_real), n_fake=int(n_fake))
+            finite = want_bank and seen and all(bool(np.isfinite(a).all()) for a in (sum_r, gram_r, sum_f, gram_f))
             if manifold_k is not None:
-                finite = seen and all(bool(np.isfinite(a).all()) for a in (sum_r, gram_r, sum_f, gram_f))
                 out.update(tgm.manifold_metrics(real.bank, fake.bank, manifold_k, cx.stream) if finite
                            else dict.fromkeys(tgm.MANIFOLD_KEYS, float('nan')))
+            if kernel_distance:
+                out.update(self._kernel_distance(real.bank, fake.bank, lab_real, lab_fake, kernel_distance == 'per_class', finite))
             if rep_real is not None:
                 out['val_report'] = rep_real.result()
             if rep_fake is not None:
                 out['g_report'] = rep_fake.result()
-        return out, (None if manifold_k is None else (real.bank, fake.bank))
+        return out, ((real.bank, fake.bank) if want_bank else None)
+
+    def _kernel_distance(self, real_bank, fake_bank, lab_real, lab_fake, per_class, finite):
+        """tg.metrics.kernel_distance of the two banks of a sample-metrics pass (lab_*: the per-batch host labels, used with
+        per_class); every number NaN, and no launch, unless `finite` (both sides seen, their moment sums finite)."""
+        K = int(self.options.num_classes)
+        if not finite:
+            out = dict(kernel_distance=float('nan'))
+            if per_class:
+                out.update(kernel_distance_per_class=np.full(K, np.nan), kernel_distance_worst=float('nan'), kernel_distance_worst_class=-1)
+            return out
+        if not per_class:
+            return tgm.kernel_distance(real_bank, fake_bank, stream=self.cx.stream)
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.int64)
+        return tgm.kernel_distance(real_bank, fake_bank, cat(lab_real), cat(lab_fake), K, stream=self.cx.stream)
 
     NEAREST_KEYS = ('g_nn_rmse', 'g_nn_rmse_min', 'g_nn_class_agreement', 'val_nn_rmse')
 

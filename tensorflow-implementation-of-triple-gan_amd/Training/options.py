@@ -216,6 +216,25 @@ def check_sample_manifold_k(config):
     return v
 
 
+def check_sample_kid(config):
+    """config.SAMPLE_KID: None / False (default; also when the attribute is absent — config.Config does not declare it), True, or
+    'per_class': the epoch tail's sample metrics also record `kernel_distance`, the unbiased cubic-kernel MMD^2 between the real and the
+    generated features, and with 'per_class' also `kernel_distance_worst`, the largest of the per-class distances, which are written
+    beside the validation events as kid_per_class_<epoch>.npy (Train.sample_kernel_distance).  -> None, True or
+    'per_class'.  Needs no device; ValueError for any other value (a number, another string) and when set without SAMPLE_METRICS (the
+    numbers come out of that pass)."""
+    v = getattr(config, 'SAMPLE_KID', None)
+    if v is None or (isinstance(v, (bool, np.bool_)) and not v):
+        return None
+    if isinstance(v, (bool, np.bool_)):
+        v = True
+    elif not (isinstance(v, str) and v == 'per_class'):
+        raise ValueError("SAMPLE_KID must be None, False, True or 'per_class', got %r" % (v,))
+    if check_sample_metrics(config) is None:
+        raise ValueError("SAMPLE_KID = %r needs SAMPLE_METRICS = N: the sample-metrics pass computes the kernel distance" % (v,))
+    return v
+
+
 def check_sample_nearest(config, Dataset=None):
     """config.SAMPLE_NEAREST: None (default; also when the attribute is absent — config.Config does not declare it) or an int k in
     1..16: the epoch tail also finds the k nearest training images, in pixel space, of the generated samples the sample-metrics pass
@@ -247,17 +266,18 @@ _Fields = collections.namedtuple('Options', 'mfma_dtype act_dtype num_classes lo
 
 class Options(_Fields):
     """the record resolve() returns.  Its tuple fields are the settings config.Config declares a default for (and NO_GRAD_BUCKETS);
-    `wn_init`, `eval_ema`, `sample_metrics`, `sample_manifold_k`, `eval_report` and `sample_nearest` (check_wn_init, check_eval_ema,
-    check_sample_metrics, check_sample_manifold_k, check_eval_report, check_sample_nearest: settings Config deliberately does not
-    declare) are carried as attributes beside them, so the field list — what _asdict() and unpacking give — stays what it was.  Two
-    records are equal when the fields and these attributes are."""
-    EXTRAS = ('wn_init', 'eval_ema', 'sample_metrics', 'sample_manifold_k', 'eval_report', 'sample_nearest')
+    `wn_init`, `eval_ema`, `sample_metrics`, `sample_manifold_k`, `eval_report`, `sample_kid` and `sample_nearest` (check_wn_init,
+    check_eval_ema, check_sample_metrics, check_sample_manifold_k, check_eval_report, check_sample_kid, check_sample_nearest: settings
+    Config deliberately does not declare) are carried as attributes beside them, so the field list — what _asdict() and unpacking give
+    — stays what it was.  Two records are equal when the fields and these attributes are."""
+    EXTRAS = ('wn_init', 'eval_ema', 'sample_metrics', 'sample_manifold_k', 'eval_report', 'sample_kid', 'sample_nearest')
+    _EXTRA_DEFAULTS = (None, False, None, None, False, None, None)
 
     def __new__(cls, wn_init=None, eval_ema=False, sample_metrics=None, sample_manifold_k=None, eval_report=False, sample_nearest=None,
-                **fields):
+                sample_kid=None, **fields):
         self = super(Options, cls).__new__(cls, **fields)
         self.wn_init, self.eval_ema, self.sample_metrics, self.sample_manifold_k = wn_init, eval_ema, sample_metrics, sample_manifold_k
-        self.eval_report, self.sample_nearest = eval_report, sample_nearest
+        self.eval_report, self.sample_kid, self.sample_nearest = eval_report, sample_kid, sample_nearest
         return self
 
     def _extras(self):
@@ -265,7 +285,7 @@ class Options(_Fields):
 
     def __eq__(self, other):
         return (tuple.__eq__(self, other)
-                and tuple(getattr(other, k, d) for k, d in zip(self.EXTRAS, (None, False, None, None, False, None))) == self._extras())
+                and tuple(getattr(other, k, d) for k, d in zip(self.EXTRAS, self._EXTRA_DEFAULTS)) == self._extras())
 
     def __ne__(self, other):
         return not self == other
@@ -280,7 +300,7 @@ def resolve(config):
     check_zca(config)
     return Options(wn_init=check_wn_init(config), eval_ema=check_eval_ema(config), sample_metrics=check_sample_metrics(config),
                    sample_manifold_k=check_sample_manifold_k(config), eval_report=check_eval_report(config),
-                   sample_nearest=check_sample_nearest(config),
+                   sample_kid=check_sample_kid(config), sample_nearest=check_sample_nearest(config),
                    mfma_dtype=check_mfma_dtype(config), act_dtype=check_act_dtype(config), num_classes=check_num_classes(config),
                    loss=check_loss(config), optimizers=check_optimizer(config), clip_norms=check_clip_norm(config),
                    momentum=float(opt(config, 'MOMENTUM')), seed=opt(config, 'SEED'),

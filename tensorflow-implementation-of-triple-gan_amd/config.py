@@ -85,7 +85,7 @@ class Config(object):
     # training batch, g <- init_scale / sqrt(var + eps), b <- -mean * g (Salimans & Kingma 2016; Train.data_dependent_init,
     # DESIGN §9.9); absent or None: g = 1, b = 0 as created.  Read by Training/options.check_wn_init.
 
-    # EVAL_EMA, SAMPLE_METRICS, SAMPLE_MANIFOLD_K, EVAL_REPORT, SAMPLE_NEAREST — NOT declared here either, for the same reason; an
+    # EVAL_EMA, SAMPLE_METRICS, SAMPLE_MANIFOLD_K, EVAL_REPORT, SAMPLE_KID, SAMPLE_NEAREST — NOT declared here either, for the same reason; an
     # instance or subclass may set
     #   EVAL_EMA = True (--eval-ema): the epoch tail also evaluates the classifier's averaged weights (the EMA shadows, decay 0.9999
     #     without bias correction: they lag the weights by roughly 1e4 iterations) and records `val_accuracy_ema`;
@@ -102,13 +102,20 @@ class Config(object):
     #     same with an `_ema` suffix; with SAMPLE_METRICS `g_worst_class_accuracy`, the lowest per-class share of generated samples
     #     classified as asked.  With summaries on, rank 0 writes confusion_<epoch>.npy (and g_confusion_<epoch>.npy) beside the
     #     validation events (Train.evaluate_report).
+    #   SAMPLE_KID = True or 'per_class' (--sample-kid [per_class]), with SAMPLE_METRICS = N: the same pass also records
+    #     `kernel_distance`, the unbiased cubic-kernel MMD^2 ("Kernel Inception Distance", Binkowski et al. 2018) between the
+    #     classifier features of the validation split and of the samples (tg_poly3_sums_f32: fp64 sums on the fp64 MFMA, the Gram
+    #     matrices never written); 'per_class' also `kernel_distance_worst`, the largest of the per-class distances (real rows by
+    #     label, samples by the class asked for), and with summaries on rank 0 writes kid_per_class_<epoch>.npy beside the
+    #     validation events.  Unbiased at any N, so runs scored at different N compare; the extractor still moves with training
+    #     (Train.sample_kernel_distance).
     #   SAMPLE_NEAREST = k (--sample-nearest k), an int in 1..16, with SAMPLE_METRICS = N and a TFRecord Dataset: the epoch tail also
     #     finds the k nearest training images, in pixel space, of those N samples (tg_nearest_u8_i32: exact integer distances against
     #     the whole training split, resident on the device as uint8) and records `g_nn_rmse`, `g_nn_rmse_min`,
     #     `g_nn_class_agreement` and the held-out control `val_nn_rmse`; rank 0 writes SAMPLE_DIR/nearest_<epoch>.png
     #     (Train.nearest_training).
     # Absent, None or False: the epoch tail is what it was.  Read by Training/options.check_eval_ema / check_sample_metrics /
-    # check_sample_manifold_k / check_eval_report / check_sample_nearest.
+    # check_sample_manifold_k / check_eval_report / check_sample_kid / check_sample_nearest.
 
     def __init__(self):
         """Set values of computed attributes (config.py:70-73)."""

@@ -64,8 +64,8 @@ _NEGATIVE_IS_ERROR = {"tg_wgrad_splits", "tg_wgrad_splits_bf16", "tg_wgrad_works
                       "tg_conv3x3_packed_wgrad_workspace_bytes", "tg_grad_norm_workspace_bytes",
                       "tg_tf_histogram_workspace_bytes", "tg_feature_moments_workspace_bytes", "tg_knn_self_workspace_bytes",
                       "tg_manifold_query_workspace_bytes", "tg_eval_report_workspace_bytes", "tg_nearest_u8_workspace_bytes",
-                      "tg_nearest_u8_ranges"}                                             # return a count / size, < 0 on error
-HOST_INT_ARRAYS = {"seg_rows", "tapmap"}          # pointer arguments that are HOST arrays
+                      "tg_nearest_u8_ranges", "tg_poly3_sums_workspace_bytes"}              # return a count / size, < 0 on error
+HOST_INT_ARRAYS = {"seg_rows", "tapmap", "seg_a", "seg_b"}          # pointer arguments that are HOST arrays
 
 
 def _ctype_of(decl):

@@ -4,16 +4,17 @@ tg_knn_self_f32 / tg_manifold_query_f32 (csrc/knn.hip) and the k-nearest-neighbo
 classifier's own evaluation report (Train.evaluate_report): the host side of tg_eval_report_f32 (csrc/evalreport.hip) —
 ClassifierReport — and the algebra on its counts, report_from_counts.  And the nearest training images of generated samples in pixel
 space (Train.nearest_training): PixelBank and nearest_pixels, the host side of tg_nearest_u8_i32 / tg_f32_quantize_u8
-(csrc/nearest.hip).
+(csrc/nearest.hip).  And the unbiased kernel distance of generated samples, whole-set and per class (Train.sample_kernel_distance,
+DESIGN §9.14): poly3_sums, the host side of tg_poly3_sums_f32 (csrc/kernel_distance.hip), kid_from_sums and kernel_distance.
 
 The device adds up a feature matrix's column sums and Gram matrix in fp64, batch after batch; the host turns them into a mean and a
 covariance once, at the end, and takes the distance — c x c eigenproblems, no scipy.  Importable without a device: torch and the HIP
-library are touched only by FeatureMoments, FeatureBank, manifold_metrics, ClassifierReport, PixelBank and nearest_pixels."""
+library are touched only by FeatureMoments, FeatureBank, manifold_metrics, poly3_sums, kernel_distance, ClassifierReport, PixelBank and nearest_pixels."""
 import numpy as np
 
 from . import lib
 
-MAX_FEATURES = 512          # tg_feature_moments_f32, tg_knn_self_f32 and tg_manifold_query_f32 accept 1 <= c <= 512
+MAX_FEATURES = 512          # tg_feature_moments_f32, tg_knn_self_f32, tg_manifold_query_f32 and tg_poly3_sums_f32 accept 1 <= c <= 512
 MAX_K = 16                  # tg_knn_self_f32 accepts 1 <= k <= 16
 MANIFOLD_KEYS = ('precision', 'recall', 'density', 'coverage')
 
@@ -212,6 +213,123 @@ def manifold_metrics(real_bank, fake_bank, k, stream=None):
     count_fr, _, _ = manifold_query(fake, real, r2_real, stream)
     count_rf, nn_rf, _ = manifold_query(real, fake, r2_fake, stream)
     return manifold_from_counts(k, fake_bank.n, count_fr.cpu().numpy(), count_rf.cpu().numpy(), nn_rf.cpu().numpy(), r2_real.cpu().numpy())
+
+
+# ---- the unbiased kernel distance of generated samples, whole-set and per class (Train.sample_kernel_distance) -----------
+KERNEL_DISTANCE_KEYS = ('kernel_distance', 'kernel_distance_per_class', 'kernel_distance_worst', 'kernel_distance_worst_class')
+MAX_SEGMENTS = 1024         # tg_poly3_sums_f32 accepts 1 <= nseg <= 1024
+
+
+def poly3_sums(a, b, seg_a, seg_b, exclude_diag, stream=None):
+    """a [., c], b [., c] dense fp32 device tensors; seg_a, seg_b: nseg + 1 non-decreasing row offsets each (host) -> float64 NumPy
+    [nseg] of tg_poly3_sums_f32: out[s] = the sum over rows i of a in [seg_a[s], seg_a[s+1]) and j of b in [seg_b[s], seg_b[s+1]) of
+    (<a_i, b_j> / c + 1)^3 in fp64, with exclude_diag without the pairs i - seg_a[s] == j - seg_b[s].  The offsets must lie inside
+    the tensors (ValueError otherwise).  An eager launch sequence: refused inside a hipGraph capture / launch-plan recording.
+    Synchronises."""
+    import ctypes as C
+    import torch
+    if lib._recorder is not None or torch.cuda.is_current_stream_capturing():
+        raise lib.TgError("poly3_sums: called inside a hipGraph capture / launch-plan recording; the segment map is copied from the host")
+    sa, sb = np.asarray(seg_a, np.int64).reshape(-1), np.asarray(seg_b, np.int64).reshape(-1)
+    nseg = sa.shape[0] - 1
+    if sb.shape[0] != sa.shape[0] or not 1 <= nseg <= MAX_SEGMENTS:
+        raise ValueError("poly3_sums: seg_a and seg_b must hold nseg + 1 offsets each, 1 <= nseg <= %d (got %d and %d entries)"
+                         % (MAX_SEGMENTS, sa.shape[0], sb.shape[0]))
+    for what, t, seg in (('a', a, sa), ('b', b, sb)):
+        if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("poly3_sums: %s must be a contiguous [n, c] float32 tensor, got %s %s" % (what, tuple(t.shape), t.dtype))
+        if seg[0] < 0 or seg[-1] > t.shape[0] or (np.diff(seg) < 0).any():
+            raise ValueError("poly3_sums: seg_%s must be non-decreasing offsets inside the %d rows of %s, got %r" % (what, t.shape[0], what, seg.tolist()))
+    c = int(a.shape[1])
+    if int(b.shape[1]) != c or not 1 <= c <= MAX_FEATURES:
+        raise ValueError("poly3_sums: a and b must share a width in 1..%d, got %d and %d" % (MAX_FEATURES, c, int(b.shape[1])))
+    ca, cb = (C.c_int32 * (nseg + 1))(*sa.tolist()), (C.c_int32 * (nseg + 1))(*sb.tolist())
+    need = lib.call('tg_poly3_sums_workspace_bytes', ca, cb, nseg)
+    work = torch.empty(max((need + 7) // 8, 2), dtype=torch.float64, device=a.device)
+    out = torch.empty(nseg, dtype=torch.float64, device=a.device)
+    # a tensor without rows has no storage to point at; the kernel never follows the pointer of a side whose segments are all empty
+    pa, pb = (lib.ptr(t if t.shape[0] else work) for t in (a, b))
+    lib.call('tg_poly3_sums_f32', pa, c, pb, c, c, ca, cb, nseg, int(bool(exclude_diag)), lib.ptr(out), lib.ptr(work), work.numel() * 8,
+             lib.cur_stream() if stream is None else stream)
+    return out.cpu().numpy()
+
+
+def kid_from_sums(sxx, syy, sxy, m, n):
+    """the unbiased estimator of MMD^2 from the kernel sums, elementwise in float64:
+        sxx / (m (m - 1)) + syy / (n (n - 1)) - 2 sxy / (m n)
+    sxx, syy: the sums over the ordered pairs i != j of one side (m rows, n rows), sxy: the sum over all m n cross pairs.  NaN where
+    m < 2 or n < 2.  No device work."""
+    sxx, syy, sxy = (np.asarray(v, np.float64) for v in (sxx, syy, sxy))
+    m, n = np.asarray(m, np.float64), np.asarray(n, np.float64)
+    ok = (m >= 2) & (n >= 2)
+    ms, ns = np.where(ok, m, 2.0), np.where(ok, n, 2.0)
+    val = sxx / (ms * (ms - 1.0)) + syy / (ns * (ns - 1.0)) - 2.0 * sxy / (ms * ns)
+    return np.where(ok, val, np.nan)
+
+
+def class_order(labels, num_classes):
+    """host labels [n] -> (order int64 [n]: the rows in class order, a stable sort; offsets int64 [K + 1] of the classes in it).
+    ValueError for a label outside 0..K-1."""
+    lab = np.asarray(labels).reshape(-1).astype(np.int64)
+    K = int(num_classes)
+    if lab.size and (lab.min() < 0 or lab.max() >= K):
+        raise ValueError("kernel_distance: labels must lie in 0..%d, got %d..%d" % (K - 1, lab.min(), lab.max()))
+    return np.argsort(lab, kind='stable'), np.concatenate([[0], np.cumsum(np.bincount(lab, minlength=K))]).astype(np.int64)
+
+
+def worst_of(per_class):
+    """(the largest non-NaN entry, the lowest index attaining it) of a per-class array; (NaN, -1) when every entry is NaN."""
+    v = np.asarray(per_class, np.float64)
+    if not (~np.isnan(v)).any():
+        return float('nan'), -1
+    k = int(np.argmax(np.where(np.isnan(v), -np.inf, v)))
+    return float(v[k]), k
+
+
+def kernel_distance(real_bank, fake_bank, labels_real=None, labels_fake=None, num_classes=None, stream=None):
+    """The unbiased cubic-kernel MMD^2 ("Kernel Inception Distance", Binkowski et al. 2018) between the rows of two FeatureBanks
+     -> dict(kernel_distance=...): kid_from_sums of three one-segment tg_poly3_sums_f32 calls — real x real and
+    fake x fake without their diagonals, real x fake — on the banks as they are, so the number is the same bits whether or not labels
+    are given.  NaN (no launch) with fewer than two rows on either side.
+    labels_real, labels_fake (host integer arrays, one label per bank row) and num_classes = K add
+      kernel_distance_per_class    float64 [K]: the same estimator between the rows of each class, from three K-segment calls on the
+                                   rows gathered into class order (a stable sort of the labels and index_select on the bank: buffer
+                                   plumbing, no arithmetic); NaN where a class has fewer than two rows on either side
+      kernel_distance_worst        its largest non-NaN entry (NaN if there is none)
+      kernel_distance_worst_class  the lowest index attaining it (-1 if there is none)
+    Unbiased at any sample count — which is what keeps it meaningful per class — and therefore possibly negative.  stream: as
+    manifold_metrics.  Synchronises."""
+    import torch
+    if real_bank.c != fake_bank.c:
+        raise ValueError("kernel_distance: the banks hold features of different widths (%d, %d)" % (real_bank.c, fake_bank.c))
+    if (labels_real is None) != (labels_fake is None):
+        raise ValueError("kernel_distance: give the labels of both sides or of neither")
+    real, fake = real_bank.rows(), fake_bank.rows()
+    m, n = int(real.shape[0]), int(fake.shape[0])
+    out = dict(kernel_distance=float('nan'))
+    if m >= 2 and n >= 2:
+        sxx = poly3_sums(real, real, [0, m], [0, m], True, stream)
+        syy = poly3_sums(fake, fake, [0, n], [0, n], True, stream)
+        sxy = poly3_sums(real, fake, [0, m], [0, n], False, stream)
+        out['kernel_distance'] = float(kid_from_sums(sxx, syy, sxy, m, n)[0])
+    if labels_real is None:
+        return out
+    if num_classes is None or not 1 <= int(num_classes) <= MAX_SEGMENTS:
+        raise ValueError("kernel_distance: with labels, num_classes must be in 1..%d, got %r" % (MAX_SEGMENTS, num_classes))
+    K = int(num_classes)
+    if np.size(labels_real) != m or np.size(labels_fake) != n:
+        raise ValueError("kernel_distance: %d / %d labels for %d / %d rows" % (np.size(labels_real), np.size(labels_fake), m, n))
+    (ord_r, off_r), (ord_f, off_f) = class_order(labels_real, K), class_order(labels_fake, K)
+    cm, cn = np.diff(off_r), np.diff(off_f)
+    per = np.full(K, np.nan)
+    if m and n and ((cm >= 2) & (cn >= 2)).any():
+        rs = real.index_select(0, torch.from_numpy(ord_r).to(real.device))
+        fs = fake.index_select(0, torch.from_numpy(ord_f).to(fake.device))
+        per = kid_from_sums(poly3_sums(rs, rs, off_r, off_r, True, stream), poly3_sums(fs, fs, off_f, off_f, True, stream),
+                            poly3_sums(rs, fs, off_r, off_f, False, stream), cm, cn)
+    worst, which = worst_of(per)
+    out.update(kernel_distance_per_class=per, kernel_distance_worst=worst, kernel_distance_worst_class=which)
+    return out
 
 
 # ---- the nearest training images of generated samples, in pixel space (Train.nearest_training, DESIGN §9.13) ----------------------------

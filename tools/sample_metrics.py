@@ -2,12 +2,13 @@
 """Restore a run's checkpoint and print its generated-sample metrics (Train.sample_metrics): the validation accuracy, the
 class-conditional accuracy of N generated samples and the Fréchet distance between the classifier features of the validation split and
 of the samples — with the raw weights, or with the classifier's averaged weights (--ema); with --manifold-k K also the
-k-nearest-neighbour precision, recall, density and coverage of the samples (K = 3 is Kynkäänniemi et al.'s).  The
+k-nearest-neighbour precision, recall, density and coverage of the samples (K = 3 is Kynkäänniemi et al.'s); with --kid
+[per_class] also their unbiased kernel distance, with per_class per class too (Train.sample_kernel_distance).  The
 extractor is the checkpoint's own classifier: the numbers compare generators scored by ONE classifier, not checkpoints of different
 epochs, and the manifold metrics' radii depend on K and on both sample counts.
 
     python tools/sample_metrics.py --experiment mnist [--weight-dir DIR] [--run Run_...] [--epoch N] [--samples 10000] [--ema]
-                                   [--manifold-k K] [--data-dir DIR]
+                                   [--manifold-k K] [--kid [per_class]] [--data-dir DIR]
 
 --weight-dir defaults to the experiment's WEIGHT_DIR (Training/Weight_<data>), --run to its latest Run_* directory, --epoch to that
 run's last checkpoint.  Without --data-dir the validation split is the synthetic one the entry points train on; with it, the
@@ -67,6 +68,8 @@ def main():
     ap.add_argument('--samples', type=int, default=10000, help='generated samples to score')
     ap.add_argument('--ema', action='store_true', help="score with the classifier's averaged weights (the EMA shadows)")
     ap.add_argument('--manifold-k', type=int, help='also the k-nearest-neighbour precision / recall / density / coverage, with this k (1..16)')
+    ap.add_argument('--kid', nargs='?', const='whole', choices=('whole', 'per_class'),
+                    help="also the unbiased kernel distance (cubic-kernel MMD^2) of the samples; 'per_class': per class too, and the worst class")
     ap.add_argument('--data-dir', help="DATA_DIR of the experiment's TFRecords (default: the synthetic validation split)")
     a = ap.parse_args()
     from Training.Saver import Saver
@@ -77,9 +80,15 @@ def main():
     _, init_op_val, NNIO = train.inputpipline_train_val(val)
     init_op_val()
     if a.manifold_k is None:
-        out = tr.sample_metrics(NNIO.val_batches(), a.samples, ema=a.ema)
+        out = tr.sample_metrics(NNIO.val_batches(), a.samples, ema=a.ema) if a.kid is None else {}
     else:
         out = dict(tr.sample_manifold_metrics(NNIO.val_batches(), a.samples, a.manifold_k, ema=a.ema), manifold_k=int(a.manifold_k))
+    if a.kid is not None:                                              # a pass of its own: the same latents, the same five values
+        init_op_val()
+        kid = tr.sample_kernel_distance(NNIO.val_batches(), a.samples, ema=a.ema, per_class=a.kid == 'per_class')
+        if 'kernel_distance_per_class' in kid:                         # (NaN: a class with fewer than two rows on a side; JSON has no NaN)
+            kid['kernel_distance_per_class'] = [None if v != v else float(v) for v in kid['kernel_distance_per_class']]
+        out = dict(kid, **out)
     print(json.dumps(dict(out, experiment=a.experiment, epoch=int(epoch), ema=bool(a.ema), samples=int(a.samples),
                           weight_dir=cfg.WEIGHT_DIR, run=a.run)))
 
