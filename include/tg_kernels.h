@@ -594,6 +594,16 @@ int tg_grad_penalty_f32(const float* gx, int ld_g, int n, int h, int w, int c, f
 int tg_grad_penalty_rows_f32(const float* gx, int ld_g, int n, int f, float weight, float* r, int ld_r, double* partials, float* gp, void* stream);
 int tg_wgan_loss_f32(const float* logits, int ld, int n_real, int n_fake, int n_unl, float lambda_1, float lambda_2, float* dlogits, int ld_d,
                      float* dfake, int ld_df, float* loss, void* stream);
+/* R1, the zero-centred gradient penalty on real data (config.R1_GAMMA; csrc/wgan_gp.hip).  gx: the input gradient of n
+ * images, image i = `rows` rows of c valid floats, row stride ld_g (NHWC: rows = H*W, c = C <= ld_g; rank-2 [n, F]: rows = 1, c = F).
+ * The norm is PER IMAGE, over all rows * c elements: out[0] = gamma / 2 * mean_i ||g_i||^2, out[1] = mean_i ||g_i||^2,
+ * r = (float)(gamma / n) * gx with row stride ld_r (one fp32 multiply per element), padding columns c..ld_r written 0; g = 0 gives r = 0,
+ * a non-finite gradient propagates.  gamma_dev: 1 float on the device, read by the kernels (a replayed plan follows a new value).
+ * partials: scratch of n doubles.  Squares and sums in double, fixed order, no atomics: bit-identical run to run.  Two launches (one
+ * workgroup per image, float4 where ld_g, ld_r and the pointers allow; then one workgroup sums the partials in index order).
+ * rows * c <= 2^21, rows * ld < 2^31, n <= 2^20. */
+int tg_r1_penalty_f32(const float* gx, int ld_g, int n, int rows, int c, const float* gamma_dev, float* r, int ld_r, double* partials, float* out,
+                      void* stream);
 /* loss heads of the training step with config.LOSS = 'WGAN_GP' (Training/Train_goodGAN.py): replayable — lambdas is the trainer's device
  * pair {lambda_1, lambda_2} (hyper[2:4]), nothing is a host value that a recorded plan or graph would freeze.  One workgroup each, fixed
  * summation order (bit-identical run to run); padding columns of the gradients are written 0.

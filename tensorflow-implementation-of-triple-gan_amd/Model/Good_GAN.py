@@ -176,7 +176,15 @@ class Good_GAN(model_base.NN_Base):
         the four sweeps, in_step).  real, fake: Act of one shape — MNIST [N,784] (the generator's and as_image()'s layout: axis 1 is the
         feature axis, one slope per image) or [N,28,28,1] (axis 1 is H), SVHN [N,32,32,3]; y: label Act [N,NUM_CLASSES].  Minibatch
         discrimination (config.MINIBATCH_DIS) couples the images of a batch and is refused."""
-        return grad_penalty.penalty(self, *self._gp, real, fake, y, weight, in_step, minibatch_dis=getattr(self.config, 'MINIBATCH_DIS', False))
+        return grad_penalty.penalty(self, *self._gp, grad_penalty.Wgan(fake, weight), real, y, in_step,
+                                    minibatch_dis=getattr(self.config, 'MINIBATCH_DIS', False))
+
+    def discriminator_r1_penalty(self, real, y, gamma, in_step=False):
+        """gamma / 2 * mean_i ||d logit_i / d x_i||^2 at the real rows `real` (MNIST [N,784] or [N,28,28,1], SVHN [N,32,32,3]) with their
+        own labels y, and its gradient laid out like the discriminator's ParamStore.g (R1): the same sweeps,
+        tg/grad_penalty.py.  gamma: a number or a 1-element device tensor.  Minibatch discrimination is refused as above."""
+        return grad_penalty.penalty(self, *self._gp, grad_penalty.R1(gamma), real, y, in_step,
+                                    minibatch_dis=getattr(self.config, 'MINIBATCH_DIS', False))
 
     def classifier(self, image, train_ph, reuse=False, segments=None, init=False):
         """:212-350.  init (extension): the two network-in-network layers of the SVHN classifier assign their g and b

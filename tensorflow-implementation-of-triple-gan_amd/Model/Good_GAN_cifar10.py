@@ -152,7 +152,13 @@ class Good_GAN_cifar10(model_base.NN_Base):
     def discriminator_gradient_penalty(self, real, fake, y, weight=1.0, in_step=False):
         """weight * gp and weight * d gp / d theta_D of the WGAN-GP gradient penalty on this discriminator: tg/grad_penalty.py (contract,
         the four sweeps, in_step) over D_CONVS and the dense head.  real, fake: Act [N,H,W,3]; y: label Act [N,NUM_CLASSES]."""
-        return grad_penalty.penalty(self, *self._gp, real, fake, y, weight, in_step)
+        return grad_penalty.penalty(self, *self._gp, grad_penalty.Wgan(fake, weight), real, y, in_step)
+
+    def discriminator_r1_penalty(self, real, y, gamma, in_step=False):
+        """gamma / 2 * mean_i ||d logit_i / d x_i||^2 at the real rows `real` with their own labels y, and its gradient laid out like the
+        discriminator's ParamStore.g (R1): the same sweeps, tg/grad_penalty.py.  gamma: a number or a 1-element device
+        tensor."""
+        return grad_penalty.penalty(self, *self._gp, grad_penalty.R1(gamma), real, y, in_step)
 
     def classifier(self, inp, is_training, init=False, reuse=False, getter=None, segments=None):
         """:101-174.  inp: Act [N,32,32,3] (ZCA-whitened).  Returns (logits Act [N,10], feature Act [N,128]).

@@ -27,8 +27,9 @@ from Model.zca import resolve_zca, synthetic_zca as _synthetic_zca         # (to
 from Training.epoch_tail import EpochTail
 from Training.evaluation import Evaluation
 from Training.options import (LOSSES, NETS, NUM_CLASSES_RANGE, OPTIMIZERS, Options, check_act_dtype, check_clip_norm, check_eval_ema,  # noqa: F401
-                              check_eval_report, check_loss, check_mfma_dtype, check_num_classes, check_optimizer, check_sample_manifold_k,
-                              check_sample_metrics, check_sample_nearest, check_wn_init, check_zca, cla_lr, opt, resolve)
+                              check_eval_report, check_loss, check_mfma_dtype, check_num_classes, check_optimizer, check_r1_gamma,
+                              check_sample_manifold_k, check_sample_metrics, check_sample_nearest, check_wn_init, check_zca, cla_lr, opt,
+                              resolve)
 from Training.schedule import epoch_schedule
 from Training.train_base import Train_base, clip_workspace_floats
 from tg import dist as tgdist
@@ -69,11 +70,16 @@ class Train(Evaluation, EpochTail, Train_base):
         self.clip_norms = o.clip_norms               # (D, G, C), each a threshold or None: clip_by_global_norm
         self.clip_dev = None                         # with a clip: per network [threshold, 0, norm, factor] on the device
         self._clip_views = {}                        # network -> (threshold, {norm, factor}) views of it (Train_base._clip_state)
-        self._gp_w = self._gp_grad = None            # WGAN-GP: the D-update's weighted penalty and its parameter gradient (device)
+        self._gp_w = self._gp_grad = None            # WGAN-GP / R1: the D-update's weighted penalty and its parameter gradient (device)
+        # config.R1_GAMMA: [gamma] on the device, read by the penalty kernel — None with the option off, and nothing else
+        # of R1 exists then; _r1_out: the in-step penalty's {R1, mean_i ||g_i||^2}, at its call site of phase D
+        self.r1_dev = self._r1_out = None
         cx.bf16_act_layers = set()
         # device-resident hyper-parameters (the reference's lr_ph / cla_lr_ph / lambda placeholders, :30-31,416-420)
         self.hyper = torch.zeros(4, dtype=torch.float32, device=cx.device)       # lr, cla_lr, lambda_1, lambda_2
         self.loss_dev = torch.zeros(3, dtype=torch.float32, device=cx.device)    # d_loss, g_loss, c_loss
+        if o.r1_gamma is not None:
+            self.r1_dev = torch.full((1,), o.r1_gamma, dtype=torch.float32, device=cx.device)
         self.model = None
         self.executor = executor.StepExecutor(cx)        # how an iteration is launched, and every graph / launch plan it replays
         self._refusal_warned = False
@@ -180,6 +186,25 @@ class Train(Evaluation, EpochTail, Train_base):
         for net, v in new:                               # only the threshold elements: {norm, factor} beside them are the kernels'
             self._clip_views[net][0].fill_(v)
 
+    def set_r1_gamma(self, gamma):
+        """a new R1 weight, written to the device like set_hyper: a replayed plan or graph follows.  Only for a trainer built with
+        config.R1_GAMMA — without it the recorded launches hold no penalty."""
+        if self.r1_dev is None:
+            raise lib.TgError("set_r1_gamma: this trainer was built with R1_GAMMA = None; the penalty is part of the recorded launches")
+        if isinstance(gamma, bool) or not 0.0 < float(gamma) < float('inf'):
+            raise lib.TgError("set_r1_gamma: gamma must be a positive finite number, got %r" % (gamma,))
+        self.r1_dev.fill_(float(gamma))
+
+    def r1_terms(self):
+        """{'penalty': gamma / 2 * mean_i ||g_i||^2, 'grad_sq_mean': mean_i ||g_i||^2} of the last D-update as floats — ONE device->host
+        copy; zeros before the first D-update.  lib.TgError for a trainer built with R1_GAMMA = None."""
+        if self.r1_dev is None:
+            raise lib.TgError("r1_terms: this trainer was built with R1_GAMMA = None")
+        if self._r1_out is None:
+            return dict(penalty=0.0, grad_sq_mean=0.0)
+        v = self._r1_out[:2].detach().cpu().numpy()
+        return dict(penalty=float(v[0]), grad_sq_mean=float(v[1]))
+
     def grad_norms(self):
         """{'d': (norm, factor), 'g': ..., 'c': ...} of the last iteration's gradients as floats — ONE device->host copy; None for an
         unclipped network (and (0, 0) for one whose solver has not run yet).  A NaN factor is a non-finite norm."""
@@ -235,13 +260,27 @@ class Train(Evaluation, EpochTail, Train_base):
             self._d_labels = (oh_unl, oh_unl_d)          # the labels this run's discriminator sees (parity tests read them back)
             ximg = concat_acts([m.as_image(a) for a in (self.x_l_d_ph, self.x_u_d_ph, G, self.x_u_c_ph)])   # X_P | G | x_u_c (:258-271)
             yall = concat_acts([self.y_l_d_ph, oh_unl_d, self.y_g_ph, oh_unl])
+            if self.r1_dev is not None:
+                # R1 at the rows the head counts as real, X_P with [y_l_d | oh_unl_d]: the labels are this run's classifier's (after the
+                # override), so the penalty cannot go beside the classifier's forward pass as WGAN-GP's does.  With the side stream it
+                # goes beside the discriminator's forward pass (it reads the batch and the weights, and writes buffers of its own call
+                # sites only) and is joined before the head adds it; without one (eager, graph) it is on the chain
+                n_real = c.BATCH_SIZE_L_D + c.BATCH_SIZE_U_D
+                with cx.wgrad_on_side():
+                    self._gp_w, self._gp_grad = m.discriminator_r1_penalty(ximg.view_rows(0, n_real), yall.view_rows(0, n_real), self.r1_dev,
+                                                                           in_step=True)
+                self._r1_out = m.last_gp_state['out']
             with cx.rng_scoped('D/D'):
                 _, d_logits = m.discriminator(ximg, yall, want_prob=False)
+            if self.r1_dev is not None:
+                cx.join_wgrad_side()
             if wgan:
                 self._wgan_d_head(d_logits, c.BATCH_SIZE_L_D + c.BATCH_SIZE_U_D, c.BATCH_SIZE_G, c.BATCH_SIZE_U_C, self.hyper[2:4], self._gp_w,
                                   self.loss_dev[0:1])
             else:
                 self._d_loss(d_logits, c.BATCH_SIZE_L_D + c.BATCH_SIZE_U_D, c.BATCH_SIZE_G, c.BATCH_SIZE_U_C, self.loss_dev[0:1])
+                if self.r1_dev is not None:              # d_loss += R1, on the device
+                    lib.call('tg_add_f32', lib.ptr(self.loss_dev[0:1]), lib.ptr(self.loss_dev[0:1]), lib.ptr(self._gp_w), 1, cx.stream)
             self._keep_rest('D', cx.backward(stop_at_boundary='discriminator' if split else False))
 
     def _g_forward_backward(self, split=False):
@@ -310,7 +349,7 @@ class Train(Evaluation, EpochTail, Train_base):
                 self._keep_rest(phase, self.cx.run_tape(rest, stop_at_boundary=net if split else False))
 
     def _add_gp_slice(self, sl):
-        """WGAN-GP: add the penalty's parameter gradient to the slice `sl` of the discriminator's store.g, once the D backward pass has
+        """WGAN-GP / R1: add the penalty's parameter gradient to the slice `sl` of the discriminator's store.g, once the D backward pass has
         finished that slice and before it is exchanged (with replicas it is averaged like every other gradient)."""
         st = self.cx.stores['discriminator']
         off = (sl.data_ptr() - st.g.data_ptr()) // sl.element_size()
@@ -343,7 +382,7 @@ class Train(Evaluation, EpochTail, Train_base):
         for k, sl in enumerate(slices[1:]):
             last = k == len(slices) - 2
             segs.append((lambda last=last: self._backward_rest(phase, net, not last), sl))
-        if net == 'discriminator' and self.loss_kind == 'WGAN_GP':
+        if net == 'discriminator' and (self.loss_kind == 'WGAN_GP' or self.r1_dev is not None):       # the D-update has a penalty
             segs = [(lambda fn=fn, sl=sl: (fn(), self._add_gp_slice(sl)), sl) for fn, sl in segs]
         return segs
 
@@ -700,9 +739,9 @@ def _run(TempConfig, Model, Dataset, FLAGS, comments, epochs=None):
     _synthetic_zca(tmp_config)                                         # a default like the class body's: FLAGS below override it
     if FLAGS:
         _customize_config(tmp_config, FLAGS)
-        # --wn-init data, --eval-ema, --sample-metrics N, --sample-manifold-k K, --eval-report, --sample-kid [per_class],
+        # --wn-init data, --r1-gamma X, --eval-ema, --sample-metrics N, --sample-manifold-k K, --eval-report, --sample-kid [per_class],
         # --sample-nearest K: Config does not declare these settings, so the hasattr rule of _customize_config would drop them
-        # (Training/options.check_wn_init ... check_sample_nearest).  Flag objects without the attribute are common: getattr with a default
+        # (Training/options.check_wn_init, check_r1_gamma ... check_sample_nearest).  Flag objects without the attribute are common: getattr with a default
         for name in Options.EXTRAS:
             if getattr(FLAGS, name, None) is not None:
                 setattr(tmp_config, name.upper(), getattr(FLAGS, name))

@@ -53,6 +53,8 @@ class EpochTail(object):
         acc = self.evaluate(NNIO.val_batches()) if main_report is None else self.evaluate(NNIO.val_batches(), report=main_report)
         rec = dict(epoch=epoch + start_epoch, d_loss=d_loss, g_loss=g_loss, c_loss=c_loss, val_accuracy=acc,
                    images_per_sec=iters * c.BATCH_SIZE * self.world / dt)
+        if self.options.r1_gamma:                                                  # R1_GAMMA: the last D-update's penalty
+            rec['d_r1'] = self.r1_terms()['penalty']
         extra = self._tail_metrics(NNIO, init_op_val, main_report)                 # EVAL_EMA / SAMPLE_METRICS / EVAL_REPORT: {} with all off
         rec.update(extra)
         samples = None
@@ -113,8 +115,9 @@ class EpochTail(object):
             sm._image_outputs = sm._image_summary(kinds['image'], min(self.options.summary_image_max_outputs, int(c.SAMPLE_SIZE)))
 
     def _norm_tags(self):
-        """the train summary's extra scalars: '<d|g|c>_grad_norm' for every clipped network (none without a clip)."""
-        return tuple(k + '_grad_norm' for k, net in zip('dgc', NETS) if net in self._clip_views)
+        """the train summary's extra scalars: '<d|g|c>_grad_norm' for every clipped network (none without a clip), then 'd_r1' with
+        config.R1_GAMMA."""
+        return tuple(k + '_grad_norm' for k, net in zip('dgc', NETS) if net in self._clip_views) + (('d_r1',) if self.options.r1_gamma else ())
 
     def _tail_rows(self):
         """the epoch tail's extra records and val-summary scalars, in order, as (tag, result, key): the value of `tag` is `key` of the
@@ -210,7 +213,8 @@ class EpochTail(object):
                 samples = self.sample(sample_z, sample_y)
             imgs = {'generated': samples}
         self.summary_train.write(dict(dict(g_loss=rec['g_loss'], d_loss=rec['d_loss'], c_loss=rec['c_loss']),
-                                      **{k + '_grad_norm': v[0] for k, v in norms.items() if v is not None}), rec['epoch'],
+                                      **dict({k + '_grad_norm': v[0] for k, v in norms.items() if v is not None},
+                                             **({'d_r1': rec['d_r1']} if 'd_r1' in rec else {}))), rec['epoch'],
                                  histograms=hists, images=imgs)
         self.summary_val.write(dict(dict(val_accuracy=rec['val_accuracy']), **{k: rec[k] for k in self._tail_metric_tags()}), rec['epoch'])
         if o.eval_report:                                                              # the matrices behind the scalars, int64 [K, K]

@@ -65,6 +65,26 @@ def check_loss(config):
     return loss
 
 
+def check_r1_gamma(config):
+    """config.R1_GAMMA: None (default; also when the attribute is absent — config.Config does not declare it) or a positive finite
+    number gamma: the D-update adds the R1 gradient penalty gamma / 2 * mean_i ||d D_logit(x_i, y_i) / d x_i||^2 on the discriminator's
+    real rows to d_loss.  -> None or float.  Needs no device and no relation between the batch sizes.  ValueError for
+    zero, a negative number, NaN, infinity, a bool or anything that is not a number, and when set together with LOSS = 'WGAN_GP' (two
+    penalties, one slot for their gradient); lib.TgError for what the penalty's sweeps cannot run: bf16 MFMA operands and minibatch
+    discrimination."""
+    v = getattr(config, 'R1_GAMMA', None)
+    if v is None:
+        return None
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not (0.0 < float(v) < float('inf')):
+        raise ValueError("R1_GAMMA must be None or a positive finite number, got %r" % (v,))
+    if opt(config, 'LOSS') == 'WGAN_GP':
+        raise ValueError("R1_GAMMA = %r cannot be combined with LOSS = 'WGAN_GP': that loss brings its own gradient penalty, and the "
+                         "D-update holds one penalty gradient" % (v,))
+    from tg import grad_penalty                       # (tg.runtime behind it imports torch: only on this branch)
+    grad_penalty.check_supported("R1_GAMMA (the R1 gradient penalty)", opt(config, 'MFMA_DTYPE'), opt(config, 'MINIBATCH_DIS'))
+    return float(v)
+
+
 OPTIMIZERS = ('adam', 'rmsprop', 'momentum')
 
 
@@ -266,18 +286,18 @@ _Fields = collections.namedtuple('Options', 'mfma_dtype act_dtype num_classes lo
 
 class Options(_Fields):
     """the record resolve() returns.  Its tuple fields are the settings config.Config declares a default for (and NO_GRAD_BUCKETS);
-    `wn_init`, `eval_ema`, `sample_metrics`, `sample_manifold_k`, `eval_report`, `sample_kid` and `sample_nearest` (check_wn_init,
+    `wn_init`, `r1_gamma`, `eval_ema`, `sample_metrics`, `sample_manifold_k`, `eval_report`, `sample_kid` and `sample_nearest` (check_wn_init, check_r1_gamma,
     check_eval_ema, check_sample_metrics, check_sample_manifold_k, check_eval_report, check_sample_kid, check_sample_nearest: settings
     Config deliberately does not declare) are carried as attributes beside them, so the field list — what _asdict() and unpacking give
     — stays what it was.  Two records are equal when the fields and these attributes are."""
-    EXTRAS = ('wn_init', 'eval_ema', 'sample_metrics', 'sample_manifold_k', 'eval_report', 'sample_kid', 'sample_nearest')
-    _EXTRA_DEFAULTS = (None, False, None, None, False, None, None)
+    EXTRAS = ('wn_init', 'r1_gamma', 'eval_ema', 'sample_metrics', 'sample_manifold_k', 'eval_report', 'sample_kid', 'sample_nearest')
+    _EXTRA_DEFAULTS = (None, None, False, None, None, False, None, None)
 
     def __new__(cls, wn_init=None, eval_ema=False, sample_metrics=None, sample_manifold_k=None, eval_report=False, sample_nearest=None,
-                sample_kid=None, **fields):
+                sample_kid=None, r1_gamma=None, **fields):
         self = super(Options, cls).__new__(cls, **fields)
         self.wn_init, self.eval_ema, self.sample_metrics, self.sample_manifold_k = wn_init, eval_ema, sample_metrics, sample_manifold_k
-        self.eval_report, self.sample_kid, self.sample_nearest = eval_report, sample_kid, sample_nearest
+        self.eval_report, self.sample_kid, self.sample_nearest, self.r1_gamma = eval_report, sample_kid, sample_nearest, r1_gamma
         return self
 
     def _extras(self):
@@ -298,7 +318,7 @@ def resolve(config):
     """every device-free check of `config`, once -> the Options record of what Train reads with a default (EXEC_MODE / USE_HIP_GRAPH
     excepted: those stay live, read per iteration).  The string form of ZCA is checked here; against a Dataset, where one is known."""
     check_zca(config)
-    return Options(wn_init=check_wn_init(config), eval_ema=check_eval_ema(config), sample_metrics=check_sample_metrics(config),
+    return Options(wn_init=check_wn_init(config), r1_gamma=check_r1_gamma(config), eval_ema=check_eval_ema(config), sample_metrics=check_sample_metrics(config),
                    sample_manifold_k=check_sample_manifold_k(config), eval_report=check_eval_report(config),
                    sample_kid=check_sample_kid(config), sample_nearest=check_sample_nearest(config),
                    mfma_dtype=check_mfma_dtype(config), act_dtype=check_act_dtype(config), num_classes=check_num_classes(config),

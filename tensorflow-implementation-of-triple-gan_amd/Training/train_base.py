@@ -495,6 +495,21 @@ class Train_base(object):
         gp, self.last_gp_grad = self._gp_sweeps(f)(real, fake, label, weight)
         return gp
 
+    def _r1_penalty(self, real, label, f, gamma):
+        """R1 (config.R1_GAMMA; not in the reference): gamma / 2 * mean_i ||d logit_i / d x_i||^2 at the real rows `real`
+        with their own labels `label`, the norm over all elements of image i.  f: the discriminator, as in _gradient_penalty; gamma: a
+        number or a 1-element device tensor.  Returns the penalty (1-element device tensor) and leaves its parameter gradient in
+        self.last_gp_grad, for _add_gp_grad()."""
+        if real.n != label.n:
+            raise lib.TgError("_r1_penalty: batch sizes differ (real %d, labels %d)" % (real.n, label.n))
+        model = getattr(f, '__self__', f)
+        fn = getattr(model, 'discriminator_r1_penalty', None)
+        if fn is None:
+            raise lib.TgError("_r1_penalty: %s has no discriminator_r1_penalty; R1 is implemented for Good_GAN (MNIST / SVHN), "
+                              "Good_GAN_cifar10 and Good_GAN_stress64" % type(model).__name__)
+        pen, self.last_gp_grad = fn(real, label, gamma)
+        return pen
+
     def _loss_WGAN_GP(self, G, D, C, X, Y, Lambda, discriminator):
         """train_base.py:576-596 -> (d_loss, g_loss, c_loss) as Python floats.  G: the generated images (the penalty's `fake`);
         D: the reference's 9-tuple (D_real, D_real_logits, fm_real, D_fake, D_fake_logits, fm_fake, D_unl, D_unl_logits, fm_unl; the fm

@@ -117,6 +117,12 @@ class Config(object):
     # Absent, None or False: the epoch tail is what it was.  Read by Training/options.check_eval_ema / check_sample_metrics /
     # check_sample_manifold_k / check_eval_report / check_sample_kid / check_sample_nearest.
 
+    # R1_GAMMA — NOT declared here either, for the same reason; absent or None is the default, the step exactly as it is.  An instance
+    # or subclass may set R1_GAMMA = gamma (--r1-gamma X), a positive finite number: with LOSS = 'GAN' the D-update adds the R1
+    # gradient penalty gamma / 2 * mean_i ||d D_logit(x_i, y_i) / d x_i||^2 on the discriminator's real rows [x_l_d | x_u_d] to d_loss
+    # (Mescheder et al. 2018; fp32 MFMA operands, no minibatch discrimination, not with LOSS = 'WGAN_GP'; Train.set_r1_gamma changes it
+    # during a run).  Read by Training/options.check_r1_gamma.
+
     def __init__(self):
         """Set values of computed attributes (config.py:70-73)."""
         self.MIN_QUEUE_EXAMPLES = self.BATCH_SIZE * 3

@@ -121,6 +121,63 @@ __global__ void __launch_bounds__(BLK) gp_rows(const float* __restrict__ g, int 
   if (threadIdx.x == 0) partials[i] = (s - 1.0) * (s - 1.0);
 }
 
+// ---- R1 (config.R1_GAMMA): the zero-centred penalty on the input gradient at the real rows, per image.
+// One workgroup per image i = `rows` rows of c valid floats (row stride ld_g): ss_i = sum of g^2 over all rows * c elements, every square
+// taken in double (exact), per-thread strides then block_sum_d: bit-identical run to run.  r = scale * g with scale = (float)(gamma / n),
+// one fp32 multiply per element; padding columns c..ld_r of r written 0.  The image is read twice (the sum, then r): nothing is kept in
+// registers, so an image of any size goes through one workgroup.  V = 4: rows start 16-byte aligned in g and r, a row is ceil(c / 4)
+// float4s whose components at or beyond c count as 0.
+template <int V> struct R1Vec;
+template <> struct R1Vec<1> {
+  static __device__ __forceinline__ float4 load(const float* p) { return make_float4(p[0], 0.f, 0.f, 0.f); }
+  static __device__ __forceinline__ float4 first(float4 v, int left) { return v; }
+  static __device__ __forceinline__ void store(float* p, float4 v) { p[0] = v.x; }
+};
+template <> struct R1Vec<4> {
+  static __device__ __forceinline__ float4 load(const float* p) { return *reinterpret_cast<const float4*>(p); }
+  static __device__ __forceinline__ float4 first(float4 v, int left) {            // the first `left` components, 0 behind them
+    return make_float4(left > 0 ? v.x : 0.f, left > 1 ? v.y : 0.f, left > 2 ? v.z : 0.f, left > 3 ? v.w : 0.f);
+  }
+  static __device__ __forceinline__ void store(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+};
+
+template <int V>
+__global__ void __launch_bounds__(BLK) r1_rows(const float* __restrict__ g, int ld_g, int n, int rows, int c, const float* __restrict__ gamma_dev,
+                                               float* __restrict__ r, int ld_r, double* __restrict__ partials) {
+  __shared__ double red[4];
+  using Vec = R1Vec<V>;
+  const float* __restrict__ gi = g + (int64_t)blockIdx.x * rows * ld_g;
+  float* __restrict__ ri = r + (int64_t)blockIdx.x * rows * ld_r;
+  const int cv = (c + V - 1) / V, lv = ld_r / V;                    // vectors of a row that hold valid columns / that r has
+  double ss = 0.0;
+  for (int q = threadIdx.x; q < rows * cv; q += BLK) {              // (rows * ld < 2^31: the entry point checks)
+    const int row = q / cv, k = (q - row * cv) * V;
+    ss += sq_sum(Vec::first(Vec::load(gi + (int64_t)row * ld_g + k), c - k));
+  }
+  ss = block_sum_d(ss, red);
+  const float scale = (float)((double)gamma_dev[0] / (double)n);
+  for (int q = threadIdx.x; q < rows * lv; q += BLK) {
+    const int row = q / lv, k = (q - row * lv) * V;
+    float4 v = zero_of<float4>();
+    if (k < c) v = Vec::first(scaled(Vec::load(gi + (int64_t)row * ld_g + k), scale), c - k);
+    Vec::store(ri + (int64_t)row * ld_r + k, v);
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = ss;
+}
+
+// out[0] = gamma / 2 * mean_i ss_i, out[1] = mean_i ss_i: the n partials summed by one workgroup in index order
+__global__ void __launch_bounds__(BLK) r1_finish(const double* __restrict__ partials, int n, const float* __restrict__ gamma_dev, float* __restrict__ out) {
+  __shared__ double red[4];
+  double v = 0.0;
+  for (int b = threadIdx.x; b < n; b += BLK) v += partials[b];
+  v = block_sum_d(v, red);
+  if (threadIdx.x == 0) {
+    const double m = v / (double)n;
+    out[0] = (float)(0.5 * (double)gamma_dev[0] * m);
+    out[1] = (float)m;
+  }
+}
+
 constexpr int WV = BLK / 64;
 
 // The Wasserstein distances of both loss heads below, written once.  Rows [real | fake | unl] of the discriminator logits (column 0, row
@@ -297,6 +354,25 @@ int tg_grad_penalty_rows_f32(const float* gx, int ld_g, int n, int f, float weig
   TG_CHECK_LAUNCH("gp_rows");
   hipLaunchKernelGGL(gp_finish, dim3(1), dim3(BLK), 0, s, partials, n, (double)weight / (double)n, gp);
   TG_CHECK_LAUNCH("gp_finish");
+  return TG_OK;
+}
+
+int tg_r1_penalty_f32(const float* gx, int ld_g, int n, int rows, int c, const float* gamma_dev, float* r, int ld_r, double* partials, float* out,
+                      void* stream) {
+  TG_REQUIRE(gx && gamma_dev && r && partials && out && n > 0 && n <= (1 << 20) && rows > 0 && c > 0 && c <= ld_g && c <= ld_r,
+             "r1_penalty: bad args (n=%d rows=%d c=%d ld_g=%d ld_r=%d)", n, rows, c, ld_g, ld_r);
+  TG_REQUIRE((int64_t)rows * c <= (1LL << 21) && (int64_t)rows * ld_g < (1LL << 31) && (int64_t)rows * ld_r < (1LL << 31),
+             "r1_penalty: an image of %d rows (c=%d ld_g=%d ld_r=%d) is beyond one workgroup's pass", rows, c, ld_g, ld_r);
+  hipStream_t s = tg::as_stream(stream);
+  tg::ProfScope prof(tg::PC_LOSS, 0, 4.0 * (double)n * rows * (2 * c + ld_r), s);
+  const bool vec = ld_g % 4 == 0 && ld_r % 4 == 0 && reinterpret_cast<uintptr_t>(gx) % 16 == 0 && reinterpret_cast<uintptr_t>(r) % 16 == 0;
+  if (vec)
+    hipLaunchKernelGGL(r1_rows<4>, dim3((unsigned)n), dim3(BLK), 0, s, gx, ld_g, n, rows, c, gamma_dev, r, ld_r, partials);
+  else
+    hipLaunchKernelGGL(r1_rows<1>, dim3((unsigned)n), dim3(BLK), 0, s, gx, ld_g, n, rows, c, gamma_dev, r, ld_r, partials);
+  TG_CHECK_LAUNCH("r1_rows");
+  hipLaunchKernelGGL(r1_finish, dim3(1), dim3(BLK), 0, s, partials, n, gamma_dev, out);
+  TG_CHECK_LAUNCH("r1_finish");
   return TG_OK;
 }
 

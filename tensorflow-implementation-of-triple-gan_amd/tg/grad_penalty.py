@@ -22,12 +22,18 @@ Masks, noise and alpha are drawn in their own RNG scope 'GP' ('alpha', 'drop0', 
 phase 'wgan_gp', apart from every buffer a recorded launch plan or graph of the trainer names.  in_step=True (the trainer's D-update
 with config.LOSS = 'WGAN_GP'): the same sweeps inside the caller's solver run (Context.detached) — no phase of their own, buffers and
 draws at call sites of the caller's phase, so that its launch plan or graph records them.  After a call the model's last_gp_state holds
-x, alpha, masks or noise, acts, gx and r."""
+x, alpha, masks or noise, acts, gx, r and out (the penalty kernel's device result: [0] the penalty, for R1 [1] mean_i ||gx_i||^2).
+
+Two penalties share the sweeps; what differs between them is written once each, in a rule object (Wgan, R1) the frame hands the sweep body:
+where the input gradient is evaluated (`point`), the penalty kernel (`penalise`), and the names of its RNG scope, phase and buffers.
+R1 (config.R1_GAMMA; a model's discriminator_r1_penalty(real, y, gamma, in_step=False)): gamma / 2 * mean_i ||gx_i||^2 at the
+real rows themselves with their own labels — no interpolation, no alpha; the norm runs over ALL elements of image i (tg_r1_penalty_f32),
+r = gamma / n * gx; RNG scope 'R1', phase 'r1'."""
 import collections
 
 from tg import geom, lib, ops
 from tg.lib import ACT
-from tg.runtime import ctx, pad32
+from tg.runtime import Act, ctx, pad32
 
 KEEP = 0.8          # every dropout of the discriminators keeps 0.8
 LRE = ACT['lrelu']
@@ -60,24 +66,107 @@ def check_supported(who, mfma_dtype, minibatch_dis):
                           "discriminator is not piecewise linear in one image and the penalty's gradient needs second-order terms" % who)
 
 
-def penalty(model, sweeps, layers, head, real, fake, y, weight, in_step, minibatch_dis=False):
-    """the frame of a model's discriminator_gradient_penalty: checks, the gradient buffer, phase and RNG scope, zero fill, the alpha
-    draw, then sweeps(cx, st, layers, head, real, fake, y, weight, alpha, grad) -> (gp, state), and model.last_gp_state."""
-    who = 'discriminator_gradient_penalty'
+class _Rule(object):
+    """what one penalty kind decides.  who: the model method, for messages; scope: the RNG scope of its draws; phase: the phase of a
+    standalone call, and the prefix of its gradient buffer."""
+
+    def penalise(self, cx, gx):
+        """sweep 3's kernel on the input gradient gx (an Act in the layout the penalty reduces over) -> (penalty[0:1] on the device, r = d
+        penalty / d gx as an Act of gx's shape: rank-2 [N, F] channel-padded, NHWC with gx's row stride, padding written 0)."""
+        rank2 = (gx.h, gx.w) == (1, 1)
+        r = cx.new_act(gx.n, gx.h, gx.w, gx.c, pad32(gx.c) if rank2 else gx.ld)
+        out = cx.scratch('gp', 4)
+        self._kernel(cx, gx, r, rank2, out)
+        return out, r
+
+
+class Wgan(_Rule):
+    """WGAN-GP: evaluated at real + alpha (fake - real), alpha ~ U[0,1) per image; weight * mean((s - 1)^2) over the slopes along axis 1."""
+    who, scope, phase = 'discriminator_gradient_penalty', 'GP', 'wgan_gp'
+
+    def __init__(self, fake, weight):
+        self.fake, self.weight, self.alpha = fake, float(weight), None
+
+    def check(self, real):
+        fake = self.fake
+        if (real.n, real.h, real.w, real.c) != (fake.n, fake.h, fake.w, fake.c):
+            raise lib.TgError("%s: real %s and fake %s differ in shape — bring both to one layout with model.as_image() first"
+                              % (self.who, (real.n, real.h, real.w, real.c), (fake.n, fake.h, fake.w, fake.c)))
+        return getattr(fake, 'dtype', 'f32') == 'f32'
+
+    def begin(self, cx, n):
+        self.alpha = cx.rng.uniform(cx, 'alpha', n, 0.0, 1.0)
+
+    def point(self, cx, real, *shape):
+        """the interpolates as a dense Act of `shape` = (n, h, w, c, ld): [N,H,W,C], or [N,F] whatever real's layout."""
+        x, fake = cx.new_act(*shape), self.fake
+        lib.call('tg_wgan_interp_f32', real.ptr, real.ld, fake.ptr, fake.ld, lib.ptr(self.alpha), x.ptr, real.c, real.n, real.h * real.w, real.c,
+                 cx.stream)
+        return x
+
+    def _kernel(self, cx, gx, r, rank2, out):
+        n, h, w, c = gx.n, gx.h, gx.w, gx.c
+        if rank2:                                                    # axis 1 is the feature axis: one slope per image
+            partials = cx.scratch('gpp', 2 * n)
+            lib.call('tg_grad_penalty_rows_f32', gx.ptr, gx.ld, n, c, self.weight, r.ptr, r.ld, lib.ptr(partials), lib.ptr(out), cx.stream)
+        else:                                                        # axis 1 is H
+            partials = cx.scratch('gpp', 2 * ((n * w * r.ld + 255) // 256))
+            lib.call('tg_grad_penalty_f32', gx.ptr, gx.ld, n, h, w, c, self.weight, r.ptr, r.ld, lib.ptr(partials), lib.ptr(out), cx.stream)
+
+    def state(self):
+        return dict(alpha=self.alpha)
+
+
+class R1(_Rule):
+    """R1: evaluated at the real rows; gamma / 2 * mean_i ||gx_i||^2, the norm over all elements of image i.  gamma: a number, or a
+    1-element device tensor the kernel reads (the trainer's: a replayed plan or graph follows Train.set_r1_gamma)."""
+    who, scope, phase = 'discriminator_r1_penalty', 'R1', 'r1'
+
+    def __init__(self, gamma):
+        self.gamma = gamma
+
+    def check(self, real):
+        return True
+
+    def begin(self, cx, n):
+        if not hasattr(self.gamma, 'data_ptr'):
+            value, self.gamma = float(self.gamma), cx.scratch('r1gamma', 4)
+            lib.call('tg_fill_f32', lib.ptr(self.gamma), value, 1, cx.stream)
+
+    def point(self, cx, real, *shape):
+        """real itself, viewed as `shape`; a channel-padded real is brought to the dense layout the sweeps read first."""
+        if real.ld == real.c:
+            return Act(real.t, *shape)
+        x = cx.new_act(*shape)
+        ops.copy2d(x.t, real.c, 0, real.t, real.ld, real.rows, real.c)
+        return x
+
+    def _kernel(self, cx, gx, r, rank2, out):
+        partials = cx.scratch('gpp', 2 * gx.n)
+        lib.call('tg_r1_penalty_f32', gx.ptr, gx.ld, gx.n, gx.h * gx.w, gx.c, lib.ptr(self.gamma), r.ptr, r.ld, lib.ptr(partials), lib.ptr(out),
+                 cx.stream)
+
+    def state(self):
+        return dict(gamma=self.gamma)
+
+
+def penalty(model, sweeps, layers, head, rule, real, y, in_step, minibatch_dis=False):
+    """the frame of a model's discriminator_gradient_penalty / discriminator_r1_penalty: checks, the gradient buffer, phase and RNG scope,
+    zero fill, the rule's own draws (Wgan: alpha), then sweeps(cx, st, layers, head, rule, real, y, grad) -> (penalty, state), and
+    model.last_gp_state."""
+    who = rule.who
     cx = ctx()
     check_supported(who, cx.mfma_dtype, minibatch_dis)
-    if (real.n, real.h, real.w, real.c) != (fake.n, fake.h, fake.w, fake.c):
-        raise lib.TgError("%s: real %s and fake %s differ in shape — bring both to one layout with model.as_image() first"
-                          % (who, (real.n, real.h, real.w, real.c), (fake.n, fake.h, fake.w, fake.c)))
-    if y.n != real.n or y.ld != y.c or getattr(real, 'dtype', 'f32') != 'f32' or getattr(fake, 'dtype', 'f32') != 'f32':
+    f32 = rule.check(real)
+    if y.n != real.n or y.ld != y.c or getattr(real, 'dtype', 'f32') != 'f32' or not f32:
         raise lib.TgError("%s: dense fp32 labels [%d] and fp32 images of %d expected" % (who, y.n, real.n))
     st = cx.stores['discriminator']
-    grad = cx.scratch('gpgrad', st.n_p) if in_step else cx.ws('wgan_gp:grad', st.n_p)
-    with (cx.detached() if in_step else cx.phase_scope('wgan_gp', record=False)), cx.rng_scoped('GP'):
+    grad = cx.scratch('gpgrad', st.n_p) if in_step else cx.ws(rule.phase + ':grad', st.n_p)
+    with (cx.detached() if in_step else cx.phase_scope(rule.phase, record=False)), cx.rng_scoped(rule.scope):
         lib.call('tg_fill_f32', lib.ptr(grad), 0.0, st.n_p, cx.stream)
-        alpha = cx.rng.uniform(cx, 'alpha', real.n, 0.0, 1.0)
-        gp, state = sweeps(cx, st, layers, head, real, fake, y, float(weight), alpha, grad)
-    state['alpha'] = alpha
+        rule.begin(cx, real.n)
+        gp, state = sweeps(cx, st, layers, head, rule, real, y, grad)
+    state.update(rule.state(), out=gp)
     model.last_gp_state = state
     return gp[0:1], grad
 
@@ -126,21 +215,20 @@ def _label_copies(cx, y, copies):
     return out.t
 
 
-def conv_sweeps(cx, st, layers, head, real, fake, y, weight, alpha, grad):
+def conv_sweeps(cx, st, layers, head, rule, real, y, grad):
     """the sweeps on a convolutional discriminator: input dropout, lrelu 3x3 convolutions (`layers`: label concat in front, dropout
     behind where the row says so), global mean, label concat, dense `head`."""
     n, H, W, c0 = real.n, real.h, real.w, real.c
     ncls, s = y.c, cx.stream
     c_img = st.shape(layers[0].w)[2] - layers[0].copies * ncls
     if c0 != c_img or (H, W) == (1, 1):
-        raise lib.TgError("discriminator_gradient_penalty: images [N,H,W,%d] expected, got %s" % (c_img, (H, W, c0)))
+        raise lib.TgError("%s: images [N,H,W,%d] expected, got %s" % (rule.who, c_img, (H, W, c0)))
     if layers[-1].drop:
-        raise lib.TgError("discriminator_gradient_penalty: a dropout behind the last convolution is not supported")
+        raise lib.TgError("%s: a dropout behind the last convolution is not supported" % rule.who)
     labels = {k: _label_copies(cx, y, k) for k in {row.copies for row in layers}}
     zlab = cx.scratch('zlab', max(labels) * n * ncls)
     lib.call('tg_fill_f32', lib.ptr(zlab), 0.0, max(labels) * n * ncls, s)
-    x = cx.new_act(n, H, W, c0, c0)
-    lib.call('tg_wgan_interp_f32', real.ptr, real.ld, fake.ptr, fake.ld, lib.ptr(alpha), x.ptr, x.ld, n, H * W, c0, s)
+    x = rule.point(cx, real, n, H, W, c0, c0)
     m0 = cx.rng.keep_mask(cx, cx.next_rng_name('drop'), n * H * W * c0, KEEP)
     # ---- sweep 1: forward, keeping every layer's input, activation and filter layouts
     L = []
@@ -181,11 +269,8 @@ def conv_sweeps(cx, st, layers, head, real, fake, y, weight, alpha, grad):
                      yp.rows, yp.c, LRE, 0.2, s)
     gx = cx.new_act(n, H, W, c0, pad32(c0))
     lib.call('tg_actgrad_f32', da.ptr, da.ld, None, 0, lib.ptr(m0), c0, 1.0 / KEEP, gx.ptr, gx.ld, gx.rows, c0, 0, 0.0, s)
-    # ---- sweep 3: the penalty (slopes over H, axis 1 of NHWC), then the tangent forward from r = weight * d gp / d gx
-    r = cx.new_act(n, H, W, c0, gx.ld)
-    partials = cx.scratch('gpp', 2 * ((n * W * r.ld + 255) // 256))
-    gp = cx.scratch('gp', 4)
-    lib.call('tg_grad_penalty_f32', gx.ptr, gx.ld, n, H, W, c0, weight, r.ptr, r.ld, lib.ptr(partials), lib.ptr(gp), s)
+    # ---- sweep 3: the penalty (Wgan: slopes over H, axis 1 of NHWC; R1: per image), then the tangent forward from r = d penalty / d gx
+    gp, r = rule.penalise(cx, gx)
     src, mask = r, m0
     for Lk in L:
         a, yk, row = Lk['a'], Lk['y'], Lk['row']
@@ -209,19 +294,17 @@ def conv_sweeps(cx, st, layers, head, real, fake, y, weight, alpha, grad):
     return gp, dict(x=x, masks=[m0] + [Lk['mask'] for Lk in L if Lk['mask'] is not None], acts=[Lk['y'] for Lk in L], gx=gx, r=r)
 
 
-def mnist_sweeps(cx, st, layers, head, real, fake, y, weight, alpha, grad):
+def mnist_sweeps(cx, st, layers, head, rule, real, y, grad):
     """the sweeps on the MNIST discriminator: lrelu dense `layers` with additive noise behind each activation, label concats, dense
     `head`.  real, fake: [N,784] (the generator's and as_image()'s layout: one slope per image) or [N,28,28,1] (slopes over H)."""
     n, ncls, s = real.n, y.c, cx.stream
     F = real.h * real.w * real.c
     if F + ncls != st.shape(layers[0].w)[0]:
-        raise lib.TgError("discriminator_gradient_penalty: MNIST images of %d values expected, got %s" % (
-            st.shape(layers[0].w)[0] - ncls, (real.h, real.w, real.c)))
+        raise lib.TgError("%s: MNIST images of %d values expected, got %s" % (rule.who, st.shape(layers[0].w)[0] - ncls, (real.h, real.w, real.c)))
     P = lib.ptr
     zlab = cx.scratch('zlab', n * ncls)
     lib.call('tg_fill_f32', P(zlab), 0.0, n * ncls, s)
-    x = cx.new_act(n, 1, 1, F, F)                                      # dense [N, F] whatever the input's layout
-    lib.call('tg_wgan_interp_f32', real.ptr, real.ld, fake.ptr, fake.ld, P(alpha), x.ptr, real.c, n, real.h * real.w, real.c, s)
+    x = rule.point(cx, real, n, 1, 1, F, F)                            # dense [N, F] whatever the input's layout
 
     def noisy_concat(h, noise):                                        # concat([h + noise, y], 1)
         a = cx.new_act(n, 1, 1, h.c + ncls, pad32(h.c + ncls))
@@ -255,19 +338,10 @@ def mnist_sweeps(cx, st, layers, head, real, fake, y, weight, alpha, grad):
         _igemm(cx, 'tg_igemm_multi_f32', dds, len(dds), dpre.ptr, P(Lk['w_hwio']), None, da.ptr, s)
     gx = cx.new_act(n, 1, 1, F, F)
     lib.call('tg_actgrad_f32', da.ptr, da.ld, None, 0, None, 0, 1.0, gx.ptr, F, n, F, 0, 0.0, s)
-    # ---- sweep 3: the penalty (axis 1 of the tensor passed in: the features of [N, F], H of NHWC), then the tangent forward
-    gp = cx.scratch('gp', 4)
-    if (real.h, real.w) == (1, 1):
-        r = cx.new_act(n, 1, 1, F, pad32(F))
-        partials = cx.scratch('gpp', 2 * n)
-        lib.call('tg_grad_penalty_rows_f32', gx.ptr, F, n, F, weight, r.ptr, r.ld, P(partials), P(gp), s)
-        r_ld = r.ld
-    else:
-        hh, ww, cc = real.h, real.w, real.c
-        r = cx.new_act(n, hh, ww, cc, cc)
-        partials = cx.scratch('gpp', 2 * ((n * ww * cc + 255) // 256))
-        lib.call('tg_grad_penalty_f32', gx.ptr, cc, n, hh, ww, cc, weight, r.ptr, cc, P(partials), P(gp), s)
-        r_ld = F
+    # ---- sweep 3: the penalty (Wgan: over axis 1 of the tensor passed in, the features of [N, F], H of NHWC — gx is viewed in real's
+    # layout; R1: per image in either), then the tangent forward
+    gp, r = rule.penalise(cx, Act(gx.t, n, real.h, real.w, real.c, real.c))
+    r_ld = r.h * r.w * r.ld                                            # r as [N, F]: its row stride
     ta = cx.new_act(n, 1, 1, F + ncls, L[0]['a'].ld)
     lib.call('tg_cond_concat_f32', r.ptr, r_ld, F, None, 0, 1.0, P(zlab), ncls, ta.ptr, ta.ld, n, 1, s)
     for Lk in L:

@@ -16,6 +16,8 @@
                                                      the default --optimizer adam is the step above, with exactly the output it always had
     --clip-norm X                                    any configuration with config.CLIP_NORM = X for all three networks: three
                                                      global-norm launches and the clipped optimisers; without it the step and the output above
+    --r1-gamma X                                     any fp32 GAN-loss configuration with config.R1_GAMMA = X: the R1 gradient penalty
+                                                     in the D-update; without it the step and the output above
 
 Runs the D+G+C step on synthetic images already resident in HBM, then one instrumented eager iteration with
 per-kernel-class HIP-event timing.  Prints ONE JSON line: ms/step, images/sec and, per kernel class, launches,
@@ -52,7 +54,7 @@ SHAPES = {   # name: (data, H, C, B_G, L_C, U_C, L_D, U_D, mfma dtype, lambda_1,
 }
 
 
-def make_config(name='stress64', loss='gan', num_classes=None, optimizer='adam', clip_norm=None):
+def make_config(name='stress64', loss='gan', num_classes=None, optimizer='adam', clip_norm=None, r1_gamma=None):
     from config import Config
     data, hw, ch, bg, lc, uc, ld, ud, prec, lam, lr, clr = SHAPES[name]
 
@@ -86,7 +88,10 @@ def make_config(name='stress64', loss='gan', num_classes=None, optimizer='adam',
         OPTIMIZER = optimizer
         CLIP_NORM = clip_norm
 
-    return TempConfig()
+    cfg = TempConfig()
+    if r1_gamma is not None:                              # (Config does not declare R1_GAMMA: set only when asked for)
+        cfg.R1_GAMMA = r1_gamma
+    return cfg
 
 
 def main():
@@ -97,6 +102,7 @@ def main():
     ap.add_argument('--loss', choices=('gan', 'wgan_gp'), default='gan')
     ap.add_argument('--optimizer', choices=('adam', 'rmsprop', 'momentum'), default='adam', help='config.OPTIMIZER of all three networks')
     ap.add_argument('--clip-norm', type=float, default=None, help='config.CLIP_NORM of all three networks (default: no clip)')
+    ap.add_argument('--r1-gamma', type=float, default=None, help='config.R1_GAMMA (default: no R1 penalty)')
     ap.add_argument('--num-classes', type=int, default=None, help='config.NUM_CLASSES (default: 100 for cifar100, else 10)')
     args = ap.parse_args()
     import torch
@@ -109,7 +115,7 @@ def main():
     else:
         from Model.Good_GAN import Good_GAN as Model
 
-    cfg = make_config(args.config, args.loss, args.num_classes, args.optimizer, args.clip_norm)
+    cfg = make_config(args.config, args.loss, args.num_classes, args.optimizer, args.clip_norm, args.r1_gamma)
     if args.config.startswith('cifar10'):
         q, _ = np.linalg.qr(np.random.default_rng(4321).standard_normal((3072, 3072)))      # SURVEY §8d synthetic whitening
         cfg.ZCA = (np.zeros(3072, np.float32), q.astype(np.float32))
@@ -190,7 +196,9 @@ def main():
                           args.config, cfg.IMAGE_HEIGHT, cfg.IMAGE_WIDTH, cfg.CHANNEL, cfg.BATCH_SIZE_G, cfg.BATCH_SIZE_L_C, cfg.BATCH_SIZE_U_C,
                           cfg.BATCH_SIZE_L_D, cfg.BATCH_SIZE_U_D, Model.__name__, cfg.MFMA_DTYPE) + (", WGAN-GP loss" if args.loss == 'wgan_gp' else "")
                           + (", %d classes" % k if k != 10 else "") + (", optimizer %s" % args.optimizer if args.optimizer != 'adam' else "")
-                          + (", clip norm %g" % args.clip_norm if args.clip_norm is not None else ""),
+                          + (", clip norm %g" % args.clip_norm if args.clip_norm is not None else "")
+                          + (", R1 gamma %g" % args.r1_gamma if args.r1_gamma is not None else ""),
+                      **({"r1_terms": {k: round(v, 6) for k, v in tr.r1_terms().items()}} if args.r1_gamma is not None else {}),
                       **({"grad_norms_d_g_c": [[round(x, 6) for x in v] for v in tr.grad_norms().values()]} if args.clip_norm is not None else {}),
                       "act_dtype": cfg.ACT_DTYPE, "bf16_act_edges": tr.bf16_act_edges,
                       "ms_per_step": round(dt * 1e3, 3), "images_per_sec": round(cfg.BATCH_SIZE_G / dt, 1), "steps": args.steps, "hbm_gib_allocated": round(mem, 2),

@@ -3,7 +3,10 @@
 or on the MNIST / SVHN one of Good_GAN (--data), eager, fp32, at n images (default 100), after warm-up — and, for scale, one plain
 discriminator forward + backward (weight gradients) at the same n.  Prints ONE JSON line (with --data mnist / svhn it names the data).
 
-    python tools/bench_wgan_gp.py [--data cifar10|mnist|svhn] [--n 100] [--iters 50]
+    python tools/bench_wgan_gp.py [--data cifar10|mnist|svhn] [--n 100] [--iters 50] [--penalty wgan_gp|r1]
+
+--penalty r1 times Train_base._r1_penalty (config.R1_GAMMA, DESIGN §9.15: the same sweeps at the real rows, gamma 10) instead; the default
+is the output it always had.
 
 The penalty is four sweeps through the discriminator (forward, input gradient, tangent forward, filter gradients: DESIGN §9.1), so
 about twice a forward + backward is the expectation."""
@@ -39,6 +42,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=100)
     ap.add_argument('--iters', type=int, default=50)
+    ap.add_argument('--penalty', choices=('wgan_gp', 'r1'), default='wgan_gp')
     ap.add_argument('--data', choices=('cifar10', 'mnist', 'svhn'), default='cifar10')
     args = ap.parse_args()
     from config import Config
@@ -65,7 +69,10 @@ def main():
 
     def gp():
         with cx.phase_scope('bench_gp', record=False):
-            tb._gradient_penalty(real, fake, y, model.discriminator)
+            if args.penalty == 'r1':
+                tb._r1_penalty(real, y, model.discriminator, 10.0)
+            else:
+                tb._gradient_penalty(real, fake, y, model.discriminator)
 
     ones = cx.from_numpy(np.ones((n, 1)), ld=32, key='bench:ones')
 
@@ -82,6 +89,8 @@ def main():
                ratio=round(ms_gp / ms_d, 3))
     if args.data != 'cifar10':
         out = dict(out, data=args.data)
+    if args.penalty != 'wgan_gp':
+        out = dict(out, penalty=args.penalty)
     print(json.dumps(out))
 
 
