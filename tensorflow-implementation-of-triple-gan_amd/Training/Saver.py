@@ -16,6 +16,11 @@ TensorFlow name, in ONE file `model_<epoch>.ckpt.npz` (so `_findfilename`'s name
     tg/rng_state                             Philox (seed, step) of the writing rank — TF's graph-level seeds have no equivalent.  On
                                              restore every rank takes the STEP and keeps its own seed (replicas draw different
                                              z / y / masks / noise: config.SEED + 7919 * rank, Train.__init__)
+    tg/rng_streams                           the Philox stream names ('<rng scope>/<draw>') in the order of their ids, a plain string array.
+                                             PhiloxRNG numbers a stream when it is first used, so the numbering is the history of the
+                                             run: pre-training uses the C-update's streams before the D-update's, a run that starts
+                                             with a full iteration the other way round.  Restored with the state, on every rank (names
+                                             are rank-independent); a file without the key leaves the numbering to the order of use
     tg/epoch                                 epoch the file was written after
 
 Save gathers from the flat device buffers; restore scatters back — the MFMA-side filter layouts are rebuilt from the values every
@@ -73,12 +78,15 @@ def state_dict(stores, rng=None, epoch=0):
         out['tg/adam_step/' + net] = st.step.detach().cpu().numpy().astype(np.int64)
     if rng is not None and hasattr(rng, 'state'):
         out['tg/rng_state'] = rng.state.detach().cpu().numpy()
+    if rng is not None and hasattr(rng, 'stream_ids'):        # ids are 1..n in order of first use: the names in that order say it all
+        out['tg/rng_streams'] = np.asarray(sorted(rng.stream_ids, key=rng.stream_ids.get), dtype=np.str_)
     out['tg/epoch'] = np.asarray(epoch, np.int64)
     return out
 
 
 def load_state_dict(stores, d, rng=None, strict=True, keep_seed=False):
-    """keep_seed: restore only the RNG's step counter (data-parallel resume: the file holds rank 0's seed)."""
+    """keep_seed: of the RNG's (seed, step) restore only the step counter (data-parallel resume: the file holds rank 0's seed); the
+    stream-id table (tg/rng_streams) is restored either way."""
     import torch
     missing = []
     for net, st in stores.items():                   # before anything is copied: another optimiser's slots mean something else, and a
@@ -113,6 +121,12 @@ def load_state_dict(stores, d, rng=None, strict=True, keep_seed=False):
             rng.state[1:2].copy_(saved[1:2])
         else:
             rng.state.copy_(saved)
+    if rng is not None and hasattr(rng, 'stream_ids') and 'tg/rng_streams' in d:
+        # the writing run's numbering, whatever this process will use first (keep_seed too: the names do not depend on the rank).  The
+        # RNG's own multi-launch plans hold ids and are recorded again; restore before the first iteration, as train() does — a hipGraph
+        # or launch plan recorded earlier keeps the ids it was recorded with
+        rng.stream_ids = {str(nm): i + 1 for i, nm in enumerate(np.asarray(d['tg/rng_streams']).reshape(-1))}
+        rng.plans.clear()
     if strict and missing:
         raise KeyError("checkpoint lacks %d variables, e.g. %s" % (len(missing), missing[:3]))
     return missing

@@ -282,7 +282,7 @@ def _state(tr):
 
 
 def _expected_keys(tr, kinds):
-    keys = {'tg/rng_state', 'tg/epoch'}
+    keys = {'tg/rng_state', 'tg/rng_streams', 'tg/epoch'}
     for net, kind in zip(NETS, kinds):
         st = tr.cx.stores[net]
         keys.add('tg/adam_step/' + net)

@@ -97,7 +97,7 @@ def test_checkpoint_holds_exactly_the_variables_tensorflow_would_save(tmp_path, 
     """the key set of a checkpoint equals the names tf.train.Saver() would write for the reference's graph — derived
     independently of the package's own variable tables from the reference's scopes (oracle/tf_names.py) — with two documented
     substitutions: TensorFlow's six beta1_power / beta2_power scalars are replaced by one step count per optimiser (tg/adam_step/<net>),
-    and tg/rng_state, tg/epoch have no TensorFlow counterpart."""
+    and tg/rng_state, tg/rng_streams, tg/epoch have no TensorFlow counterpart."""
     from oracle import tf_names
     from Training.Saver import Saver
     if data == 'cifar10':
@@ -109,7 +109,8 @@ def test_checkpoint_holds_exactly_the_variables_tensorflow_would_save(tmp_path, 
     saver.set_save_path(comments='names')
     keys = set(np.load(saver.save(tr, 'model_0001.ckpt')).files)
     extras = {k for k in keys if k.startswith('tg/')}
-    assert extras == {'tg/adam_step/good_generator', 'tg/adam_step/discriminator', 'tg/adam_step/classifier', 'tg/rng_state', 'tg/epoch'}
+    assert extras == {'tg/adam_step/good_generator', 'tg/adam_step/discriminator', 'tg/adam_step/classifier', 'tg/rng_state', 'tg/rng_streams',
+                      'tg/epoch'}
     want = set(tf_names.saver_variables(data)) - set(tf_names.NON_SLOT)
     assert keys - extras == want, (sorted((keys - extras) - want)[:5], sorted(want - (keys - extras))[:5])
     for name in ('classifier/conv1_1/V', 'classifier/NiN1/NiN1/V', 'good_generator/gg_h0_lin/gg_h0_lin/kernel') if data == 'cifar10' else ():

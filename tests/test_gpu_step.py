@@ -58,8 +58,16 @@ def check_grads(st, tr, key):
         assert np.linalg.norm(d) <= GRAD_L2_TOL * np.linalg.norm(gref) + 1e-7 * np.sqrt(d.size), ('grad L2', k)
 
 
-def check_update_and_sync(st, tr, key, before, lr):
-    """post-Adam variables: mean error small, every element inside Adam's envelope; then copy the oracle's state in."""
+def moving_stat_close(got, ref):
+    """a batch-norm moving statistic of the generator against the oracle's."""
+    return np.abs(got - ref).max() <= 1e-5 * max(1.0, np.abs(ref).max())
+
+
+def check_update_and_sync(st, tr, key, before, lr, mean=True):
+    """post-Adam variables: mean error small, every element inside Adam's envelope; then copy the oracle's state in.
+    mean=False: the envelope alone.  The mean bound below is sized for the CIFAR-10 networks at init_params, where one variable's true
+    gradient is 0; the scrambled MNIST / SVHN weights of tests/test_gpu_goodgan.py have whole variables and single channels like that
+    (ANALYTIC_ZERO there, dead first-layer channels), on which Adam at t = 1 turns rounding residue into steps of a fraction of lr."""
     store = tr.cx.stores[NETS[key]]
     for k in store.names():
         ref, got = st['P'][k], store.get(k)
@@ -67,20 +75,31 @@ def check_update_and_sync(st, tr, key, before, lr):
             # the generator's batch-norm moving statistics (dead for the losses, checkpoint content): the oracle updates them once per
             # solver run that evaluates the generator — three times per iteration, Model/modle_base.py:229-237 under
             # Train_goodGAN.py:267,270,275; the HIP path re-applies the update its re-used forward pass skipped
-            assert np.abs(got - ref).max() <= 1e-5 * max(1.0, np.abs(ref).max()), (k, np.abs(got - ref).max())
+            assert moving_stat_close(got, ref), (k, np.abs(got - ref).max())
             store.set(k, ref)
             continue
         upd = np.abs(ref - before[k]).max() + 1e-12
         err = np.abs(got - ref)
         # 0.01*lr: variables whose true gradient is 0 (NiN2/b) receive fp32 rounding noise ~1e-9 ~ Adam's epsilon,
         # which Adam turns into updates of a fraction of lr (TensorFlow's fp32 Adam does the same)
-        assert err.mean() <= 0.02 * upd + 0.01 * lr, (k, err.mean(), err.max(), upd)
+        assert not mean or err.mean() <= 0.02 * upd + 0.01 * lr, (k, err.mean(), err.max(), upd)
         assert err.max() <= 2.1 * lr + 1e-7, (k, err.max())
         store.set(k, ref)
     for k in store.names(True):
         kind, off, n, shape = store.index[k]
         store.m[off:off + n].copy_(torch.from_numpy(st['m'][k].astype(np.float32).reshape(-1)))
         store.v[off:off + n].copy_(torch.from_numpy(st['v'][k].astype(np.float32).reshape(-1)))
+
+
+def check_ema_and_sync(st, tr, cla_lr):
+    """EMA shadows of the HIP-updated classifier variables (call it before check_update_and_sync copies the oracle's variables in); then
+    copy the oracle's shadows in."""
+    cs = tr.cx.stores['classifier']
+    for k, v in st['ema'].items():
+        kind, off, n, shape = cs.index[k]
+        got = cs.ema[off:off + n].cpu().numpy().reshape(shape)
+        assert np.abs(got - v).max() <= 1e-4 * 2.1 * cla_lr + 1e-6 * np.abs(v).max() + 1e-7, k
+        cs.ema[off:off + n].copy_(torch.from_numpy(v.astype(np.float32).reshape(-1)))
 
 
 def sync_pop_means(st, tr, check=True):
@@ -123,12 +142,7 @@ def run_synchronised(sizes, n_steps, hyper):
         tr._c_forward_backward()
         check_grads(st, tr, 'C')
         tr._c_apply()
-        cs = stores['classifier']
-        for k, v in st['ema'].items():       # EMA of the HIP-updated variables (checked before the sync below)
-            kind, off, n, shape = cs.index[k]
-            got = cs.ema[off:off + n].cpu().numpy().reshape(shape)
-            assert np.abs(got - v).max() <= 1e-4 * 2.1 * hyper['cla_lr'] + 1e-6 * np.abs(v).max() + 1e-7, k
-            cs.ema[off:off + n].copy_(torch.from_numpy(v.astype(np.float32).reshape(-1)))
+        check_ema_and_sync(st, tr, hyper['cla_lr'])
         check_update_and_sync(st, tr, 'C', before, hyper['cla_lr'])
         sync_pop_means(st, tr)
         for r, g in zip((d_ref, g_ref, c_ref), tr.losses()):
@@ -139,7 +153,7 @@ def run_synchronised(sizes, n_steps, hyper):
     gs = stores['good_generator']
     for k in gs.names(False):
         ref = st['P'][k]
-        assert np.abs(gs.get(k) - ref).max() <= 1e-5 * max(1.0, np.abs(ref).max()), (k, np.abs(gs.get(k) - ref).max())
+        assert moving_stat_close(gs.get(k), ref), (k, np.abs(gs.get(k) - ref).max())
         assert np.abs(ref - (1.0 if k.endswith('variance') else 0.0)).max() > 1e-3          # and they did move
     return st, tr
 
@@ -152,6 +166,25 @@ def test_synchronised_two_iterations_small_batches():
 def test_synchronised_iteration_reference_batch_sizes():
     """the CIFAR-10 config of the reference: 100/50/50/20/80 (Training/Train_goodGAN.py:566-572)."""
     run_synchronised({}, 1, dict(lr=3e-4, cla_lr=3e-3, beta1=0.5, lambda_1=0.3, lambda_2=0.5))
+
+
+def check_free_running_losses(ref, got, it):
+    """losses of free-running iteration `it` (0-based) against the oracle's: the bound test_free_running_three_iterations explains."""
+    for r, g in zip(ref, got):
+        assert abs(r - g) <= 1.5e-2 * max(1.0, abs(r)) * (it + 1), (it, ref, got)
+
+
+def check_free_running_envelope(st, tr, hyper, steps, p0):
+    """every trainable variable after steps[key] free-running optimiser steps of network `key`, against the oracle's and against its
+    initial value p0."""
+    for key, net in NETS.items():
+        store = tr.cx.stores[net]
+        lr = hyper['cla_lr'] if key == 'C' else hyper['lr']
+        for k in store.names(True):
+            # each Adam step moves an element by at most ~1.1*lr (beta1 = 0.5, early bias correction): two free trajectories
+            # can end up 2 * 1.1 * lr * steps apart in the worst element
+            assert np.abs(store.get(k) - st['P'][k]).max() <= 2.2 * lr * steps[key] + 1e-7, k
+            assert np.abs(store.get(k) - p0[k]).max() > 0, k          # every variable was trained
 
 
 def test_free_running_three_iterations():
@@ -172,13 +205,5 @@ def test_free_running_three_iterations():
         # rounding noise sit 2*lr apart on the two sides, and WHICH elements those are depends on the last bit of every
         # reduction — two equally accurate statistics kernels (two-pass centred vs fp64 sum of squares) gave 0.4e-2 and
         # 1.9e-2 on g_loss of the second iteration.  The bound is the order of magnitude of that effect (module docstring).
-        for r, g in zip(ref, got):
-            assert abs(r - g) <= 1.5e-2 * max(1.0, abs(r)) * (it + 1), (it, ref, got)
-    for key, net in NETS.items():
-        store = tr.cx.stores[net]
-        lr = hyper['cla_lr'] if key == 'C' else hyper['lr']
-        for k in store.names(True):
-            # each Adam step moves an element by at most ~1.1*lr (beta1 = 0.5, early bias correction): two free trajectories
-            # can end up 2 * 1.1 * lr * steps apart in the worst element
-            assert np.abs(store.get(k) - st['P'][k]).max() <= 2.2 * lr * 3 + 1e-7, k
-            assert np.abs(store.get(k) - p0[k]).max() > 0, k          # every variable was trained
+        check_free_running_losses(ref, got, it)
+    check_free_running_envelope(st, tr, hyper, dict(D=3, G=3, C=3), p0)
